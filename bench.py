@@ -11,7 +11,20 @@ the reference sampler.  Arithmetic is fp32 throughout; the hidden-layer matmuls 
 fp32 operands split into two fp16 pieces ("fp16x3": three products, fp32 accumulate; --opt split=0: three bf16 pieces,
 six products) — fp32-equivalent, held to the fp32 parity tolerances.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--hidden H] [--no-cpu-baseline] [--no-config3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--hidden H] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-config3]]
+
+A plain run sets up, warms up, times the K steps and prints the headline line; `roofline`, `phases_ms`, `config3`,
+`config3_1gpu_1M` and `cpu_baseline` are null there or absent.  `--full` adds them: the untimed per-kernel pass, the 8x512
+blocks and the CPU baseline (`--no-cpu-baseline` / `--no-config3` / `--no-config3-1m` leave parts of that out).
+`--dump-outputs DIR` writes what one step of the timed engine returns to a caller, as float32 `.npy` files: `loss_terms`
+(the four loss terms), `theta` (the parameters after its Adam update) and `dtheta` (its global gradient).  After the timed
+steps (and the `--full` pass) the timed engine is put back to its seeded inputs (theta as initialised, Adam moments zero,
+step count 0) and takes ONE more step on the same configuration, kernels and launch shapes it was timed with.  That step
+is what is written: its inputs are a pure function of the arguments, so two runs, or two builds, agree output for output
+to the rounding of the step's own cross-workgroup float atomics (tests/test_hip_parity.py measures that default launches
+agree to rounding).  The timed steps' last step itself is not written: each step's atomics add in a varying order and
+Adam carries the differences forward, so after W + K steps its inputs already differ from run to run.  Cost: one step.
 
 Prints ONE JSON line on rank 0.  Timing protocol: W untimed warm-up steps, then EXACTLY K steps between two
 barrier + synchronize pairs with the library's HIP-event profiler OFF; `value` = global batch x K / that wall time (MAX
@@ -47,6 +60,7 @@ PEAK_F32_MFMA_TFLOPS = 157.3           # /opt/skills/guides/MI355X_MICROARCH.md,
 PEAK_HBM_TB_S = 8.0                     # HBM3E, same table
 PEAK_BF16_MFMA_TFLOPS = 2500.0         # same table: BF16 MFMA, dense
 PROFILE_STEPS = 8                       # untimed per-kernel pass
+DUMP_LIMIT_BYTES = 64 << 20             # --dump-outputs: larger outputs are written as a fixed, seeded sample
 
 
 def f0(hidden, layers):
@@ -64,6 +78,30 @@ def shard_batch(n_per_gpu, world, rank, seed):
         x, nrm, sdf = synth.training_batch(n_global, seed=seed, lo=int(part[0]), hi=int(part[-1]) + 1)
         xs.append(x); ns.append(nrm); ss.append(sdf)
     return np.concatenate(xs), np.concatenate(ns), np.concatenate(ss), n_global
+
+
+def extras(args, world):
+    """What this run does beyond timing the headline: a plain run nothing, `--full` the per-kernel pass, the 8x512 blocks (the
+    headline workload only; the 1 M-point one on one GPU) and the CPU baseline (one GPU)."""
+    headline = args.loss == "eikonal" and args.hidden == 256 and args.layers == 8 and args.points == 100000
+    config3 = args.full and headline and not args.no_config3
+    return {"profile_steps": PROFILE_STEPS if args.full else 0, "config3": config3,
+            "config3_1m": config3 and world == 1 and not args.no_config3_1m,
+            "cpu_baseline": args.full and not args.no_cpu_baseline and world == 1}
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """{name: float32 array} -> dirname/<name>.npy.  Over `limit` bytes in all, every array is cut to its share of the limit by
+    the same seeded choice of elements in every run (flattened, in index order)."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > limit:
+            keep = max(1, int(a.size * limit // total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def cpu_baseline(hidden, layers, seed, sizes=(100000, 29970), budget_s=9.0):
@@ -149,13 +187,15 @@ class Runner:
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    def run(self, hidden, layers, points, steps, warmup, loss, profile_steps=PROFILE_STEPS, seed=123):
+    def run(self, hidden, layers, points, steps, warmup, loss, profile_steps=PROFILE_STEPS, seed=123, keep_outputs=False):
         """(elapsed seconds for `steps` steps [max over ranks], per-kernel {name: avg ms} from an untimed pass,
-        final loss, n_global, n_hess)."""
+        final loss, n_global, n_hess).  keep_outputs: info["outputs"] = host copies of what one more step of the timed engine
+        returns from the seeded inputs (every rank takes part: the step's collectives)."""
         from diffudf_amd import hip_ops, synth
         from diffudf_amd.engine import TrainEngine
         hid = [hidden] * layers
-        theta = torch.from_numpy(synth.flatten_params(synth.siren_params(hid, seed=seed))).to(self.dev)
+        theta0 = synth.flatten_params(synth.siren_params(hid, seed=seed))
+        theta = torch.from_numpy(theta0).to(self.dev)
         x, nrm, sdf, n_global = shard_batch(points, self.world, self.rank, seed)
         x, nrm, sdf = [torch.from_numpy(a).to(self.dev) for a in (x, nrm, sdf.reshape(-1))]
         eng = TrainEngine(hid, theta, collectives=self.args.collectives)
@@ -185,7 +225,8 @@ class Runner:
             el, med = float(t[0]), float(t[1])
         info = {"median_ms": med, "min_ms": per_step[0], "max_ms": per_step[-1], "kern": {}, "clocks_mhz": {}, "products": {}, "phases_ms": None,
                 "event_cost_per_launch_ms": None,
-                "event_pair_overhead_ms": None, "profiled_step_ms": None, "collectives": getattr(eng, "collectives", None)}
+                "event_pair_overhead_ms": None, "profiled_step_ms": None, "collectives": getattr(eng, "collectives", None),
+                "outputs": None}
         if profile_steps:
             # what an empty event pair reads on this stream: subtracted from every per-kernel duration (round 2: the raw
             # figures summed to more than the step they are part of)
@@ -236,6 +277,13 @@ class Runner:
             info["profiled_step_ms"] = prof_step
             if self.world > 1:
                 info["phases_ms"] = {k: round(v, 4) for k, v in eng.phase_times().items()}
+        if keep_outputs:
+            # The timed engine itself, back at the seeded inputs, one more step: the timed path's kernels and launch shapes, from
+            # inputs that are the same in every run (after W + K steps the engine's own state no longer is: see the docstring)
+            eng.theta.copy_(torch.from_numpy(theta0))
+            eng.exp_avg.zero_(); eng.exp_avg_sq.zero_(); eng.t = 0
+            terms = step()
+            info["outputs"] = {"loss_terms": terms.cpu().numpy(), "theta": eng.theta.cpu().numpy(), "dtheta": eng.dtheta.cpu().numpy()}
         del eng
         return el, info, final_loss, n_global, n_hess
 
@@ -412,7 +460,7 @@ def self_launch(n):
     return subprocess.run(cmd, env=env).returncode
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)
@@ -430,10 +478,19 @@ def main():
     ap.add_argument("--share-device", action="store_true",
                     help="N > 1 on a ONE-GPU box: every rank on cuda:0 over gloo (RCCL refuses two ranks on one device).  A functional "
                          "check of the sharded path, never a measurement: the JSON line says \"share_device\": true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-config3", action="store_true", help="skip the secondary 8x512 blocks (125 000 points per GPU; 1 M points on one GPU)")
-    ap.add_argument("--no-config3-1m", action="store_true", help="skip only the 8x512 / 1 000 000-points-on-one-GPU block (110 GB workspace)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the untimed per-kernel pass (roofline, phases_ms), the 8x512 blocks and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what one more step of the timed engine, from the seeded inputs, returns (loss_terms, theta, "
+                         "dtheta) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-config3", action="store_true", help="--full without the secondary 8x512 blocks (125 000 points per GPU; 1 M points on one GPU)")
+    ap.add_argument("--no-config3-1m", action="store_true", help="--full without just the 8x512 / 1 000 000-points-on-one-GPU block (110 GB workspace)")
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     if args.share_device:
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "1")  # read by the HIP runtime when this process first touches the GPU (see self_launch)
@@ -462,10 +519,15 @@ def main():
         k, v = item.split("=", 1)
         hip_ops.set_option(k, int(v))
     R = Runner(args, world, rank, dev)
-    el, info, final_loss, n_global, n_hess = R.run(args.hidden, args.layers, args.points, args.steps, args.warmup, args.loss)
+    plan = extras(args, world)
+    el, info, final_loss, n_global, n_hess = R.run(args.hidden, args.layers, args.points, args.steps, args.warmup, args.loss,
+                                                   profile_steps=plan["profile_steps"],
+                                                   keep_outputs=args.dump_outputs is not None)
+    if rank == 0 and info["outputs"] is not None:
+        dump_outputs(args.dump_outputs, info["outputs"])
     config3 = None
     headline = args.loss == "eikonal" and args.hidden == 256 and args.layers == 8 and args.points == 100000
-    if headline and not args.no_config3:
+    if plan["config3"]:
         # BASELINE.json configs[2]: SIREN 8x512, 1 M synthetic points sharded over 8 GPUs = 125 000 per GPU (weak scaling
         # at other N).  Reported as a block of its own, never as `value`.
         s3 = max(10, args.steps // 4)
@@ -478,7 +540,7 @@ def main():
                    "roofline": roofline_block(args, info3, 512, 8, 125000, 0, ms3) if rank == 0 else None}
 
     config3_1m = None
-    if headline and not args.no_config3 and world == 1 and not args.no_config3_1m:
+    if plan["config3_1m"]:
         # BASELINE.json configs[2] as north_star words it — "1 M points, 8x512, sharded across 8" — on ONE GPU: the whole 1 M-point
         # batch in one 110 GB workspace (288 GB of HBM).  The denominator of the ">= 6x at 8 GPUs vs 1" target on that config
         # (strong scaling: 8 x 125 000 = the same global batch); the `config3` block above is its per-GPU share.
@@ -519,7 +581,7 @@ def main():
                           "16-bit significand (relative error <= 2^-16; read only by the adjoint sweeps); C = cos(w0 z) as fixed point on "
                           "a 2^-22 grid (absolute error 2^-23); S, Q, A, Z (the weight-gradient GEMM's operands) as the same fixed point "
                           "relative to a per-layer, per-column power of two 2^E (absolute error 2^(E-23)).  512-wide networks keep S, Q, "
-                          "A, Z at fp32 (their kernel reads them back as the next layer's operand).  roofline.stash names the format of this run (dudf_stash_mode); every fp32 parity tolerance and "
+                          "A, Z at fp32 (their kernel reads them back as the next layer's operand).  With --full, roofline.stash names the format of this run (dudf_stash_mode); every fp32 parity tolerance and "
                           "the trajectory bars are held in it (tests/test_traj50_gpu.py)",
             "config": {"workload": f"SIREN {args.layers}x{args.hidden} (w0=30), loss_s1 weights {weights} "
                                    f"({'Eikonal-only' if args.loss == 'eikonal' else 'Hessian term on'}), alpha=100, {args.points} "
@@ -527,13 +589,13 @@ def main():
                                    f"{'RCCL all-reduce + ' if world > 1 else ''}Adam",
                        "points_per_gpu": args.points, "global_batch": n_global, "hidden": args.hidden,
                        "layers": args.layers, "parallelism": f"point-batch sharding x{world}, replicated theta"},
-            "roofline": roofline_block(args, info, args.hidden, args.layers, args.points, n_hess, ms_step),
+            "roofline": roofline_block(args, info, args.hidden, args.layers, args.points, n_hess, ms_step) if args.full else None,
             "phases_ms": info["phases_ms"], "collectives": info["collectives"] if world > 1 else None,
             "final_loss": final_loss,
             "config3": config3,
             "config3_1gpu_1M": config3_1m,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if plan["cpu_baseline"]:
             out["cpu_baseline"] = cpu_baseline(args.hidden, args.layers, 123)
         print(json.dumps(out))
     if world > 1:

@@ -299,6 +299,30 @@ def make_g10():
     np.savez_compressed(os.path.join(HERE, "g10_meshudf.npz"), **out)
 
 
+def make_g13():
+    """MeshUDF marching cubes on the randomised fields of tests/test_meshudf.py: the reference's own extension (as in g10),
+    recorded as digests of its outputs (the meshes themselves would be megabytes), of the fields it ran on and of its tables."""
+    sys.path.insert(0, REPO)
+    from oracle import build_ref
+    ref = build_ref.load()
+    assert ref is not None, "needs the reference sources and Cython"
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_meshudf import digest, random_fields
+    from diffudf_amd import marching_cubes as mc
+    luts = mc.load_luts()                                   # the reference's table module, decoded as its wrapper does
+    inputs, outputs = [], []
+    for trial, udf, gg, sp in random_fields():
+        inputs.append(digest(udf, gg))
+        try:
+            v, f, nn, val = ref.udf_mc_lewiner(udf, gg, spacing=sp)
+            outputs.append(digest(f, v, val, nn))
+        except RuntimeError:
+            outputs.append("RuntimeError")
+        print(trial, udf.shape[0], outputs[-1][:16])
+    np.savez_compressed(os.path.join(HERE, "g13_meshudf_random.npz"), input_digests=np.array(inputs), output_digests=np.array(outputs),
+                        lut_digest=np.array(digest(*(luts[k] for k in mc.LUT_NAMES))))
+
+
 def make_g11():
     """G11 (round 4): the two constructor arguments no shipped config uses but the reference's model accepts.
       ww: SIREN(3, 1, hidden, w0=30, ww=15) — first SineLayer at w0, the others at ww (reference src/model.py:89-106): value,
@@ -558,5 +582,7 @@ if __name__ == "__main__":
         make_g11()
     elif sys.argv[1:] == ["g12"]:
         make_g12()
+    elif sys.argv[1:] == ["g13"]:
+        make_g13()
     else:
         main()

@@ -55,7 +55,7 @@ def test_bench_gpus_n_as_typed_on_one_gpu(gpus, points):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DUDF_BENCH_DRY_LAUNCH"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, BENCH, "--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-config3", "--points", str(points), "--share-device"], env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
+                        "--no-config3", "--points", str(points), "--share-device", "--full"], env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

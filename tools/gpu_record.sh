@@ -10,7 +10,7 @@ O=$R/gpurun_out
 mkdir -p $O
 export TMPDIR=/tmp
 rm -rf $O/pmc_core_* $O/pmc_core_512_*
-timeout 900 python bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout 900 python bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err
 echo "bench rc $?"; python tools/show_bench.py $O/${T}_bench.json | grep -E "value|config3|cpu"
 bash tools/prof_stats.sh $T | head -12
 python - <<'PY'
