@@ -50,6 +50,16 @@ SYMBOLS = {
                                        ctypes.c_size_t, _P]),
     "dudf_descend_rays": (ctypes.c_int, [_CFG, _P, _P, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                          ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "dudf_project_points": (ctypes.c_int, [_CFG, _P, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                           _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_pointcloud_append_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "dudf_pointcloud_append": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P,
+                                              ctypes.c_size_t, _P]),
+    "dudf_pointcloud_workspace_bytes": (ctypes.c_size_t, [_CFG, ctypes.c_int64]),
+    "dudf_pointcloud_read_proposals": (ctypes.c_int, [_CFG, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_pointcloud_round": (ctypes.c_int, [_CFG, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                             _P, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, _P, _P, ctypes.c_int64, _P,
+                                             ctypes.POINTER(ctypes.c_int64), _P, ctypes.c_size_t, _P]),
     "dudf_grid_fields": (ctypes.c_int, [_CFG, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.c_double, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "dudf_query": (ctypes.c_int, [_CFG, _P, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_size_t, _P]),
@@ -96,7 +106,7 @@ SYMBOLS = {
     "dudf_reset_options": (ctypes.c_int, []),
     "dudf_abi_version": (ctypes.c_int, []),
 }
-ABI_VERSION = 7          # DUDF_ABI_VERSION of include/dudf_hip.h this mirror was written against
+ABI_VERSION = 8          # DUDF_ABI_VERSION of include/dudf_hip.h this mirror was written against
 
 
 def load():

@@ -240,6 +240,19 @@ int dudf_launch_rays_step(const DudfLayout& lo, const float* ws, const double* r
                           int* active, hipStream_t st);
 int dudf_launch_rays_descend(const DudfLayout& lo, const float* ws, double* t0, const unsigned char* hits,
                              int inverse_mode, double alpha, double min_step, hipStream_t st);
+// dense point cloud (reference src/render_pc.py:26-73; dudf_pointcloud.hip): proposals (double rows + x4), one projection step
+// behind the sweeps (writes the next x4; the last one the accept flags), ordered compaction / append behind a device row
+// counter (scratch: 2 * dudf_pc_tiles(n) ints), normals from the frame query's eigenvectors
+int64_t dudf_pc_tiles(int64_t n);
+int dudf_launch_pc_propose(const DudfLayout& lo, const double* rand, int64_t rand_count, uint64_t seed, int64_t round, const double* surface,
+                           const int64_t* counter, int64_t quota, double* samples, double* proposals, float* ws, hipStream_t st);
+int dudf_launch_pc_step(const DudfLayout& lo, float* ws, double* samples, int inverse_mode, double alpha, double thresh,
+                        int last, double* out_step, double* out_unit, float* out_pre, unsigned char* out_accept,
+                        const int64_t* counter, int64_t quota, hipStream_t st);
+int dudf_launch_pc_append(const unsigned char* flags, int64_t n, const double* src_a, const double* src_b, const float* src_f,
+                          double* dst_a, double* dst_b, float* out_f, int64_t capacity, int64_t quota, int64_t* counter,
+                          int* scratch, hipStream_t st);
+int dudf_launch_pc_normals(const float* V, int64_t m, double* normals, hipStream_t st);
 // third-order jets: x4 of n points x one 16-column tile (value + the eigen-frame V as three directions), and the
 // epilogue that turns the jets' mixed third-order coefficients into curvature
 int dudf_launch_make_x4_jet(const float* x, const float* V, int64_t n, int64_t npj, float* x4j, hipStream_t st);

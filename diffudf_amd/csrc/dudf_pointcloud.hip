@@ -1,0 +1,244 @@
+// Dense point-cloud extraction on the device — the kernels around the value+gradient sweeps and the frame query that replace
+// the host loop of reference src/render_pc.py:26-73 (`Sampler.generate_point_cloud`): propose, project step, ordered
+// compaction / append, normals.  Sequencing: dudf_api.hip (dudf_project_points, dudf_pointcloud_append, dudf_pointcloud_round).
+//
+// The reference keeps the samples in float64 numpy, feeds float32 copies to the network (src/evaluate.py:18), forms the step
+// with `inverse` in float64 on the float32 value WITHOUT abs (:51) and moves in float64 (:53).  Same here, operation by
+// operation (no contraction: numpy rounds every product and sum).
+#include "dudf_internal.h"
+
+namespace {
+
+inline int grid_for(int64_t n, int block = 256, int cap = 2048) {
+    int64_t g = (n + block - 1) / block;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (int)g;
+}
+
+// counter-based random numbers: the splitmix64 construction of dudf_sample.hip, keyed by (seed, round, stream)
+__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ double uniform01(uint64_t key, uint64_t idx) {
+    uint64_t b = splitmix64(idx ^ key);
+    b = splitmix64(b + key);
+    return (double)(b >> 11) * (1.0 / 9007199254740992.0);
+}
+__device__ __forceinline__ double normal01(uint64_t key, uint64_t idx) {        // Box-Muller on two counters of one stream
+    const double u1 = 1.0 - uniform01(key, 2 * idx), u2 = uniform01(key, 2 * idx + 1);   // u1 in (0, 1]
+    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
+// ---- propose (reference :35-39): the float64 sample rows and the padded float32 x4 of the sweep in one pass ------------------
+//   held == 0 : n uniform rows;   held > 0 : n/2 rows surface[idx] + N(0, 0.1), then n/2 uniform rows (2*(n/2) rows in all: a
+//   last odd row is NaN and can never be accepted).  rand != nullptr: the host's numbers (layout: include/dudf_hip.h).
+__global__ __launch_bounds__(256) void pc_propose_kernel(const double* __restrict__ rand, int64_t rand_count, uint64_t key, int64_t n, int64_t np,
+                                                         const double* __restrict__ surface, const int64_t* __restrict__ counter,
+                                                         int64_t quota, double* __restrict__ samples, double* __restrict__ proposals,
+                                                         float* __restrict__ x4) {
+#pragma clang fp contract(off)
+    const int64_t held = counter[0];
+    if (held >= quota) return;
+    const int64_t half = n / 2;
+    const bool short_rand = rand && rand_count < (held ? 7 * half : 3 * n);     // never read past the host's buffer
+    const int64_t m = short_rand ? 0 : (held ? 2 * half : n);
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < np; p += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (p < n) {
+            double q[3];
+            if (p >= m) {
+                q[0] = q[1] = q[2] = __builtin_nan("");
+            } else if (held && p < half) {
+                int64_t idx = rand ? (int64_t)rand[p] : (int64_t)(uniform01(key, (uint64_t)p) * (double)held);
+                idx = idx < 0 ? 0 : (idx >= held ? held - 1 : idx);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const double z = rand ? rand[half + p * 3 + k] : 0.1 * normal01(key + 1 + k, (uint64_t)p);
+                    q[k] = surface[idx * 3 + k] + z;
+                }
+            } else {
+                const int64_t r = held ? p - half : p;
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    q[k] = rand ? rand[(held ? 4 * half : 0) + r * 3 + k] : uniform01(key + 4 + k, (uint64_t)p) * 2.0 - 1.0;
+            }
+            samples[p * 3] = q[0]; samples[p * 3 + 1] = q[1]; samples[p * 3 + 2] = q[2];
+            proposals[p * 3] = q[0]; proposals[p * 3 + 1] = q[1]; proposals[p * 3 + 2] = q[2];     // kept for dudf_pointcloud_read_proposals
+            if (p < m) v = f32x4{(float)q[0], (float)q[1], (float)q[2], 1.f};
+        }
+        *reinterpret_cast<f32x4*>(x4 + p * 4) = v;
+    }
+}
+
+// ---- one projection step (reference :50-53) behind the value+gradient sweeps; writes the NEXT step's x4 itself.  The last
+// step also leaves the step length, the pre-move unit gradient and float32 position, and the accept flag (:55-56).
+struct PcStepArgs {
+    const float* y; const float* g;       // sweep outputs: [np], [np][4]
+    double* samples; float* x4;
+    int64_t n;
+    int inverse_mode; double alpha, inv_alpha, sqrt_alpha, thresh;
+    int last;
+    double* out_step; double* out_unit; float* out_pre; unsigned char* out_accept;
+    const int64_t* counter; int64_t quota;     // round mode: nothing moves once the quota is reached
+};
+
+__global__ __launch_bounds__(256) void pc_step_kernel(PcStepArgs a) {
+#pragma clang fp contract(off)
+    if (a.counter && a.counter[0] >= a.quota) return;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < a.n; p += (int64_t)gridDim.x * blockDim.x) {
+        const double u = (double)a.y[p];
+        double step;
+        if (a.inverse_mode == 0) step = (u < a.inv_alpha) ? sqrt(u / a.alpha) : u;                 // 'tanh': NaN for u < 0
+        else if (a.inverse_mode == 1) step = (u > 0.0) ? u : 0.0;                                  // 'siren', min_step = 0
+        else step = ((u > 0.0) ? sqrt(u) : 0.0) / a.sqrt_alpha;                                    // 'squared'
+        const double gx = (double)a.g[p * 4], gy = (double)a.g[p * 4 + 1], gz = (double)a.g[p * 4 + 2];
+        const double nrm = sqrt(gx * gx + gy * gy + gz * gz);
+        const double ux = gx / nrm, uy = gy / nrm, uz = gz / nrm;
+        const double o0 = a.samples[p * 3], o1 = a.samples[p * 3 + 1], o2 = a.samples[p * 3 + 2];
+        const double q0 = o0 - step * ux, q1 = o1 - step * uy, q2 = o2 - step * uz;
+        a.samples[p * 3] = q0; a.samples[p * 3 + 1] = q1; a.samples[p * 3 + 2] = q2;
+        if (!a.last) {
+            *reinterpret_cast<f32x4*>(a.x4 + p * 4) = f32x4{(float)q0, (float)q1, (float)q2, 1.f};
+        } else {
+            if (a.out_step) a.out_step[p] = step;
+            if (a.out_unit) { a.out_unit[p * 3] = ux; a.out_unit[p * 3 + 1] = uy; a.out_unit[p * 3 + 2] = uz; }
+            if (a.out_pre) { a.out_pre[p * 3] = (float)o0; a.out_pre[p * 3 + 1] = (float)o1; a.out_pre[p * 3 + 2] = (float)o2; }
+            if (a.out_accept) {
+                const bool inside = q0 >= -1.0 && q0 <= 1.0 && q1 >= -1.0 && q1 <= 1.0 && q2 >= -1.0 && q2 <= 1.0;
+                a.out_accept[p] = (inside && step < a.thresh) ? 1 : 0;
+            }
+        }
+    }
+}
+
+// ---- ordered compaction + append (reference :58-65: samples[mask] / vstack) ----------------------------------------------------
+// Tiles of 256 rows (one workgroup pass = 4 waves of 64).  count: accepted rows per tile (wave ballot + popcount, summed over
+// the waves);  scan: one workgroup turns the counts into exclusive offsets and moves the row counter;  scatter: row -> base +
+// tile offset + waves before it + lanes before it.  Order of the rows is kept: later rounds index the buffer.
+constexpr int kTile = 256;
+
+__global__ __launch_bounds__(256) void pc_count_kernel(const unsigned char* __restrict__ flags, int64_t n, int64_t ntiles,
+                                                       int* __restrict__ tile_cnt) {
+    __shared__ int wcnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int64_t row = t * kTile + threadIdx.x;
+        const bool f = row < n && flags[row] != 0;
+        const unsigned long long b = __ballot(f);
+        if (lane == 0) wcnt[wave] = __popcll(b);
+        __syncthreads();
+        if (threadIdx.x == 0) tile_cnt[t] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+}
+
+// counter: [0] rows held, [1] rows this call adds, [2] rows held before it
+__global__ __launch_bounds__(256) void pc_scan_kernel(const int* __restrict__ tile_cnt, int* __restrict__ tile_off, int64_t ntiles,
+                                                      int64_t capacity, int64_t quota, int64_t* __restrict__ counter) {
+    __shared__ int64_t part[256];
+    const int64_t per = (ntiles + 255) / 256;
+    const int64_t t0 = (int64_t)threadIdx.x * per, t1 = (t0 + per < ntiles) ? t0 + per : ntiles;
+    int64_t s = 0;
+    for (int64_t t = t0; t < t1; ++t) s += tile_cnt[t];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t run = 0;
+        for (int i = 0; i < 256; ++i) { const int64_t c = part[i]; part[i] = run; run += c; }
+        const int64_t held = counter[0];
+        const bool ok = held < quota && held + run <= capacity;
+        counter[2] = held; counter[1] = ok ? run : 0; counter[0] = held + (ok ? run : 0);
+    }
+    __syncthreads();
+    int64_t run = part[threadIdx.x];
+    for (int64_t t = t0; t < t1; ++t) { tile_off[t] = (int)run; run += tile_cnt[t]; }
+}
+
+__global__ __launch_bounds__(256) void pc_scatter_kernel(const unsigned char* __restrict__ flags, int64_t n, int64_t ntiles,
+                                                         const int* __restrict__ tile_off, const int64_t* __restrict__ counter,
+                                                         const double* __restrict__ src_a, const double* __restrict__ src_b,
+                                                         const float* __restrict__ src_f, double* __restrict__ dst_a,
+                                                         double* __restrict__ dst_b, float* __restrict__ out_f) {
+    __shared__ int wcnt[4];
+    if (counter[1] == 0) return;                   // nothing accepted, quota reached or no room: nothing is written
+    const int64_t base = counter[2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int64_t row = t * kTile + threadIdx.x;
+        const bool f = row < n && flags[row] != 0;
+        const unsigned long long b = __ballot(f);
+        if (lane == 0) wcnt[wave] = __popcll(b);
+        __syncthreads();
+        int before = __popcll(b & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) before += wcnt[w];
+        if (f) {
+            const int64_t local = (int64_t)tile_off[t] + before, d = base + local;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                dst_a[d * 3 + k] = src_a[row * 3 + k];
+                if (dst_b) dst_b[d * 3 + k] = src_b[row * 3 + k];
+                if (out_f) out_f[local * 3 + k] = src_f[row * 3 + k];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- normals of the accepted rows from the frame query's eigenvectors: n = v_2 (reference :65, `eigh(...)[1][:, 2]`) ---------
+__global__ __launch_bounds__(256) void pc_normals_kernel(const float* __restrict__ V, int64_t m, double* __restrict__ normals) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += (int64_t)gridDim.x * blockDim.x) {
+        normals[p * 3] = (double)V[p * 9 + 2]; normals[p * 3 + 1] = (double)V[p * 9 + 5]; normals[p * 3 + 2] = (double)V[p * 9 + 8];
+    }
+}
+
+}  // namespace
+
+int64_t dudf_pc_tiles(int64_t n) { return (n + kTile - 1) / kTile; }
+
+int dudf_launch_pc_propose(const DudfLayout& lo, const double* rand, int64_t rand_count, uint64_t seed, int64_t round, const double* surface,
+                           const int64_t* counter, int64_t quota, double* samples, double* proposals, float* ws, hipStream_t st) {
+    DudfProfScope prof(PROF_OTHER, st);
+    const uint64_t key = splitmix64(splitmix64(seed) ^ (uint64_t)round * 0x100000001B3ull) & ~0xFull;   // streams key + 0 .. 6
+    hipLaunchKernelGGL(pc_propose_kernel, dim3(grid_for(lo.np)), dim3(256), 0, st, rand, rand_count, key, lo.n, lo.np, surface, counter,
+                       quota, samples, proposals, ws + lo.ws_x4);
+    return (int)hipGetLastError();
+}
+
+int dudf_launch_pc_step(const DudfLayout& lo, float* ws, double* samples, int inverse_mode, double alpha, double thresh,
+                        int last, double* out_step, double* out_unit, float* out_pre, unsigned char* out_accept,
+                        const int64_t* counter, int64_t quota, hipStream_t st) {
+    DudfProfScope prof(PROF_OTHER, st);
+    PcStepArgs a;
+    a.y = ws + lo.ws_y; a.g = ws + lo.ws_g; a.samples = samples; a.x4 = ws + lo.ws_x4; a.n = lo.n;
+    a.inverse_mode = inverse_mode; a.alpha = alpha; a.inv_alpha = 1.0 / alpha; a.sqrt_alpha = sqrt(alpha); a.thresh = thresh;
+    a.last = last; a.out_step = out_step; a.out_unit = out_unit; a.out_pre = out_pre; a.out_accept = out_accept;
+    a.counter = counter; a.quota = quota;
+    hipLaunchKernelGGL(pc_step_kernel, dim3(grid_for(lo.n)), dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+}
+
+// scratch: [tile counts | tile offsets], dudf_pc_tiles(n) ints each
+int dudf_launch_pc_append(const unsigned char* flags, int64_t n, const double* src_a, const double* src_b, const float* src_f,
+                          double* dst_a, double* dst_b, float* out_f, int64_t capacity, int64_t quota, int64_t* counter,
+                          int* scratch, hipStream_t st) {
+    DudfProfScope prof(PROF_OTHER, st);
+    const int64_t ntiles = dudf_pc_tiles(n);
+    int* tile_cnt = scratch; int* tile_off = scratch + ntiles;
+    if (!src_b) dst_b = nullptr;
+    if (!src_f) out_f = nullptr;
+    hipLaunchKernelGGL(pc_count_kernel, dim3(grid_for(n)), dim3(256), 0, st, flags, n, ntiles, tile_cnt);
+    hipLaunchKernelGGL(pc_scan_kernel, dim3(1), dim3(256), 0, st, tile_cnt, tile_off, ntiles, capacity, quota, counter);
+    hipLaunchKernelGGL(pc_scatter_kernel, dim3(grid_for(n)), dim3(256), 0, st, flags, n, ntiles, tile_off, counter, src_a, src_b,
+                       src_f, dst_a, dst_b, out_f);
+    return (int)hipGetLastError();
+}
+
+int dudf_launch_pc_normals(const float* V, int64_t m, double* normals, hipStream_t st) {
+    DudfProfScope prof(PROF_OTHER, st);
+    hipLaunchKernelGGL(pc_normals_kernel, dim3(grid_for(m)), dim3(256), 0, st, V, m, normals);
+    return (int)hipGetLastError();
+}

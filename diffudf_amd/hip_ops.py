@@ -300,6 +300,120 @@ def descend_rays(cfg, theta, t0, hits, gt_mode, alpha, gd_steps, min_step=0.01):
     _lib.check(rc, "dudf_descend_rays")
 
 
+def _f64_dev(t, what, cols=3):
+    if not torch.is_tensor(t) or t.device.type != "cuda":
+        raise _lib.DudfError(f"{what} must be a CUDA tensor (got {getattr(t, 'device', type(t).__name__)}); the HIP path has no CPU fallback")
+    if t.dtype != torch.float64 or not t.is_contiguous() or (cols and (t.dim() != 2 or t.shape[1] != cols)):
+        raise _lib.DudfError(f"{what} must be a contiguous float64 (n,{cols}) tensor; got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def project_points(cfg, theta, points, gt_mode, alpha, num_steps=5, surf_thresh=0.01):
+    """The inner loop of reference src/render_pc.py:43-56 on the device: `points` (n,3) float64 CUDA tensor, moved in place by
+    `num_steps` projection steps.  Returns (last_step (n,) float64, unit_grad (n,3) float64 = normalize(grad) before the last move,
+    pre_pos (n,3) float32 = the position the network saw at the last step, accept (n,) uint8 = in the closed domain after the
+    move and last step < surf_thresh)."""
+    lib = _lib.load()
+    theta = _theta(cfg, theta)
+    points = _f64_dev(points, "project_points: points")
+    n, dev = points.shape[0], points.device
+    last = torch.empty(n, dtype=torch.float64, device=dev); unit = torch.empty(n, 3, dtype=torch.float64, device=dev)
+    pre = torch.empty(n, 3, dtype=torch.float32, device=dev); acc = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = query_workspace_for(cfg, n, dev)
+    with torch.cuda.device(dev):
+        rc = lib.dudf_project_points(ctypes.byref(cfg), _ptr(theta), _ptr(points), n, int(num_steps), INVERSE_MODES[gt_mode],
+                                     float(alpha), float(surf_thresh), _ptr(last), _ptr(unit), _ptr(pre), _ptr(acc), _ptr(ws.buf),
+                                     ws.nbytes, _stream())
+    _lib.check(rc, "dudf_project_points")
+    return last, unit, pre, acc
+
+
+def pointcloud_append(flags, src_a, dst_a, counter, src_b=None, dst_b=None, src_f=None, out_f=None, quota=None):
+    """`dst = np.vstack((dst, src[flags]))` on the device (reference src/render_pc.py:58-65): the flagged rows of src_a (and
+    src_b) (n,3) float64 go, in their order, behind row counter[0] of dst_a (dst_b); the flagged rows of src_f (n,3) float32 to
+    out_f from row 0.  counter: int64 CUDA tensor of 4 — [0] rows held (advanced), [1] rows added by this call, [2] rows held
+    before it.  Nothing is added once counter[0] >= quota (default: never) or when the rows would not fit into dst_a."""
+    lib = _lib.load()
+    if flags.dtype != torch.uint8 or not flags.is_cuda or not flags.is_contiguous():
+        raise _lib.DudfError("pointcloud_append: flags must be a contiguous uint8 CUDA tensor")
+    n, dev = flags.shape[0], flags.device
+    src_a = _f64_dev(src_a, "pointcloud_append: src_a"); dst_a = _f64_dev(dst_a, "pointcloud_append: dst_a")
+    if (src_b is None) != (dst_b is None) or (src_f is None) != (out_f is None):
+        raise _lib.DudfError("pointcloud_append: src_b / dst_b and src_f / out_f come in pairs")
+    if src_b is not None:
+        src_b = _f64_dev(src_b, "pointcloud_append: src_b"); dst_b = _f64_dev(dst_b, "pointcloud_append: dst_b")
+    if src_f is not None and (src_f.dtype != torch.float32 or out_f.dtype != torch.float32 or not src_f.is_contiguous()
+                              or not out_f.is_contiguous() or out_f.shape[0] < n or not src_f.is_cuda or not out_f.is_cuda):
+        raise _lib.DudfError("pointcloud_append: src_f / out_f must be contiguous float32 (n,3) CUDA tensors")
+    if counter.dtype != torch.int64 or counter.numel() != 4 or not counter.is_cuda:
+        raise _lib.DudfError("pointcloud_append: counter must be an int64 CUDA tensor of 4")
+    if src_a.shape[0] != n or (src_b is not None and (src_b.shape[0] != n or dst_b.shape[0] != dst_a.shape[0])) or \
+            (src_f is not None and src_f.shape[0] != n):
+        raise _lib.DudfError("pointcloud_append: row counts of flags and sources differ")
+    nbytes = int(lib.dudf_pointcloud_append_workspace_bytes(n))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.dudf_pointcloud_append(_ptr(flags), n, _ptr(src_a), _ptr(src_b), _ptr(src_f), _ptr(dst_a), _ptr(dst_b), _ptr(out_f),
+                                        dst_a.shape[0], (1 << 62) if quota is None else int(quota), _ptr(counter), _ptr(ws), nbytes,
+                                        _stream())
+    _lib.check(rc, "dudf_pointcloud_append")
+
+
+class PointCloudState:
+    """Caller-owned state of `pointcloud_round`: surface points and normals (2 * num_points rows, float64), the device row
+    counter and the round workspace."""
+
+    def __init__(self, cfg, num_points, device):
+        lib = _lib.load()
+        self.cfg, self.num_points = cfg, int(num_points)
+        self.capacity = max(2 * self.num_points, 1)
+        self.points = torch.zeros(self.capacity, 3, dtype=torch.float64, device=device)
+        self.normals = torch.zeros(self.capacity, 3, dtype=torch.float64, device=device)
+        self.counter = torch.zeros(4, dtype=torch.int64, device=device)
+        self.nbytes = int(lib.dudf_pointcloud_workspace_bytes(ctypes.byref(cfg), self.num_points))
+        if self.nbytes == 0:
+            _lib.check(-1, "dudf_pointcloud_workspace_bytes")
+        self.buf = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
+        self.rounds = 0
+
+    def count(self):
+        return int(self.counter[0].item())
+
+    def proposals(self):
+        """(num_points,3) float64: the rows the last round proposed, before any move (diagnostic; reference :36-39)."""
+        out = torch.empty(self.num_points, 3, dtype=torch.float64, device=self.points.device)
+        with torch.cuda.device(self.points.device):
+            rc = _lib.load().dudf_pointcloud_read_proposals(ctypes.byref(self.cfg), self.num_points, _ptr(out), _ptr(self.buf),
+                                                            self.nbytes, _stream())
+        _lib.check(rc, "dudf_pointcloud_read_proposals")
+        return out
+
+
+def pointcloud_round(cfg, theta, state, gt_mode, alpha, num_steps=5, surf_thresh=0.01, rand=None, seed=0, want_count=True):
+    """One round of reference src/render_pc.py:33-68 on `state` (propose -> project -> ordered append -> normals).  rand: float64
+    CUDA tensor with the host-drawn numbers of this round (layout: include/dudf_hip.h) or None for the in-kernel generator keyed by
+    (seed, round).  Returns the host copy of the counter [rows held, rows added, rows held before] or None (want_count=False)."""
+    lib = _lib.load()
+    theta = _theta(cfg, theta)
+    if rand is not None:
+        if rand.dtype != torch.float64 or not rand.is_cuda or not rand.is_contiguous():
+            raise _lib.DudfError("pointcloud_round: rand must be a contiguous float64 CUDA tensor")
+        half = state.num_points // 2
+        if rand.numel() not in (3 * state.num_points, 7 * half):
+            raise _lib.DudfError(f"pointcloud_round: rand has {rand.numel()} numbers; a round of {state.num_points} points takes "
+                                 f"{3 * state.num_points} (first form) or {7 * half}")
+    hc = (ctypes.c_int64 * 4)() if want_count else None
+    with torch.cuda.device(state.points.device):
+        rc = lib.dudf_pointcloud_round(ctypes.byref(cfg), _ptr(theta), state.num_points, int(num_steps), INVERSE_MODES[gt_mode],
+                                       float(alpha), float(surf_thresh), _ptr(rand), 0 if rand is None else rand.numel(), int(seed) & ((1 << 64) - 1),
+                                       state.rounds,
+                                       _ptr(state.points), _ptr(state.normals), state.capacity, _ptr(state.counter), hc,
+                                       _ptr(state.buf), state.nbytes, _stream())
+    _lib.check(rc, "dudf_pointcloud_round")
+    state.rounds += 1
+    return list(hc)[:3] if want_count else None
+
+
 def grid_fields(cfg, theta, grid_n, start, count, gt_mode, alpha, out_df, out_vec, ws=None):
     """Fills out_df[start:start+count], out_vec[start:start+count] (device tensors over the flattened N^3 grid);
     returns the device int32 counter of points that need the Hessian-eigenvector fallback."""

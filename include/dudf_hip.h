@@ -27,8 +27,8 @@ extern "C" {
 
 /* ABI number of this header; dudf_abi_version() returns the one the library was built with.  A caller built against another
  * header must not call the library: dudf_net_cfg grew by `ww` in ABI 5, dudf_stash_mode took (n, n_hess) and the options arrived in
- * ABI 6.  The Python mirror checks it when it loads the library (diffudf_amd/_lib.py). */
-#define DUDF_ABI_VERSION 7
+ * ABI 6, the point-cloud calls (dudf_project_points .. dudf_pointcloud_round) in ABI 8.  The Python mirror checks it when it loads the library (diffudf_amd/_lib.py). */
+#define DUDF_ABI_VERSION 8
 int dudf_abi_version(void);
 
 #define DUDF_E_BADCFG   (-1)   /* unsupported network shape: `hidden` must be one of {32,64,128,256,512} (the Python mirror pads any
@@ -114,6 +114,61 @@ int dudf_trace_rays(const dudf_net_cfg* cfg, const float* theta, const double* r
 int dudf_descend_rays(const dudf_net_cfg* cfg, const float* theta, double* t0, const unsigned char* hits, int64_t m,
                       int inverse_mode, double alpha, double min_step, int gd_steps, void* workspace,
                       size_t workspace_bytes, void* stream);
+
+/* Dense oriented point cloud — replaces `Sampler.generate_point_cloud` (reference src/render_pc.py:26-73).
+ *
+ * dudf_project_points: the deterministic inner loop (:43-56) for n float64 points, in place: num_steps (>= 1) times
+ *   udf, grad = evaluate(float32 copy of the points)                         (:46-50, src/evaluate.py:18)
+ *   step = inverse(gt_mode, udf, alpha, min_step = 0)  — NO abs, in float64 on the float32 value (:51, src/inverses.py:3-21);
+ *          'tanh' with udf < 0 gives NaN, which propagates into the point and fails the domain test, as it does there
+ *   points -= step * normalize(grad)                                         (:53, src/util.py:34-39), float64
+ * and after the last step  accept = all(-1 <= moved point <= 1) and last step < surf_thresh  (:55-56).
+ * out_last_step (n) double; out_unit_grad (n,3) double = normalize(grad) at the position BEFORE the last move (the normal of
+ * gt_mode 'siren', :63); out_pre_pos (n,3) float = that position as the network saw it (where the reference's Hessian of :46 was
+ * evaluated); out_accept (n) 0/1 bytes.  Any output may be NULL.  inverse_mode 0 'tanh' / 1 'siren' / 2 'squared'.
+ * workspace: dudf_workspace_bytes_query(cfg, n, 0). */
+int dudf_project_points(const dudf_net_cfg* cfg, const float* theta, double* points, int64_t n, int num_steps,
+                        int inverse_mode, double alpha, double surf_thresh, double* out_last_step, double* out_unit_grad,
+                        float* out_pre_pos, unsigned char* out_accept, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Ordered append — replaces `surface_points = np.vstack((surface_points, samples[mask]))` and the same for the normals
+ * (reference src/render_pc.py:58-65): the rows of src_a (n,3) double, src_b (n,3) double and src_f (n,3) float whose flag is
+ * non-zero are appended IN THEIR ORDER (stable compaction: wave ballots, per-workgroup counts, a scan, a scatter) to dst_a / dst_b
+ * (capacity rows) behind the device row counter, and to out_f from its row 0.  counter (device, 4 x int64): [0] rows held
+ * (in/out), [1] rows this call added, [2] rows held before it, [3] unused.  A call that finds counter[0] >= quota, or whose rows
+ * would not fit into `capacity`, adds nothing ([1] = 0).  Any of src_b / dst_b, src_f / out_f may be NULL; n = 0 launches nothing
+ * (and leaves the counter alone).  workspace: dudf_pointcloud_append_workspace_bytes(n), 256-byte aligned. */
+size_t dudf_pointcloud_append_workspace_bytes(int64_t n);
+int dudf_pointcloud_append(const unsigned char* flags, int64_t n, const double* src_a, const double* src_b, const float* src_f,
+                           double* dst_a, double* dst_b, float* out_f, int64_t capacity, int64_t quota, int64_t* counter,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* One round of the reference's outer loop (src/render_pc.py:33-68) on a caller-owned state: surface_points, normals
+ * (capacity >= 2 * num_points rows of 3 doubles; a round adds at most num_points) and counter (device, 4 x int64 as above, zeroed
+ * by the caller before the first round).
+ *   propose : counter[0] == 0: num_points uniform rows in [-1,1]^3 (:39); otherwise num_points/2 rows gathered from ALL surface
+ *             rows held, index = uniform(0, rows) truncated, plus N(0, 0.1) noise, then num_points/2 uniform rows (:36-37).
+ *             rand != NULL (device, float64): the numbers the host drew in the reference's call order — (num_points,3) uniforms
+ *             in the first form; [num_points/2 indices (already truncated, as doubles) | (num_points/2,3) noise |
+ *             (num_points/2,3) uniforms] in the second; rand_count = how many doubles it holds (a buffer too short for the form
+ *             the counter selects proposes nothing: every row of that round is NaN and rejected).  rand == NULL: a counter-based generator in the kernel, a pure function
+ *             of (seed, round, row).
+ *   project : dudf_project_points on those rows;  append: dudf_pointcloud_append with quota = num_points;
+ *   normals : normalize(grad) for inverse_mode 1 ('siren', :63), otherwise the eigenvector of the largest Hessian eigenvalue at
+ *             the pre-move position (:65) — dudf_query_frame's v_2, for the ACCEPTED rows only, in chunks.
+ * A round issued when counter[0] >= num_points changes nothing.  host_counter (host, 4 x int64) or NULL: the counter after the
+ * round.  The Hessian path needs the accepted count on the host to size its sweeps, so the call synchronises the stream once
+ * unless inverse_mode == 1 and host_counter == NULL (then it only enqueues).  num_points = 0 is valid and launches nothing.
+ * workspace: dudf_pointcloud_workspace_bytes(cfg, num_points); 0 for a refused cfg. */
+size_t dudf_pointcloud_workspace_bytes(const dudf_net_cfg* cfg, int64_t num_points);
+int dudf_pointcloud_round(const dudf_net_cfg* cfg, const float* theta, int64_t num_points, int num_steps, int inverse_mode,
+                          double alpha, double surf_thresh, const double* rand, int64_t rand_count, uint64_t seed, int64_t round,
+                          double* surface_points, double* normals, int64_t capacity, int64_t* counter, int64_t* host_counter,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* Test/diagnostic hook: the rows the last round on this workspace PROPOSED (reference src/render_pc.py:36-39, before any move),
+ * out (num_points,3) double. */
+int dudf_pointcloud_read_proposals(const dudf_net_cfg* cfg, int64_t num_points, double* out, void* workspace,
+                                   size_t workspace_bytes, void* stream);
 
 /* The field part of `extract_fields` (reference src/render_mc.py:20-99) for grid points start .. start+count-1 of the
  * regular grid_n^3 grid on [-1,1]^3 (linear index, first axis slowest, coordinates derived from the index):
