@@ -60,6 +60,14 @@ SYMBOLS = {
     "dudf_pointcloud_round": (ctypes.c_int, [_CFG, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                              _P, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, _P, _P, ctypes.c_int64, _P,
                                              ctypes.POINTER(ctypes.c_int64), _P, ctypes.c_size_t, _P]),
+    "dudf_render_setup_rays": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _DBL, _DBL, _DBL,
+                                              _P, _P, _P, _P]),
+    "dudf_render_gather": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_render_orient": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, _P, _P, _P, _P, _P]),
+    "dudf_render_colormap": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, _P]),
+    "dudf_render_shade": (ctypes.c_int, [ctypes.c_int, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, _P, _DBL, _DBL,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "dudf_render_finish": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_double, _P, _P]),
     "dudf_grid_fields": (ctypes.c_int, [_CFG, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.c_double, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "dudf_query": (ctypes.c_int, [_CFG, _P, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_size_t, _P]),
@@ -127,7 +135,11 @@ def load():
         raise DudfError(f"{LIB_PATH} has ABI {abi}, this package binds ABI {ABI_VERSION}: rebuild it "
                         "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)          # AttributeError if the .so does not export it
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:           # calls added without an ABI bump (dudf_render_*: no existing signature changed)
+            raise DudfError(f"{LIB_PATH} does not export {name}: it is older than this package; rebuild it "
+                            "(`python -c 'import __graft_entry__ as g; g.build()'`)") from None
         fn.restype = res
         fn.argtypes = args
     _lib = lib

@@ -591,6 +591,63 @@ int dudf_pointcloud_round(const dudf_net_cfg* cfg, const float* theta, int64_t n
     return 0;
 }
 
+// ---- sphere-traced images: the entry points around dudf_trace_rays / dudf_descend_rays and the frame / curvature queries -------
+int dudf_render_setup_rays(int64_t width, int64_t height, double fov, double noise, const double* rotation, const double* camera_position,
+                           const double* planes, double* rays, double* t0, unsigned char* mask, void* stream) {
+    if (width < 1 || height < 1 || width * height > (1ll << 30) || !rotation || !camera_position || !planes) return DUDF_E_BADCFG;
+    if (!rays || !t0 || !mask) return DUDF_E_BADCFG;
+    return dudf_launch_render_setup(width, height, fov, noise, rotation, camera_position, planes, rays, t0, mask,
+                                    reinterpret_cast<hipStream_t>(stream));
+}
+
+int dudf_render_gather(const unsigned char* hits, int64_t m, const double* t0, const double* rays, double* out_pos, double* out_rays,
+                       int32_t* out_rows, int64_t* counter, void* workspace, size_t workspace_bytes, void* stream) {
+    if (m < 0 || m > (1ll << 30) || !counter) return DUDF_E_BADCFG;
+    if (!workspace || workspace_bytes < dudf_pointcloud_append_workspace_bytes(m) || (reinterpret_cast<uintptr_t>(workspace) & 255))
+        return DUDF_E_WORKSPACE;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(counter, 0, 4 * sizeof(int64_t), st);
+    if (e != hipSuccess) return (int)e;
+    if (m == 0) return 0;
+    if (!hits || !t0 || !out_pos || !out_rows || (rays && !out_rays)) return DUDF_E_BADCFG;
+    int rc = dudf_launch_pc_append(hits, m, t0, rays, nullptr, out_pos, rays ? out_rays : nullptr, nullptr, m, (int64_t)1 << 62, counter,
+                                   reinterpret_cast<int*>(workspace), st);
+    if (rc) return rc;
+    return dudf_launch_render_rows(hits, m, counter, reinterpret_cast<const int*>(workspace), out_rows, st);
+}
+
+int dudf_render_orient(const float* frame_v, const float* grad, const double* hit_rays, int64_t k, double* out_normals,
+                       double* out_pc1, double* out_pc2, float* mean, void* stream) {
+    if (k < 0 || (frame_v != nullptr) == (grad != nullptr) || !out_normals || (frame_v && !hit_rays)) return DUDF_E_BADCFG;
+    if (k == 0) return 0;
+    return dudf_launch_render_orient(frame_v, grad, hit_rays, k, out_normals, out_pc1, out_pc2, grad ? nullptr : mean,
+                                     reinterpret_cast<hipStream_t>(stream));
+}
+
+int dudf_render_colormap(const float* curvatures, int64_t k, const float* bounds, const double* lut, double* out_colors, void* stream) {
+    if (k < 0 || !bounds || !lut || (k > 0 && (!curvatures || !out_colors))) return DUDF_E_BADCFG;
+    if (k == 0) return 0;
+    return dudf_launch_render_colormap(curvatures, k, bounds, lut, out_colors, reinterpret_cast<hipStream_t>(stream));
+}
+
+int dudf_render_shade(int model, const unsigned char* hits, int64_t m, const int32_t* rows, int64_t k, const double* hit_pos,
+                      const double* normals, const double* pc1, const double* pc2, const double* color_map, const double* light_position,
+                      const double* camera_position, double shininess, double alpha1, double alpha2, double* accumulator, void* stream) {
+    if (model != DUDF_SHADE_PHONG && model != DUDF_SHADE_WARD) return DUDF_E_BADMODE;
+    if (m < 0 || k < 0 || k > m || !light_position || !accumulator || (m > 0 && !hits)) return DUDF_E_BADCFG;
+    if (k > 0 && (!rows || !hit_pos || !normals)) return DUDF_E_BADCFG;
+    if (model == DUDF_SHADE_WARD && (!camera_position || (k > 0 && (!pc1 || !pc2)))) return DUDF_E_BADCFG;
+    if (m == 0) return 0;
+    return dudf_launch_render_shade(model, hits, m, rows, k, hit_pos, normals, pc1, pc2, color_map, light_position, camera_position,
+                                    shininess, alpha1, alpha2, accumulator, reinterpret_cast<hipStream_t>(stream));
+}
+
+int dudf_render_finish(const double* accumulator, int64_t count, double sample_rate, unsigned char* out_image, void* stream) {
+    if (count < 0 || !(sample_rate > 0.0) || (count > 0 && (!accumulator || !out_image))) return DUDF_E_BADCFG;
+    if (count == 0) return 0;
+    return dudf_launch_render_finish(accumulator, count, sample_rate, out_image, reinterpret_cast<hipStream_t>(stream));
+}
+
 int dudf_grid_fields(const dudf_net_cfg* cfg, const float* theta, int64_t grid_n, int64_t start, int64_t count,
                      int inverse_mode, double alpha, float* out_df, float* out_vec, int* out_flag_count,
                      void* workspace, size_t workspace_bytes, void* stream) {

@@ -253,6 +253,18 @@ int dudf_launch_pc_append(const unsigned char* flags, int64_t n, const double* s
                           double* dst_a, double* dst_b, float* out_f, int64_t capacity, int64_t quota, int64_t* counter,
                           int* scratch, hipStream_t st);
 int dudf_launch_pc_normals(const float* V, int64_t m, double* normals, hipStream_t st);
+// sphere-traced images (dudf_render.hip): camera rays, the image row of every gathered hit (from the tile offsets
+// dudf_launch_pc_append left in `scratch`), normals, colour map, reflection models + scatter, 8-bit image
+int dudf_launch_render_setup(int64_t width, int64_t height, double fov, double noise, const double* R, const double* cam,
+                             const double* planes, double* rays, double* t0, unsigned char* mask, hipStream_t st);
+int dudf_launch_render_rows(const unsigned char* flags, int64_t n, const int64_t* counter, const int* scratch, int* rows, hipStream_t st);
+int dudf_launch_render_orient(const float* frame, const float* grad, const double* rays, int64_t k, double* normals, double* pc1,
+                              double* pc2, float* mean, hipStream_t st);
+int dudf_launch_render_colormap(const float* curv, int64_t k, const float* bounds, const double* lut, double* out, hipStream_t st);
+int dudf_launch_render_shade(int model, const unsigned char* hits, int64_t m, const int* rows, int64_t k, const double* pos,
+                             const double* normals, const double* pc1, const double* pc2, const double* cmap, const double* light,
+                             const double* camera, double shininess, double alpha1, double alpha2, double* acc, hipStream_t st);
+int dudf_launch_render_finish(const double* acc, int64_t count, double sample_rate, unsigned char* out, hipStream_t st);
 // third-order jets: x4 of n points x one 16-column tile (value + the eigen-frame V as three directions), and the
 // epilogue that turns the jets' mixed third-order coefficients into curvature
 int dudf_launch_make_x4_jet(const float* x, const float* V, int64_t n, int64_t npj, float* x4j, hipStream_t st);

@@ -606,3 +606,229 @@ def read_stash(cfg, which, layer, n, ws, channel=0):
                                    ws.nbytes, _stream())
     _lib.check(rc, "dudf_debug_read_stash")
     return out
+
+
+# ---- sphere-traced images (reference generate_st.py, src/render_st.py:67-245) ---------------------------------------------------
+SHADE_MODELS = {"blinn-phong": 0, "ward": 1}
+
+
+def _dbl(values, n, what):
+    vals = [float(v) for v in values]
+    if len(vals) != n:
+        raise _lib.DudfError(f"{what} takes {n} numbers; got {len(vals)}")
+    return (ctypes.c_double * n)(*vals)
+
+
+def render_setup_rays(width, height, fov, noise, rotation, camera_position, planes, device):
+    """`dudf_render_setup_rays`: rays (m,3), t0 (m,3) float64 and mask (m,) uint8 on `device` for the width * height pixels of
+    `get_pixels_camera(width, height, fov, noise)` — reference generate_st.py:41-101.  rotation: the 3x3 of :49-61 (host)."""
+    lib = _lib.load()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.DudfError(f"render_setup_rays: device must be a GPU (got {dev}); the HIP path has no CPU fallback")
+    m = int(width) * int(height)
+    rays = torch.empty(m, 3, dtype=torch.float64, device=dev); t0 = torch.empty(m, 3, dtype=torch.float64, device=dev)
+    mask = torch.empty(m, dtype=torch.uint8, device=dev)
+    rot = _dbl([v for row in rotation for v in row], 9, "rotation")
+    with torch.cuda.device(dev):
+        rc = lib.dudf_render_setup_rays(int(width), int(height), float(fov), float(noise), rot, _dbl(camera_position, 3, "camera_position"),
+                                        _dbl(planes, 6, "planes"), _ptr(rays), _ptr(t0), _ptr(mask), _stream())
+    _lib.check(rc, "dudf_render_setup_rays")
+    return rays, t0, mask
+
+
+def _u8_dev(t, what):
+    if not torch.is_tensor(t) or t.device.type != "cuda":
+        raise _lib.DudfError(f"{what} must be a CUDA tensor (got {getattr(t, 'device', type(t).__name__)}); the HIP path has no CPU fallback")
+    if t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 1:
+        raise _lib.DudfError(f"{what} must be a contiguous uint8 vector; got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def render_gather(hits, t0, rays=None):
+    """`t0[hits]`, `rays[hits]` and the ray index of every gathered row (`dudf_render_gather`).  Returns (pos (k,3), rays (k,3) or
+    None, rows (k,) int32, k); k is the ONE host read of a pass."""
+    lib = _lib.load()
+    hits = _u8_dev(hits, "render_gather: hits")
+    t0 = _f64_dev(t0, "render_gather: t0")
+    m, dev = hits.shape[0], hits.device
+    if rays is not None:
+        rays = _f64_dev(rays, "render_gather: rays")
+    if t0.shape[0] != m or (rays is not None and rays.shape[0] != m):
+        raise _lib.DudfError("render_gather: row counts of hits, t0 and rays differ")
+    pos = torch.empty(m, 3, dtype=torch.float64, device=dev)
+    hr = torch.empty(m, 3, dtype=torch.float64, device=dev) if rays is not None else None
+    rows = torch.empty(m, dtype=torch.int32, device=dev)
+    counter = torch.empty(4, dtype=torch.int64, device=dev)
+    nbytes = int(lib.dudf_pointcloud_append_workspace_bytes(m))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.dudf_render_gather(_ptr(hits), m, _ptr(t0), _ptr(rays), _ptr(pos), _ptr(hr), _ptr(rows), _ptr(counter), _ptr(ws), nbytes,
+                                    _stream())
+    _lib.check(rc, "dudf_render_gather")
+    k = int(counter[1].item())
+    return pos[:k], (hr[:k] if hr is not None else None), rows[:k], k
+
+
+def render_orient(hit_rays, frame_v=None, grad=None, mean=None, want_pc=False):
+    """Normals of k hits (`dudf_render_orient`, reference src/render_st.py:80-83, :101-108): from the eigen-frame `frame_v` (k,3,3),
+    oriented against the rays (`mean` (k,) float32 is multiplied in place by the same alignment), or from `grad` (k,3) ('siren').
+    Returns (normals (k,3) float64, pc1, pc2 (k,3) float64 or None)."""
+    lib = _lib.load()
+    src = frame_v if frame_v is not None else grad
+    if src is None or (frame_v is not None and grad is not None):
+        raise _lib.DudfError("render_orient: exactly one of frame_v / grad")
+    src = _f32(src, "render_orient: frame_v / grad")
+    k, dev = src.shape[0], src.device
+    if frame_v is not None:
+        hit_rays = _f64_dev(hit_rays, "render_orient: hit_rays")
+        if tuple(src.shape) != (k, 3, 3) or hit_rays.shape[0] != k:
+            raise _lib.DudfError(f"render_orient: frame_v must be (k,3,3) with k rays; got {tuple(src.shape)}, {tuple(hit_rays.shape)}")
+        if mean is not None and (mean.dtype != torch.float32 or not mean.is_cuda or not mean.is_contiguous() or mean.numel() != k):
+            raise _lib.DudfError("render_orient: mean must be a contiguous float32 CUDA vector of k")
+    elif tuple(src.shape) != (k, 3):
+        raise _lib.DudfError(f"render_orient: grad must be (k,3); got {tuple(src.shape)}")
+    normals = torch.empty(k, 3, dtype=torch.float64, device=dev)
+    pc1 = torch.empty(k, 3, dtype=torch.float64, device=dev) if want_pc and frame_v is not None else None
+    pc2 = torch.empty(k, 3, dtype=torch.float64, device=dev) if want_pc and frame_v is not None else None
+    with torch.cuda.device(dev):
+        rc = lib.dudf_render_orient(_ptr(src) if frame_v is not None else None, _ptr(src) if frame_v is None else None,
+                                    _ptr(hit_rays) if frame_v is not None else None, k, _ptr(normals), _ptr(pc1), _ptr(pc2),
+                                    _ptr(mean) if frame_v is not None else None, _stream())
+    _lib.check(rc, "dudf_render_orient")
+    return normals, pc1, pc2
+
+
+def render_percentile_bounds(curvatures, q_low, q_high):
+    """(2,) float32 on the device: `np.percentile(curvatures, q)` for the two q of reference src/render_st.py:111, numpy's default
+    linear interpolation between the two order statistics (its _lerp: float32 difference, float64 weight, rounded to float32 once).
+    torch.sort is the plumbing; nothing goes to the host."""
+    k = curvatures.numel()
+    s = torch.sort(curvatures.reshape(-1)).values
+    out = []
+    for q in (q_low, q_high):
+        virtual = (k - 1) * (float(q) / 100.0)
+        lo = min(max(int(virtual // 1), 0), k - 1)
+        hi = min(lo + 1, k - 1)
+        t = virtual - lo
+        a, b = s[lo], s[hi]
+        diff = (b - a).double()
+        out.append((a.double() + diff * t if t < 0.5 else b.double() - diff * (1 - t)).float())
+    return torch.stack(out)
+
+
+def render_colormap(curvatures, bounds, lut):
+    """(k,3) float64 colours of k float32 curvatures (`dudf_render_colormap`, reference src/render_st.py:111-114)."""
+    lib = _lib.load()
+    curvatures = _f32(curvatures, "render_colormap: curvatures").reshape(-1)
+    bounds = _f32(bounds, "render_colormap: bounds")
+    lut = _f64_dev(lut, "render_colormap: lut")
+    if tuple(lut.shape) != (256, 3) or bounds.numel() != 2:
+        raise _lib.DudfError(f"render_colormap: lut must be (256,3) and bounds 2 floats; got {tuple(lut.shape)}, {bounds.numel()}")
+    k = curvatures.shape[0]
+    out = torch.empty(k, 3, dtype=torch.float64, device=curvatures.device)
+    with torch.cuda.device(curvatures.device):
+        rc = lib.dudf_render_colormap(_ptr(curvatures), k, _ptr(bounds), _ptr(lut), _ptr(out), _stream())
+    _lib.check(rc, "dudf_render_colormap")
+    return out
+
+
+def render_shade(model, hits, rows, hit_pos, normals, accumulator, light_position, camera_position=None, shininess=0.0, alpha1=0.0,
+                 alpha2=0.0, pc1=None, pc2=None, color_map=None):
+    """`dudf_render_shade`: accumulator (m,3) float64 += phong / ward colours of the k hits at their image rows, += 1 elsewhere
+    (reference src/render_st.py:174-245)."""
+    lib = _lib.load()
+    if model not in SHADE_MODELS:
+        raise _lib.DudfError(f"reflection_method must be one of {sorted(SHADE_MODELS)}; got {model!r}")
+    hits = _u8_dev(hits, "render_shade: hits")
+    accumulator = _f64_dev(accumulator, "render_shade: accumulator")
+    m, k = hits.shape[0], rows.shape[0]
+    if accumulator.shape[0] != m:
+        raise _lib.DudfError("render_shade: accumulator must have one row per ray")
+    if rows.dtype != torch.int32 or not rows.is_cuda or not rows.is_contiguous():
+        raise _lib.DudfError("render_shade: rows must be a contiguous int32 CUDA vector")
+    arrs = [("hit_pos", hit_pos), ("normals", normals)]
+    if model == "ward":
+        if pc1 is None or pc2 is None or camera_position is None:
+            raise _lib.DudfError("render_shade: ward takes pc1, pc2 and the camera position")
+        arrs += [("pc1", pc1), ("pc2", pc2)]
+    if color_map is not None:
+        arrs.append(("color_map", color_map))
+    for name, t in arrs:
+        if _f64_dev(t, f"render_shade: {name}").shape[0] != k:
+            raise _lib.DudfError(f"render_shade: {name} has {t.shape[0]} rows for {k} hits")
+    with torch.cuda.device(hits.device):
+        rc = lib.dudf_render_shade(SHADE_MODELS[model], _ptr(hits), m, _ptr(rows), k, _ptr(hit_pos), _ptr(normals), _ptr(pc1), _ptr(pc2),
+                                   _ptr(color_map), _dbl(light_position, 3, "light_position"),
+                                   _dbl(camera_position, 3, "camera_position") if camera_position is not None else None,
+                                   float(shininess), float(alpha1), float(alpha2), _ptr(accumulator), _stream())
+    _lib.check(rc, "dudf_render_shade")
+
+
+def render_finish(accumulator, sample_rate):
+    """uint8 tensor of accumulator's shape: `(colores / sample_rate * 255).astype(np.uint8)` (reference generate_st.py:139)."""
+    lib = _lib.load()
+    if not torch.is_tensor(accumulator) or not accumulator.is_cuda or accumulator.dtype != torch.float64 or not accumulator.is_contiguous():
+        raise _lib.DudfError("render_finish: accumulator must be a contiguous float64 CUDA tensor")
+    out = torch.empty(accumulator.shape, dtype=torch.uint8, device=accumulator.device)
+    with torch.cuda.device(accumulator.device):
+        rc = lib.dudf_render_finish(_ptr(accumulator), accumulator.numel(), float(sample_rate), _ptr(out), _stream())
+    _lib.check(rc, "dudf_render_finish")
+    return out
+
+
+def render_traced(cfg, theta, rays, t0, mask, network_config, rendering_config, lut, accumulator):
+    """Steps 2-8 of a pass on device arrays (reference src/render_st.py:67-133 `create_projectional_image`): march, descend, gather,
+    query the hits only, orient, percentiles + colour map, shade into `accumulator` (m,3) float64 (+=).  t0 and mask are updated in
+    place.  Returns (hits (m,) uint8, k).  The hit count is the only value read back; 0 hits raise the reference's ValueError."""
+    nc, rc_ = network_config, rendering_config
+    gt_mode = nc['gt_mode']
+    plot = rc_.get('plot_curvatures', 'none')
+    method = rc_.get('reflection_method', 'blinn-phong')
+    if gt_mode != 'siren':
+        if method not in SHADE_MODELS:
+            raise _lib.DudfError(f"reflection_method must be one of {sorted(SHADE_MODELS)}; got {method!r}")
+        if plot in ('mean', 'gaussian') and lut is None:
+            raise _lib.DudfError("plotting curvatures needs the (256,3) colour table (matplotlib's RdYlBu in the reference); none was given")
+    with torch.cuda.device(t0.device):
+        hits, _ = trace_rays(cfg, theta, rays, t0, mask, gt_mode, nc['alpha'], rc_['surface_threshold'], rc_['max_iterations'])
+        if rc_.get('gd_steps', 0) > 0:
+            descend_rays(cfg, theta, t0, hits, gt_mode, nc['alpha'], rc_['gd_steps'])
+        pos, hit_rays, rows, k = render_gather(hits, t0, rays)
+        if k == 0:
+            raise ValueError(f"Ray tracing did not converge in {rc_['max_iterations']} iterations to any point at distance "
+                             f"{rc_['surface_threshold']} or lower from surface.")
+        x = pos.float()                                      # the network sees float32 copies (reference src/render_st.py:25)
+        if gt_mode == 'siren':
+            _, g = query(cfg, theta, x)
+            normals, _, _ = render_orient(None, grad=g)
+            render_shade("blinn-phong", hits, rows, pos, normals, accumulator, rc_['light_position'], shininess=rc_['shininess'])
+            return hits, k
+        curv = None
+        if plot in ('mean', 'gaussian'):                     # normals and mean curvature from the SAME eigen-frame: one sign
+            _, V, mean, gauss, _ = query_curvature(cfg, theta, x, want_shape=(plot == 'gaussian'))
+            curv = mean if plot == 'mean' else gauss
+        else:
+            V = query_frame(cfg, theta, x)[4]
+        normals, pc1, pc2 = render_orient(hit_rays, frame_v=V, mean=curv if plot == 'mean' else None, want_pc=(method == 'ward'))
+        colors = None
+        if curv is not None:
+            bounds = render_percentile_bounds(curv, rc_['curv_low_bound'], rc_['curv_high_bound'])
+            colors = render_colormap(curv, bounds, lut)
+        if method == 'ward':
+            render_shade("ward", hits, rows, pos, normals, accumulator, rc_['light_position'], rc_['camera_position'],
+                         alpha1=rc_['alpha1'], alpha2=rc_['alpha2'], pc1=pc1, pc2=pc2, color_map=colors)
+        else:
+            render_shade("blinn-phong", hits, rows, pos, normals, accumulator, rc_['light_position'], shininess=rc_['shininess'],
+                         color_map=colors)
+    return hits, k
+
+
+def render_pass(cfg, theta, noise, rotation, camera_position, network_config, rendering_config, lut, accumulator):
+    """One jittered pass of reference generate_st.py:41-135 on the device: ray set-up, then `render_traced`.  accumulator
+    (height * width, 3) float64 CUDA tensor, += like `colores`.  Returns the hit count."""
+    rc_ = rendering_config
+    # the reference hands (height, width) to get_pixels_camera(width, height, ...) (:42); kept
+    rays, t0, mask = render_setup_rays(rc_['height'], rc_['width'], rc_['fov'], noise, rotation, camera_position,
+                                       rc_.get('planes', [1, -1, 1, -1, 1, -1]), accumulator.device)
+    return render_traced(cfg, theta, rays, t0, mask, network_config, rendering_config, lut, accumulator)[1]

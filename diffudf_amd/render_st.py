@@ -1,7 +1,8 @@
 # coding: utf-8
 """Differential quantities the sphere tracer derives at ray hits — the query half of reference
 src/render_st.py:42-65 (BASELINE config 4).  The marching loop itself (`propagate_rays`, `grad_descent`, :136-172)
-runs on the device too; ray set-up and shading (numpy glue) stay with the caller."""
+runs on the device too, and so do ray set-up, orientation, colour map and shading
+(`create_projectional_image`, `phong_shading`, `ward_reflectance`, :67-133, :174-245; csrc/dudf_render.hip)."""
 import numpy as np
 import torch
 import weakref
@@ -82,3 +83,88 @@ def grad_descent(model, t0, mask_rays, network_config, rendering_config, device=
         hip_ops.descend_rays(model.hip_cfg, model.flat_parameters(), d_t0, d_hits, network_config['gt_mode'],
                              network_config['alpha'], rendering_config['gd_steps'])
     t0[...] = d_t0.cpu().numpy()
+
+
+def default_colormap():
+    """The (256,3) table the reference colours curvatures with (`cm.get_cmap('RdYlBu')`, src/render_st.py:89): matplotlib's
+    data, fetched at call time — it is an input of this package, not a part of it."""
+    try:
+        import matplotlib
+    except ImportError:
+        raise DudfError("plotting curvatures needs a (256,3) colour table: matplotlib (RdYlBu) is not installed and no "
+                        "`colormap=` was given") from None
+    cmap = matplotlib.colormaps['RdYlBu']
+    return np.ascontiguousarray(cmap(np.arange(cmap.N))[:, :3], dtype=np.float64)
+
+
+def _lut_on(dev, colormap):
+    lut = np.ascontiguousarray(colormap, dtype=np.float64)
+    if lut.shape != (256, 3):
+        raise DudfError(f"colormap must be a (256,3) array; got {lut.shape}")
+    return torch.from_numpy(lut).to(dev)
+
+
+def _wants_colormap(network_config, rendering_config):
+    return network_config['gt_mode'] != 'siren' and rendering_config.get('plot_curvatures', 'none') in ('mean', 'gaussian')
+
+
+def _gpu(dev, what):
+    if dev.type != "cuda":
+        raise DudfError(f"{what}: device must be a GPU (got {dev}); the HIP path has no CPU fallback")
+    return dev
+
+
+def create_projectional_image(model, rays, t0, mask_rays, network_config, rendering_config, device=None, colormap=None):
+    """reference src/render_st.py:67-133, same signature (+ `colormap=`, a (256,3) table; default: matplotlib's RdYlBu): the
+    (height, width, 3) float64 image of one pass.  `rays` (M,3), `t0` (M,3) float64 and `mask_rays` (M,) bool are uploaded once;
+    marching, projection, the queries at the hits, orientation, colour map and shading run on the device (`hip_ops.render_traced`);
+    `t0` and `mask_rays` are updated in place as `propagate_rays` / `grad_descent` do."""
+    dev = _gpu(_device_of(model, device), "create_projectional_image")
+    lut = None
+    if _wants_colormap(network_config, rendering_config):
+        lut = _lut_on(dev, default_colormap() if colormap is None else colormap)
+    d_rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float64)).to(dev)
+    d_t0 = torch.from_numpy(np.ascontiguousarray(t0, dtype=np.float64)).to(dev)
+    d_mask = torch.from_numpy(np.ascontiguousarray(mask_rays).astype(np.uint8)).to(dev)
+    acc = torch.zeros(d_t0.shape[0], 3, dtype=torch.float64, device=dev)
+    hip_ops.render_traced(model.hip_cfg, model.flat_parameters(), d_rays, d_t0, d_mask, network_config, rendering_config, lut, acc)
+    t0[...] = d_t0.cpu().numpy()
+    mask_rays[...] = d_mask.cpu().numpy().astype(bool)
+    return acc.cpu().numpy().reshape((rendering_config['height'], rendering_config['width'], 3))
+
+
+def _shade_numpy(method, hits, samples, normals, device, color_map, **kw):
+    dev = _gpu(torch.device("cuda") if device is None else torch.device(device), method)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)          # noqa: E731
+    hits = np.asarray(hits).astype(bool).reshape(-1)
+    d_hits = torch.from_numpy(hits.astype(np.uint8)).to(dev)
+    d_samples = up(samples)
+    with torch.cuda.device(dev):
+        pos, _, rows, k = hip_ops.render_gather(d_hits, d_samples)
+        if np.shape(normals)[0] != k:
+            raise DudfError(f"{method}: {np.shape(normals)[0]} normals for {k} hits")
+        acc = torch.zeros(d_samples.shape[0], 3, dtype=torch.float64, device=dev)
+        extra = {n: up(v) for n, v in kw.items() if n in ("pc1", "pc2")}
+        scal = {n: v for n, v in kw.items() if n not in ("pc1", "pc2")}
+        hip_ops.render_shade(method, d_hits, rows, pos, up(normals), acc, color_map=None if color_map is None else up(color_map),
+                             **scal, **extra)
+    return acc.cpu().numpy()
+
+
+def phong_shading(light_position, shininess, hits, samples, normals, color_map=None, device=None):
+    """reference src/render_st.py:174-204, numpy in and out ((M,3) colours, 1.0 where `hits` is False) through
+    `dudf_render_shade`.  `device=`: the GPU to run on (default: the current one)."""
+    return _shade_numpy("blinn-phong", hits, samples, normals, device, color_map, light_position=light_position, shininess=shininess)
+
+
+def ward_reflectance(light_position, camera_position, hits, samples, normals, alpha1, alpha2, pc1, pc2, color_map=None, device=None):
+    """reference src/render_st.py:206-245 (np.nan_to_num's outcome for NaN / infinite weights included), numpy in and out."""
+    return _shade_numpy("ward", hits, samples, normals, device, color_map, light_position=light_position,
+                        camera_position=camera_position, alpha1=alpha1, alpha2=alpha2, pc1=pc1, pc2=pc2)
+
+
+def create_projectional_image_gt(*args, **kwargs):
+    """reference src/render_st.py:248-281 casts rays against a triangle mesh with open3d's RaycastingScene; that renderer is not
+    part of this build."""
+    raise DudfError("create_projectional_image_gt needs open3d's RaycastingScene (ray casting against the ground-truth mesh); "
+                    "it is outside this build — render the trained network with create_projectional_image")

@@ -170,6 +170,56 @@ int dudf_pointcloud_round(const dudf_net_cfg* cfg, const float* theta, int64_t n
 int dudf_pointcloud_read_proposals(const dudf_net_cfg* cfg, int64_t num_points, double* out, void* workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* Sphere-traced images — the stages of reference generate_st.py / src/render_st.py `create_projectional_image` around the marching
+ * loop and the queries above.  Everything is float64 like the reference's numpy arrays, evaluated in its order of operations
+ * (no contraction); normals, principal directions and curvatures are the float32 values torch hands it, promoted where they meet
+ * a float64 operand.  These entry points arrived after ABI 8 without changing any existing signature.
+ *
+ * dudf_render_setup_rays — generate_st.py:9-33 (`get_pixels_camera`) and :63-101 for width * height pixels, pixel p = iy * width + ix
+ *   (`width`, `height` are get_pixels_camera's arguments; the reference passes its config's height and width in this order, :42).
+ *   noise: the jitter of this pass; rotation (host, 9 doubles, row-major R of :49-61, formed by the caller); camera_position (host, 3
+ *   doubles; the kernel adds its float32 rounding to the rotated pixel as :44/:64 do and uses the doubles for the planes); planes
+ *   (host, 6 doubles, :76).  Per ray and plane: ds = numerator / (|denominator| < 1e-5 ? 1 : denominator), the intersection must lie
+ *   in [-1.001, 1.001]^3 with |denominator| > 1e-5; a ray with such a plane is valid and starts at the smallest ds >= 0 of them.
+ *   rays (m,3), t0 (m,3) doubles (t0 = 0 for invalid rays), mask (m) 0/1 bytes: the arguments of `create_projectional_image`. */
+int dudf_render_setup_rays(int64_t width, int64_t height, double fov, double noise, const double* rotation, const double* camera_position,
+                           const double* planes, double* rays, double* t0, unsigned char* mask, void* stream);
+
+/* dudf_render_gather — `t0[hits]`, `rays[hits]` (src/render_st.py:78, :104) through dudf_pointcloud_append's ordered compaction, plus
+ * the inverse map: out_rows (k) = the ray index of every gathered row, which `colors[hits] = ...` (:199, :240) scatters by.
+ * counter (device, 4 x int64) is zeroed first; [1] = k afterwards.  rays / out_rays may be NULL.  out_pos, out_rays, out_rows hold m
+ * rows.  workspace: dudf_pointcloud_append_workspace_bytes(m), 256-byte aligned. */
+int dudf_render_gather(const unsigned char* hits, int64_t m, const double* t0, const double* rays, double* out_pos, double* out_rays,
+                       int32_t* out_rows, int64_t* counter, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dudf_render_orient — src/render_st.py:101-108 for k hits: frame_v (k,3,3) from dudf_query_frame / dudf_query_curvature: normal = v_2,
+ * out_pc1 / out_pc2 = v_0 / v_1 (may be NULL), align = -sign(normal . ray) with sign(0) = 0, normal *= align and, when `mean` (k,
+ * in/out, the mean curvature of the SAME query) is given, mean *= align.  grad (k,3) instead of frame_v ('siren', :80-83):
+ * normal = normalize(grad) in float32, not oriented.  Exactly one of frame_v / grad. */
+int dudf_render_orient(const float* frame_v, const float* grad, const double* hit_rays, int64_t k, double* out_normals,
+                       double* out_pc1, double* out_pc2, float* mean, void* stream);
+
+/* dudf_render_colormap — src/render_st.py:111-114 behind the percentiles: bounds (device, 2 floats) = the two np.percentile values;
+ * clip, subtract the minimum, divide by the maximum in float32, then the look-up `cmap(x)[:, :3]`: row min(int(x * 256), 255) of
+ * lut (device, 256 x 3 doubles; the reference takes matplotlib's RdYlBu); NaN (both bounds equal) gives (0,0,0).
+ * out_colors (k,3) doubles. */
+int dudf_render_colormap(const float* curvatures, int64_t k, const float* bounds, const double* lut, double* out_colors, void* stream);
+
+/* dudf_render_shade — `phong_shading` (src/render_st.py:174-204) or `ward_reflectance` (:206-245) for k hits and the scatter into
+ * the image: accumulator (m,3) doubles += the colour at row rows[i] for every hit, += 1.0 at the pixels whose hits byte is 0
+ * (`np.ones_like(samples)`; `colores +=` of generate_st.py:104, :127).  hit_pos, normals (k,3); pc1, pc2 (k,3, Ward only); color_map
+ * (k,3) or NULL (0.7 / 0.7 / 0.2 grey); light_position, camera_position (host, 3 doubles; the camera for Ward only).  Phong: specular
+ * only where lambertian > 0 and shininess > 0.  Ward keeps np.nan_to_num's outcome: a NaN weight gives 0, +-inf gives +-DBL_MAX,
+ * which the clip to [0, 0.9] turns into 0.9 or 0. */
+#define DUDF_SHADE_PHONG 0
+#define DUDF_SHADE_WARD  1
+int dudf_render_shade(int model, const unsigned char* hits, int64_t m, const int32_t* rows, int64_t k, const double* hit_pos,
+                      const double* normals, const double* pc1, const double* pc2, const double* color_map, const double* light_position,
+                      const double* camera_position, double shininess, double alpha1, double alpha2, double* accumulator, void* stream);
+
+/* dudf_render_finish — `(colores / sample_rate * 255).astype(np.uint8)` (generate_st.py:139) over `count` doubles. */
+int dudf_render_finish(const double* accumulator, int64_t count, double sample_rate, unsigned char* out_image, void* stream);
+
 /* The field part of `extract_fields` (reference src/render_mc.py:20-99) for grid points start .. start+count-1 of the
  * regular grid_n^3 grid on [-1,1]^3 (linear index, first axis slowest, coordinates derived from the index):
  * out_df (count) = inverse(gt_mode, |f|, alpha) with inverse_mode 0 'tanh' / 1 'siren' / 2 'squared'
