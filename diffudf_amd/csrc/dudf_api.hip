@@ -65,40 +65,20 @@ int g_opt[OPT_COUNT] = {0, 1, 1, 1, DUDF_STASH_DEFAULT, 0, 0, 1, 256, DUDF_WGRAD
 int dudf_wgrad_max_workgroups() { return g_opt[OPT_WGRAD_MAXWG]; }
 bool dudf_deterministic() { return g_opt[OPT_DETERMINISTIC] != 0; }
 bool dudf_split_fp16() { return g_opt[OPT_SPLIT] != 0; }
-int dudf_opt_wgrad_family() { return g_opt[OPT_WGRAD_FAMILY]; }
-bool dudf_opt_wgrad_tr() { return g_opt[OPT_WGRAD_TR] != 0; }
-bool dudf_opt_pair_launch() { return g_opt[OPT_PAIR_LAUNCH] != 0; }
-int dudf_opt_wgrad_buffers() { return g_opt[OPT_WGRAD_BUFFERS]; }
-// which sweeps run fp16x3: bits 0-3 the plain columns' four sweeps (all or none: the adjoint reverse sweep's column scale
-// comes from the fp16x3 adjoint forward sweep), bit 5 the Hessian quads / jets as well (option split_quads = 0: bf16x6)
-int dudf_split_mask() { return dudf_split_fp16() ? (15 | (g_opt[OPT_SPLIT_QUADS] ? 32 : 0)) : 0; }
+DudfOptions dudf_options() {
+    DudfOptions o;
+    o.deterministic = g_opt[OPT_DETERMINISTIC]; o.split = g_opt[OPT_SPLIT]; o.split_quads = g_opt[OPT_SPLIT_QUADS];
+    o.sweep_family = g_opt[OPT_SWEEP_FAMILY]; o.stash = g_opt[OPT_STASH]; o.wgrad_family = g_opt[OPT_WGRAD_FAMILY];
+    o.wgrad_tr = g_opt[OPT_WGRAD_TR]; o.pair_launch = g_opt[OPT_PAIR_LAUNCH]; o.wgrad_max_workgroups = g_opt[OPT_WGRAD_MAXWG];
+    o.wgrad_buffers = g_opt[OPT_WGRAD_BUFFERS];
+    return o;
+}
 
 namespace {
 // option sweep_family = 0 keeps every sweep on the f32-input MFMA kernel (A/B testing); default: the 16-bit cores where built
 bool use_bf16_sweeps() { return g_opt[OPT_SWEEP_FAMILY] != 0; }
+int split_mask() { return dudf_split_mask(dudf_options()); }
 }  // namespace
-
-// Option "stash" (format of the stash a training workspace keeps; dudf_stash_mode returns what a given workspace gets):
-//   0  = every array fp32, 17 array-layer units per column (rounds 1-3);
-//   6  = R and E as 24-bit floats, C as 24-bit fixed point, tile-major (dudf_internal.h): 15 units.  Every tolerance
-//        holds, the 12-step beetle trajectory included (3e-7 .. 5e-7, as with fp32);
-//   7  = S, Q, A, Z as 24-bit FIXED POINT relative to a per-column power of two as well (12.75 units; the default): every
-//        single-step tolerance and every trajectory bar holds (round 4 stored these four as 24-bit FLOATS: 2^-17 noise on the
-//        weight-gradient GEMM's operands moved the beetle trajectory by 4e-4, bar 1e-4; tests/test_stash_p24_gpu.py).
-// The 24-bit arrays exist in the fp16x3 training kernels of 256- and 512-wide networks and in the cooperative-split weight-gradient
-// GEMM; an option that routes a kernel elsewhere drops the corresponding bits.
-int dudf_stash_p24_enabled(int H, int L) {
-    int want = g_opt[OPT_STASH] & 7;
-    if (want != 0 && want != 6 && want != 7) want = 6;
-    if (!(use_bf16_sweeps() && dudf_split_fp16() && (dudf_split_mask() & 47) == 47)) want = 0;
-    if (g_opt[OPT_WGRAD_FAMILY] != 0) want &= 6;       // f32 / per-wave weight-gradient kernels read fp32 rows
-    if (H == 256 && L >= 2 && L <= 32) return want;
-    // the 512-wide kernel relays S, Q, A, Z through the stash as fp32; R, E, C are not relays.  (Round 5 built the relay as the
-    // fixed-point array — every single-step tolerance held, the 12-step trajectory did not: 6e-4 against 7e-7, the rounding enters
-    // the layer chain itself there, not only the weight-gradient GEMM's operands — tests/test_traj512_gpu.py)
-    if (H == 512 && L >= 2) return want & 6;
-    return 0;
-}
 
 namespace {
 
@@ -120,7 +100,7 @@ SweepArgs make_sweep_args(const DudfLayout& lo, const float* theta, float* ws) {
     a.ebound = (lo.ws_ebound != lo.ws_amax) ? ws + lo.ws_ebound : nullptr;
     a.zbound = (lo.ws_zbound != lo.ws_amax) ? ws + lo.ws_zbound : nullptr;
     a.nch = lo.ncol_h;
-    a.split = dudf_split_mask();
+    a.split = split_mask();
     a.clk = nullptr;
     a.x4 = ws + lo.ws_x4; a.y = ws + lo.ws_y; a.g = ws + lo.ws_g; a.ybar = ws + lo.ws_ybar; a.gbar = ws + lo.ws_gbar;
     a.S = ws + lo.ws_S; a.C = ws + lo.ws_C; a.ZS = ws + lo.ws_ZS; a.Q = ws + lo.ws_Q; a.R = ws + lo.ws_R;
@@ -135,39 +115,41 @@ SweepArgs make_sweep_args(const DudfLayout& lo, const float* theta, float* ws) {
     return a;
 }
 
-// one sweep over both column ranges: Hessian quads first, then the plain columns
+SweepRequest make_request(int which, int H, const SweepArgs& a) {
+    return SweepRequest{which, H, a.L, a.store_s, a.store_c, a.train, a.have_e, a.split, a.p24, a.ebound != nullptr, a.zbound != nullptr};
+}
+
+// one column range of a sweep: build the request, choose, note the products, launch
+int launch_range(int which, int H, SweepArgs a, hipStream_t st) {
+    const SweepChoice c = dudf_choose_sweep(make_request(which, H, a), dudf_options());
+    if (c.status) return c.status;
+    DudfProfScope prof(PROF_SWEEP_FWD + (which & 3), st);
+    if (which <= SWEEP_ADJ_REV) dudf_note_products(PROF_SWEEP_FWD + which, c.products);
+    a.store_s = c.store_s; a.store_c = c.store_c;
+    if (c.family == DUDF_FAM_F32) return dudf_launch_sweep(c, a, st);
+    if (which <= SWEEP_ADJ_REV) a.clk = dudf_prof_clk(PROF_SWEEP_FWD + which);       // plain columns only
+    return dudf_launch_sweep_bf16(c, a, st);
+}
+
+// one sweep over both column ranges: Hessian quads and plain columns in one grid where a pair kernel is built (a training batch
+// with Hessian-path points), otherwise the quads first, then the plain columns
 int run_sweep(int base, const DudfLayout& lo, SweepArgs a, hipStream_t st) {
     int rc = 0;
     if ((lo.p24 & 1) && base >= SWEEP_FWD && base <= SWEEP_ADJ_REV) a.fxs = a.S - lo.ws_S + lo.ws_fx[base];   // (a.S - lo.ws_S = the workspace base)
-    if (lo.ncol_h > 0 && lo.ncol_n > 0 && use_bf16_sweeps()) {     // a training batch with Hessian-path points: one grid for both
-        SweepArgs aq = a, ap = a;
-        aq.tile0 = 0; aq.ntiles = (int)(lo.ncol_h / DUDF_TILE_PTS); aq.hess = 1;
-        ap.tile0 = aq.ntiles; ap.ntiles = (int)(lo.ncol_n / DUDF_TILE_PTS); ap.hess = 0;
-        rc = dudf_launch_sweep_pair(base, lo.H, aq, ap, st);
-        if (rc != DUDF_E_UNSUPPORTED) return rc;
-        rc = 0;
-    }
-    if (lo.ncol_h > 0) {
-        a.tile0 = 0; a.ntiles = (int)(lo.ncol_h / DUDF_TILE_PTS); a.hess = 1;
-        if (use_bf16_sweeps() && dudf_sweep_bf16_supported(base + 4, lo.H, lo.L)) {
-            rc = dudf_launch_sweep_bf16(base + 4, lo.H, a, st);
-        } else {
-            SweepArgs b = a;
-            if (base == SWEEP_FWD) b.store_s = 1;                 // the f32 kernel's quad forward tail always keeps its outputs
-            rc = dudf_launch_sweep(base + 4, lo.H, b, st);
+    SweepArgs aq = a, ap = a;
+    aq.tile0 = 0; aq.ntiles = (int)(lo.ncol_h / DUDF_TILE_PTS); aq.hess = 1;
+    ap.tile0 = aq.ntiles; ap.ntiles = (int)(lo.ncol_n / DUDF_TILE_PTS); ap.hess = 0;
+    if (lo.ncol_h > 0 && lo.ncol_n > 0) {
+        const SweepChoice c = dudf_choose_pair(make_request(base, lo.H, a), dudf_options());
+        if (c.status == 0) {
+            DudfProfScope prof(PROF_SWEEP_FWD + base, st);
+            dudf_note_products(PROF_SWEEP_FWD + base, c.products);
+            ap.clk = dudf_prof_clk(PROF_SWEEP_FWD + base);
+            return dudf_launch_sweep_pair(c, aq, ap, st);
         }
-        if (rc) return rc;
     }
-    if (lo.ncol_n > 0) {
-        a.tile0 = (int)(lo.ncol_h / DUDF_TILE_PTS); a.ntiles = (int)(lo.ncol_n / DUDF_TILE_PTS); a.hess = 0;
-        rc = DUDF_E_UNSUPPORTED;
-        if (use_bf16_sweeps() && dudf_sweep_bf16_handles(base, lo.H, lo.L, a)) rc = dudf_launch_sweep_bf16(base, lo.H, a, st);
-        if (rc == DUDF_E_UNSUPPORTED && !lo.p24) {                // width / variant without a 16-bit-core kernel (a 24-bit workspace has no other)
-            if (base == SWEEP_FWD) a.store_s = a.store_c = 1;     // the f32 kernel only builds its stash-everything variant
-            rc = dudf_launch_sweep(base, lo.H, a, st);
-        }
-        if (rc) return rc;
-    }
+    if (lo.ncol_h > 0 && (rc = launch_range(base + 4, lo.H, aq, st))) return rc;
+    if (lo.ncol_n > 0 && (rc = launch_range(base, lo.H, ap, st))) return rc;
     return 0;
 }
 
@@ -196,7 +178,7 @@ int forward_common(Ctx& c, const float* theta, const float* x, int train, bool r
     // and W^T are packed only when a kernel that reads them can run: everything except a training step of plain columns
     // whose four sweeps are all fp16x3 (Hessian quads, jets, A/B modes, very deep nets: bf16x6; f32-input kernels: W^T).
     const DudfLayout& lo = c.lo;
-    const bool all16 = train && lo.ncol_h == 0 && use_bf16_sweeps() && (dudf_split_mask() & 15) == 15 && lo.L <= 32;
+    const bool all16 = train && lo.ncol_h == 0 && use_bf16_sweeps() && (split_mask() & 15) == 15 && lo.L <= 32;
     const int need = (all16 ? 0 : 1) | (!use_bf16_sweeps() ? 2 : 0);
     rc = (lo.L >= 2) ? dudf_launch_prep(lo, theta, x, c.ws, need, c.st) : DUDF_E_UNSUPPORTED;
     if (rc == DUDF_E_UNSUPPORTED) {                     // widths without 16-bit weight images: the separate kernels
@@ -258,12 +240,14 @@ const char* dudf_version(void) {
 }
 
 int dudf_split_mode(void) {
-    return dudf_split_mask() | (dudf_split_fp16() ? 16 : 0);
+    return split_mask() | (dudf_split_fp16() ? 16 : 0);
 }
 
 int dudf_sweeps_bf16x6(const dudf_net_cfg* cfg) {
     if (!cfg) return 0;
-    return (use_bf16_sweeps() && dudf_sweep_bf16_supported(SWEEP_FWD, cfg->hidden, cfg->n_hidden_layers)) ? 1 : 0;
+    const SweepRequest r = {SWEEP_FWD, cfg->hidden, cfg->n_hidden_layers, 0, 0, 0, 1, split_mask(), 0, false, false};   // a value query
+    const SweepChoice c = dudf_choose_sweep(r, dudf_options());
+    return (c.status == 0 && c.family != DUDF_FAM_F32) ? 1 : 0;
 }
 
 int64_t dudf_theta_count(const dudf_net_cfg* cfg) {
@@ -374,9 +358,7 @@ int dudf_query_curvature(const dudf_net_cfg* cfg, const float* theta, const floa
     a.x4 = c.ws + cl.o_x4; a.y = c.ws + cl.o_y; a.np = cl.npj; a.stash_layer = (int64_t)c.lo.H * cl.npj;
     if (c.lo.H == 512) { a.S = c.ws + cl.o_relay; a.stash_layer = 0; }     // every layer's slot is the same one
     a.tile0 = 0; a.ntiles = (int)(cl.npj / DUDF_TILE_PTS); a.hess = 1;
-    if (use_bf16_sweeps() && dudf_sweep_bf16_supported(SWEEP_FWD_J, c.lo.H, c.lo.L)) rc = dudf_launch_sweep_bf16(SWEEP_FWD_J, c.lo.H, a, c.st);
-    else rc = dudf_launch_sweep(SWEEP_FWD_J, c.lo.H, a, c.st);
-    if (rc) return rc;
+    if ((rc = launch_range(SWEEP_FWD_J, c.lo.H, a, c.st))) return rc;
     // 3. first-order eigenvector perturbation
     if ((rc = dudf_launch_curvature(c.ws + cl.o_y, lam, V, n, out_mean, out_gauss, out_shape, c.st))) return rc;
     hipError_t e = hipSuccess;
@@ -902,6 +884,24 @@ int dudf_debug_stash_layout(const dudf_net_cfg* cfg, int64_t n, int64_t n_hess, 
     out[8] = lo.np * 16;                                  // bytes between two feature-quad rows
     out[9] = lo.stash_layer * (int64_t)sizeof(float);     // bytes between two layers
     return 0;
+}
+
+int dudf_debug_kernel_choice(const dudf_net_cfg* cfg, int64_t n, int64_t n_hess, int which, int flags, char* name, size_t name_len) {
+    DudfLayout lo;
+    int rc = dudf_make_layout(cfg, n, n_hess, &lo, (flags & 16) != 0);
+    if (rc) return rc;
+    if (!name || name_len == 0) return DUDF_E_BADCFG;
+    name[0] = 0;
+    SweepChoice c;
+    if (which == DUDF_CHOICE_WGRAD) {
+        c = dudf_choose_wgrad(WgradRequest{lo.H, lo.L, lo.p24 & 1, lo.np}, dudf_options());
+    } else {
+        const SweepRequest r = {which & 15, lo.H, lo.L, flags & 1, (flags >> 1) & 1, (flags >> 2) & 1, (flags >> 3) & 1, split_mask(), lo.p24,
+                                lo.ws_ebound != lo.ws_amax, lo.ws_zbound != lo.ws_amax};
+        c = (which & DUDF_CHOICE_PAIR) ? dudf_choose_pair(r, dudf_options()) : dudf_choose_sweep(r, dudf_options());
+    }
+    if (c.status == 0 && dudf_choice_name(c, name, name_len) >= (int)name_len) return DUDF_E_WORKSPACE;
+    return c.status;
 }
 
 int dudf_stash_mode(const dudf_net_cfg* cfg, int64_t n, int64_t n_hess) {

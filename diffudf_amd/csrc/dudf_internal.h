@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "../../include/dudf_hip.h"
+#include "dudf_variants.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -85,9 +86,8 @@ struct DudfLayout {
     size_t total_bytes;
 };
 
-// 24-bit stash selected for this network?  (dudf_api.hip: DUDF_STASH, and every kernel of the step must be the fp16x3 build
-// that reads / writes it)
-int dudf_stash_p24_enabled(int H, int L);   // the mask (0, 6 or 7)
+// the current run-time options (dudf_set_option in the C ABI; dudf_api.hip holds them)
+DudfOptions dudf_options();
 
 static inline int dudf_make_layout(const dudf_net_cfg* cfg, int64_t n, int64_t n_h, DudfLayout* lo, int query_only = 0) {
     if (!cfg || cfg->n_in != 3 || cfg->n_hidden_layers < 1) return DUDF_E_BADCFG;
@@ -98,7 +98,7 @@ static inline int dudf_make_layout(const dudf_net_cfg* cfg, int64_t n, int64_t n
     const float ww = cfg->ww > 0.f ? cfg->ww : cfg->w0;
     lo->H = H; lo->L = L; lo->w0 = ww; lo->rho = cfg->w0 / ww;
     lo->n = n; lo->n_h = n_h;
-    lo->p24 = query_only ? 0 : dudf_stash_p24_enabled(H, L);
+    lo->p24 = query_only ? 0 : dudf_stash_p24_enabled(H, L, dudf_options());   // option stash, and every kernel of the step must be the build that reads / writes it
     auto pad = [](int64_t c) { return (c + DUDF_COL_PAD - 1) / DUDF_COL_PAD * DUDF_COL_PAD; };
     lo->ncol_h = pad(4 * n_h);
     lo->ncol_n = pad(n - n_h);
@@ -175,7 +175,7 @@ struct SweepArgs {
     float* zbound;            // [L][ncol_h]: per layer and quad column, max over features of |zdot_l| (written by SWEEP_FWD_H, fp16x3), or nullptr
     int64_t nch;              // ncol_h: row stride of zbound
     unsigned long long* clk;  // profiling: [2] shader-clock / 100 MHz reference-clock ticks of workgroup 0's lifetime, or nullptr
-    int split;                // bit s: sweep s (SWEEP_FWD .. SWEEP_ADJ_REV) of the plain columns runs the fp16x3 kernel (DUDF_SPLIT)
+    int split;                // bit s: sweep s (SWEEP_FWD .. SWEEP_ADJ_REV) of the plain columns runs the fp16x3 kernel (dudf_split_mask)
     const float* x4;          // [np][4]: layer-1 B operand per column
     float* y; float* g;       // [np], [np][4]
     const float* ybar; const float* gbar;
@@ -192,16 +192,24 @@ struct SweepArgs {
                                    // THIS sweep stores (S / Q / A / Z by sweep) back into numbers; written by the sweep, read by the weight-gradient kernels
 };
 
-enum { SWEEP_FWD = 0, SWEEP_REV = 1, SWEEP_ADJ_FWD = 2, SWEEP_ADJ_REV = 3,
-       SWEEP_FWD_H = 4, SWEEP_REV_H = 5, SWEEP_ADJ_FWD_H = 6, SWEEP_ADJ_REV_H = 7,     // Hessian-quad variants
-       SWEEP_FWD_J = 8 };                                                              // third-order jets (query)
+// set-attribute-once + launch of one kernel instantiation.  The "once" is per process and per instantiation (the static below):
+// hipFuncSetAttribute on every launch would be paid on the launch path.
+template <auto Kernel, class... Args>
+int dudf_launch_kernel(dim3 grid, dim3 block, size_t lds, size_t lds_max, hipStream_t st, const Args&... args) {
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+        if (e != hipSuccess) return (int)e;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    return (int)hipGetLastError();
+}
 
-int dudf_launch_sweep(int which, int H, const SweepArgs& a, hipStream_t st);
-// the same sweeps on the bf16 matrix cores at fp32 accuracy (plain columns, H = 256)
-bool dudf_sweep_bf16_supported(int which, int H, int L);
-bool dudf_sweep_bf16_handles(int which, int H, int L, const SweepArgs& a);
-int dudf_launch_sweep_bf16(int which, int H, const SweepArgs& a, hipStream_t st);
-int dudf_launch_sweep_pair(int base, int H, const SweepArgs& aq, const SweepArgs& ap, hipStream_t st);   // quads + plain columns in one grid
+// the launchers take the kernel from a SweepChoice (dudf_variants.h: dudf_choose_sweep / dudf_choose_pair / dudf_choose_wgrad)
+int dudf_launch_sweep(const SweepChoice& c, const SweepArgs& a, hipStream_t st);          // the f32-input MFMA family
+int dudf_launch_sweep_bf16(const SweepChoice& c, const SweepArgs& a, hipStream_t st);     // the 16-bit-core families (H = 128, 256, 512)
+int dudf_launch_sweep_pair(const SweepChoice& c, const SweepArgs& aq, const SweepArgs& ap, hipStream_t st);   // quads + plain columns in one grid
 int dudf_launch_pack_bf16(const DudfLayout& lo, const float* theta, float* ws, hipStream_t st);
 
 int dudf_launch_pack(const DudfLayout& lo, const float* theta, float* ws, hipStream_t st);
@@ -275,10 +283,6 @@ int dudf_launch_curvature(const float* yj, const float* lam, const float* V, int
 #ifndef DUDF_STASH_DEFAULT
 #define DUDF_STASH_DEFAULT 7          // requested stash mask of a fresh process: all seven arrays at 24 bits (R, E floats; C, S, Q, A, Z fixed point)
 #endif
-int dudf_opt_wgrad_family();          // 0 = cooperative split (default), 1 = f32-input MFMA, 2 = bf16x6 per-wave split
-bool dudf_opt_wgrad_tr();             // fp32 rows through the [column][feature] image + transposed fragment reads
-bool dudf_opt_pair_launch();          // quads + plain columns of a training sweep in one grid
-int dudf_opt_wgrad_buffers();         // LDS image buffers of the weight-gradient GEMM that reads the 24-bit operands: 3 | 4
 // option "deterministic": every cross-workgroup sum of the training path — loss terms, loss_s2 statistics, dW, db —
 // is formed by ONE workgroup per output element (a single block for the loss sums, one column split per weight tile,
 // one block for the thin layers), so repeated launches give bit-identical results.  A test mode: the weight-gradient
@@ -287,7 +291,6 @@ bool dudf_deterministic();
 // option "split" = 0 keeps every hidden matmul on the exact three-piece bf16 split (six products); default: the fp16 hi/lo
 // split (three products) where it is built.
 bool dudf_split_fp16();
-int dudf_split_mask();
 // cap of the weight-gradient GEMM's grid (option "wgrad_max_workgroups"; 256 = one workgroup per CU)
 int dudf_wgrad_max_workgroups();
 // products per algorithmic multiply of the kernel a launcher is about to start in profile slot `slot`: 1 = f32-input MFMA,

@@ -313,73 +313,28 @@ __global__ __launch_bounds__(64 * NW, Geo<H>::WPSIMD) void sweep_kernel(SweepArg
 }
 
 template <int H>
-int launch_h(int which, const SweepArgs& a, hipStream_t st) {
+int launch_h(const SweepChoice& c, const SweepArgs& a, hipStream_t st) {
     using G = Geo<H>;
-    const size_t smem = 2 * G::BUF * sizeof(float);
-    const int ntiles = a.ntiles;
-    if (ntiles <= 0) return 0;
+    static_assert(2 * 32 * (size_t)(H + 4) == 2 * G::BUF, "dudf_choose_sweep: LDS of the f32 family");
+    if (a.ntiles <= 0) return 0;
     const int slots = 256 * G::WPSIMD;                 // resident 4-wave workgroups: two per CU (one for H = 512)
-    int grid = ntiles < slots ? ntiles : slots;
-    if (grid < 1) grid = 1;
-    hipError_t e = hipSuccess;
-#define DUDF_GO(SW, FL)                                                                                     \
-    do {                                                                                                    \
-        static bool attr_done = false;                                                                      \
-        if (!attr_done) {                                                                                   \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_kernel<H, SW, FL>),                \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                 \
-            if (e != hipSuccess) return (int)e;                                                             \
-            attr_done = true;                                                                               \
-        }                                                                                                   \
-        hipLaunchKernelGGL((sweep_kernel<H, SW, FL>), dim3(grid), dim3(G::NTHR), smem, st, a);              \
-    } while (0)
-    switch (which) {
-        case SWEEP_FWD:                                  // the stash-everything variant is the only one built: the
-            if (!(a.store_s && a.store_c)) return DUDF_E_BADMODE;   // leaner ones made the register allocator spill
-            DUDF_GO(SWEEP_FWD, 3);
-            break;
-        case SWEEP_REV:
-            if (a.train) DUDF_GO(SWEEP_REV, 1); else DUDF_GO(SWEEP_REV, 0);
-            break;
-        case SWEEP_ADJ_FWD: DUDF_GO(SWEEP_ADJ_FWD, 0); break;
-        case SWEEP_ADJ_REV:
-            if (a.have_e) DUDF_GO(SWEEP_ADJ_REV, 1); else DUDF_GO(SWEEP_ADJ_REV, 0);
-            break;
-        // Hessian-quad variants (all widths incl. 512: DPP sources are pinned to architectural VGPRs, dudf_sweep_common.h)
-        case SWEEP_FWD_H:
-            if (!a.store_s) return DUDF_E_BADMODE;
-            DUDF_GO(SWEEP_FWD_H, 1);
-            break;
-        case SWEEP_REV_H:
-            if (a.train) DUDF_GO(SWEEP_REV_H, 1); else DUDF_GO(SWEEP_REV_H, 0);
-            break;
-        case SWEEP_ADJ_FWD_H:
-            DUDF_GO(SWEEP_ADJ_FWD_H, 0);
-            break;
-        case SWEEP_ADJ_REV_H:
-            DUDF_GO(SWEEP_ADJ_REV_H, 0);
-            break;
-        case SWEEP_FWD_J:
-            DUDF_GO(SWEEP_FWD_J, 0);
-            break;
-        default: return DUDF_E_BADMODE;
-    }
-#undef DUDF_GO
-    e = hipGetLastError();
-    return (int)e;
+    const int grid = a.ntiles < slots ? a.ntiles : slots;
+    // Hessian-quad variants at all widths incl. 512: DPP sources are pinned to architectural VGPRs, dudf_sweep_common.h
+    return dudf_with_variant(kF32Variants, c.sw, c.fl, [&](auto i) {
+        constexpr DudfVariant v = kF32Variants[decltype(i)::value];
+        return dudf_launch_kernel<&sweep_kernel<H, v.sw, v.fl>>(dim3(grid), dim3(G::NTHR), c.lds, c.lds_max, st, a);
+    });
 }
 
 }  // namespace
 
-int dudf_launch_sweep(int which, int H, const SweepArgs& a, hipStream_t st) {
-    DudfProfScope prof(PROF_SWEEP_FWD + (which & 3), st);
-    if (which <= SWEEP_ADJ_REV) dudf_note_products(PROF_SWEEP_FWD + which, 1);
-    switch (H) {
-        case 32: return launch_h<32>(which, a, st);
-        case 64: return launch_h<64>(which, a, st);
-        case 128: return launch_h<128>(which, a, st);
-        case 256: return launch_h<256>(which, a, st);
-        case 512: return launch_h<512>(which, a, st);
+int dudf_launch_sweep(const SweepChoice& c, const SweepArgs& a, hipStream_t st) {
+    switch (c.H) {
+        case 32: return launch_h<32>(c, a, st);
+        case 64: return launch_h<64>(c, a, st);
+        case 128: return launch_h<128>(c, a, st);
+        case 256: return launch_h<256>(c, a, st);
+        case 512: return launch_h<512>(c, a, st);
         default: return DUDF_E_BADCFG;
     }
 }

@@ -37,9 +37,6 @@
 // forward sweep, one tile at a time, DMA pieces issued by the idle half of a partial pass, static / per-phase wave priorities,
 // other fragment prefetch distances and feed / tail slots) are no longer in this file: DESIGN.md Appendix A has their numbers,
 // `git log -- diffudf_amd/csrc/dudf_sweep_bf16.hip` (round 3) their code.
-#ifndef DUDF_FWD_F16_KERNEL
-#define DUDF_FWD_F16_KERNEL sweep_f16_np_kernel   // A/B: sweep_f16_kernel = the build WITH packed fp32 instructions
-#endif
 #ifndef DUDF_OCT
 #define DUDF_OCT 1                           // a pass with a single 16-column group is shared by all eight waves (sweep_tile_oct)
 #endif
@@ -76,8 +73,6 @@ __device__ __forceinline__ void lds_max_wave(unsigned* word, float v) {
                  : "=&s"(ex) : "v"(addr), "v"(__float_as_uint(v)) : "memory");
 #endif
 }
-constexpr int kMaxAmaxLayers = 64;                     // LDS words of the per-layer running maxima (deeper nets: no fp16x3 wgrad)
-constexpr size_t kLdsCu = 160 * 1024;
 constexpr int NWB = 8;                                 // waves per workgroup: two per SIMD
 constexpr int TILEB = NWB * 16;                        // columns per workgroup pass
 
@@ -777,7 +772,6 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
 // 32 fragments of a layer at the top of the layer, behind the exchange and the tail (a step of 6 MFMAs is far shorter than
 // an LDS-DMA round trip: with the chunk stream the pass was bound by DMA latency).  Two barriers per layer, no hand-counted
 // waits; the chunk buffers and `gc` are left alone.
-constexpr int kOctBytes = 8 * 2 * 1024 + 1024 + 8 * 64 * 16;      // B fragments | column maxima (2 x 128 floats) | output-stage partials
 template <int H, int SW, int FL, int P24 = 0>
 __device__ __forceinline__ void sweep_tile_oct(const SweepArgs& a, const int g, char* lds, unsigned& gc, const unsigned oct_off) {
     using G = GeoB<H, 1>;
@@ -1043,7 +1037,6 @@ __device__ __forceinline__ void sweep_body_b(const SweepArgs& a, const int bid, 
 // tail is as long as its MFMA stream, is therefore built WITHOUT them and overlaps the two; the other sweeps (short
 // tails, bound by the stash stream) keep them.
 // (the Hessian-quad and jet variants too: +3 % / +5 % on the Hessian-frame and curvature queries)
-template <int SW> constexpr bool sweep_no_pk() { return SW == SWEEP_FWD || SW >= SWEEP_FWD_H; }
 template <int H, int SW, int FL>
 __global__ __launch_bounds__(64 * NWB) void sweep_bf16_kernel(SweepArgs a) { sweep_body_b<H, SW, FL>(a, blockIdx.x, gridDim.x); }
 template <int H, int SW, int FL>
@@ -1054,7 +1047,7 @@ __global__ __launch_bounds__(64 * NWB) void sweep_f16_kernel(SweepArgs a) { swee
 template <int H, int SW, int FL>
 __global__ __launch_bounds__(64 * NWB) DUDF_NO_PK void sweep_f16_np_kernel(SweepArgs a) { sweep_body_b<H, SW, FL, 1>(a, blockIdx.x, gridDim.x); }
 // ... and the fp16x3 builds that keep stash arrays at 24 bits, tile-major (dudf_internal.h "p24"; training variants):
-// f16r: R, E and C (mask 6, the default stash of 256-wide networks); f16p: S, Q, A, Z as well (mask 7, DUDF_STASH=17p24)
+// f16r: R, E and C (stash mask 6); f16p: S, Q, A, Z as well (mask 7, the default stash of 256-wide networks)
 template <int H, int SW, int FL>
 __global__ __launch_bounds__(64 * NWB) void sweep_f16r_kernel(SweepArgs a) { sweep_body_b<H, SW, FL, 1, 6>(a, blockIdx.x, gridDim.x); }
 template <int H, int SW, int FL>
@@ -1244,140 +1237,32 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     }
 }
 
-template <int H, int SW, int FL>
-const void* sweep_kernel_ptr() {
-    if constexpr (sweep_no_pk<SW>()) return reinterpret_cast<const void*>(&sweep_bf16_np_kernel<H, SW, FL>);
-    else return reinterpret_cast<const void*>(&sweep_bf16_kernel<H, SW, FL>);
+// the instantiation of a family: the forward, Hessian-quad and jet sweeps are the builds without packed fp32 instructions
+template <int H, int FAM, int SW, int FL>
+constexpr auto sweep_kernel_of() {
+    constexpr bool np = sweep_no_pk<SW>();
+    if constexpr (FAM == DUDF_FAM_BF16) { if constexpr (np) return &sweep_bf16_np_kernel<H, SW, FL>; else return &sweep_bf16_kernel<H, SW, FL>; }
+    else if constexpr (FAM == DUDF_FAM_F16 && SW == SWEEP_FWD) return &DUDF_FWD_F16_KERNEL<H, SW, FL>;
+    else if constexpr (FAM == DUDF_FAM_F16) { if constexpr (np) return &sweep_f16_np_kernel<H, SW, FL>; else return &sweep_f16_kernel<H, SW, FL>; }
+    else if constexpr (FAM == DUDF_FAM_F16R) { if constexpr (np) return &sweep_f16r_np_kernel<H, SW, FL>; else return &sweep_f16r_kernel<H, SW, FL>; }
+    else { if constexpr (np) return &sweep_f16p_np_kernel<H, SW, FL>; else return &sweep_f16p_kernel<H, SW, FL>; }
 }
-constexpr int kMaxLdsBiasLayers = 32;                  // fp16x3 forward sweep: b_1..b_L live in LDS (32 KiB at H = 256); deeper nets: bf16x6
+static_assert(dudf_chunk_bytes(256, 3) == GeoB<256>::CHUNKB && dudf_chunk_bytes(128, 2) == GeoB<128, 1>::CHUNKB, "dudf_variants.h: LDS sizes");
 template <int H>
-int launch_b(int which, const SweepArgs& a0, hipStream_t st) {
-    using G = GeoB<H>;
-    SweepArgs a = a0;
-    const size_t smem = 3 * G::CHUNKB + kMaxAmaxLayers * sizeof(unsigned);   // + the per-layer running maxima
+int launch_b(const SweepChoice& c, const SweepArgs& a, hipStream_t st) {
     if (a.ntiles <= 0) return 0;
     const int ntb = (a.ntiles * TILE + TILEB - 1) / TILEB;
-    int grid = ntb < 256 ? ntb : 256;                  // one resident 8-wave workgroup per CU
-    hipError_t e = hipSuccess;
-#define DUDF_GO_B(SW, FL)                                                                                   \
-    do {                                                                                                    \
-        if (SW <= SWEEP_ADJ_REV) dudf_note_products(PROF_SWEEP_FWD + SW, 6);                                \
-        static bool attr_done = false;                                                                      \
-        if (!attr_done) {                                                                                   \
-            e = hipFuncSetAttribute(sweep_kernel_ptr<H, SW, FL>(),                                          \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                 \
-            if (e != hipSuccess) return (int)e;                                                             \
-            attr_done = true;                                                                               \
-        }                                                                                                   \
-        if constexpr (sweep_no_pk<SW>())                                                                    \
-            hipLaunchKernelGGL((sweep_bf16_np_kernel<H, SW, FL>), dim3(grid), dim3(G::NTHR), smem, st, a);  \
-        else                                                                                                \
-            hipLaunchKernelGGL((sweep_bf16_kernel<H, SW, FL>), dim3(grid), dim3(G::NTHR), smem, st, a);     \
-    } while (0)
-#define DUDF_GO_H(SW, FL, KERNEL, SMEM_MAX, SMEM)                                                           \
-    do {                                                                                                    \
-        if (SW <= SWEEP_ADJ_REV) dudf_note_products(PROF_SWEEP_FWD + SW, 3);                                \
-        static bool attr_done = false;                                                                      \
-        if (!attr_done) {                                                                                   \
-            (void)(SMEM_MAX);                                                                               \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL<H, SW, FL>),                      \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCu);               \
-            if (e != hipSuccess) return (int)e;                                                             \
-            attr_done = true;                                                                               \
-        }                                                                                                   \
-        hipLaunchKernelGGL((KERNEL<H, SW, FL>), dim3(grid), dim3(G::NTHR), (SMEM), st, a);                  \
-    } while (0)
-    // fp16x3 (DUDF_SPLIT, DUDF_SPLIT_SWEEPS): the plain columns' four sweeps
-    if (which <= SWEEP_ADJ_REV && ((a.split >> which) & 1)) {
-        constexpr size_t w3 = 3 * GeoB<H, 1>::CHUNKB;
-        constexpr size_t oct = (H == 256) ? kOctBytes : 0;                   // + the exchange area of the one-group pass
-        const size_t smem_f = w3 + (size_t)a.L * H * sizeof(float) + oct;    // + the biases (forward sweep)
-        constexpr size_t smem_fmax = w3 + kMaxLdsBiasLayers * H * sizeof(float) + oct;
-        constexpr size_t smem_o = w3 + kMaxAmaxLayers * sizeof(unsigned) + oct;   // + the per-layer running maxima
-        bool done = true;
-        // 24-bit tile-major stash (SweepArgs::p24, H = 256): the training variants have a build of their own
-#define DUDF_GO_HP(SW, FL, KERNEL, KERNELR, KERNELP, SMEM_MAX, SMEM)                                        \
-        do {                                                                                                    \
-            bool p_ = false;                                                                                    \
-            if constexpr (H == 256) {                                                                           \
-                if (a.p24 == 7) { DUDF_GO_H(SW, FL, KERNELP, SMEM_MAX, SMEM); p_ = true; }                      \
-                else if (a.p24 == 6) { DUDF_GO_H(SW, FL, KERNELR, SMEM_MAX, SMEM); p_ = true; }                 \
-            }                                                                                                   \
-            if (!p_) { if (a.p24) return DUDF_E_UNSUPPORTED; DUDF_GO_H(SW, FL, KERNEL, SMEM_MAX, SMEM); }       \
-        } while (0)
-        // (a 24-bit workspace holds C as fixed point: only the training variants, which are built for it, may touch it)
-        if (a.p24 && ((which == SWEEP_FWD && !(a.store_s && a.store_c)) || (which == SWEEP_REV && !a.train))) return DUDF_E_UNSUPPORTED;
-        if (which == SWEEP_FWD && a.L <= kMaxLdsBiasLayers) {
-            if (a.store_s && a.store_c) DUDF_GO_HP(SWEEP_FWD, 3, DUDF_FWD_F16_KERNEL, sweep_f16r_np_kernel, sweep_f16p_np_kernel, smem_fmax, smem_f);
-            else if (a.store_c) DUDF_GO_H(SWEEP_FWD, 2, DUDF_FWD_F16_KERNEL, smem_fmax, smem_f);
-            else if (!a.store_s) DUDF_GO_H(SWEEP_FWD, 0, DUDF_FWD_F16_KERNEL, smem_fmax, smem_f);
-            else return DUDF_E_BADMODE;
-        } else if (which == SWEEP_REV) {
-            if (a.train) DUDF_GO_HP(SWEEP_REV, 1, sweep_f16_kernel, sweep_f16r_kernel, sweep_f16p_kernel, smem_o, smem_o); else DUDF_GO_H(SWEEP_REV, 0, sweep_f16_kernel, smem_o, smem_o);
-        } else if (which == SWEEP_ADJ_FWD) {
-            DUDF_GO_HP(SWEEP_ADJ_FWD, 0, sweep_f16_kernel, sweep_f16r_kernel, sweep_f16p_kernel, smem_o, smem_o);
-        } else if (which == SWEEP_ADJ_REV && (!a.have_e || (a.ebound && ((a.split >> SWEEP_ADJ_FWD) & 1)))) {
-            if (a.have_e) DUDF_GO_HP(SWEEP_ADJ_REV, 1, sweep_f16_kernel, sweep_f16r_kernel, sweep_f16p_kernel, smem_o, smem_o); else DUDF_GO_HP(SWEEP_ADJ_REV, 0, sweep_f16_kernel, sweep_f16r_kernel, sweep_f16p_kernel, smem_o, smem_o);
-        } else {
-            done = false;
+    const dim3 grid(ntb < 256 ? ntb : 256), block(GeoB<H>::NTHR);     // one resident 8-wave workgroup per CU
+    return dudf_with_variant(kSweepVariants, c.sw, c.fl, [&](auto i) {
+        constexpr DudfVariant v = kSweepVariants[decltype(i)::value];
+        if (c.family == DUDF_FAM_BF16) return dudf_launch_kernel<sweep_kernel_of<H, DUDF_FAM_BF16, v.sw, v.fl>()>(grid, block, c.lds, c.lds_max, st, a);
+        if (c.family == DUDF_FAM_F16) return dudf_launch_kernel<sweep_kernel_of<H, DUDF_FAM_F16, v.sw, v.fl>()>(grid, block, c.lds, c.lds_max, st, a);
+        if constexpr (H == 256 && v.p24 != 0) {          // 24-bit tile-major stash: the training variants have a build of their own
+            if (c.family == DUDF_FAM_F16R) return dudf_launch_kernel<sweep_kernel_of<H, DUDF_FAM_F16R, v.sw, v.fl>()>(grid, block, c.lds, c.lds_max, st, a);
+            if (c.family == DUDF_FAM_F16P) return dudf_launch_kernel<sweep_kernel_of<H, DUDF_FAM_F16P, v.sw, v.fl>()>(grid, block, c.lds, c.lds_max, st, a);
         }
-        if (done) return (int)hipGetLastError();
-        if (a.p24) return DUDF_E_UNSUPPORTED;                  // a 24-bit workspace has no other kernels
-    }
-    // ... and the Hessian quads' sweeps (bit 5, DUDF_SPLIT_QUADS; the jets stay on bf16x6).  All of a workspace's or none:
-    // the forward sweep leaves zbound for the other three, the adjoint forward sweep ebound for the adjoint reverse one.
-    if (which >= SWEEP_FWD_H && which <= SWEEP_ADJ_REV_H && (a.split & 32) && a.zbound && a.L <= kMaxLdsBiasLayers) {
-        constexpr size_t w3 = 3 * GeoB<H, 1>::CHUNKB;
-        const size_t smem_q = w3 + kMaxAmaxLayers * sizeof(unsigned);
-        const size_t smem_fq = w3 + (size_t)a.L * H * sizeof(float) + kMaxAmaxLayers * sizeof(unsigned);
-        constexpr size_t smem_fqmax = w3 + kMaxLdsBiasLayers * H * sizeof(float) + kMaxAmaxLayers * sizeof(unsigned);
-        bool done = true;
-        if (a.p24 && ((which == SWEEP_FWD_H && !a.store_s) || (which == SWEEP_REV_H && !a.train))) return DUDF_E_UNSUPPORTED;
-        if (which == SWEEP_FWD_H) { if (a.store_s) DUDF_GO_HP(SWEEP_FWD_H, 1, sweep_f16_np_kernel, sweep_f16r_np_kernel, sweep_f16p_np_kernel, smem_fqmax, smem_fq); else DUDF_GO_H(SWEEP_FWD_H, 0, sweep_f16_np_kernel, smem_fqmax, smem_fq); }
-        else if (which == SWEEP_REV_H) { if (a.train) DUDF_GO_HP(SWEEP_REV_H, 1, sweep_f16_np_kernel, sweep_f16r_np_kernel, sweep_f16p_np_kernel, smem_q, smem_q); else DUDF_GO_H(SWEEP_REV_H, 0, sweep_f16_np_kernel, smem_q, smem_q); }
-        else if (which == SWEEP_ADJ_FWD_H && a.ebound) DUDF_GO_HP(SWEEP_ADJ_FWD_H, 0, sweep_f16_np_kernel, sweep_f16r_np_kernel, sweep_f16p_np_kernel, smem_q, smem_q);
-        else if (which == SWEEP_ADJ_REV_H && a.ebound) DUDF_GO_HP(SWEEP_ADJ_REV_H, 0, sweep_f16_np_kernel, sweep_f16r_np_kernel, sweep_f16p_np_kernel, smem_q, smem_q);
-        else done = false;
-        if (done) return (int)hipGetLastError();
-    }
-    if (a.p24 && which != SWEEP_FWD_J) return DUDF_E_UNSUPPORTED;     // (the jets stash nothing)
-    if (which == SWEEP_FWD_J && (a.split & 32) && a.L <= kMaxLdsBiasLayers) {      // the third-order jets (curvature query): nothing stashed
-        constexpr size_t w3 = 3 * GeoB<H, 1>::CHUNKB;
-        const size_t smem_j = w3 + (size_t)a.L * H * sizeof(float) + kMaxAmaxLayers * sizeof(unsigned);
-        constexpr size_t smem_jmax = w3 + kMaxLdsBiasLayers * H * sizeof(float) + kMaxAmaxLayers * sizeof(unsigned);
-        DUDF_GO_H(SWEEP_FWD_J, 0, sweep_f16_np_kernel, smem_jmax, smem_j);
-        return (int)hipGetLastError();
-    }
-#undef DUDF_GO_HP
-#undef DUDF_GO_H
-    switch (which) {
-        case SWEEP_FWD:
-            if (a.store_s && a.store_c) DUDF_GO_B(SWEEP_FWD, 3);
-            else if (a.store_c) DUDF_GO_B(SWEEP_FWD, 2);          // value + df/dx query: only cos is read again
-            else if (!a.store_s) DUDF_GO_B(SWEEP_FWD, 0);         // value-only query
-            else return DUDF_E_BADMODE;
-            break;
-        case SWEEP_REV:
-            if (a.train) DUDF_GO_B(SWEEP_REV, 1); else DUDF_GO_B(SWEEP_REV, 0);
-            break;
-        case SWEEP_ADJ_FWD: DUDF_GO_B(SWEEP_ADJ_FWD, 0); break;
-        case SWEEP_ADJ_REV:
-            if (a.have_e) DUDF_GO_B(SWEEP_ADJ_REV, 1); else DUDF_GO_B(SWEEP_ADJ_REV, 0);
-            break;
-        // Hessian quads: same kernel, the tails couple the 4 lanes of a quad by DPP
-        case SWEEP_FWD_H:
-            if (a.store_s) DUDF_GO_B(SWEEP_FWD_H, 1); else DUDF_GO_B(SWEEP_FWD_H, 0);   // queries do not need h | hdot again
-            break;
-        case SWEEP_REV_H:
-            if (a.train) DUDF_GO_B(SWEEP_REV_H, 1); else DUDF_GO_B(SWEEP_REV_H, 0);
-            break;
-        case SWEEP_ADJ_FWD_H: DUDF_GO_B(SWEEP_ADJ_FWD_H, 0); break;
-        case SWEEP_ADJ_REV_H: DUDF_GO_B(SWEEP_ADJ_REV_H, 0); break;
-        case SWEEP_FWD_J: DUDF_GO_B(SWEEP_FWD_J, 0); break;      // third-order Taylor jets (curvature query), nothing stashed
-        default: return DUDF_E_UNSUPPORTED;
-    }
-#undef DUDF_GO_B
-    return (int)hipGetLastError();
+        return (int)DUDF_E_UNSUPPORTED;
+    });
 }
 
 
@@ -1737,102 +1622,23 @@ __global__ __launch_bounds__(64 * NWB) void sweep_w16_kernel(SweepArgs a) { swee
 template <int SW, int FL>
 __global__ __launch_bounds__(64 * NWB) void sweep_w16r_kernel(SweepArgs a) { sweep_w_body<SW, FL, 1, 6>(a); }
 
-int launch_w(int which, const SweepArgs& a, hipStream_t st) {
-    using G = GeoW;
-    const size_t smem = 3 * G::CHUNKB + kMaxAmaxLayers * sizeof(unsigned);
+static_assert(dudf_wide_chunk_bytes(3) == GeoWT<0>::CHUNKB && dudf_wide_chunk_bytes(2) == GeoWT<1>::CHUNKB, "dudf_variants.h: LDS sizes");
+int launch_w(const SweepChoice& c, const SweepArgs& a, hipStream_t st) {
     if (a.ntiles <= 0) return 0;
     const int ntb = (a.ntiles * TILE + TILEB - 1) / TILEB;
-    const int grid = ntb < 256 ? ntb : 256;
-    hipError_t e = hipSuccess;
-#define DUDF_GO_W(SW, FL)                                                                                   \
-    do {                                                                                                    \
-        if (SW <= SWEEP_ADJ_REV) dudf_note_products(PROF_SWEEP_FWD + SW, 6);                                \
-        static bool attr_done = false;                                                                      \
-        if (!attr_done) {                                                                                   \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_w_kernel<SW, FL>),                 \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                 \
-            if (e != hipSuccess) return (int)e;                                                             \
-            attr_done = true;                                                                               \
-        }                                                                                                   \
-        hipLaunchKernelGGL((sweep_w_kernel<SW, FL>), dim3(grid), dim3(G::NTHR), smem, st, a);               \
-    } while (0)
-#define DUDF_GO_W16(SW, FL)                                                                                 \
-    do {                                                                                                    \
-        if (SW <= SWEEP_ADJ_REV) dudf_note_products(PROF_SWEEP_FWD + SW, 3);                                \
-        static bool attr_done = false;                                                                      \
-        const size_t smem16 = 3 * GeoWT<1>::CHUNKB + kMaxAmaxLayers * sizeof(unsigned);                     \
-        if (!attr_done) {                                                                                   \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_w16_kernel<SW, FL>),               \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem16);               \
-            if (e != hipSuccess) return (int)e;                                                             \
-            attr_done = true;                                                                               \
-        }                                                                                                   \
-        hipLaunchKernelGGL((sweep_w16_kernel<SW, FL>), dim3(grid), dim3(G::NTHR), smem16, st, a);           \
-    } while (0)
-#define DUDF_GO_W16R(SW, FL)                                                                                \
-    do {                                                                                                    \
-        if (SW <= SWEEP_ADJ_REV) dudf_note_products(PROF_SWEEP_FWD + SW, 3);                                \
-        static bool attr_done = false;                                                                      \
-        const size_t smem16 = 3 * GeoWT<1>::CHUNKB + kMaxAmaxLayers * sizeof(unsigned);                     \
-        if (!attr_done) {                                                                                   \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_w16r_kernel<SW, FL>),              \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem16);               \
-            if (e != hipSuccess) return (int)e;                                                             \
-            attr_done = true;                                                                               \
-        }                                                                                                   \
-        hipLaunchKernelGGL((sweep_w16r_kernel<SW, FL>), dim3(grid), dim3(G::NTHR), smem16, st, a);          \
-    } while (0)
-    // fp16x3 or bf16x6: plain columns by their bit of the split mask, quads and jets by bit 5 (DUDF_SPLIT_QUADS)
-    const bool h16 = which <= SWEEP_ADJ_REV ? ((a.split >> which) & 1) != 0 : (a.split & 32) != 0;
-    if (a.p24) {                                     // a training workspace with R, E, C at 24 bits: its training variants only
-        if (a.p24 != 6 || !h16) return DUDF_E_UNSUPPORTED;
-        switch (which) {
-            case SWEEP_FWD: if (a.store_s && a.store_c) DUDF_GO_W16R(SWEEP_FWD, 3); else return DUDF_E_UNSUPPORTED; break;
-            case SWEEP_REV: if (a.train) DUDF_GO_W16R(SWEEP_REV, 1); else return DUDF_E_UNSUPPORTED; break;
-            case SWEEP_ADJ_FWD: DUDF_GO_W16R(SWEEP_ADJ_FWD, 0); break;
-            case SWEEP_ADJ_REV: if (a.have_e) DUDF_GO_W16R(SWEEP_ADJ_REV, 1); else DUDF_GO_W16R(SWEEP_ADJ_REV, 0); break;
-            case SWEEP_FWD_H: if (a.store_s) DUDF_GO_W16R(SWEEP_FWD_H, 1); else return DUDF_E_UNSUPPORTED; break;
-            case SWEEP_REV_H: if (a.train) DUDF_GO_W16R(SWEEP_REV_H, 1); else return DUDF_E_UNSUPPORTED; break;
-            case SWEEP_ADJ_FWD_H: DUDF_GO_W16R(SWEEP_ADJ_FWD_H, 0); break;
-            case SWEEP_ADJ_REV_H: DUDF_GO_W16R(SWEEP_ADJ_REV_H, 0); break;
-            default: return DUDF_E_UNSUPPORTED;
+    const dim3 grid(ntb < 256 ? ntb : 256), block(GeoW::NTHR);
+    return dudf_with_variant(kWideVariants, c.sw, c.fl, [&](auto i) {
+        constexpr DudfVariant v = kWideVariants[decltype(i)::value];
+        if (c.family == DUDF_FAM_W) return dudf_launch_kernel<&sweep_w_kernel<v.sw, v.fl>>(grid, block, c.lds, c.lds_max, st, a);
+        if (c.family == DUDF_FAM_W16) return dudf_launch_kernel<&sweep_w16_kernel<v.sw, v.fl>>(grid, block, c.lds, c.lds_max, st, a);
+        if constexpr (v.p24 != 0) {
+            if (c.family == DUDF_FAM_W16R) return dudf_launch_kernel<&sweep_w16r_kernel<v.sw, v.fl>>(grid, block, c.lds, c.lds_max, st, a);
         }
-        return (int)hipGetLastError();
-    }
-#define DUDF_W(SW, FL) do { if (h16) DUDF_GO_W16(SW, FL); else DUDF_GO_W(SW, FL); } while (0)
-    // The stash array a layer's outputs travel through is written in every variant (wide_in): the forward sweeps always
-    // store h_l (a value-only query: nothing else), the query variants of the reverse sweeps park q_l in S.
-    switch (which) {
-        case SWEEP_FWD: if (a.store_c) DUDF_W(SWEEP_FWD, 3); else DUDF_W(SWEEP_FWD, 1); break;
-        case SWEEP_REV: if (a.train) DUDF_W(SWEEP_REV, 1); else DUDF_W(SWEEP_REV, 0); break;
-        case SWEEP_ADJ_FWD: DUDF_W(SWEEP_ADJ_FWD, 0); break;
-        case SWEEP_ADJ_REV: if (a.have_e) DUDF_W(SWEEP_ADJ_REV, 1); else DUDF_W(SWEEP_ADJ_REV, 0); break;
-        case SWEEP_FWD_H: DUDF_W(SWEEP_FWD_H, 1); break;
-        case SWEEP_REV_H: if (a.train) DUDF_W(SWEEP_REV_H, 1); else DUDF_W(SWEEP_REV_H, 0); break;
-        case SWEEP_ADJ_FWD_H: DUDF_W(SWEEP_ADJ_FWD_H, 0); break;
-        case SWEEP_ADJ_REV_H: DUDF_W(SWEEP_ADJ_REV_H, 0); break;
-        case SWEEP_FWD_J: DUDF_W(SWEEP_FWD_J, 0); break;
-        default: return DUDF_E_UNSUPPORTED;
-    }
-#undef DUDF_W
-#undef DUDF_GO_W16
-#undef DUDF_GO_W16R
-#undef DUDF_GO_W
-    return (int)hipGetLastError();
+        return (int)DUDF_E_UNSUPPORTED;
+    });
 }
 
 }  // namespace
-
-// ... and with THESE stash flags; run_sweep asks before it opens the profiling scope of a launch.  (Round 2: the 512-wide kernel
-// was built for the training variants only; now every variant is.)
-bool dudf_sweep_bf16_handles(int which, int H, int L, const SweepArgs& a) {
-    (void)a;
-    return dudf_sweep_bf16_supported(which, H, L);
-}
-
-bool dudf_sweep_bf16_supported(int which, int H, int L) {
-    return (H == 512 || H == 256 || H == 128) && L >= 2 && which >= SWEEP_FWD && which <= SWEEP_FWD_J;
-}
 
 namespace {
 // Estimated duration of one part of a pair launch, in full plain-column passes: every workgroup walks ceil(ng / nb) groups of 16
@@ -1844,36 +1650,12 @@ double pair_est(int ng, int nb, double c) {
     const double part = rem == 0 ? 0.0 : (rem <= NWB / 2 ? 0.55 : 0.55 + 0.45 * (rem - NWB / 2) / (NWB / 2));
     return c * (full + part);
 }
-constexpr size_t kPairSmemQ = 3 * GeoB<256, 0>::CHUNKB + kMaxAmaxLayers * sizeof(unsigned);                    // the quad body's LDS
-constexpr size_t kPairSmemP = 3 * GeoB<256, 1>::CHUNKB + kMaxLdsBiasLayers * 256 * sizeof(float) + kOctBytes;     // the plain body's, at most
-constexpr size_t kPairSmemMax = kPairSmemQ > kPairSmemP ? kPairSmemQ : kPairSmemP;
-static_assert(kPairSmemMax <= 160 * 1024, "LDS of a CU");
-template <int SWQ, int FLQ, int SWP, int FLP, int SPQ, int P24 = 0>
-int launch_pair_t(const SweepArgs& aq, const SweepArgs& ap, size_t smem, int nbq, int nbp, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_pair_kernel<256, SWQ, FLQ, SWP, FLP, SPQ, P24>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)kLdsCu);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((sweep_pair_kernel<256, SWQ, FLQ, SWP, FLP, SPQ, P24>), dim3(nbq + nbp), dim3(GeoB<256>::NTHR), smem, st, aq, ap, nbq);
-    return (int)hipGetLastError();
-}
 }  // namespace
 
-// One launch for the quad columns (variant base + 4, bf16x6) AND the plain columns (variant base, fp16x3) of a training sweep
-// at H = 256; DUDF_E_UNSUPPORTED when the combination has no pair kernel (the caller then launches them one after the other).
-// Option pair_launch = 0 switches it off (A/B).
-int dudf_launch_sweep_pair(int base, int H, const SweepArgs& aq0, const SweepArgs& ap0, hipStream_t st) {
-    if (!dudf_opt_pair_launch() || H != 256 || base < SWEEP_FWD || base > SWEEP_ADJ_REV || aq0.ntiles <= 0 || ap0.ntiles <= 0) return DUDF_E_UNSUPPORTED;
-    if (!((ap0.split >> base) & 1) || ap0.L < 2 || ap0.L > kMaxLdsBiasLayers) return DUDF_E_UNSUPPORTED;
-    // the training variants only (a query has no plain columns beside its quads)
-    if (base == SWEEP_FWD && !(aq0.store_s && ap0.store_s && ap0.store_c)) return DUDF_E_UNSUPPORTED;
-    if (base == SWEEP_REV && !(aq0.train && ap0.train)) return DUDF_E_UNSUPPORTED;
-    if (base == SWEEP_ADJ_REV && !(ap0.have_e && ap0.ebound && ((ap0.split >> SWEEP_ADJ_FWD) & 1))) return DUDF_E_UNSUPPORTED;
-    const int ngq = aq0.ntiles * (TILE / 16), ngp = ap0.ntiles * (TILE / 16);
+// One launch for the quad columns (variant base + 4) AND the plain columns (variant base, fp16x3) of a training sweep at H = 256
+// (dudf_choose_pair; option pair_launch = 0 switches it off).  The host splits the 256 workgroups so that both parts finish together.
+int dudf_launch_sweep_pair(const SweepChoice& c, const SweepArgs& aq, const SweepArgs& ap, hipStream_t st) {
+    const int ngq = aq.ntiles * (TILE / 16), ngp = ap.ntiles * (TILE / 16);
     const int tq = (ngq + NWB - 1) / NWB, tp = (ngp + NWB - 1) / NWB;          // passes of 8 groups
     int nbq, nbp;
     if (tq + tp <= 256) { nbq = tq; nbp = tp; }
@@ -1886,52 +1668,26 @@ int dudf_launch_sweep_pair(int base, int H, const SweepArgs& aq0, const SweepArg
         }
         nbp = 256 - nbq;
     }
-    DudfProfScope prof(PROF_SWEEP_FWD + base, st);
-    dudf_note_products(PROF_SWEEP_FWD + base, 3);        // the plain columns of a pair launch are always fp16x3
-    SweepArgs aq = aq0, ap = ap0;
-    aq.clk = nullptr;
-    ap.clk = dudf_prof_clk(PROF_SWEEP_FWD + base);
-    constexpr size_t w3 = 3 * GeoB<256, 1>::CHUNKB;
-    const size_t sp = w3 + (base == SWEEP_FWD ? (size_t)ap.L * 256 * sizeof(float) : kMaxAmaxLayers * sizeof(unsigned)) + kOctBytes;
-    const bool q16 = (aq.split & 32) && aq.zbound && aq.ebound;       // the quads on fp16x3 as well (their LDS is then the smaller part)
-    const size_t sq = q16 ? w3 + (base == SWEEP_FWD ? (size_t)aq.L * 256 * sizeof(float) : 0) + kMaxAmaxLayers * sizeof(unsigned) : kPairSmemQ;
-    const size_t smem = sq > sp ? sq : sp;
-    if (ap.p24 != aq.p24 || (ap.p24 && !q16)) return DUDF_E_UNSUPPORTED;   // (the 24-bit stash needs the quads on fp16x3 too: dudf_stash_p24_enabled)
-    if (ap.p24 == 7) switch (base) {
-        case SWEEP_FWD: return launch_pair_t<SWEEP_FWD_H, 1, SWEEP_FWD, 3, 1, 7>(aq, ap, smem, nbq, nbp, st);
-        case SWEEP_REV: return launch_pair_t<SWEEP_REV_H, 1, SWEEP_REV, 1, 1, 7>(aq, ap, smem, nbq, nbp, st);
-        case SWEEP_ADJ_FWD: return launch_pair_t<SWEEP_ADJ_FWD_H, 0, SWEEP_ADJ_FWD, 0, 1, 7>(aq, ap, smem, nbq, nbp, st);
-        default: return launch_pair_t<SWEEP_ADJ_REV_H, 0, SWEEP_ADJ_REV, 1, 1, 7>(aq, ap, smem, nbq, nbp, st);
-    }
-    if (ap.p24 == 6) switch (base) {
-        case SWEEP_FWD: return launch_pair_t<SWEEP_FWD_H, 1, SWEEP_FWD, 3, 1, 6>(aq, ap, smem, nbq, nbp, st);
-        case SWEEP_REV: return launch_pair_t<SWEEP_REV_H, 1, SWEEP_REV, 1, 1, 6>(aq, ap, smem, nbq, nbp, st);
-        case SWEEP_ADJ_FWD: return launch_pair_t<SWEEP_ADJ_FWD_H, 0, SWEEP_ADJ_FWD, 0, 1, 6>(aq, ap, smem, nbq, nbp, st);
-        default: return launch_pair_t<SWEEP_ADJ_REV_H, 0, SWEEP_ADJ_REV, 1, 1, 6>(aq, ap, smem, nbq, nbp, st);
-    }
-    if (ap.p24) return DUDF_E_UNSUPPORTED;
-    if (q16) switch (base) {
-        case SWEEP_FWD: return launch_pair_t<SWEEP_FWD_H, 1, SWEEP_FWD, 3, 1>(aq, ap, smem, nbq, nbp, st);
-        case SWEEP_REV: return launch_pair_t<SWEEP_REV_H, 1, SWEEP_REV, 1, 1>(aq, ap, smem, nbq, nbp, st);
-        case SWEEP_ADJ_FWD: return launch_pair_t<SWEEP_ADJ_FWD_H, 0, SWEEP_ADJ_FWD, 0, 1>(aq, ap, smem, nbq, nbp, st);
-        default: return launch_pair_t<SWEEP_ADJ_REV_H, 0, SWEEP_ADJ_REV, 1, 1>(aq, ap, smem, nbq, nbp, st);
-    }
-    switch (base) {
-        case SWEEP_FWD: return launch_pair_t<SWEEP_FWD_H, 1, SWEEP_FWD, 3, 0>(aq, ap, smem, nbq, nbp, st);
-        case SWEEP_REV: return launch_pair_t<SWEEP_REV_H, 1, SWEEP_REV, 1, 0>(aq, ap, smem, nbq, nbp, st);
-        case SWEEP_ADJ_FWD: return launch_pair_t<SWEEP_ADJ_FWD_H, 0, SWEEP_ADJ_FWD, 0, 0>(aq, ap, smem, nbq, nbp, st);
-        default: return launch_pair_t<SWEEP_ADJ_REV_H, 0, SWEEP_ADJ_REV, 1, 0>(aq, ap, smem, nbq, nbp, st);
-    }
+    const dim3 grid(nbq + nbp), block(GeoB<256>::NTHR);
+    return dudf_with_variant(kPairVariants, c.sw, c.fl, [&](auto i) {
+        constexpr DudfVariant v = kPairVariants[decltype(i)::value];
+        auto go = [&](auto spq, auto p24) {
+            return dudf_launch_kernel<&sweep_pair_kernel<256, v.sw + 4, dudf_pair_flq(v.sw), v.sw, v.fl, decltype(spq)::value, decltype(p24)::value>>(
+                grid, block, c.lds, c.lds_max, st, aq, ap, nbq);
+        };
+        using std::integral_constant;
+        if (c.p24 == 7) return go(integral_constant<int, 1>{}, integral_constant<int, 7>{});
+        if (c.p24 == 6) return go(integral_constant<int, 1>{}, integral_constant<int, 6>{});
+        if (c.spq) return go(integral_constant<int, 1>{}, integral_constant<int, 0>{});
+        return go(integral_constant<int, 0>{}, integral_constant<int, 0>{});
+    });
 }
 
-int dudf_launch_sweep_bf16(int which, int H, const SweepArgs& a0, hipStream_t st) {
-    DudfProfScope prof(PROF_SWEEP_FWD + (which & 3), st);
-    SweepArgs a = a0;
-    a.clk = (which <= SWEEP_ADJ_REV) ? dudf_prof_clk(PROF_SWEEP_FWD + which) : nullptr;   // plain columns only
-    switch (H) {
-        case 256: return launch_b<256>(which, a, st);
-        case 128: return launch_b<128>(which, a, st);
-        case 512: return launch_w(which, a, st);
+int dudf_launch_sweep_bf16(const SweepChoice& c, const SweepArgs& a, hipStream_t st) {
+    switch (c.H) {
+        case 256: return launch_b<256>(c, a, st);
+        case 128: return launch_b<128>(c, a, st);
+        case 512: return launch_w(c, a, st);
         default: return DUDF_E_UNSUPPORTED;
     }
 }

@@ -1245,127 +1245,33 @@ __global__ __launch_bounds__(256) DUDF_NO_PK void wgrad_small_p24_kernel(WgradSm
     }
 }
 
+static_assert(KTP == 33 && NRING == 4 && KB == 16, "dudf_choose_wgrad: LDS sizes");
 template <int H>
-int launch_hidden(const WgradArgs& a, hipStream_t st) {
+int launch_hidden(const SweepChoice& c, const WgradArgs& a, hipStream_t st) {
     using W = WG<H>;
-    constexpr int NTHR = 64 * W::WO * W::WI;
-    const size_t smem = 4 * (size_t)(H / 4) * KTP * 4 * sizeof(float);   // 2 buffers x (X tile + Y tile)
-    const size_t smem_bf = (size_t)NRING * 2 * (H / 4) * KB * 4 * sizeof(float);   // ring of 4 x (X image + Y image)
-    const int nl = a.nj;
-    if (nl <= 0) return 0;
     const int tz = a.Hs / H, ntz = tz * tz;              // output tiles of a layer wider than the 256 x 256 tile
     // one resident workgroup per CU, a single round.  dudf_set_wgrad_max_workgroups (default 256) caps the grid: with more
     // than one rank the engine sets 240, so that an RCCL kernel queued behind the previous layer group finds free CUs
     // beside this GEMM (its workgroups fill the register file of the CUs they run on)
-    const int maxwg = dudf_wgrad_max_workgroups();
-    int nsplit = maxwg / (nl * ntz);
+    int nsplit = dudf_wgrad_max_workgroups() / (a.nj * ntz);
     if (nsplit > a.steps_total) nsplit = a.steps_total;
     if (nsplit < 1 || dudf_deterministic()) nsplit = 1;      // deterministic: one workgroup per weight tile, one add per element
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_hidden_kernel<H>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    // option wgrad_family = 1 selects the f32-input MFMA kernel (A/B testing); default: the 16-bit cores at fp32 accuracy
-    const bool use_f32 = dudf_opt_wgrad_family() == 1;
-    dudf_note_products(PROF_WGRAD_HIDDEN, use_f32 ? 1 : 6);         // (the fp16x3 branch below overrides)
-    if (a.p24 && (use_f32 || H != 256)) return DUDF_E_UNSUPPORTED;   // 24-bit operands: only the cooperative-split fp16x3 kernel reads them
-    if (use_f32) {
-        hipLaunchKernelGGL((wgrad_hidden_kernel<H>), dim3(nl, nsplit, ntz), dim3(NTHR), smem, st, a);
-    } else {
-        static bool attr2 = false;
-        if (!attr2) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_hidden_bf16_kernel<H>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_bf);
-            if (e != hipSuccess) return (int)e;
-            attr2 = true;
+    const dim3 grid(a.nj, nsplit, ntz), block(64 * W::WO * W::WI);
+    if (c.family == DUDF_FAM_WG_F32) return dudf_launch_kernel<&wgrad_hidden_kernel<H>>(grid, block, c.lds, c.lds_max, st, a);
+    if (c.family == DUDF_FAM_WG_BF16) return dudf_launch_kernel<&wgrad_hidden_bf16_kernel<H>>(grid, block, c.lds, c.lds_max, st, a);
+    if constexpr (H == 256) {                                // the cooperative-split kernels
+        if (c.family == DUDF_FAM_WG_F16P24 && c.fl == 25) return dudf_launch_kernel<&wgrad_hidden_f16p24_kernel<H, 25>>(grid, block, c.lds, c.lds_max, st, a);
+        if (c.family == DUDF_FAM_WG_F16P24) return dudf_launch_kernel<&wgrad_hidden_f16p24_kernel<H, 9>>(grid, block, c.lds, c.lds_max, st, a);
+        if (c.family == DUDF_FAM_WG_F16TR) return dudf_launch_kernel<&wgrad_hidden_f16tr_kernel<H, 9>>(grid, block, c.lds, c.lds_max, st, a);
+        if (c.family == DUDF_FAM_WG_BF16P) return dudf_launch_kernel<&wgrad_hidden_bf16p_kernel<H, 9>>(grid, block, c.lds, c.lds_max, st, a);
+        if (c.family == DUDF_FAM_WG_F16P && c.remap) {       // 2 x 2 tiles: a group's tiles on one XCD
+            WgradArgs b = a;
+            b.remap_nsplit = nsplit;
+            return dudf_launch_kernel<&wgrad_hidden_f16p_kernel<H, 9>>(dim3(((a.nj * nsplit + 7) / 8) * 32), block, c.lds, c.lds_max, st, b);
         }
-        // option wgrad_family = 2 keeps the per-wave split kernel for the 256-wide tiles (A/B testing)
-        const bool per_wave = dudf_opt_wgrad_family() == 2;
-        if constexpr (H == 256) {
-            if (a.p24 && per_wave) return DUDF_E_UNSUPPORTED;
-            if (!per_wave) {
-                static bool attr3 = false;
-                const size_t smem_p = 2 * 2 * 3 * (size_t)(H / 32) * 2 * (32 * 16 + 16);   // 2 buffers x (X | Y) x 3 pieces x blocks
-                if ((int64_t)(a.Hs / 4) * a.np * 16 >= (1ll << 32)) {       // beyond the 32-bit lane byte offsets of the staging loads:
-                    hipLaunchKernelGGL((wgrad_hidden_bf16_kernel<H>), dim3(nl, nsplit, ntz), dim3(NTHR), smem_bf, st, a);   // per-wave split
-                    return (int)hipGetLastError();
-                }
-                // The shipped body is VAR 9: conflict-free producer lanes + progress flags in LDS instead of the stage barrier (three
-                // image buffers, MFMAs first, split two images ahead, SIMD partners alternating on the matrix pipe).  Its
-                // barrier-synchronised predecessors (VAR 1, 3) and the static-priority variants are no longer instantiated:
-                // DESIGN.md Appendix A has their numbers.
-                constexpr int var = 9;
-                if (a.p24) {                                                      // 24-bit tile-major operands: their own build
-                    if (!(dudf_split_fp16() && a.amax && a.L <= 64 && var == 9 && ntz == 1)) return DUDF_E_UNSUPPORTED;
-                    dudf_note_products(PROF_WGRAD_HIDDEN, 3);
-                    static bool attr5 = false;
-                    const size_t smem_t = 3 * (size_t)(2 * 2 * 16 * 576) + 512;    // three buffers x (X | Y) x 2 pieces x 16 rows of 576 B + the flags
-                    const size_t smem_t4 = 4 * (size_t)(2 * 2 * 16 * 576) + 512;   // four (VAR bit 4)
-                    if (!attr5) {
-                        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_hidden_f16p24_kernel<H, 9>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_t);
-                        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_hidden_f16p24_kernel<H, 25>),
-                                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_t4);
-                        if (e != hipSuccess) return (int)e;
-                        attr5 = true;
-                    }
-                    if (dudf_opt_wgrad_buffers() == 4) hipLaunchKernelGGL((wgrad_hidden_f16p24_kernel<H, 25>), dim3(nl, nsplit, ntz), dim3(NTHR), smem_t4, st, a);
-                    else hipLaunchKernelGGL((wgrad_hidden_f16p24_kernel<H, 9>), dim3(nl, nsplit, ntz), dim3(NTHR), smem_t, st, a);
-                    return (int)hipGetLastError();
-                }
-                const bool tr = dudf_opt_wgrad_tr();
-                if (tr && dudf_split_fp16() && a.amax && a.L <= 64 && var == 9 && ntz == 1 && !dudf_deterministic()) {
-                    dudf_note_products(PROF_WGRAD_HIDDEN, 3);
-                    static bool attr6 = false;
-                    const size_t smem_t = 3 * (size_t)(2 * 2 * 16 * 576) + 512;
-                    if (!attr6) {
-                        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_hidden_f16tr_kernel<H, 9>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_t);
-                        if (e != hipSuccess) return (int)e;
-                        attr6 = true;
-                    }
-                    hipLaunchKernelGGL((wgrad_hidden_f16tr_kernel<H, 9>), dim3(nl, nsplit, ntz), dim3(NTHR), smem_t, st, a);
-                    return (int)hipGetLastError();
-                }
-                if (dudf_split_fp16() && a.amax && a.L <= 64 && var == 9) {       // fp16x3 (DUDF_SPLIT=bf16 keeps bf16x6)
-                    dudf_note_products(PROF_WGRAD_HIDDEN, 3);
-                    static bool attr4 = false;
-                    // (three image buffers here: the four-buffer form of the body, VAR bit 4, is 2-3 % SLOWER with fp32 operands —
-                    //  0.557 vs 0.543 ms at 256, 2.52 vs 2.46 ms at 512, profiles/r05_j_ab512.txt — and 2-3 % faster with 24-bit ones)
-                    const size_t smem_h = 3 * (size_t)(2 * 2 * (H / 32) * 2 * (32 * 16 + 16)) + 512;   // three buffers x (X | Y) x 2 pieces + the flags
-                    if (!attr4) {
-                        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_hidden_f16p_kernel<H, 9>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_h);
-                        if (e != hipSuccess) return (int)e;
-                        attr4 = true;
-                    }
-                    if (ntz == 4 && !dudf_deterministic()) {                       // 2 x 2 tiles: a group's tiles on one XCD
-                        WgradArgs b = a;
-                        b.remap_nsplit = nsplit;
-                        const int groups = nl * nsplit, grid1 = ((groups + 7) / 8) * 32;
-                        hipLaunchKernelGGL((wgrad_hidden_f16p_kernel<H, 9>), dim3(grid1), dim3(NTHR), smem_h, st, b);
-                    } else {
-                        hipLaunchKernelGGL((wgrad_hidden_f16p_kernel<H, 9>), dim3(nl, nsplit, ntz), dim3(NTHR), smem_h, st, a);
-                    }
-                    return (int)hipGetLastError();
-                }
-                if (!attr3) {                                                       // bf16x6 (DUDF_SPLIT=bf16), same body
-                    const size_t smem_cs = smem_p / 2 * 3 + 512;                     // three buffers + the flags
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_hidden_bf16p_kernel<H, 9>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_cs);
-                    if (e != hipSuccess) return (int)e;
-                    attr3 = true;
-                }
-                hipLaunchKernelGGL((wgrad_hidden_bf16p_kernel<H, 9>), dim3(nl, nsplit, ntz), dim3(NTHR), smem_p / 2 * 3 + 512, st, a);
-                return (int)hipGetLastError();
-            }
-        }
-        hipLaunchKernelGGL((wgrad_hidden_bf16_kernel<H>), dim3(nl, nsplit, ntz), dim3(NTHR), smem_bf, st, a);
+        if (c.family == DUDF_FAM_WG_F16P) return dudf_launch_kernel<&wgrad_hidden_f16p_kernel<H, 9>>(grid, block, c.lds, c.lds_max, st, a);
     }
-    return (int)hipGetLastError();
+    return DUDF_E_UNSUPPORTED;
 }
 
 }  // namespace
@@ -1391,13 +1297,14 @@ int dudf_launch_wgrad(const DudfLayout& lo, float* ws, float* dtheta, int have_g
     int rc = 0;
     if (a.nj > 0) {
         DudfProfScope prof(PROF_WGRAD_HIDDEN, st);
-        switch (lo.H) {
-            case 32: rc = launch_hidden<32>(a, st); break;
-            case 64: rc = launch_hidden<64>(a, st); break;
-            case 128: rc = launch_hidden<128>(a, st); break;
-            case 256: rc = launch_hidden<256>(a, st); break;
-            case 512: rc = launch_hidden<256>(a, st); break;      // 2 x 2 output tiles of 256 x 256
-            default: return DUDF_E_BADCFG;
+        const SweepChoice c = dudf_choose_wgrad(WgradRequest{lo.H, lo.L, a.p24, lo.np}, dudf_options());
+        if (c.status) return c.status;
+        dudf_note_products(PROF_WGRAD_HIDDEN, c.products);
+        switch (c.H) {
+            case 32: rc = launch_hidden<32>(c, a, st); break;
+            case 64: rc = launch_hidden<64>(c, a, st); break;
+            case 128: rc = launch_hidden<128>(c, a, st); break;
+            default: rc = launch_hidden<256>(c, a, st); break;
         }
     }
     if (rc) return rc;

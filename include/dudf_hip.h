@@ -349,6 +349,18 @@ int dudf_debug_read_stash(const dudf_net_cfg* cfg, int which, int layer, int cha
  * quarter's 256-byte segment is exactly two cache lines (tests/test_cabi_symbols.py holds the layout to that). */
 int dudf_debug_stash_layout(const dudf_net_cfg* cfg, int64_t n, int64_t n_hess, int64_t* out);
 
+/* Host-only diagnostic (nothing is launched): the kernel a launch of this workspace gets under the CURRENT options.
+ * which: 0..3 the forward / reverse / adjoint forward / adjoint reverse sweep of the plain columns, 4..7 of the Hessian quads,
+ *        8 the third-order jets; | DUDF_CHOICE_PAIR (0..3 only): the one-grid launch of quads + plain columns — DUDF_E_UNSUPPORTED
+ *        means the two ranges are launched one after the other; DUDF_CHOICE_WGRAD: the hidden layers' weight-gradient GEMM.
+ * flags: 1 = the forward sweep keeps h, 2 = keeps cos, 4 = training stores, 8 = the adjoint forward sweep ran (df/dx terms),
+ *        16 = a query workspace (dudf_workspace_bytes_query) instead of a training one.
+ * name: the kernel's name as a profiler prints it, without namespace and argument list, e.g. sweep_f16p_np_kernel<256,0,3>.
+ * Returns 0, or the error the launch would return (DUDF_E_UNSUPPORTED / DUDF_E_BADMODE; `name` is then empty). */
+#define DUDF_CHOICE_PAIR 16
+#define DUDF_CHOICE_WGRAD (-1)
+int dudf_debug_kernel_choice(const dudf_net_cfg* cfg, int64_t n, int64_t n_hess, int which, int flags, char* name, size_t name_len);
+
 /* Format of the stash a training workspace of this network and batch keeps between the sweeps and the weight-gradient GEMM
  * (the activations `backward()` needs — what autograd saves for reference src/model.py:116-135 / src/diff_operators.py:208-212),
  * as a bit mask of the arrays held at 24 bits, 12 bytes per 4 values, tile-major [layer][feature/16][column/16][64 lanes][3 dwords]:

@@ -16,6 +16,16 @@ def emit_asm(src, out, flags=()):
                     "--cuda-device-only", *flags, src, "-o", out], check=True, stderr=subprocess.DEVNULL)
 
 
+def variant_table(name):
+    """The built (SW, FL, p24) variants of a kernel family: the instantiation table `name` of csrc/dudf_variants.h."""
+    import os
+    hdr = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "diffudf_amd", "csrc", "dudf_variants.h")
+    m = re.search(r"constexpr\s+DudfVariant\s+%s\s*\[\s*\]\s*=\s*\{(.*?)\}\s*;" % name, open(hdr).read(), re.S)
+    rows = re.findall(r"\{\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)\s*\}", m.group(1)) if m else []
+    assert rows, "no table `%s` of {sw, fl, p24} rows in %s" % (name, hdr)
+    return [tuple(int(v) for v in r) for r in rows]
+
+
 def analyse(asm_path):
     txt = open(asm_path).read()
     out = {}

@@ -8,10 +8,14 @@ import pytest
 
 import sys, os as _os
 sys.path.insert(0, _os.path.dirname(_os.path.abspath(__file__)))
-from isa_contract import analyse, analyse_bf16, analyse_f16, analyse_wgrad_presplit, emit_asm
+from isa_contract import analyse, analyse_bf16, analyse_f16, analyse_wgrad_presplit, emit_asm, variant_table
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BF16_SRC = os.path.join(REPO, "diffudf_amd", "csrc", "dudf_sweep_bf16.hip")
+# the built (SW, FL) variants of the 256-wide bf16x6 / fp16x3 kernels, and those with builds for a 24-bit stash: the instantiation
+# table the launchers dispatch through (tests/test_kernel_choice.py pins its contents)
+SWEEP_KEYS = {(sw, fl) for sw, fl, p24 in variant_table("kSweepVariants")}
+P24_KEYS = {(sw, fl) for sw, fl, p24 in variant_table("kSweepVariants") if p24}
 
 
 @pytest.fixture(scope="module")
@@ -49,8 +53,7 @@ def test_bf16_sweep_wait_counts(tmp_path, bf16_asm):
     traffic in flight (a larger N would let a wave read a weight chunk that has not landed; a smaller one only
     stalls), the idle-wave loop waits for all but its newest pieces, and nothing spills at 2 waves per SIMD."""
     src = os.path.join(REPO, "diffudf_amd", "csrc", "dudf_sweep_bf16.hip")
-    keys = {(0, 3), (0, 2), (0, 0), (1, 1), (1, 0), (2, 0), (3, 1), (3, 0),
-            (4, 1), (4, 0), (5, 1), (5, 0), (6, 0), (7, 0), (8, 0)}                        # + the Hessian-quad variants
+    keys = SWEEP_KEYS                                                                      # + the Hessian-quad variants
     # The shipped kernels hold BOTH halves' program orders behind a wave-uniform branch (waves 0-3: DMA pieces and
     # operand loads at the top of a step, tail early; waves 4-7: MFMAs first, then DMA pieces, loads and tail).  The
     # count is a property of each order: check each one in a build where that order is the only one (straight-line steps).
@@ -97,8 +100,7 @@ def test_f16_sweep_wait_counts(tmp_path, bf16_asm):
     for force in (0, 1):
         asm = bf16_asm[f"late{force}"]
         res = analyse_f16(asm)
-        assert set(res) == {(0, 3), (0, 2), (0, 0), (1, 1), (1, 0), (2, 0), (3, 1), (3, 0),
-                            (4, 1), (4, 0), (5, 1), (5, 0), (6, 0), (7, 0), (8, 0)}, sorted(res)   # + the Hessian quads' training / query sweeps, the jets
+        assert set(res) == SWEEP_KEYS, sorted(res)   # + the Hessian quads' training / query sweeps, the jets
         for key, v in res.items():
             assert len(v["waits"]) >= 8, (force, key, v["waits"])
             for n, late, slack in v["waits"]:
@@ -107,10 +109,10 @@ def test_f16_sweep_wait_counts(tmp_path, bf16_asm):
             # strict (the other sweeps' operand waits, placed by the compiler, retire the older DMA pieces anyway)
             if key[0] == 0 and force == 0:
                 assert sum(1 for n, late, slack in v["waits"] if slack == 0) >= 7, (force, key, v["waits"])
-    # the builds that keep stash arrays at 24 bits (training variants of the plain columns and of the quads) — f16r: R, E and C (the
-    # default stash of 256-wide networks), f16p: S, Q, A, Z as well (opt-in): same step structure, dwordx3 stash accesses — the
+    # the builds that keep stash arrays at 24 bits (training variants of the plain columns and of the quads) — f16r: R, E and C (stash
+    # mask 6), f16p: S, Q, A, Z as well (mask 7, the default of 256-wide networks): same step structure, dwordx3 stash accesses — the
     # same replay must hold
-    p24_keys = {(0, 3), (1, 1), (2, 0), (3, 1), (3, 0), (4, 1), (5, 1), (6, 0), (7, 0)}
+    p24_keys = P24_KEYS
     for fam in ("f16r", "f16p"):
         for force in (0, 1):
             res = analyse_f16(bf16_asm[f"late{force}"], family=fam)
