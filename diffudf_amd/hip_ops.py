@@ -832,3 +832,86 @@ def render_pass(cfg, theta, noise, rotation, camera_position, network_config, re
     rays, t0, mask = render_setup_rays(rc_['height'], rc_['width'], rc_['fov'], noise, rotation, camera_position,
                                        rc_.get('planes', [1, -1, 1, -1, 1, -1]), accumulator.device)
     return render_traced(cfg, theta, rays, t0, mask, network_config, rendering_config, lut, accumulator)[1]
+
+
+# ---- Chamfer distance / normal consistency (reference cuantitative.py:10-19, :99-100; csrc/dudf_chamfer.hip) -------------------
+def _rows3(t, what, dtype):
+    if not torch.is_tensor(t) or t.device.type != "cuda":
+        raise _lib.DudfError(f"{what} must be a CUDA tensor (got {getattr(t, 'device', type(t).__name__)}); the HIP path has no CPU fallback")
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise _lib.DudfError(f"{what} must have shape (n,3); got {tuple(t.shape)}")
+    return t.to(dtype).contiguous()
+
+
+def _scratch(nbytes, device):
+    buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    assert buf.data_ptr() % 256 == 0
+    return buf
+
+
+def nearest_points(x, y, norm=2, want_dist=True, want_idx=True):
+    """For every row of x (n,3) the nearest row of y (m,3) — `knn_points(x, y, norm=norm, K=1)` of pytorch3d: (dist (n,) float32,
+    idx (n,) int64).  norm 2: SQUARED Euclidean distance; norm 1: L1 distance.  Smallest index among ties; bit-reproducible."""
+    lib = _lib.load()
+    x = _rows3(x, "nearest_points: x", torch.float32); y = _rows3(y, "nearest_points: y", torch.float32)
+    if y.device != x.device:
+        raise _lib.DudfError("nearest_points: x and y live on different devices")
+    n, m, dev = x.shape[0], y.shape[0], x.device
+    dist = torch.empty(n, dtype=torch.float32, device=dev) if want_dist else None
+    idx = torch.empty(n, dtype=torch.int64, device=dev) if want_idx else None
+    nbytes = int(lib.dudf_nearest_workspace_bytes(n))
+    ws = _scratch(nbytes, dev)
+    with torch.cuda.device(dev):
+        rc = lib.dudf_nearest_points(_ptr(x), n, _ptr(y), m, int(norm), _ptr(dist), _ptr(idx), _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "dudf_nearest_points")
+    return dist, idx
+
+
+def chamfer_terms(dist, idx, x_normals=None, y_normals=None, out=None):
+    """(2,) float64 CUDA tensor: sum of dist and sum of 1 - |cos(x_normals[p], y_normals[idx[p]])| (the second stays 0 without
+    normals).  Double accumulation in a fixed order: bit-reproducible."""
+    lib = _lib.load()
+    if not torch.is_tensor(dist) or not dist.is_cuda or dist.dtype != torch.float32 or dist.dim() != 1 or not dist.is_contiguous():
+        raise _lib.DudfError("chamfer_terms: dist must be a contiguous float32 (n,) CUDA tensor")
+    n, dev, m = dist.shape[0], dist.device, 0
+    if (x_normals is None) != (y_normals is None):
+        raise _lib.DudfError("chamfer_terms: x_normals and y_normals come together")
+    if x_normals is not None:
+        x_normals = _rows3(x_normals, "chamfer_terms: x_normals", torch.float32)
+        y_normals = _rows3(y_normals, "chamfer_terms: y_normals", torch.float32)
+        if idx is None or idx.dtype != torch.int64 or idx.shape != dist.shape or not idx.is_cuda or not idx.is_contiguous():
+            raise _lib.DudfError("chamfer_terms: idx must be a contiguous int64 (n,) CUDA tensor")
+        if x_normals.shape[0] != n:
+            raise _lib.DudfError("chamfer_terms: x_normals must have one row per distance")
+        m = y_normals.shape[0]
+    if out is None:
+        out = torch.zeros(2, dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or out.numel() != 2 or not out.is_cuda or not out.is_contiguous():
+        raise _lib.DudfError("chamfer_terms: out must be a contiguous float64 CUDA tensor of 2")
+    nbytes = int(lib.dudf_chamfer_terms_workspace_bytes(n))
+    ws = _scratch(nbytes, dev)
+    with torch.cuda.device(dev):
+        rc = lib.dudf_chamfer_terms(_ptr(dist), _ptr(idx) if x_normals is not None else _ptr(None), n, _ptr(x_normals), _ptr(y_normals),
+                                    m, _ptr(out), _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "dudf_chamfer_terms")
+    return out
+
+
+def vertex_normals(vertices, faces):
+    """(V,3) float32 area-weighted unit vertex normals of a triangle mesh — open3d's `compute_vertex_normals(normalized=True)`
+    (reference cuantitative.py:99-100).  vertices (V,3) float64 and faces (F,3) int64 CUDA tensors (other dtypes are converted)."""
+    lib = _lib.load()
+    vertices = _rows3(vertices, "vertex_normals: vertices", torch.float64)
+    if torch.is_tensor(faces) and faces.numel() == 0:
+        faces = faces.reshape(0, 3)
+    faces = _rows3(faces, "vertex_normals: faces", torch.int64)
+    if faces.device != vertices.device:
+        raise _lib.DudfError("vertex_normals: vertices and faces live on different devices")
+    nv, nf, dev = vertices.shape[0], faces.shape[0], vertices.device
+    out = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    nbytes = int(lib.dudf_vertex_normals_workspace_bytes(nv))
+    ws = _scratch(nbytes, dev)
+    with torch.cuda.device(dev):
+        rc = lib.dudf_vertex_normals(_ptr(vertices), nv, _ptr(faces), nf, _ptr(out), _ptr(ws), nbytes, _stream())
+    _lib.check(rc, "dudf_vertex_normals")
+    return out

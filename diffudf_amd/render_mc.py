@@ -59,6 +59,16 @@ class TriangleSoup:
         self.vertices = np.asarray(vertices, dtype=np.float64)
         self.faces = np.asarray(faces, dtype=np.int64)
 
+    @property
+    def vertex_normals(self):
+        """(V,3) float64 area-weighted unit vertex normals (what `mesh.as_open3d.compute_vertex_normals(normalized=True)` gives the
+        reference's cuantitative.py:99-100), computed on the device by `metrics.vertex_normals`."""
+        from . import metrics
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        n = metrics.vertex_normals(torch.from_numpy(np.ascontiguousarray(self.vertices)).to(dev),
+                                   torch.from_numpy(np.ascontiguousarray(self.faces)).to(dev))
+        return n.cpu().numpy().astype(np.float64)
+
     def export(self, path):
         v, f = self.vertices, self.faces
         if str(path).endswith(".ply"):

@@ -220,6 +220,42 @@ int dudf_render_shade(int model, const unsigned char* hits, int64_t m, const int
 /* dudf_render_finish — `(colores / sample_rate * 255).astype(np.uint8)` (generate_st.py:139) over `count` doubles. */
 int dudf_render_finish(const double* accumulator, int64_t count, double sample_rate, unsigned char* out_image, void* stream);
 
+/* Chamfer distance and normal consistency — the device side of reference cuantitative.py:10-19 (`pytorch3d.loss.chamfer_distance`;
+ * pytorch3d is a CUDA extension) and of :99-100 (open3d's vertex normals).  csrc/dudf_chamfer.hip.  These entry points arrived after
+ * ABI 8 without changing any existing signature.
+ *
+ * dudf_nearest_points — for every row of x (n,3) the nearest row of y (m,3), both fp32: the `dists` / `idx` of pytorch3d's
+ *   `knn_points(x, y, norm=norm, K=1)`.  norm 2: out_dist (n) = SQUARED Euclidean distance; norm 1: the L1 distance sum |x_i - y_i|.
+ *   out_idx (n) int64 = the row of y.  Either output may be NULL.  Distances are formed from the differences, (x - y) then square or
+ *   abs, in fp32 — never from |x|^2 + |y|^2 - 2 x.y, which cancels.  Among rows of y at equal fp32 distance the smallest index wins;
+ *   the result does not depend on launch geometry or execution order, and two calls on the same inputs are bit-identical.  Inputs are
+ *   expected finite: a row of x with a NaN gets a NaN distance and an index in [0, m); NaN rows of y are never chosen.
+ *   norm not in {1, 2}: DUDF_E_BADMODE; n == 0: nothing is launched, 0; m <= 0 with n > 0: DUDF_E_BADCFG; n or m >= 2^31:
+ *   DUDF_E_UNSUPPORTED; workspace: dudf_nearest_workspace_bytes(n) (one 64-bit key per row), 256-byte aligned, else DUDF_E_WORKSPACE. */
+size_t dudf_nearest_workspace_bytes(int64_t n);
+int dudf_nearest_points(const float* x, int64_t n, const float* y, int64_t m, int norm, float* out_dist, int64_t* out_idx,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* dudf_chamfer_terms — the two sums behind chamfer_distance's mean reductions for one direction: out_sums (device, 2 doubles) =
+ *   sum_p dist[p]  and  sum_p (1 - |cos(x_normals[p], y_normals[idx[p]])|),  cos = a.b / (max(|a|, 1e-6) max(|b|, 1e-6))
+ *   (`F.cosine_similarity(..., eps=1e-6)`; pytorch3d's `abs_cosine=True` normal term).  dist (n) fp32 and idx (n) int64 as
+ *   dudf_nearest_points wrote them; normals fp32 (n,3) / (m,3).  Both normals NULL: only out_sums[0] is written (one of them NULL:
+ *   DUDF_E_BADCFG).  An idx outside [0, m) is not dereferenced and turns the normal sum into NaN.  Accumulated in double in a fixed
+ *   order — per-workgroup partials in the workspace, added in index order by one workgroup — so a repeated call is bit-identical;
+ *   no floating-point atomics.  workspace: dudf_chamfer_terms_workspace_bytes(n). */
+size_t dudf_chamfer_terms_workspace_bytes(int64_t n);
+int dudf_chamfer_terms(const float* dist, const int64_t* idx, int64_t n, const float* x_normals, const float* y_normals, int64_t m,
+                       double* out_sums, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dudf_vertex_normals — open3d's `compute_vertex_normals(normalized=True)` (reference cuantitative.py:99-100): every face adds its
+ *   unnormalised (v1 - v0) x (v2 - v0) to its three vertices (area weighting), then each sum is normalised.  vertices (V,3) double,
+ *   faces (F,3) int64, out_normals (V,3) fp32.  A vertex with a zero sum gets (0, 0, 1); a face with an index outside [0, V) is
+ *   skipped, not dereferenced.  Sums in double (atomic adds into the workspace; their order moves the sum by ~1e-16 relative, which
+ *   the rounding to fp32 hides except at a rounding boundary).  workspace: dudf_vertex_normals_workspace_bytes(V). */
+size_t dudf_vertex_normals_workspace_bytes(int64_t n_vertices);
+int dudf_vertex_normals(const double* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, float* out_normals,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* The field part of `extract_fields` (reference src/render_mc.py:20-99) for grid points start .. start+count-1 of the
  * regular grid_n^3 grid on [-1,1]^3 (linear index, first axis slowest, coordinates derived from the index):
  * out_df (count) = inverse(gt_mode, |f|, alpha) with inverse_mode 0 'tanh' / 1 'siren' / 2 'squared'
