@@ -74,6 +74,10 @@ SYMBOLS = {
     "dudf_chamfer_terms": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
     "dudf_vertex_normals_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "dudf_vertex_normals": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_mesh_index_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "dudf_mesh_morton_codes": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_size_t, _P, _P]),
+    "dudf_mesh_index_build": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_mesh_distance": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_size_t, _P, ctypes.c_int64, _P, _P, _P, _P, _P]),
     "dudf_grid_fields": (ctypes.c_int, [_CFG, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.c_double, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "dudf_query": (ctypes.c_int, [_CFG, _P, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_size_t, _P]),
@@ -144,7 +148,7 @@ def load():
     for name, (res, args) in SYMBOLS.items():
         try:
             fn = getattr(lib, name)
-        except AttributeError:           # calls added without an ABI bump (dudf_render_*, dudf_nearest_points ..: no existing signature changed)
+        except AttributeError:           # calls added without an ABI bump (dudf_render_*, dudf_nearest_points, dudf_mesh_* ..: no existing signature changed)
             raise DudfError(f"{LIB_PATH} does not export {name}: it is older than this package; rebuild it "
                             "(`python -c 'import __graft_entry__ as g; g.build()'`)") from None
         fn.restype = res

@@ -19,9 +19,7 @@
 // and the numpy restatement in oracle/sampler_oracle.py reproduces every sample.
 #include "dudf_internal.h"
 
-#ifndef DUDF_SAMPLE_DBG
-#define DUDF_SAMPLE_DBG 0          // timing experiments (tools/build_dbg.sh): 1 no exact evaluations, 2 nothing behind pass 0, 3 no sphere setup, 4 no scans at all
-#endif
+#include "dudf_tridist.h"          // tri_dist2, DUDF_SAMPLE_DBG
 
 namespace {
 
@@ -55,58 +53,6 @@ __host__ __device__ __forceinline__ void sample_keys(SampleArgs& a, uint64_t see
     a.k_on = stream_key(seed, base + 400); a.k_fx = stream_key(seed, base + 401); a.k_fy = stream_key(seed, base + 402);
     a.k_fz = stream_key(seed, base + 403); a.k_pick = stream_key(seed, base + 404);
     a.k_n1 = stream_key(seed, base + 405); a.k_n2 = stream_key(seed, base + 406);
-}
-
-// squared distance from p to triangle (a,b,c): closest point by Voronoi regions of the triangle.  In fp64, like the
-// oracle (and like nothing in fp32 can be: |p - c|^2 of coordinates ~1 carries 1e-7 absolute, 1e-4 of a near-surface
-// distance of 1e-3); 2 k triangles x 2 k queries per step is noise for the fp64 vector pipe.
-__device__ __forceinline__ double tri_dist2(double px, double py, double pz, const float* t) {
-    if (DUDF_SAMPLE_DBG == 1) return px + t[0];
-    const double ax = t[0], ay = t[1], az = t[2];
-    const double abx = t[3] - ax, aby = t[4] - ay, abz = t[5] - az;
-    const double acx = t[6] - ax, acy = t[7] - ay, acz = t[8] - az;
-    const double apx = px - ax, apy = py - ay, apz = pz - az;
-    const double d1 = abx * apx + aby * apy + abz * apz;
-    const double d2 = acx * apx + acy * apy + acz * apz;
-    double cx, cy, cz;                                  // closest point - a
-    if (d1 <= 0.0 && d2 <= 0.0) { cx = cy = cz = 0.0; }
-    else {
-        const double bpx = apx - abx, bpy = apy - aby, bpz = apz - abz;
-        const double d3 = abx * bpx + aby * bpy + abz * bpz;
-        const double d4 = acx * bpx + acy * bpy + acz * bpz;
-        if (d3 >= 0.0 && d4 <= d3) { cx = abx; cy = aby; cz = abz; }
-        else {
-            const double vc = d1 * d4 - d3 * d2;
-            if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
-                const double v = d1 / (d1 - d3);
-                cx = v * abx; cy = v * aby; cz = v * abz;
-            } else {
-                const double cpx = apx - acx, cpy = apy - acy, cpz = apz - acz;
-                const double d5 = abx * cpx + aby * cpy + abz * cpz;
-                const double d6 = acx * cpx + acy * cpy + acz * cpz;
-                if (d6 >= 0.0 && d5 <= d6) { cx = acx; cy = acy; cz = acz; }
-                else {
-                    const double vb = d5 * d2 - d1 * d6;
-                    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
-                        const double w = d2 / (d2 - d6);
-                        cx = w * acx; cy = w * acy; cz = w * acz;
-                    } else {
-                        const double va = d3 * d6 - d5 * d4;
-                        if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
-                            const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-                            cx = abx + w * (acx - abx); cy = aby + w * (acy - aby); cz = abz + w * (acz - abz);
-                        } else {
-                            const double den = 1.0 / (va + vb + vc);
-                            const double v = vb * den, w = vc * den;
-                            cx = abx * v + acx * w; cy = aby * v + acy * w; cz = abz * v + acz * w;
-                        }
-                    }
-                }
-            }
-        }
-    }
-    const double dx = apx - cx, dy = apy - cy, dz = apz - cz;
-    return dx * dx + dy * dy + dz * dz;
 }
 
 constexpr int QSPLIT = 8;                 // lanes that share one query point (each scans every QSPLIT-th primitive)

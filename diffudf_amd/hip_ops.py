@@ -915,3 +915,77 @@ def vertex_normals(vertices, faces):
         rc = lib.dudf_vertex_normals(_ptr(vertices), nv, _ptr(faces), nf, _ptr(out), _ptr(ws), nbytes, _stream())
     _lib.check(rc, "dudf_vertex_normals")
     return out
+
+
+# ---- distance to a triangle mesh (reference generate_df.py:108-110, open3d RaycastingScene; csrc/dudf_meshdist.hip) -------------
+MESH_INDEX_FLAGS_OFFSET, MESH_FLAG_NONFINITE, MESH_FLAG_BAD_ORDER = 24, 1, 2       # include/dudf_hip.h
+
+
+def _soup(tri, what):
+    if not torch.is_tensor(tri) or tri.device.type != "cuda":
+        raise _lib.DudfError(f"{what} must be a CUDA tensor (got {getattr(tri, 'device', type(tri).__name__)}); the HIP path has no CPU fallback")
+    if tri.dim() != 2 or tri.shape[1] != 9:
+        raise _lib.DudfError(f"{what} must have shape (T,9); got {tuple(tri.shape)}")
+    return tri.to(torch.float32).contiguous()
+
+
+def mesh_index_build(tri, order=None):
+    """Index of a triangle soup tri (T,9) float32 for `mesh_distance`: a uint8 CUDA tensor.  Morton codes on the device, a stable
+    `torch.sort`, then the boxes level by level; one host read at the end (the flag word).  ValueError for a NaN / infinite vertex.
+    order (T,) int64: a permutation of the triangles to build the leaves from instead of the Morton order (any permutation gives
+    the same answers, more slowly)."""
+    lib = _lib.load()
+    tri = _soup(tri, "mesh_index_build: tri")
+    T, dev = tri.shape[0], tri.device
+    if T == 0:
+        raise _lib.DudfError("mesh_index_build: a mesh without triangles has no index (DUDF_E_BADCFG)")
+    nbytes = int(lib.dudf_mesh_index_bytes(T))
+    if nbytes == 0:
+        _lib.check(-4, "dudf_mesh_index_bytes")
+    index = torch.zeros(nbytes, dtype=torch.uint8, device=dev)     # zeros: the padding between the sections is part of "same bytes"
+    assert index.data_ptr() % 256 == 0
+    with torch.cuda.device(dev):
+        if order is None:
+            codes = torch.empty(T, dtype=torch.int64, device=dev)
+            _lib.check(lib.dudf_mesh_morton_codes(_ptr(tri), T, _ptr(index), nbytes, _ptr(codes), _stream()), "dudf_mesh_morton_codes")
+            order = torch.sort(codes, stable=True).indices
+        elif not torch.is_tensor(order) or order.device != dev or order.dtype != torch.int64 or order.shape != (T,):
+            raise _lib.DudfError("mesh_index_build: order must be an int64 (T,) CUDA tensor on the device of tri")
+        order = order.contiguous()
+        _lib.check(lib.dudf_mesh_index_build(_ptr(tri), T, _ptr(order), _ptr(index), nbytes, _stream()), "dudf_mesh_index_build")
+    flags = int(index[MESH_INDEX_FLAGS_OFFSET:MESH_INDEX_FLAGS_OFFSET + 4].view(torch.int32).item())
+    if flags & MESH_FLAG_NONFINITE:
+        raise ValueError("mesh_index_build: the mesh has a NaN or infinite vertex")
+    if flags & MESH_FLAG_BAD_ORDER:
+        raise _lib.DudfError("mesh_index_build: the sorted order is not a permutation of the triangles")
+    return index
+
+
+def mesh_distance(tri, index, points, want_idx=False, want_closest=False, stats=None):
+    """(dist (Q,) float32, idx (Q,) int64 | None, closest (Q,3) float32 | None) for points (Q,3): the exact unsigned distance to
+    the soup tri (T,9), the nearest triangle (smallest index among ties) and the closest point on it.  index: what
+    `mesh_index_build(tri)` returned, or None for the brute-force scan (same bits).  stats: int64 CUDA tensor of 1, the number of
+    exact triangle evaluations is ADDED to it."""
+    lib = _lib.load()
+    tri = _soup(tri, "mesh_distance: tri")
+    points = _rows3(points, "mesh_distance: points", torch.float32)
+    if points.device != tri.device:
+        raise _lib.DudfError("mesh_distance: tri and points live on different devices")
+    T, Q, dev = tri.shape[0], points.shape[0], tri.device
+    nbytes = 0
+    if index is not None:
+        if not torch.is_tensor(index) or index.device != dev or index.dtype != torch.uint8 or not index.is_contiguous():
+            raise _lib.DudfError("mesh_distance: index must be the uint8 CUDA tensor of mesh_index_build on the device of tri")
+        nbytes = index.numel()
+    if stats is not None and (not torch.is_tensor(stats) or stats.device != dev or stats.dtype != torch.int64 or stats.numel() != 1):
+        raise _lib.DudfError("mesh_distance: stats must be an int64 CUDA tensor of 1")
+    dist = torch.empty(Q, dtype=torch.float32, device=dev)
+    idx = torch.empty(Q, dtype=torch.int64, device=dev) if want_idx else None
+    closest = torch.empty(Q, 3, dtype=torch.float32, device=dev) if want_closest else None
+    if Q and T == 0:
+        _lib.check(-1, "dudf_mesh_distance (no triangles)")
+    with torch.cuda.device(dev):
+        rc = lib.dudf_mesh_distance(_ptr(tri), T, _ptr(index), nbytes, _ptr(points), Q, _ptr(dist), _ptr(idx), _ptr(closest),
+                                    _ptr(stats), _stream())
+    _lib.check(rc, "dudf_mesh_distance")
+    return dist, idx, closest

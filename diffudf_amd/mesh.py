@@ -121,10 +121,12 @@ def read_ply_points(path):
     return pos, nrm
 
 
-def write_obj(path, verts, tris):
+def write_obj(path, verts, tris, fmt="%.9g"):
+    """fmt: how a coordinate is printed; "%.17g" reads back to the same float64."""
+    line = "v " + " ".join([fmt] * 3) + "\n"
     with open(path, "w") as f:
         for v in verts:
-            f.write("v %.9g %.9g %.9g\n" % tuple(v))
+            f.write(line % tuple(v))
         for t in tris:
             f.write("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1))
 

@@ -3,7 +3,12 @@
 cuantitative.py:10-19 uses (pytorch3d is a CUDA extension), and the vertex normals open3d computes for it at :99-100.
 
 The nearest-neighbour search, the sums behind the means and the vertex normals are HIP kernels (csrc/dudf_chamfer.hip);
-there is no CPU path: CPU tensors raise DudfError."""
+there is no CPU path: CPU tensors raise DudfError.
+
+`MeshIndex` / `mesh_distance` stand in for `o3d.t.geometry.RaycastingScene().add_triangles(...)` / `.compute_distance(...)`
+(reference generate_df.py:108-110): the exact unsigned distance from points to a triangle mesh through a bounding-volume
+hierarchy built and walked on the device (csrc/dudf_meshdist.hip)."""
+import numpy as np
 import torch
 
 from . import hip_ops
@@ -67,3 +72,51 @@ def vertex_normals(vertices, faces):
     """(V,3) float32 CUDA tensor: area-weighted unit vertex normals (open3d `compute_vertex_normals(normalized=True)`).
     vertices (V,3), faces (F,3): CUDA tensors."""
     return hip_ops.vertex_normals(vertices, faces)
+
+
+def _cuda(a, dtype, device):
+    if torch.is_tensor(a):
+        if a.device.type != "cuda":
+            raise DudfError(f"MeshIndex: tensors must live on the GPU (got {a.device}); there is no CPU fallback")
+        return a.to(dtype)
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=dtype)      # numpy from the mesh readers
+
+
+class MeshIndex:
+    """The scene of a triangle mesh, built once: `MeshIndex(vertices (V,3), faces (F,3))` or `MeshIndex.from_soup(tri (T,9))`.
+    Tensors are CUDA tensors; numpy arrays (what `diffudf_amd.mesh.load_obj` returns) are uploaded to `device`.  A NaN or infinite
+    vertex raises ValueError."""
+
+    def __init__(self, vertices, faces, device="cuda:0"):
+        v = _cuda(vertices, torch.float32, device)
+        f = _cuda(faces, torch.int64, v.device if torch.is_tensor(vertices) else device)
+        if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+            raise DudfError(f"MeshIndex: vertices (V,3) and faces (F,3) expected; got {tuple(v.shape)}, {tuple(f.shape)}")
+        if f.numel() and (int(f.min()) < 0 or int(f.max()) >= v.shape[0]):
+            raise ValueError("MeshIndex: a face refers to a vertex that does not exist")
+        self._init_soup(v[f].reshape(-1, 9))                       # the layout of diffudf_amd.mesh.triangle_soup
+
+    @classmethod
+    def from_soup(cls, tri, device="cuda:0"):
+        self = cls.__new__(cls)
+        self._init_soup(_cuda(tri, torch.float32, device))
+        return self
+
+    def _init_soup(self, tri):
+        self.tri = tri.contiguous()
+        self.index = hip_ops.mesh_index_build(self.tri)
+
+    def distance(self, points, return_index=False, return_closest=False, brute=False, stats=None):
+        """Unsigned distance (Q,) float32 of points (Q,3) — `scene.compute_distance(points)`; with return_index / return_closest a
+        tuple (dist[, idx (Q,) int64][, closest (Q,3) float32]).  brute=True scans every triangle without the index (the same
+        bits); stats: see `hip_ops.mesh_distance`."""
+        dist, idx, closest = hip_ops.mesh_distance(self.tri, None if brute else self.index, points, return_index, return_closest, stats)
+        if not (return_index or return_closest):
+            return dist
+        return (dist,) + ((idx,) if return_index else ()) + ((closest,) if return_closest else ())
+
+
+def mesh_distance(points, vertices, faces):
+    """One-shot `MeshIndex(vertices, faces).distance(points)`."""
+    dev = points.device if torch.is_tensor(points) and points.device.type == "cuda" else "cuda:0"
+    return MeshIndex(vertices, faces, device=dev).distance(points)

@@ -256,6 +256,38 @@ size_t dudf_vertex_normals_workspace_bytes(int64_t n_vertices);
 int dudf_vertex_normals(const double* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, float* out_normals,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Exact unsigned distance from points to a triangle mesh with a bounding-volume hierarchy — the device side of open3d's
+ * `RaycastingScene.add_triangles / compute_distance` (reference generate_df.py:108-110).  csrc/dudf_meshdist.hip.  Like the Chamfer
+ * entry points these arrived after ABI 8 without changing any existing signature.  tri (n_tri,9) fp32 is the triangle soup
+ * dudf_sample_batch takes; 0 < n_tri < 2^31 (n_tri <= 0: DUDF_E_BADCFG, larger: DUDF_E_UNSUPPORTED).
+ *
+ * dudf_mesh_index_bytes — size of the index of n_tri triangles (O(n_tri): sorted copy of the soup, original indices, the boxes of a
+ *   complete binary tree over leaves of 8 triangles); 0 for an n_tri out of range.  The buffer is 256-byte aligned device memory
+ *   (else DUDF_E_WORKSPACE).
+ * dudf_mesh_morton_codes — codes (n_tri) int64 = 63-bit Morton code of every triangle's centroid inside the bounding box of all
+ *   vertices.  The caller sorts them — a STABLE sort, so that the index is a function of the triangles alone — and passes the
+ *   permutation on.  Uses the head of `index` as scratch.
+ * dudf_mesh_index_build — builds the index for `order` (n_tri) int64, order[s] = original index of the s-th triangle along the
+ *   curve; any permutation gives a correct index, the Morton order gives a fast one.  Nothing comes back to the host; the 32-bit
+ *   word at byte DUDF_MESH_INDEX_FLAGS_OFFSET of the index then holds DUDF_MESH_FLAG_NONFINITE if a vertex is NaN or infinite and
+ *   DUDF_MESH_FLAG_BAD_ORDER if an entry of `order` lies outside [0, n_tri) (it is not dereferenced); an index with a flag set
+ *   must not be queried.  Two builds from the same inputs are byte-identical.
+ * dudf_mesh_distance — for pts (n_pts,3) fp32, every output optional (NULL): out_dist (n_pts) fp32 = sqrt of the minimum over all
+ *   triangles of the fp64 squared distance (the arithmetic of dudf_sample_batch), rounded once; out_tri (n_pts) int64 = the
+ *   triangle that attains it, in the caller's order, the smallest index among equal distances; out_closest (n_pts,3) fp32 = the
+ *   closest point on that triangle; *out_stats (device int64, ADDED to) = exact triangle evaluations of the call.
+ *   index == NULL: brute force over all triangles — the cross-check; with an index the same bits (a subtree is skipped only on a
+ *   safe-side bound STRICTLY above the best exact value).  A point with a NaN coordinate: distance NaN, triangle -1, closest NaN.
+ *   n_pts == 0: nothing is launched, 0. */
+#define DUDF_MESH_INDEX_FLAGS_OFFSET 24
+#define DUDF_MESH_FLAG_NONFINITE 1
+#define DUDF_MESH_FLAG_BAD_ORDER 2
+size_t dudf_mesh_index_bytes(int64_t n_tri);
+int dudf_mesh_morton_codes(const float* tri, int64_t n_tri, void* index, size_t index_bytes, int64_t* codes, void* stream);
+int dudf_mesh_index_build(const float* tri, int64_t n_tri, const int64_t* order, void* index, size_t index_bytes, void* stream);
+int dudf_mesh_distance(const float* tri, int64_t n_tri, const void* index, size_t index_bytes, const float* pts, int64_t n_pts,
+                       float* out_dist, int64_t* out_tri, float* out_closest, int64_t* out_stats, void* stream);
+
 /* The field part of `extract_fields` (reference src/render_mc.py:20-99) for grid points start .. start+count-1 of the
  * regular grid_n^3 grid on [-1,1]^3 (linear index, first axis slowest, coordinates derived from the index):
  * out_df (count) = inverse(gt_mode, |f|, alpha) with inverse_mode 0 'tanh' / 1 'siren' / 2 'squared'

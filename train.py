@@ -406,7 +406,7 @@ def setup_train(parameter_dict, cuda_device):
     if _is_main():
         # post-training artefacts as in reference train.py:403-446: the field slice of the best model (always) and, when
         # `resolution != 0`, its meshes (algorithm 'both') — rank 0 only, the other ranks go on to tear down
-        from generate_df import generate_df
+        from generate_df import generate_df, generate_df_pc
         from generate_mc import generate_mc
         best = osp.join(full_path, "models", "model_best.pth")
         if gt_mode != 'tanh':
@@ -415,10 +415,16 @@ def setup_train(parameter_dict, cuda_device):
             print(f"post-training artefacts skipped: {best} was never written (no epoch improved on the initial loss)")
         else:
             print('Generating distance field slices')
-            generate_df(best, None, osp.join(full_path, "reconstructions/"),
-                        {'device': f"cuda:{int(device.index or 0)}", 'surf_thresh': 1e-3, 'width': 512, 'weight0': network_params["w0"],
-                         'gt_mode': gt_mode, 'alpha': parameter_dict.get('alpha', 1),
-                         'hidden_layer_nodes': network_params["hidden_layer_nodes"], 'activation': network_params.get('activation', 'sine')})
+            df_options = {'device': f"cuda:{int(device.index or 0)}", 'surf_thresh': 1e-3, 'width': 512, 'weight0': network_params["w0"],
+                          'gt_mode': gt_mode, 'alpha': parameter_dict.get('alpha', 1),
+                          'hidden_layer_nodes': network_params["hidden_layer_nodes"], 'activation': network_params.get('activation', 'sine')}
+            # ground truth of the slice as in reference train.py:415-428: the preprocessed mesh, or with onlyPCloud the preprocessed
+            # cloud, when preprocess.py wrote one; otherwise (synthetic data, a bare <prefix>.obj) the predicted panels only
+            gt_file = str(parameter_dict["dataset"]) + ('_t.ply' if parameter_dict.get('onlyPCloud', False) else '_t.obj')
+            if parameter_dict.get('onlyPCloud', False) and osp.isfile(gt_file):
+                generate_df_pc(best, gt_file, osp.join(full_path, "reconstructions/"), df_options)
+            else:
+                generate_df(best, gt_file if osp.isfile(gt_file) else None, osp.join(full_path, "reconstructions/"), df_options)
             if parameter_dict.get('resolution', 256) != 0:
                 print('Generating mesh')
                 meshes = generate_mc(model=None, gt_mode=gt_mode, device=int(device.index or 0), N=parameter_dict.get('resolution', 256),
