@@ -37,33 +37,14 @@
 // forward sweep, one tile at a time, DMA pieces issued by the idle half of a partial pass, static / per-phase wave priorities,
 // other fragment prefetch distances and feed / tail slots) are no longer in this file: DESIGN.md Appendix A has their numbers,
 // `git log -- diffudf_amd/csrc/dudf_sweep_bf16.hip` (round 3) their code.
-#ifndef DUDF_OCT
-#define DUDF_OCT 1                           // a pass with a single 16-column group is shared by all eight waves (sweep_tile_oct)
-#endif
-#ifndef DUDF_W_RELAY_NT
-#define DUDF_W_RELAY_NT 0                    // 512-wide kernel: 1 = non-temporal stores for the relay array as well (rounds 2-3)
-#endif
-#ifndef DUDF_TAIL_TOP
-#define DUDF_TAIL_TOP (SP != 0 && BS == SWEEP_FWD)   // early half: tail in front of the step's DMA pieces
-#endif
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // one LDS atomic per wave: 64 lanes hitting the same LDS word serialise (measured: the per-layer publish of the quads' forward
 // sweep cost 0.09 ms per launch that way), so the wave reduces first
 __device__ __forceinline__ void lds_max_wave(unsigned* word, float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-#ifdef DUDF_LDSMAX_BRANCH
-    if ((threadIdx.x & 63) == 0) atomicMax(word, __float_as_uint(v));
-#else
     // lane 0 alone, WITHOUT a compiler-visible branch: `if (lane == 0)` ends the basic block, and the sweeps call this in the last
     // k-block step of every layer — the step then loses the interleaving of its tail with its MFMAs (round 5: the same shape of store
     // cost the reverse sweeps 12-18 %, profiles/r05_e_ab.txt)
@@ -71,7 +52,6 @@ __device__ __forceinline__ void lds_max_wave(unsigned* word, float v) {
     uint64_t ex;
     asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_max_u32 %1, %2\n\ts_mov_b64 exec, %0"
                  : "=&s"(ex) : "v"(addr), "v"(__float_as_uint(v)) : "memory");
-#endif
 }
 constexpr int NWB = 8;                                 // waves per workgroup: two per SIMD
 constexpr int TILEB = NWB * 16;                        // columns per workgroup pass
@@ -100,12 +80,6 @@ __device__ __forceinline__ f32x4 mfma_b(bf16x8 a, bf16x8 b, f32x4 c) {
     asm volatile("" : "+v"(c) : "v"(a), "v"(b)); return c;
 #endif
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned cvt_pk(f32x2 v) {              // one v_cvt_pk_bf16_f32: lo = bf16(v.x), hi = bf16(v.y)
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ f32x2 unpack(unsigned p) {              // the two bf16 back as exact floats
-    return f32x2{__builtin_bit_cast(float, p << 16), __builtin_bit_cast(float, p & 0xffff0000u)};
 }
 // 8 fp32 values (two accumulator tiles' registers of one lane) -> the three bf16x8 pieces of a B / A operand
 __device__ __forceinline__ void split8(const f32x4 e0, const f32x4 e1, u32x4& h, u32x4& m, u32x4& l) {
@@ -223,6 +197,32 @@ __device__ __forceinline__ unsigned amax_lds_off(const SweepArgs& a) {
     return 3u * GeoB<H, SP>::CHUNKB + ((SP != 0 && base_of(SW) == SWEEP_FWD) ? (unsigned)(a.L * H * sizeof(float)) : 0u);
 }
 
+// Shared by the three tile bodies.  (Their other repeated lambdas — image, in_layer, stash_base, the LaneOff construction — and the
+// drivers' amax / clock code stay per body: as free functions they moved the generated code of 3 to 140 kernels, tools/asm_diff.py.)
+__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+// fp16x3 column scale from a bound < 2^(E - 126) of the column: sb = 2^(15 - (E - 126)) brings it below 2^15, inv_sb = 1 / sb
+__device__ __forceinline__ void col_scale(float bound, float& sb, float& inv_sb) {
+    unsigned E = (__float_as_uint(bound) >> 23) & 255u;
+    E = E < 27u ? 27u : (E > 250u ? 250u : E);             // all-zero (padding) columns, infinities: any finite scale will do
+    sb = __uint_as_float((268u - E) << 23);
+    inv_sb = __uint_as_float((E - 14u) << 23);
+}
+// max |.| over N accumulator tiles' registers and the 4 lane quarters: per column
+template <int N>
+__device__ __forceinline__ float col_absmax(const f32x4 (&t)[N]) {
+    float m = 0.f;
+    // dudf_track is inline asm, and these are MFMA results: hipcc's hazard recogniser does not see an asm statement's
+    // register reads, so the wait states between the last MFMA and the first read are spelled out (found the hard way:
+    // the last layer's column scale came from stale accumulators)
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_nop 15\n\ts_nop 15");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int T = 0; T < N; ++T) dudf_track(m, t[T]);
+    m = fmaxf(m, __shfl_xor(m, 16));
+    return fmaxf(m, __shfl_xor(m, 32));
+}
+
 // One pass: the workgroup's waves 0..nact-1 take the 16-column groups g_first.. through a whole sweep.  Waves beyond
 // nact (the last, partial pass of a workgroup's share) only keep the weight stream and the barriers going.
 template <int H, int SW, int FL, int SP = 0, int P24 = 0>
@@ -266,19 +266,6 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
     constexpr bool kColScale = SP != 0 && (BS != SWEEP_FWD || HS);
     constexpr bool kTrackE = SP != 0 && BS == SWEEP_ADJ_FWD;   // (the fp16x3 adjoint reverse sweep therefore needs the fp16x3 adjoint forward one)
     float sb = 1.f, inv_sb = 1.f;                       // scale of the B operand being built (tails of `prev`) and its inverse
-    auto colmax = [&](const f32x4 (&t)[G::NT]) -> float {      // max |.| over the 16 tiles' registers and the 4 lane quarters: per column
-        float m = 0.f;
-        // dudf_track is inline asm, and these are MFMA results: hipcc's hazard recogniser does not see an asm statement's
-        // register reads, so the wait states between the last MFMA and the first read are spelled out (found the hard way:
-        // the last layer's column scale came from stale accumulators)
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop 15\n\ts_nop 15");
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int T = 0; T < G::NT; ++T) dudf_track(m, t[T]);
-        m = fmaxf(m, __shfl_xor(m, 16));
-        return fmaxf(m, __shfl_xor(m, 32));
-    };
     // amax_true: max_f |accumulator| of this column (true values); extra: the bound of what the tail adds (adjoint reverse:
     // e_l); zb: max_f |zdot_l| of this column (quads, tangent channels).  Quads (tails in dudf_sweep_common.h::epilogue):
     //   forward          value: |sin| <= 1                  tangent k: w0 |zdot^k|
@@ -315,11 +302,7 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
         // on their own path (and R, E come back rounded to 16 significant bits): a column whose bound sits an ulp under a power of two
         // could hand the fixed-point stash a value a grid step outside [-1, 1] 2^E, which fx24_pack would wrap to +5 2^E.
         // Once per layer and column, not per value; costs a bit of the column's precision in 0.14 % of the scale decisions.
-        bound *= DUDF_FX_HEADROOM;
-        unsigned E = (__float_as_uint(bound) >> 23) & 255u;    // bound < 2^(E - 126)
-        E = E < 27u ? 27u : (E > 250u ? 250u : E);             // all-zero (padding) columns, infinities: any finite scale will do
-        sb = __uint_as_float((268u - E) << 23);                // 2^(15 - (E - 126))
-        inv_sb = __uint_as_float((E - 14u) << 23);
+        col_scale(bound * DUDF_FX_HEADROOM, sb, inv_sb);
     };
     auto ebound_of = [&](int layer) -> float {                 // adjoint reverse sweep with df/dx terms: max_f |e_layer| of this column
         if constexpr (kColScale && BS == SWEEP_ADJ_REV && (HS || (FL & 1) != 0)) return a.ebound[(int64_t)layer * a.np + p];
@@ -346,28 +329,21 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
     // — stores NaN as its 2^E, and every reader's (t - 3) 2^E is NaN: d(theta) of a poisoned batch is NaN, as autograd's would be,
     // not finite garbage (tests/test_stash_formats_gpu.py, tests/test_api_gpu.py::test_on_surface_count_hint).
     bool poison = false;                                // (a divergent bool: one lane-mask SGPR pair, no vector register)
-    auto nonfinite = [](float v) -> bool { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; };
     auto store_fx = [&](int layer) {
         if constexpr (kFx) {
             if constexpr (kColScale) tmax.fs = sb * 0x1p-15f;
-#if !(DUDF_FX_DBG & 1)
             // (the plain columns' forward sweep has no column scale: its array is written once, at the end of the pass)
             // (every lane stores — the four lane quarters of a column the same number to the same address: a store under `if (q == 0)`
             //  splits the last k-block step of every layer into several basic blocks, and the reverse sweeps, which had no such
             //  store before, lost 12-18 % to it: profiles/r05_e_ab.txt)
             if constexpr (kColScale) a.fxs[(int64_t)layer * a.np + p] = poison ? __uint_as_float(0x7fc00000u) : inv_sb * 0x1p15f;
-#endif
         }
     };
     unsigned* lds_amax = reinterpret_cast<unsigned*>(lds + amax_lds_off<H, SW, SP>(a));
     auto publish = [&](int layer) {
-#ifdef DUDF_DBG_NOPUBLISH
-        if constexpr (kRow >= 0) { asm volatile("" :: "v"(tmax.t)); tmax.t = 0.f; }
-#else
         // (layers beyond the table share its last word: only networks of more than kMaxAmaxLayers layers have them, and their
         //  weight-gradient GEMM does not read the table — no uniform branch in the layer-switch step either)
         if constexpr (kRow >= 0) { lds_max_wave(lds_amax + (layer < kMaxAmaxLayers ? layer : kMaxAmaxLayers - 1), tmax.t); tmax.t = 0.f; }
-#endif
     };
     // layer whose tail feeds matrix j (j == nhid: the last one, feeding the output stage), 0-based
     auto in_layer = [&](int j) -> int { return kFwdDir ? j : a.L - 1 - j; };
@@ -524,7 +500,7 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
     if constexpr (kColScale) {                         // first layer (fp32 MFMA / W_out^T ybar: true values): its column scale
         const float eb0 = ebound_of(in_layer(0)), zb0 = zbound_of(in_layer(0));
         if (nhid > 0) { eb_next = ebound_of(in_layer(1)); zb_next = zbound_of(in_layer(1)); }
-        const float cm = colmax(prev);
+        const float cm = col_absmax(prev);
         store_zbound(in_layer(0), cm);
         set_scale(cm, eb0, zb0);
     }
@@ -582,7 +558,7 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
             // fp16x3: the half that does not multiply first runs its tail at the very top of the step, in front of its DMA
             // pieces (fetched two steps ahead: no hurry) and of its first LDS fragment: the step is (tail of one half beside the
             // MFMAs of the other) twice, and neither tail should wait for anything
-            constexpr bool kTailTop = DUDF_TAIL_TOP;
+            constexpr bool kTailTop = SP != 0 && BS == SWEEP_FWD;
             if (kTailTop && !late && kb + 1 < G::NKB) {
                 DUDF_STAMP(2);
                 f32x4 e0, e1;
@@ -676,7 +652,7 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
                     // a layer ahead: its latency hides behind 8 steps.  (No branch at the end of the stream: the last switches re-read the
                     // last layer's entry — a uniform branch would end the basic block of this step as well, see store_fx)
                     { const int jn = j + 2 <= nhid ? j + 2 : nhid; eb_next = ebound_of(in_layer(jn)); zb_next = zbound_of(in_layer(jn)); }
-                    const float cm = colmax(acc) * unscale;
+                    const float cm = col_absmax(acc) * unscale;
                     store_zbound(lnx, cm);
                     set_scale(cm, ebl, zbl);                            // ... and the scale of the operand its tails are about to build
                 } else if constexpr (SP) unscale = unscale_of(j);
@@ -813,7 +789,6 @@ __device__ __forceinline__ void sweep_tile_oct(const SweepArgs& a, const int g, 
     // first layer (fp32, K = 3): my two tiles
     f32x4 prev[2], acc[2];
     bool poison = false;
-    auto nonfinite = [](float v) -> bool { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; };
     {
         float b = 0.f, yb = 1.f;
         if constexpr (BS == SWEEP_FWD) b = (q < 3) ? a.x4[p * 4 + q] : 0.f;
@@ -857,23 +832,13 @@ __device__ __forceinline__ void sweep_tile_oct(const SweepArgs& a, const int g, 
     for (int j = 0; j <= nhid; ++j) {
         const int lin = in_layer(j);
         if constexpr (kColScale) {                      // the column's scale from ALL 16 tiles: max over the eight waves
-            float m = 0.f;
-            __builtin_amdgcn_sched_barrier(0);          // MFMA results read by inline asm: explicit wait states (see colmax)
-            asm volatile("s_nop 15\n\ts_nop 15");
-            __builtin_amdgcn_sched_barrier(0);
-            dudf_track(m, prev[0]); dudf_track(m, prev[1]);
-            m = fmaxf(m, __shfl_xor(m, 16));
-            m = fmaxf(m, __shfl_xor(m, 32));
+            const float m = col_absmax(prev);
             if (q == 0) cmx[wave * 16 + li] = m;
             __syncthreads();
             float mm = 0.f;
 #pragma unroll
             for (int w = 0; w < NWB; ++w) mm = fmaxf(mm, cmx[w * 16 + li]);
-            const float bound = (a.w0 * (mm * unscale) + eb) * DUDF_FX_HEADROOM;   // (2^-10 of head room: see set_scale)
-            unsigned E = (__float_as_uint(bound) >> 23) & 255u;
-            E = E < 27u ? 27u : (E > 250u ? 250u : E);
-            sb = __uint_as_float((268u - E) << 23);
-            inv_sb = __uint_as_float((E - 14u) << 23);
+            col_scale((a.w0 * (mm * unscale) + eb) * DUDF_FX_HEADROOM, sb, inv_sb);   // (2^-10 of head room: see set_scale)
         }
         if constexpr (kFx) {                            // fixed-point stash: this layer's column scale for the readers
             if constexpr (kColScale) tk.fs = sb * 0x1p-15f;
@@ -1008,7 +973,7 @@ __device__ __forceinline__ void sweep_body_b(const SweepArgs& a, const int bid, 
     // a pass with one wave per SIMD (or a single wave) costs about half a full one, a whole extra round would cost all of it
     const int ng = a.ntiles * (TILE / 16), gbase = a.tile0 * (TILE / 16);
     const int g0 = (int)((int64_t)bid * ng / nblk), g1 = (int)((int64_t)(bid + 1) * ng / nblk);
-    constexpr bool kOct = DUDF_OCT && SP != 0 && H == 256 && SW <= SWEEP_ADJ_REV;
+    constexpr bool kOct = SP != 0 && H == 256 && SW <= SWEEP_ADJ_REV;
     for (int g = g0; g < g1; g += NWB) {
         if constexpr (kOct) {
             if (g1 - g == 1) {                          // a pass with one group: all eight waves share it
@@ -1242,7 +1207,6 @@ template <int H, int FAM, int SW, int FL>
 constexpr auto sweep_kernel_of() {
     constexpr bool np = sweep_no_pk<SW>();
     if constexpr (FAM == DUDF_FAM_BF16) { if constexpr (np) return &sweep_bf16_np_kernel<H, SW, FL>; else return &sweep_bf16_kernel<H, SW, FL>; }
-    else if constexpr (FAM == DUDF_FAM_F16 && SW == SWEEP_FWD) return &DUDF_FWD_F16_KERNEL<H, SW, FL>;
     else if constexpr (FAM == DUDF_FAM_F16) { if constexpr (np) return &sweep_f16_np_kernel<H, SW, FL>; else return &sweep_f16_kernel<H, SW, FL>; }
     else if constexpr (FAM == DUDF_FAM_F16R) { if constexpr (np) return &sweep_f16r_np_kernel<H, SW, FL>; else return &sweep_f16r_kernel<H, SW, FL>; }
     else { if constexpr (np) return &sweep_f16p_np_kernel<H, SW, FL>; else return &sweep_f16p_kernel<H, SW, FL>; }
@@ -1414,9 +1378,9 @@ __device__ __forceinline__ void sweep_tile_w(const SweepArgs& a, const int g_fir
             else if constexpr (SW == SWEEP_FWD) z += bs[s];
             else if constexpr (BS == SWEEP_FWD) z = (SP != 0 ? z * unscale : z) + (isv ? bs[s] : zero4);   // the bias: value channel only
             else if constexpr (SP != 0) z *= unscale;
-            // (RL: the array the next layer reads its operand back from keeps the default cache policy — DUDF_W_RELAY_NT=1: A/B)
-            const f32x4 e = epilogue<SW, FL, false, P24, !DUDF_W_RELAY_NT>(a, z, o1[s], o2[s], o3[s], stash_base(layer, T), vl, isv, tmax);
-            if constexpr (wide_relay_store<SW, FL>()) { if constexpr (DUDF_W_RELAY_NT) DUDF_ST(a.S, stash_base(layer, T), vo, e); else DUDF_ST_CACHED(a.S, stash_base(layer, T), vo, e); }
+            // (RL: the array the next layer reads its operand back from keeps the default cache policy)
+            const f32x4 e = epilogue<SW, FL, false, P24, true>(a, z, o1[s], o2[s], o3[s], stash_base(layer, T), vl, isv, tmax);
+            if constexpr (wide_relay_store<SW, FL>()) DUDF_ST_CACHED(a.S, stash_base(layer, T), vo, e);
             if constexpr (kColScale) dudf_track(cmax, e);
             if (T + PD < G::NT) ld(T + PD, s);
             if (last) {
@@ -1442,10 +1406,7 @@ __device__ __forceinline__ void sweep_tile_w(const SweepArgs& a, const int g_fir
         if constexpr (kColScale) {                     // the next layer's B operand = these outputs: scale the column below 2^15
             cmax = fmaxf(cmax, __shfl_xor(cmax, 16));
             cmax = fmaxf(cmax, __shfl_xor(cmax, 32));
-            unsigned E = (__float_as_uint(cmax) >> 23) & 255u;         // cmax < 2^(E - 126)
-            E = E < 27u ? 27u : (E > 250u ? 250u : E);
-            sb = __uint_as_float((268u - E) << 23);
-            inv_sb = __uint_as_float((E - 14u) << 23);
+            col_scale(cmax, sb, inv_sb);
         }
     };
     // ---- first layer (fp32, K = 3): pre-activations / incoming adjoints of the 32 tiles, then their tails ----

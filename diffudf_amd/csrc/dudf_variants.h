@@ -13,12 +13,6 @@ enum { SWEEP_FWD = 0, SWEEP_REV = 1, SWEEP_ADJ_FWD = 2, SWEEP_ADJ_REV = 3,
        SWEEP_FWD_H = 4, SWEEP_REV_H = 5, SWEEP_ADJ_FWD_H = 6, SWEEP_ADJ_REV_H = 7,     // Hessian-quad variants
        SWEEP_FWD_J = 8 };                                                              // third-order jets (query)
 
-#ifndef DUDF_FWD_F16_KERNEL
-#define DUDF_FWD_F16_KERNEL sweep_f16_np_kernel   // A/B: sweep_f16_kernel = the build WITH packed fp32 instructions
-#endif
-#define DUDF_STRINGIZE_(x) #x
-#define DUDF_STRINGIZE(x) DUDF_STRINGIZE_(x)
-
 // snapshot of the run-time options (dudf_set_option; dudf_api.hip holds them): the choosers read no globals
 struct DudfOptions {
     int deterministic, split, split_quads, sweep_family, stash, wgrad_family, wgrad_tr, pair_launch, wgrad_max_workgroups, wgrad_buffers;
@@ -235,9 +229,9 @@ inline SweepChoice dudf_choose_wgrad(const WgradRequest& r, const DudfOptions& o
     const size_t lds_wave = (size_t)4 * 2 * (H / 4) * 16 * 4 * sizeof(float);                                  // ring of 4 x (X image + Y image)
     // per-wave split: narrow layers, option wgrad_family = 2, and beyond the 32-bit lane byte offsets of the cooperative kernel's staging loads
     if (H != 256 || o.wgrad_family == 2 || (int64_t)(r.H / 4) * r.np * 16 >= (1ll << 32)) return pick(DUDF_FAM_WG_BF16, 0, 6, lds_wave);
-    // The cooperative-split body is VAR 9: conflict-free producer lanes + progress flags in LDS instead of the stage barrier (three
-    // image buffers, MFMAs first, split two images ahead, SIMD partners alternating on the matrix pipe); DESIGN.md Appendix A has
-    // the numbers of its predecessors.  fp16x3 needs the running maxima of every layer in LDS (L <= 64).
+    // The cooperative-split body (conflict-free producer lanes, progress flags in LDS instead of a stage barrier, MFMAs first, split
+    // two images ahead, SIMD partners alternating on the matrix pipe) has two builds, named by `var`: 9 = three image buffers,
+    // 25 = four; DESIGN.md Appendix A has the numbers of its predecessors.  fp16x3 needs the running maxima of every layer in LDS (L <= 64).
     const bool f16 = o.split && r.L <= kMaxAmaxLayers;
     const size_t lds_t = (size_t)(2 * 2 * 16 * 576);            // one buffer: (X | Y) x 2 pieces x 16 rows of 576 B; + 512: the flags
     if (r.p24) {                                                // 24-bit tile-major operands: their own build, three or four buffers
@@ -247,7 +241,7 @@ inline SweepChoice dudf_choose_wgrad(const WgradRequest& r, const DudfOptions& o
     if (o.wgrad_tr && f16 && ntz == 1 && !o.deterministic) return pick(DUDF_FAM_WG_F16TR, 9, 3, 3 * lds_t + 512);
     const size_t lds_piece = (size_t)2 * (H / 32) * 2 * (32 * 16 + 16);      // one buffer: (X | Y) x blocks, per piece
     if (f16) {
-        // (three image buffers: the four-buffer form of the body, VAR bit 4, is 2-3 % SLOWER with fp32 operands — 0.557 vs 0.543 ms
+        // (three image buffers: the four-buffer form of the body, var 25, is 2-3 % SLOWER with fp32 operands — 0.557 vs 0.543 ms
         //  at 256, 2.52 vs 2.46 ms at 512, profiles/r05_j_ab512.txt — and 2-3 % faster with 24-bit ones)
         SweepChoice c = pick(DUDF_FAM_WG_F16P, 9, 3, 3 * 2 * lds_piece + 512);
         c.remap = ntz == 4 && !o.deterministic;                 // 2 x 2 tiles: a group's tiles on one XCD
@@ -286,7 +280,6 @@ inline int dudf_choice_name(const SweepChoice& c, char* buf, size_t n) {
         case DUDF_FAM_F32: return snprintf(buf, n, "sweep_kernel<%d,%d,%d>", c.H, c.sw, c.fl);
         case DUDF_FAM_BF16: return snprintf(buf, n, "sweep_bf16%s_kernel<%d,%d,%d>", np, c.H, c.sw, c.fl);
         case DUDF_FAM_F16:
-            if (c.sw == SWEEP_FWD) return snprintf(buf, n, DUDF_STRINGIZE(DUDF_FWD_F16_KERNEL) "<%d,%d,%d>", c.H, c.sw, c.fl);
             return snprintf(buf, n, "sweep_f16%s_kernel<%d,%d,%d>", np, c.H, c.sw, c.fl);
         case DUDF_FAM_F16R: return snprintf(buf, n, "sweep_f16r%s_kernel<%d,%d,%d>", np, c.H, c.sw, c.fl);
         case DUDF_FAM_F16P: return snprintf(buf, n, "sweep_f16p%s_kernel<%d,%d,%d>", np, c.H, c.sw, c.fl);

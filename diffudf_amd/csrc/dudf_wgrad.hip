@@ -199,24 +199,11 @@ __global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_h
 // v_mfma_f32_32x32x16_bf16 (32 cycles, K = 16) replace eight v_mfma_f32_32x32x2_f32 (64 cycles, K = 2) per 16 points:
 // 2.67x less matrix-pipe time for the same 183 GFLOP.  The split (5.5 VALU ops per element, only of the fragments a
 // wave consumes) runs beside the MFMAs.  tests/test_hip_parity.py holds the result to the SAME tolerances as fp32.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
 struct Split3 { bf16x8 h, m, l; };
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned cvt_pk(f32x2 v) {              // one v_cvt_pk_bf16_f32: lo = bf16(v.x), hi = bf16(v.y)
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ f32x2 unpack(unsigned p) {              // the two bf16 back as exact floats
-    return f32x2{__builtin_bit_cast(float, p << 16), __builtin_bit_cast(float, p & 0xffff0000u)};
-}
 
 // 8 consecutive columns c0..c0+7 of one feature out of the swizzled [fq][16][4] image (column c sits at slot c ^ swz)
 // -> three bf16 fragments, worked on as packed pairs (3 cvt_pk + 4 bit ops + 2 packed subtracts per pair), + the
@@ -396,30 +383,22 @@ __global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_h
 // an X element is split by 2 waves and a Y element by 4 (7.5 VALU instructions per MFMA, PMC).  Here every element is
 // split ONCE: a stage (16 columns x 256 features x 2 operands = 2048 16-byte granules) is dealt out 4 granules per lane
 // — four consecutive columns of one feature quad, 64 contiguous bytes of the stash — loaded straight into registers
-// (non-temporal; no raw copy in LDS), split, and written as bf16 pieces into an LDS image laid out in MFMA-FRAGMENT
+// (no raw copy in LDS), split, and written as bf16 pieces into an LDS image laid out in MFMA-FRAGMENT
 // order ([operand][piece][32-feature block][column half][feature][8 columns]: a fragment is two lane-linear 512-byte
-// halves, conflict-free for ds_read_b128; the halves are 528 bytes apart so that the 8-byte writes do not collide).  The image is double buffered (2 x 48 KiB); one barrier per stage; the next stage's split runs in
-// front of this stage's MFMAs while the stage after that is in flight in registers.
-// VAR bit 0: producer lanes are dealt out so that each ds_write_b64 wave-instruction is bank-conflict free (a 16-lane
-//   service group spans offsets 16 a + 2 b + 4 c + 8 d dwords: fq bit 0 | column-group bit 0 | column half | fq bit 3);
-//   the plain (tid >> 2) order put feature quads 0/2 and 1/3 of a group on the same banks (PMC r01: 29 % of LDS cycles).
-// VAR bit 1: the split of the next stage is cut into four feature slices issued BETWEEN the four MFMA groups of this
-//   stage instead of in front of them: the two waves of a SIMD then leave the post-barrier lockstep (both splitting,
-//   matrix core idle) after the first slice — one wave's slice runs beside the other's MFMAs.
-#ifndef DUDF_WG_NT
+// halves, conflict-free for ds_read_b128; the halves are 528 bytes apart so that the 8-byte writes do not collide).
+// Producer lanes are dealt out so that each ds_write_b64 wave-instruction is bank-conflict free (a 16-lane service group
+// spans offsets 16 a + 2 b + 4 c + 8 d dwords: fq bit 0 | column-group bit 0 | column half | fq bit 3); the plain (tid >> 2)
+// order put feature quads 0/2 and 1/3 of a group on the same banks (PMC r01: 29 % of LDS cycles).
+// There is no workgroup barrier per stage: NB = 3 or 4 images live in LDS beside per-wave progress counters (the flags, see
+// `poll` below).  A wave starts stage `it` when all eight waves have written image `it`, multiplies FIRST, and behind its
+// MFMAs splits image it + 2 — two images ahead — whose register set is then refilled with the stage three further on.
+// (Predecessors — two images and a barrier per stage, split slices between the MFMA groups, static wave priorities: DESIGN.md
+// Appendix A has their numbers, `git log -- diffudf_amd/csrc/dudf_wgrad.hip` their code.)
 // Cache policy of the staging loads: no non-temporal hint.  A lane's four loads sit 64 bytes apart, so every 128-byte line is
 // touched by two different instructions.  While round 3's workspace layout had the stash 64 bytes off the line grid (fixed:
 // dudf_make_layout), the hinted loads fetched 4.17 GB per launch against 2.87 GB of operands and 3.04 GB without the hint
-// (profiles/r03_wgrad_nt.txt); on the aligned layout both forms fetch 2.87 GB and take the same time.  A/B: -DDUDF_WG_NT_ON=1.
-#if DUDF_WG_NT_ON
-#define DUDF_WG_NT " nt"
-#else
-#define DUDF_WG_NT ""
-#endif
-#endif
-#ifndef DUDF_WG_HREL
-#define DUDF_WG_HREL 2             // flag-synchronised variant: hand the matrix pipe over this many MFMA groups before the end of a stage
-#endif
+// (profiles/r03_wgrad_nt.txt); on the aligned layout both forms fetch 2.87 GB and take the same time.
+constexpr int kHandOver = 2;       // a wave hands the matrix pipe over this many MFMA groups before the end of a stage
 #ifndef DUDF_WGRAD_DBG
 #define DUDF_WGRAD_DBG 0           // timing experiments only (wrong results): 1 no loads, 2 no barrier, 4 no MFMA, 8 no split,
 #endif                             // 16 no LDS fragment reads, 32 stage stamps, 64 no output atomics
@@ -441,8 +420,6 @@ extern "C" int dudf_dbg_wstamps(unsigned long long* out) { return (int)hipMemcpy
 // brought to a common product scale 2^P, and the accumulators are multiplied by 2^-P at the end.  Elements more than 2^16
 // below their tensor's maximum lose relative (not absolute) accuracy: they are fp16 subnormals, which v_cvt_pk_f16_f32
 // produces and the MFMA honours (profiles/r03_f16_split_facts.txt).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x16 mfma_f16(f16x8 a, f16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
@@ -467,11 +444,12 @@ __device__ __forceinline__ float dudf_pow2(int k) { return __uint_as_float((unsi
 // the 32 write banks once) and the fragments come out of it through ds_read_b64_tr_b16, gfx950's transposing LDS read: a
 // 16-lane group reads 4 rows (columns k) x 16 features and every lane receives its feature's four k — two of them per
 // fragment (tools/micro/tr_image.hip checks image, swizzle and fragment maps against a host GEMM).
-template <int H, int VAR, int SP = 0, int P24 = 0>
+// NB: image buffers in LDS, 3 or 4 (see the flags below)
+template <int H, int NB, int SP = 0, int P24 = 0>
 __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
     using W = WG<H>;
-    static_assert(H == 256, "256 x 256 output tiles");
-    static_assert(P24 == 0 || (SP != 0 && (VAR & 8) != 0), "24-bit operands: the fp16x3, flag-synchronised build");
+    static_assert(H == 256 && (NB == 3 || NB == 4), "256 x 256 output tiles, three or four images");
+    static_assert(P24 == 0 || SP != 0, "24-bit operands: the fp16x3 build");
     constexpr int NPC = SP ? 2 : 3;                         // pieces per operand
     constexpr int NW_ = W::WO * W::WI;
     constexpr int FQ = H / 4;
@@ -481,7 +459,7 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
     constexpr int PIECEB = P24 ? 16 * ROWB : (H / 32) * BLKB;   // 8.25 KiB (P24: 9)
     constexpr int OPERB = NPC * PIECEB;                     // 24 KiB (16.5; P24: 18)
     constexpr int BUFB = 2 * OPERB;                         // 48 KiB (33; P24: 36)
-    extern __shared__ __attribute__((aligned(16))) char ldsb[];     // [2 buffers][X | Y][h | m | l][feature][16 columns]
+    extern __shared__ __attribute__((aligned(16))) char ldsb[];     // [NB buffers][X | Y][h | m | l][feature][16 columns], then the flags
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -529,8 +507,7 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
     // producer role of this lane: operand, feature quad, group of four columns
     const int p_oper = wave / (NW_ / 2);                                  // wave-uniform: waves 0..3 stage X, 4..7 stage Y
     const int p_cg = tid & 3;
-    const int p_fq = (VAR & 1) ? (((tid >> 2) & 1) | (((tid >> 4) & 3) << 1) | (((tid >> 3) & 1) << 3) | (((tid >> 6) & 3) << 4))
-                               : ((tid >> 2) & (FQ - 1));
+    const int p_fq = ((tid >> 2) & 1) | (((tid >> 4) & 3) << 1) | (((tid >> 3) & 1) << 3) | (((tid >> 6) & 3) << 4);   // conflict-free writes: see above
     // granule j of this lane = stage column p_cg + 4 j: one load instruction then reads 64 contiguous bytes per feature
     // quad (4 lanes x 16 B) and touches each 128-byte line twice instead of four times (PMC r01: 2x the ideal L2
     // requests; the loads alone held the kernel at 0.8 ms).  The image slot 4 p_cg + j therefore holds column p_cg + 4 j:
@@ -587,8 +564,8 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
             const uint64_t g0 = (uint64_t)(size_t)(reinterpret_cast<const char*>(pair_of(it) ? P1 : P0) + (int64_t)step_of(it) * (KB * 16));
             const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)g0), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(g0 >> 32));
             const uint64_t sbase = ((uint64_t)hi32 << 32) | lo32;
-            asm volatile("global_load_dwordx4 %0, %4, %8" DUDF_WG_NT "\n\tglobal_load_dwordx4 %1, %5, %8" DUDF_WG_NT "\n\t"
-                         "global_load_dwordx4 %2, %6, %8" DUDF_WG_NT "\n\tglobal_load_dwordx4 %3, %7, %8" DUDF_WG_NT
+            asm volatile("global_load_dwordx4 %0, %4, %8\n\tglobal_load_dwordx4 %1, %5, %8\n\t"
+                         "global_load_dwordx4 %2, %6, %8\n\tglobal_load_dwordx4 %3, %7, %8"
                          : "=&v"(r.g0), "=&v"(r.g1), "=&v"(r.g2), "=&v"(r.g3)
                          : "v"(t_voff0), "v"(t_voff0 + t_vstep), "v"(t_voff0 + 2 * t_vstep), "v"(t_voff0 + 3 * t_vstep), "s"(sbase) : "memory");
         } else if constexpr (P24 != 0) {
@@ -598,8 +575,8 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
             const uint64_t f0 = (uint64_t)(size_t)((pair_of(it) ? F1 : F0) + (int64_t)step_of(it) * KB);
             const unsigned flo = __builtin_amdgcn_readfirstlane((unsigned)f0), fhi = __builtin_amdgcn_readfirstlane((unsigned)(f0 >> 32));
             const uint64_t fbase = ((uint64_t)fhi << 32) | flo;
-            asm volatile("global_load_dwordx3 %0, %5, %9" DUDF_WG_NT "\n\tglobal_load_dwordx3 %1, %6, %9" DUDF_WG_NT "\n\t"
-                         "global_load_dwordx3 %2, %7, %9" DUDF_WG_NT "\n\tglobal_load_dwordx3 %3, %8, %9" DUDF_WG_NT "\n\t"
+            asm volatile("global_load_dwordx3 %0, %5, %9\n\tglobal_load_dwordx3 %1, %6, %9\n\t"
+                         "global_load_dwordx3 %2, %7, %9\n\tglobal_load_dwordx3 %3, %8, %9\n\t"
                          "global_load_dword %4, %10, %11"
                          : "=&v"(r.g0), "=&v"(r.g1), "=&v"(r.g2), "=&v"(r.g3), "=&v"(r.sc)
                          : "v"(t_voff0), "v"(t_voff0 + t_vstep), "v"(t_voff0 + 2 * t_vstep), "v"(t_voff0 + 3 * t_vstep), "s"(sbase),
@@ -608,8 +585,8 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
         const uint64_t g0 = (uint64_t)(size_t)((pair_of(it) ? P1 : P0) + (int64_t)step_of(it) * KB * 4);
         const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)g0), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(g0 >> 32));
         const uint64_t sbase = ((uint64_t)hi32 << 32) | lo32;
-        asm volatile("global_load_dwordx4 %0, %4, %5" DUDF_WG_NT "\n\tglobal_load_dwordx4 %1, %4, %5 offset:64" DUDF_WG_NT "\n\t"
-                     "global_load_dwordx4 %2, %4, %5 offset:128" DUDF_WG_NT "\n\tglobal_load_dwordx4 %3, %4, %5 offset:192" DUDF_WG_NT
+        asm volatile("global_load_dwordx4 %0, %4, %5\n\tglobal_load_dwordx4 %1, %4, %5 offset:64\n\t"
+                     "global_load_dwordx4 %2, %4, %5 offset:128\n\tglobal_load_dwordx4 %3, %4, %5 offset:192"
                      : "=&v"(r.g0), "=&v"(r.g1), "=&v"(r.g2), "=&v"(r.g3) : "v"(p_voff), "s"(sbase) : "memory");
         }
     };
@@ -642,17 +619,14 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
         if constexpr (P24 == 1) asm volatile("s_waitcnt vmcnt(%5)" : "+v"(r.g0), "+v"(r.g1), "+v"(r.g2), "+v"(r.g3), "+v"(r.sc) : "n"(decltype(younger)::value));
         else asm volatile("s_waitcnt vmcnt(%4)" : "+v"(r.g0), "+v"(r.g1), "+v"(r.g2), "+v"(r.g3) : "n"(decltype(younger)::value));
     };
-    // VAR bit 3: THREE image buffers and per-buffer counters in LDS instead of the workgroup barrier of every stage: a wave
-    // starts stage `it` when all eight waves have written their part of image `it` (counter W) and have finished reading
-    // the buffer its own slices are about to overwrite (counter R, image it - 2): waves may drift up to a stage apart, so the
-    // SIMD partner that the issue arbitration serves first (the older wave) no longer idles a third of every stage at the
-    // barrier while the younger one finishes.
-    constexpr bool CS = (VAR & 8) != 0;
-    // VAR bit 4 (with bit 3): FOUR image buffers.  With three, a wave must ask — a second poll per stage — whether every wave has
-    // finished READING image it - 1 before it splits image it + 2 into that buffer.  With four the buffer of image it + 2 is the one
-    // image it - 2 lived in, and the poll at the top of stage `it` (every wave has WRITTEN image it, which it does behind its reads
-    // of image it - 2: LDS executes a wave's operations in order) already says so: one poll and one flag less per stage.
-    constexpr int NB = (CS && (VAR & 16) != 0) ? 4 : 3;
+    // The flags: per-buffer stage counters in LDS instead of a workgroup barrier per stage.  A wave starts stage `it` when all
+    // eight waves have written their part of image `it` (counter W) and have finished reading the buffer its own split is about
+    // to overwrite (counter R): waves may drift up to a stage apart, so the SIMD partner that the issue arbitration serves first
+    // (the older wave) no longer idles a third of every stage at the barrier while the younger one finishes.
+    // NB = 3: a wave must ask — a second poll per stage — whether every wave has finished READING image it - 1 before it splits
+    // image it + 2 into that buffer.  NB = 4: the buffer of image it + 2 is the one image it - 2 lived in, and the poll at the top
+    // of stage `it` (every wave has WRITTEN image it, which it does behind its reads of image it - 2: LDS executes a wave's
+    // operations in order) already says so: one poll and one flag less per stage.
     // Per-wave progress words in LDS (no atomics, no address registers).  A wave publishes with ds_write_addtid_b32 from lane 0
     // (address M0) and polls the whole block with one ds_read_addtid_b32 (lane i reads word i).  Inline asm: the poll is a
     // loop, and a compiler-visible loop inside the hand-counted stage loop makes hipcc spill registers that still have loads
@@ -810,44 +784,33 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
         else return *reinterpret_cast<const u32x4*>(buf + OPERB + pc * PIECEB + (wi * W::NTL + n) * BLKB + c_lane);
     };
 
-    if constexpr (CS) {
-        if (tid < 128) reinterpret_cast<unsigned*>(ldsb + NB * BUFB)[tid] = 0;
-        __syncthreads();
-    }
-    if constexpr (CS) {                                  // images 0 and 1 written, images 2, 3, 4 in flight (image k: set k % 3)
-        if (nit > 0) {
-            load_raw_plain(0, R0);
-            if (nit > 1) load_raw_plain(1, R1);
-            if (nit > 2) load_raw_plain(2, R2);
-            split_store(0, R0, 0);
-            publish(flag0 + 4u * (unsigned)wave, 1u);                          // one image written
-            if (nit > 3) load_raw_plain(3, R0);
-            if (nit > 1) {
-                split_store(1, R1, 1);
-                publish(flag0 + 4u * (unsigned)wave, 2u);                      // two
-            }
-            if (nit > 4) load_raw_plain(4, R1);
-        }
-    } else if (nit > 0) {
+    if (tid < 128) reinterpret_cast<unsigned*>(ldsb + NB * BUFB)[tid] = 0;
+    __syncthreads();
+    if (nit > 0) {                                       // images 0 and 1 written, images 2, 3, 4 in flight (image k: set k % 3)
         load_raw_plain(0, R0);
-        split_store(0, R0, 0);
         if (nit > 1) load_raw_plain(1, R1);
         if (nit > 2) load_raw_plain(2, R2);
+        split_store(0, R0, 0);
+        publish(flag0 + 4u * (unsigned)wave, 1u);                              // one image written
         if (nit > 3) load_raw_plain(3, R0);
+        if (nit > 1) {
+            split_store(1, R1, 1);
+            publish(flag0 + 4u * (unsigned)wave, 2u);                          // two
+        }
+        if (nit > 4) load_raw_plain(4, R1);
     }
     __syncthreads();
-    // one stage: the next stage's registers -> pieces (its set is then refilled with the stage three further on, so three
-    // stages = 96 KiB per CU stay in flight: with one, the kernel measured latency-bound at 2 TB/s), then 48 MFMAs
+    // one stage: 48 MFMAs, then the registers of the stage two further on -> pieces (that set is then refilled with the stage
+    // three further on, so three stages = 96 KiB per CU stay in flight: with one, the kernel measured latency-bound at 2 TB/s)
 #if DUDF_WGRAD_DBG & 32
     unsigned long long wst[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     auto stage = [&](int it, RawSet& r, auto hot, auto bidx) {
         constexpr int BI = decltype(bidx)::value;             // it % 3 (the loops advance by three stages)
-        const int bcur = !CS ? (it & 1) : (NB == 4 ? (it & 3) : BI), bnext = CS ? (BI + 1) % 3 : ((it + 1) & 1);
-        const char* buf = ldsb + bcur * BUFB;
+        const char* buf = ldsb + (NB == 4 ? (it & 3) : BI) * BUFB;
         constexpr bool HOT = decltype(hot)::value;
         DUDF_WSTAMP(0);
-        if constexpr (CS) {
+        {
             // every wave has written its part of image `it` (generation g + 1 of W[BI]) and has finished reading image
             // it - 1, whose buffer this wave's split of image it + 2 is going to overwrite (R[(BI + 2) % 3])
             // (the second condition is checked in front of the split, behind this stage's MFMAs: the SIMD partner runs half
@@ -860,52 +823,23 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
             poll(uit + 1u, 0u, hi ? uit + 1u : 0u, hi ? 0u : uit);
         }
         constexpr int DBG = HOT ? DUDF_WGRAD_DBG : 0;
-        constexpr bool IL = (VAR & 2) != 0;
-        static_assert(!IL || W::NTL == 4, "one split slice per MFMA group");
-        static_assert(!(CS && IL), "the flag-synchronised variant multiplies first and splits two images ahead");
-        const bool more = HOT || it + 1 < nit;
-        if constexpr (!IL && !CS) {
-            if constexpr (HOT) {                  // steady state: the two younger sets (8 loads) stay in flight
-                wait_raw(r, std::integral_constant<int, 2 * kSetLoads>{});
-                split_store(it + 1, r, bnext);
-                load_raw(it + 4, r);
-            } else if (more) {
-                split_store(it + 1, r, bnext);
-                if (it + 4 < nit) load_raw_plain(it + 4, r);
-            }
-        }
         u32x4 af[W::MT][NPC], bn[NPC];
 #pragma unroll
         for (int m = 0; m < W::MT; ++m)
 #pragma unroll
             for (int pc = 0; pc < NPC; ++pc) af[m][pc] = fragA(buf, m, pc);
         DUDF_WSTAMP(1);
-        if constexpr (!IL) {
 #pragma unroll
-            for (int pc = 0; pc < NPC; ++pc) bn[pc] = fragB(buf, 0, pc);
-        }
+        for (int pc = 0; pc < NPC; ++pc) bn[pc] = fragB(buf, 0, pc);
 #pragma unroll
         for (int n = 0; n < W::NTL; ++n) {
-            if constexpr (IL) {
-                // this group's B fragments, then slice n of the next stage's split (its VALU covers the read latency: no
-                // second fragment set in registers), then this group's MFMAs
-#pragma unroll
-                for (int pc = 0; pc < NPC; ++pc) bn[pc] = fragB(buf, n, pc);
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (HOT && !(DBG & 1)) { if (n == 0) wait_raw(r, std::integral_constant<int, 2 * kSetLoads>{}); }
-                if constexpr (!(DBG & 8)) { if (more) split_slice(it + 1, r, n, bnext); }
-                __builtin_amdgcn_sched_barrier(0);
-                DUDF_WSTAMP(2 + 2 * n);
-            }
             u32x4 bc[NPC];
 #pragma unroll
             for (int pc = 0; pc < NPC; ++pc) bc[pc] = bn[pc];
-            if constexpr (!IL) {
-                if (n + 1 < W::NTL) {
+            if (n + 1 < W::NTL) {
 #pragma unroll
-                    for (int pc = 0; pc < NPC; ++pc) bn[pc] = fragB(buf, n + 1, pc);
-                    __builtin_amdgcn_sched_barrier(0x76);        // LDS reads and MFMAs keep their order: fragments one block ahead
-                }
+                for (int pc = 0; pc < NPC; ++pc) bn[pc] = fragB(buf, n + 1, pc);
+                __builtin_amdgcn_sched_barrier(0x76);        // LDS reads and MFMAs keep their order: fragments one block ahead
             }
 #pragma unroll
             for (int m = 0; m < W::MT; ++m) {
@@ -928,55 +862,40 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
                 }
                 acc[m][n] = c;
             }
-            if constexpr (IL) __builtin_amdgcn_sched_barrier(0);
-            if constexpr (CS) {
-                if (n == W::NTL - DUDF_WG_HREL) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    publish(flag0 + 64u + 4u * (unsigned)wave, (unsigned)it + 1u);                 // nearly done with the matrix pipe
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+            if (n == W::NTL - kHandOver) {
+                __builtin_amdgcn_sched_barrier(0);
+                publish(flag0 + 64u + 4u * (unsigned)wave, (unsigned)it + 1u);                     // nearly done with the matrix pipe
+                __builtin_amdgcn_sched_barrier(0);
             }
             DUDF_WSTAMP(3 + 2 * n);
         }
-        if constexpr (IL) {
-            if constexpr (HOT) { if constexpr (!(DBG & 1)) load_raw(it + 4, r); }
-            else if (it + 4 < nit) load_raw_plain(it + 4, r);
+        // behind this stage's last fragment reads (LDS executes a wave's operations in order): image `it` read; then
+        // the split of image it + 2 into the buffer image it - 1 (NB = 4: it - 2) lived in, and its flag
+        __builtin_amdgcn_sched_barrier(0);
+        const int BW = NB == 4 ? ((it + 2) & 3) : (BI + 2) % 3;
+        if constexpr (NB == 3) {
+            publish(flag0 + 32u + 4u * (unsigned)wave, (unsigned)it + 1u);                       // fragment reads of stage `it` done
+            DUDF_WSTAMP(2);
+            if (HOT || it + 2 < nit) poll(0u, (unsigned)it, 0u, 0u);                             // image it - 1 read by everybody: its buffer is free
         }
-        if constexpr (CS) {
-            // behind this stage's last fragment reads (LDS executes a wave's operations in order): image `it` read; then
-            // the split of image it + 2 into the buffer image it - 1 lived in, and its flag
-            __builtin_amdgcn_sched_barrier(0);
-            const int BW = NB == 4 ? ((it + 2) & 3) : (BI + 2) % 3;
-            if constexpr (NB == 3) {
-                publish(flag0 + 32u + 4u * (unsigned)wave, (unsigned)it + 1u);                   // fragment reads of stage `it` done
-                DUDF_WSTAMP(2);
-                if (HOT || it + 2 < nit) poll(0u, (unsigned)it, 0u, 0u);                         // image it - 1 read by everybody: its buffer is free
-            }
-            DUDF_WSTAMP(4);
-            if constexpr (HOT) {
-                if constexpr (!(DBG & 1)) wait_raw(r, std::integral_constant<int, 2 * kSetLoads>{});         // (DBG: timing experiments, wrong results)
-                DUDF_WSTAMP(6);
-                if constexpr (!(DBG & 8)) split_store(it + 2, r, BW);
-                DUDF_WSTAMP(8);
-                if constexpr (!(DBG & 1)) load_raw(it + 5, r);
-                publish(flag0 + 4u * (unsigned)wave, (unsigned)it + 3u);                         // images 0 .. it + 2 written
-            } else if (it + 2 < nit) {
-                split_store(it + 2, r, BW);
-                if (it + 5 < nit) load_raw_plain(it + 5, r);
-                publish(flag0 + 4u * (unsigned)wave, (unsigned)it + 3u);
-            }
+        DUDF_WSTAMP(4);
+        if constexpr (HOT) {
+            if constexpr (!(DBG & 1)) wait_raw(r, std::integral_constant<int, 2 * kSetLoads>{});             // (DBG: timing experiments, wrong results)
+            DUDF_WSTAMP(6);
+            if constexpr (!(DBG & 8)) split_store(it + 2, r, BW);
+            DUDF_WSTAMP(8);
+            if constexpr (!(DBG & 1)) load_raw(it + 5, r);
+            publish(flag0 + 4u * (unsigned)wave, (unsigned)it + 3u);                             // images 0 .. it + 2 written
+        } else if (it + 2 < nit) {
+            split_store(it + 2, r, BW);
+            if (it + 5 < nit) load_raw_plain(it + 5, r);
+            publish(flag0 + 4u * (unsigned)wave, (unsigned)it + 3u);
         }
         DUDF_WSTAMP(10);
-        if constexpr (!(DBG & 2) && !CS) __syncthreads();
         DUDF_WSTAMP(11);
     };
-    // VAR bit 2: static priority for waves 0-3 (their SIMD partners are waves 4-7).  Both waves of a SIMD leave every
-    // barrier in lockstep, so their split slices (VALU, matrix core idle) and their MFMA groups (matrix core contended)
-    // coincide and interleaving alone buys nothing; with one of them served first at every contended issue slot the other
-    // falls behind by one slice and from then on runs its slices beside the partner's MFMAs.  No per-stage flips.
-    if constexpr ((VAR & 4) != 0) { if (wave < NW_ / 2) __builtin_amdgcn_s_setprio(1); }
-    int it = 0;                                                  // stage it+1 lives in set (it+1) % 3
-    const int nhot = CS ? (nit >= 8 ? ((nit - 5) / 3) * 3 : 0) : (nit >= 7 ? ((nit - 4) / 3) * 3 : 0);
+    int it = 0;
+    const int nhot = nit >= 8 ? ((nit - 5) / 3) * 3 : 0;
     // hipcc does not know the sets are in flight: enter (and leave) the hand-counted loop with everything landed, so that
     // the register copies it places on the loop's edges are harmless; inside, the sets stay put (tests/isa_contract.py
     // replays the loop body twice and fails on any instruction that touches a register with a load in flight)
@@ -987,18 +906,17 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
     };
     drain();
     using B0 = std::integral_constant<int, 0>; using B1 = std::integral_constant<int, 1>; using B2 = std::integral_constant<int, 2>;
-    // register set of a stage: the image it splits — it + 1 (set (it + 1) % 3), or it + 2 with the flags (set (it + 2) % 3)
-    RawSet& Sa = CS ? R2 : R1; RawSet& Sb = CS ? R0 : R2; RawSet& Sc = CS ? R1 : R0;
+    // register set of a stage: that of the image it splits, it + 2 (set (it + 2) % 3)
     for (; it < nhot; it += 3) {
-        stage(it, Sa, std::true_type{}, B0{});
-        stage(it + 1, Sb, std::true_type{}, B1{});
-        stage(it + 2, Sc, std::true_type{}, B2{});
+        stage(it, R2, std::true_type{}, B0{});
+        stage(it + 1, R0, std::true_type{}, B1{});
+        stage(it + 2, R1, std::true_type{}, B2{});
     }
     drain();
     for (; it < nit; it += 3) {
-        stage(it, Sa, std::false_type{}, B0{});
-        if (it + 1 < nit) stage(it + 1, Sb, std::false_type{}, B1{});
-        if (it + 2 < nit) stage(it + 2, Sc, std::false_type{}, B2{});
+        stage(it, R2, std::false_type{}, B0{});
+        if (it + 1 < nit) stage(it + 1, R0, std::false_type{}, B1{});
+        if (it + 2 < nit) stage(it + 2, R1, std::false_type{}, B2{});
     }
 #if DUDF_WGRAD_DBG & 32
     if (bx == 3 && by == 10 && lane == 0)
@@ -1054,23 +972,25 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
 // built without packed fp32 instructions (dudf_internal.h, DUDF_NO_PK): the split slices of one wave then execute beside its
 // SIMD partner's MFMAs (-5 % on this kernel).  The body is a forced-inline function: lambdas defined inside a function
 // that carries the target attribute do not inherit it and would not be inlined.
+// VAR in the kernels' names (profiles, DESIGN.md and the tests know them by it): 9 = three image buffers, 25 = four.
+template <int VAR> constexpr int wg_buffers() { static_assert(VAR == 9 || VAR == 25, "VAR 9: three image buffers, 25: four"); return VAR == 25 ? 4 : 3; }
 template <int H, int VAR>
 __global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_bf16p_kernel(WgradArgs a) {
-    wgrad_hidden_bf16p_body<H, VAR>(a);
+    wgrad_hidden_bf16p_body<H, wg_buffers<VAR>()>(a);
 }
 template <int H, int VAR>
 __global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_f16p_kernel(WgradArgs a) {
-    wgrad_hidden_bf16p_body<H, VAR, 1>(a);
+    wgrad_hidden_bf16p_body<H, wg_buffers<VAR>(), 1>(a);
 }
 // ... the fp32 rows staged 4 rows x 256 bytes per wave-instruction, [column][feature] image, transposed fragment reads
 template <int H, int VAR>
 __global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_f16tr_kernel(WgradArgs a) {
-    wgrad_hidden_bf16p_body<H, VAR, 1, 2>(a);
+    wgrad_hidden_bf16p_body<H, wg_buffers<VAR>(), 1, 2>(a);
 }
 // ... reading 24-bit tile-major operands (dudf_internal.h "p24")
 template <int H, int VAR>
 __global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_f16p24_kernel(WgradArgs a) {
-    wgrad_hidden_bf16p_body<H, VAR, 1, 1>(a);
+    wgrad_hidden_bf16p_body<H, wg_buffers<VAR>(), 1, 1>(a);
 }
 
 // ---- first and last layer: thin reductions over columns (bandwidth-bound, VALU) -------------------------

@@ -150,7 +150,7 @@ def test_wgrad_register_staging_contract(tmp_path):
     behind hand-counted waits; no instruction may read or write such a register before its wait."""
     asm = str(tmp_path / "wgrad.s")
     emit_asm(os.path.join(REPO, "diffudf_amd", "csrc", "dudf_wgrad.hip"), asm)
-    # VAR 9 = conflict-free producer lanes + progress flags instead of the stage barrier: the only variant still instantiated
+    # VAR 9 = the cooperative-split body with three image buffers (25, below: four)
     res = analyse_wgrad_presplit(asm, 9)
     assert res["loads"] == 12 and res["carried"] == 12, res
     assert not res["bad"], res["bad"][:5]

@@ -4,8 +4,10 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 tag=$1; flags=$2
 mkdir -p "$R/dbg/obj_$tag"
 objs=""
-for u in sweep sweep_bf16 wgrad misc sample capudf api; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $flags -c "$R/diffudf_amd/csrc/dudf_$u.hip" -o "$R/dbg/obj_$tag/$u.o" &
+# the translation units of the library: SRCS of csrc/Makefile
+for src in $(sed -n 's/^SRCS *= *//p' "$R/diffudf_amd/csrc/Makefile"); do
+  u=${src%.hip}
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $flags -c "$R/diffudf_amd/csrc/$src" -o "$R/dbg/obj_$tag/$u.o" &
   objs="$objs $R/dbg/obj_$tag/$u.o"
 done
 wait
