@@ -320,7 +320,7 @@ int make_curv_layout(const dudf_net_cfg* cfg, int64_t n, CurvLayout* cl) {
     int64_t o = (int64_t)(cl->q.total_bytes / sizeof(float));
     auto take = [&](int64_t cnt) { int64_t r = o; o += (cnt + 63) / 64 * 64; return r; };
     cl->o_lam = take(3 * n); cl->o_V = take(9 * n); cl->o_x4 = take(4 * cl->npj); cl->o_y = take(cl->npj);
-    // 512-wide layers: a layer's outputs reach the next one through memory (dudf_sweep_bf16.hip, sweep_tile_w) — one layer's
+    // 512-wide layers: a layer's outputs reach the next one through memory (dudf_sweep_wide.hip, sweep_tile_w) — one layer's
     // worth of the jet columns, reused by every layer
     cl->o_relay = cl->q.H == 512 ? take((int64_t)cl->q.H * cl->npj) : cl->o_y;
     cl->total_bytes = (size_t)o * sizeof(float);

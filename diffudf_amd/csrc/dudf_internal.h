@@ -45,7 +45,7 @@ __device__ __forceinline__ f32x2 unpack(unsigned p) {              // the two bf
 //   b1s    [L][H]      = rho b_1 | b_2 | .. | b_L: the hidden layers' biases, contiguous per layer (the forward tails index it by layer)
 //   w1t16  [16][H]     rows 0..2 = rho W_1^T, rest 0: A-operand of the last reverse step (df/dx)
 //   wt     [L-1][H][H] W_l^T for l=2..L     A-operand of the reverse sweeps (f32 kernel)
-//   wimg   bf16x3 images of W_l, then of W_l^T, in A-fragment order (dudf_sweep_bf16.hip)
+//   wimg   bf16x3 images of W_l, then of W_l^T, in A-fragment order (dudf_sweep16.h)
 //   wimg16 fp16 hi/lo images of 2^k_l W_l, then of 2^k_l W_l^T (same order, two pieces; "fp16x3" split)
 //   wsc    [2][L-1]: 2^-k_l (what the accumulators of matrix l are multiplied with), then 2^k_l
 //   ebound [L][np]: max over the features of |e_l| per column (the adjoint forward sweep leaves it for the fp16x3 adjoint
@@ -180,7 +180,7 @@ static inline int dudf_make_layout(const dudf_net_cfg* cfg, int64_t n, int64_t n
 // ---- launchers implemented in the .hip translation units -------------------------------------
 struct SweepArgs {
     const float* theta; const float* w1b; const float* b1s; const float* w1t16; const float* wt;   // b1s: [L][H] biases as packed (row 0 = rho b_1)
-    const char* wimg_f; const char* wimg_t;   // bf16x3 weight images (forward / transposed), dudf_sweep_bf16.hip
+    const char* wimg_f; const char* wimg_t;   // bf16x3 weight images (forward / transposed), dudf_sweep16.h
     const char* wimg16_f; const char* wimg16_t;   // fp16 hi/lo weight images, scaled by 2^k_l per matrix
     const float* wsc;         // [2][L-1]: 2^-k_l | 2^k_l
     unsigned* amax;           // [4][L]: running maxima of |q_l|, |A_l|, |zbar_l|, |h_l| of the quads (bit patterns), or nullptr
@@ -222,6 +222,7 @@ int dudf_launch_kernel(dim3 grid, dim3 block, size_t lds, size_t lds_max, hipStr
 // the launchers take the kernel from a SweepChoice (dudf_variants.h: dudf_choose_sweep / dudf_choose_pair / dudf_choose_wgrad)
 int dudf_launch_sweep(const SweepChoice& c, const SweepArgs& a, hipStream_t st);          // the f32-input MFMA family
 int dudf_launch_sweep_bf16(const SweepChoice& c, const SweepArgs& a, hipStream_t st);     // the 16-bit-core families (H = 128, 256, 512)
+int dudf_launch_sweep_wide(const SweepChoice& c, const SweepArgs& a, hipStream_t st);     // ... of which H = 512 (called by dudf_launch_sweep_bf16)
 int dudf_launch_sweep_pair(const SweepChoice& c, const SweepArgs& aq, const SweepArgs& ap, hipStream_t st);   // quads + plain columns in one grid
 int dudf_launch_pack_bf16(const DudfLayout& lo, const float* theta, float* ws, hipStream_t st);
 

@@ -3,11 +3,14 @@
 //
 // Same sweeps, same tails, same stash as dudf_sweep.hip (see there for what each sweep computes and which reference
 // lines it replaces); what changes is how a hidden layer  OUT[feature][column] = M[feature][k] * IN[k][column]  is
-// multiplied.  Every fp32 operand is split EXACTLY into three bf16 pieces v = h + m + l (8+8+8 significand bits,
-// round-to-nearest at each step so the three pieces always hold all 24 bits); a product is the six partial products
-// whose weight is >= 2^-16 (hh, hm, mh, hl, lh, mm — the dropped ml, lm, ll are below fp32 rounding), accumulated in
-// fp32 by v_mfma_f32_16x16x32_bf16.  Six of those (16 cycles each, K = 32) replace eight v_mfma_f32_16x16x4_f32
-// (32 cycles each, K = 4): 96 instead of 256 matrix-core cycles per 16x16 tile and 32 features.
+// multiplied: on v_mfma_f32_16x16x32_bf16 with every fp32 operand split exactly into three bf16 pieces, or on the fp16
+// instruction with two (dudf_sweep16.h: the split, the weight image and the helpers built on them).
+//
+// The 16-bit sweeps are three translation units over that header.  This one holds the scheme for 128- and 256-wide layers — a
+// layer's accumulators stay in registers (sweep_tile_b, sweep_tile_oct), the kernels of its four families, the pair kernel and
+// their launchers — and dudf_launch_sweep_bf16, which sends 512-wide layers on to dudf_sweep_wide.hip: there a layer's outputs
+// reach the next one through the stash (sweep_tile_w).  dudf_prep.hip holds the kernels that write what both read: the weight
+// images (pack_bf16_kernel, pack_f16_kernel) and the one launch in front of a training forward (prep_kernel).
 //
 // Mapping (output-stationary, K streamed):
 //   * a wave owns 16 columns for a whole sweep; a workgroup is 8 waves = 128 columns, two waves per SIMD, one
@@ -22,16 +25,13 @@
 //     formulas, stash stores) of those two tiles of the previous layer, splits the 8 results into pieces and packs
 //     them (v_cvt_pk_bf16_f32) into 12 registers: the B operand, used at once by 16 tiles x 6 MFMAs and then dead.
 //     Activations never touch LDS, and the tail of step kb+1 overlaps the MFMAs of step kb inside a wave.
-//   * the weights are pre-split once per step (pack kernel below) into an image in A-FRAGMENT ORDER: for every
-//     (k-block, 16-row tile, piece) the 1 KiB that one ds_read_b128 wave-instruction fetches, lane L = (g<<4 | m)
-//     holding M[row m][the 8 features of k-slots (g, 0..7)].  The 48 KiB of a k-block (16 tiles x 3 pieces at H = 256)
-//     are contiguous, so LDS-DMA moves them verbatim in 1 KiB wave-instructions and the reads are lane-linear:
-//     conflict-free without padding or swizzle.  Three buffers (144 KiB), fetched two steps ahead, one barrier per
+//   * the weights are pre-split once per step (dudf_prep.hip) into an image in A-FRAGMENT ORDER (dudf_sweep16.h): the 48 KiB
+//     of a k-block (16 tiles x 3 pieces at H = 256) are contiguous and go to LDS verbatim.  Three buffers (144 KiB), fetched
+//     two steps ahead, one barrier per
 //     k-block, hand-counted vmcnt as in the f32 kernel.  128 columns share every byte fetched from L2: at bf16 rates
 //     the f32 kernel's 64-column workgroups would be bound by L2 -> LDS weight traffic, not by the matrix cores.
 //   * the first layer (K = 3+1) and the output / df/dx matmuls stay on the fp32 MFMA.
-#include "dudf_sweep_common.h"
-#include <type_traits>
+#include "dudf_sweep16.h"
 
 // Variants that were built, measured and NOT kept (tails of a pair half a step apart, one operand set for the fp16x3 adjoint
 // forward sweep, one tile at a time, DMA pieces issued by the idle half of a partial pass, static / per-phase wave priorities,
@@ -39,189 +39,6 @@
 // `git log -- diffudf_amd/csrc/dudf_sweep_bf16.hip` (round 3) their code.
 
 namespace {
-
-// one LDS atomic per wave: 64 lanes hitting the same LDS word serialise (measured: the per-layer publish of the quads' forward
-// sweep cost 0.09 ms per launch that way), so the wave reduces first
-__device__ __forceinline__ void lds_max_wave(unsigned* word, float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    // lane 0 alone, WITHOUT a compiler-visible branch: `if (lane == 0)` ends the basic block, and the sweeps call this in the last
-    // k-block step of every layer — the step then loses the interleaving of its tail with its MFMAs (round 5: the same shape of store
-    // cost the reverse sweeps 12-18 %, profiles/r05_e_ab.txt)
-    const unsigned addr = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned*)word;
-    uint64_t ex;
-    asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_max_u32 %1, %2\n\ts_mov_b64 exec, %0"
-                 : "=&s"(ex) : "v"(addr), "v"(__float_as_uint(v)) : "memory");
-}
-constexpr int NWB = 8;                                 // waves per workgroup: two per SIMD
-constexpr int TILEB = NWB * 16;                        // columns per workgroup pass
-
-// SP = 0: exact three-piece bf16 split, six products ("bf16x6").  SP = 1: fp16 hi/lo split, three products ("fp16x3"):
-// v * 2^k = hi + lo with two round-to-nearest fp16 pieces (|v 2^k - hi - lo| <= 2^-23 |v 2^k|; fp16 subnormals are
-// produced by v_cvt_pk_f16_f32 and honoured by the MFMA — tools/micro/f16_split.hip, profiles/r03_f16_split_facts.txt),
-// products hi*hi + hi*lo + lo*hi; the dropped lo*lo is <= 2^-22 of the product.  Half the matrix-core work, a third less
-// LDS traffic, 2 conversions instead of 3 per value; the price is fp16's range: the weights are scaled per matrix by a power
-// of two (pack kernel), the activations where their size is not known a priori (see `ColScale`).
-template <int H, int SP = 0>
-struct GeoB {
-    static constexpr int NPC = SP ? 2 : 3;             // pieces per operand
-    static constexpr int NT = H / 16;                  // 16-feature tiles per activation vector
-    static constexpr int NKB = H / 32;                 // 32-feature k-blocks = weight chunks per layer
-    static constexpr int FRAG = 1024;                  // bytes of one A fragment: 64 lanes x 8 x 16 bits
-    static constexpr int CHUNKB = NT * NPC * FRAG;     // one k-block of a matrix: [tile][piece]
-    static constexpr int IMGB = NKB * CHUNKB;          // one matrix: 6 (4) bytes per weight
-    static constexpr int NDMA = NT * NPC / NWB;        // LDS-DMA wave-instructions per wave and chunk
-    static constexpr int NTHR = 64 * NWB;
-};
-
-
-__device__ __forceinline__ f32x4 mfma_b(bf16x8 a, bf16x8 b, f32x4 c) {
-#if DUDF_SWEEP_DBG & 4
-    asm volatile("" : "+v"(c) : "v"(a), "v"(b)); return c;
-#endif
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-// 8 fp32 values (two accumulator tiles' registers of one lane) -> the three bf16x8 pieces of a B / A operand
-__device__ __forceinline__ void split8(const f32x4 e0, const f32x4 e1, u32x4& h, u32x4& m, u32x4& l) {
-    const f32x2 v[4] = {{e0[0], e0[1]}, {e0[2], e0[3]}, {e1[0], e1[1]}, {e1[2], e1[3]}};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned hp = cvt_pk(v[i]);
-        const f32x2 r1 = v[i] - unpack(hp);                        // exact
-        const unsigned mp = cvt_pk(r1);
-        const f32x2 r2 = r1 - unpack(mp);                          // exact
-        h[i] = hp; m[i] = mp; l[i] = cvt_pk(r2);
-    }
-}
-__device__ __forceinline__ f32x4 mfma_h(f16x8 a, f16x8 b, f32x4 c) {
-#if DUDF_SWEEP_DBG & 4
-    asm volatile("" : "+v"(c) : "v"(a), "v"(b)); return c;
-#endif
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-// 8 fp32 values -> the two fp16x8 pieces hi = fp16(v), lo = fp16(v - hi) (the caller has scaled v into fp16's range)
-__device__ __forceinline__ void split8h(const f32x4 e0, const f32x4 e1, u32x4& h, u32x4& l) {
-    const f32x2 v[4] = {{e0[0], e0[1]}, {e0[2], e0[3]}, {e1[0], e1[1]}, {e1[2], e1[3]}};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f16x2 hp = __builtin_convertvector(v[i], f16x2);      // v_cvt_pk_f16_f32, round to nearest even
-        // r = v - hi, exact.  v_fma_mix_f32 reads the fp16 half directly (no v_cvt_f32_f16) and issues beside the SIMD
-        // partner's MFMAs like a plain v_fma_f32 (tools/micro/coissue.hip); hipcc folds `fma(v, 1, -hi)` back into
-        // convert + subtract, hence the asm
-        f32x2 r;
-        asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r.x) : "v"(v[i].x), "v"(hp));
-        asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r.y) : "v"(v[i].y), "v"(hp));
-        h[i] = __builtin_bit_cast(unsigned, hp);
-        l[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-    }
-}
-__device__ __forceinline__ f16x8 as_h(u32x4 v) { return __builtin_bit_cast(f16x8, v); }
-__device__ __forceinline__ bf16x8 as_bf(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ u32x4 as_u(f32x4 v) { return __builtin_bit_cast(u32x4, v); }
-__device__ __forceinline__ f32x4 as_f(u32x4 v) { return __builtin_bit_cast(f32x4, v); }
-
-// One chunk of a weight image -> LDS buffer, 1 KiB per wave-instruction (see dudf_sweep.hip for why this is inline asm).
-// `lds_off` is the buffer's LDS byte offset, `voff` = lane * 16; this wave moves pieces wave*NDMA .. +NDMA-1.  One asm
-// block: scalar base + lane offset addressing, M0 (the LDS destination) saved and restored once — under 2 instructions
-// per piece instead of 11 through generic pointers.
-template <int H, int SP = 0>
-__device__ __forceinline__ void dma_issue(const char* __restrict__ chunk, unsigned lds_off, unsigned voff, int wave) {
-    using G = GeoB<H, SP>;
-    static_assert(G::NDMA == 6 || G::NDMA == 3 || G::NDMA == 4 || G::NDMA == 2, "asm below is written for 2, 3, 4 or 6 pieces per wave");
-#if DUDF_SWEEP_DBG & 8
-    return;
-#endif
-    const uint64_t g0 = (uint64_t)(size_t)chunk + (uint64_t)wave * (G::NDMA * G::FRAG);       // wave-uniform
-    const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)g0), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(g0 >> 32));
-    const uint64_t sbase = ((uint64_t)hi32 << 32) | lo32;
-    const unsigned l0 = __builtin_amdgcn_readfirstlane(lds_off + (unsigned)wave * (G::NDMA * G::FRAG));
-    unsigned keep;
-    if constexpr (G::NDMA == 6) {
-        // the instruction offset is added to the global AND to the LDS address; past its 4 KiB reach: a second lane
-        // offset and M0 + 4096
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, %2\n\t"
-                     "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                     "global_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                     "global_load_lds_dwordx4 %1, %2 offset:3072\n\t"
-                     "s_add_u32 m0, m0, 0x1000\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %4, %2\n\t"
-                     "global_load_lds_dwordx4 %4, %2 offset:1024\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(l0), "v"(voff + 4096u) : "memory", "scc");
-    } else if constexpr (G::NDMA == 4) {
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, %2\n\t"
-                     "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                     "global_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                     "global_load_lds_dwordx4 %1, %2 offset:3072\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(l0) : "memory");
-    } else if constexpr (G::NDMA == 3) {
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, %2\n\t"
-                     "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                     "global_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(l0) : "memory");
-    } else {
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, %2\n\t"
-                     "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(l0) : "memory");
-    }
-}
-template <int N>
-__device__ __forceinline__ void dma_wait_b() {
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-}
-
-#if DUDF_SWEEP_DBG & 128
-// phase stamps (timing experiments): [sweep][wave][k-block][stamp] of one workgroup's first pass, layer 3
-__device__ unsigned long long g_stamp[4][8][8][8];
-extern "C" int dudf_dbg_stamps(unsigned long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp), sizeof(g_stamp));
-}
-#define DUDF_STAMP(i) do { if (stamp_on && j == 3) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-        if (lane == 0) g_stamp[BS & 3][wave][kb][i] = t_; __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define DUDF_STAMP(i) do { } while (0)
-#endif
-struct TailOps { f32x4 o1a, o2a, o3a, o1b, o2b, o3b, ba, bb; };   // operands of one pair of tiles (+ bias, forward sweeps)
-
-// LDS offset of the per-layer running maxima: behind the three weight buffers — and behind the biases where the fp16x3 forward
-// sweeps keep them (the quads' forward sweep has both)
-template <int H, int SW, int SP>
-__device__ __forceinline__ unsigned amax_lds_off(const SweepArgs& a) {
-    return 3u * GeoB<H, SP>::CHUNKB + ((SP != 0 && base_of(SW) == SWEEP_FWD) ? (unsigned)(a.L * H * sizeof(float)) : 0u);
-}
-
-// Shared by the three tile bodies.  (Their other repeated lambdas — image, in_layer, stash_base, the LaneOff construction — and the
-// drivers' amax / clock code stay per body: as free functions they moved the generated code of 3 to 140 kernels, tools/asm_diff.py.)
-__device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
-// fp16x3 column scale from a bound < 2^(E - 126) of the column: sb = 2^(15 - (E - 126)) brings it below 2^15, inv_sb = 1 / sb
-__device__ __forceinline__ void col_scale(float bound, float& sb, float& inv_sb) {
-    unsigned E = (__float_as_uint(bound) >> 23) & 255u;
-    E = E < 27u ? 27u : (E > 250u ? 250u : E);             // all-zero (padding) columns, infinities: any finite scale will do
-    sb = __uint_as_float((268u - E) << 23);
-    inv_sb = __uint_as_float((E - 14u) << 23);
-}
-// max |.| over N accumulator tiles' registers and the 4 lane quarters: per column
-template <int N>
-__device__ __forceinline__ float col_absmax(const f32x4 (&t)[N]) {
-    float m = 0.f;
-    // dudf_track is inline asm, and these are MFMA results: hipcc's hazard recogniser does not see an asm statement's
-    // register reads, so the wait states between the last MFMA and the first read are spelled out (found the hard way:
-    // the last layer's column scale came from stale accumulators)
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 15\n\ts_nop 15");
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int T = 0; T < N; ++T) dudf_track(m, t[T]);
-    m = fmaxf(m, __shfl_xor(m, 16));
-    return fmaxf(m, __shfl_xor(m, 32));
-}
 
 // One pass: the workgroup's waves 0..nact-1 take the 16-column groups g_first.. through a whole sweep.  Waves beyond
 // nact (the last, partial pass of a workgroup's share) only keep the weight stream and the barriers going.
@@ -1033,175 +850,6 @@ __global__ __launch_bounds__(64 * NWB) DUDF_NO_PK void sweep_pair_kernel(SweepAr
     else sweep_body_b<H, SWP, FLP, 1, P24>(ap, (int)blockIdx.x - nbq, (int)gridDim.x - nbq);
 }
 
-// theta -> bf16x3 images in A-fragment order of W_l (forward sweeps) and W_l^T (reverse sweeps), l = 2..L
-template <int H>
-__device__ __forceinline__ void pack_bf16_body(const float* __restrict__ theta, char* __restrict__ img_f,
-                                               char* __restrict__ img_t, int nhid, int64_t off_hid,
-                                               int64_t hid_stride, int64_t block, int64_t nblocks) {
-    using G = GeoB<H>;
-    const int64_t total = (int64_t)2 * nhid * G::NKB * G::NT * 64;
-    for (int64_t idx = block * 256 + threadIdx.x; idx < total; idx += nblocks * 256) {
-        int64_t v = idx;
-        const int lane = (int)(v & 63); v >>= 6;
-        const int T = (int)(v % G::NT); v /= G::NT;
-        const int kb = (int)(v % G::NKB); v /= G::NKB;
-        const int j = (int)(v % nhid); v /= nhid;
-        const int dir = (int)v;
-        const int m = lane & 15, g = lane >> 4;
-        const int row = 16 * T + m;
-        const float* W = theta + off_hid + (int64_t)j * hid_stride;
-        f32x4 e0, e1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int f0 = 32 * kb + 4 * g + e, f1 = f0 + 16;
-            e0[e] = dir == 0 ? W[(int64_t)row * H + f0] : W[(int64_t)f0 * H + row];
-            e1[e] = dir == 0 ? W[(int64_t)row * H + f1] : W[(int64_t)f1 * H + row];
-        }
-        u32x4 h, mm, l;
-        split8(e0, e1, h, mm, l);
-        char* base = (dir == 0 ? img_f : img_t) + (size_t)j * G::IMGB + (size_t)kb * G::CHUNKB + (size_t)T * 3 * G::FRAG + lane * 16;
-        *reinterpret_cast<u32x4*>(base) = h;
-        *reinterpret_cast<u32x4*>(base + G::FRAG) = mm;
-        *reinterpret_cast<u32x4*>(base + 2 * G::FRAG) = l;
-    }
-}
-template <int H>
-__global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict__ theta, char* __restrict__ img_f,
-                                                        char* __restrict__ img_t, int nhid, int64_t off_hid,
-                                                        int64_t hid_stride) {
-    pack_bf16_body<H>(theta, img_f, img_t, nhid, off_hid, hid_stride, blockIdx.x, gridDim.x);
-}
-
-// theta -> fp16 hi/lo images of 2^k_j W_l and 2^k_j W_l^T in the same A-fragment order, k_j = 15 - (exponent of max |W_l|):
-// the largest weight lands in [2^14, 2^15), weights down to 2^-18 of it keep two full pieces, smaller ones an absolute
-// error of 2^-40 of the largest.  grid = (blocks per matrix, L - 1); every block reduces max |W_l| itself (256 KB from L2).
-template <int H>
-__device__ __forceinline__ void pack_f16_body(const float* __restrict__ theta, char* __restrict__ img_f,
-                                              char* __restrict__ img_t, float* __restrict__ wsc, int nhid,
-                                              int64_t off_hid, int64_t hid_stride, int j, int sub, int nsub) {
-    using G = GeoB<H, 1>;
-    const float* W = theta + off_hid + (int64_t)j * hid_stride;
-    __shared__ float red[4];
-    float mx = 0.f;
-    for (int i = threadIdx.x; i < H * H / 4; i += 256) {
-        const f32x4 v = reinterpret_cast<const f32x4*>(W)[i];
-        mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    int ex = 0;
-    (void)frexpf(mx, &ex);                              // mx < 2^ex (0 -> 0; inf / nan: whatever, the step is lost anyway)
-    ex = ex < -100 ? -100 : (ex > 100 ? 100 : ex);
-    const float sc = ldexpf(1.f, 15 - ex);
-    if (sub == 0 && threadIdx.x == 0) { wsc[j] = ldexpf(1.f, ex - 15); wsc[nhid + j] = sc; }
-    const int per = 2 * G::NKB * G::NT * 64;            // lane-items of this matrix: [dir][k-block][tile][lane]
-    for (int idx = sub * 256 + threadIdx.x; idx < per; idx += nsub * 256) {
-        int v = idx;
-        const int lane = v & 63; v >>= 6;
-        const int T = v % G::NT; v /= G::NT;
-        const int kb = v % G::NKB; v /= G::NKB;
-        const int dir = v;
-        const int m = lane & 15, g = lane >> 4;
-        const int row = 16 * T + m;
-        f32x4 e0, e1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int f0 = 32 * kb + 4 * g + e, f1 = f0 + 16;
-            e0[e] = sc * (dir == 0 ? W[(int64_t)row * H + f0] : W[(int64_t)f0 * H + row]);
-            e1[e] = sc * (dir == 0 ? W[(int64_t)row * H + f1] : W[(int64_t)f1 * H + row]);
-        }
-        u32x4 h, l;
-        split8h(e0, e1, h, l);
-        char* base = (dir == 0 ? img_f : img_t) + (size_t)j * G::IMGB + (size_t)kb * G::CHUNKB + (size_t)T * 2 * G::FRAG + lane * 16;
-        *reinterpret_cast<u32x4*>(base) = h;
-        *reinterpret_cast<u32x4*>(base + G::FRAG) = l;
-    }
-}
-template <int H>
-__global__ __launch_bounds__(256) void pack_f16_kernel(const float* __restrict__ theta, char* __restrict__ img_f,
-                                                       char* __restrict__ img_t, float* __restrict__ wsc, int nhid,
-                                                       int64_t off_hid, int64_t hid_stride) {
-    pack_f16_body<H>(theta, img_f, img_t, wsc, nhid, off_hid, hid_stride, blockIdx.y, blockIdx.x, gridDim.x);
-}
-
-// ---- everything a training forward needs in front of its sweeps, in ONE launch (the C ABI keeps its entry points; round 2
-// launched pack, pack_bf16, x4 and two memsets separately: ~5 us each, 1.7 % of a 3.5 ms step).  Block roles by index range.
-struct PrepArgs {
-    const float* theta; const float* x;
-    float *w1b, *b1s, *w1t16, *wt, *x4, *wsc;
-    float rho;                                          // w0 / ww: the first layer as the kernels see it
-    char *img16_f, *img16_t, *img_f, *img_t;
-    unsigned* zero; int nzero;                          // the loss sums + ticket and the running maxima: nzero dwords from `zero`
-    unsigned* zero2; int nzero2;
-    int L, nsub;
-    int64_t off_hid, hid_stride, n, n_h, ncol_h, np;
-    int nb_f16, nb_bf16, nb_x4, nb_thin, nb_wt;         // blocks per role
-};
-template <int H>
-__global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
-    int b = blockIdx.x;
-    const int nhid = a.L - 1;
-    if (b < a.nb_f16) { pack_f16_body<H>(a.theta, a.img16_f, a.img16_t, a.wsc, nhid, a.off_hid, a.hid_stride, b / a.nsub, b % a.nsub, a.nsub); return; }
-    b -= a.nb_f16;
-    if (b < a.nb_bf16) { pack_bf16_body<H>(a.theta, a.img_f, a.img_t, nhid, a.off_hid, a.hid_stride, b, a.nb_bf16); return; }
-    b -= a.nb_bf16;
-    if (b < a.nb_x4) {
-        // x4: the layer-1 B operand of every column.  plain column: (x0,x1,x2,1); Hessian quad: channel 0 the same, channel
-        // 1+k = (e_k, 0); padding: zeros (as make_x4_kernel, dudf_misc.hip)
-        for (int64_t c = (int64_t)b * 256 + threadIdx.x; c < a.np; c += (int64_t)a.nb_x4 * 256) {
-            f32x4 v = {0, 0, 0, 0};
-            if (c < a.ncol_h) {
-                const int64_t p = c >> 2; const int ch = (int)(c & 3);
-                if (p < a.n_h) {
-                    if (ch == 0) v = f32x4{a.x[p * 3], a.x[p * 3 + 1], a.x[p * 3 + 2], 1.f};
-                    else v[ch - 1] = 1.f;
-                }
-            } else {
-                const int64_t p = a.n_h + (c - a.ncol_h);
-                if (p < a.n) v = f32x4{a.x[p * 3], a.x[p * 3 + 1], a.x[p * 3 + 2], 1.f};
-            }
-            *reinterpret_cast<f32x4*>(a.x4 + c * 4) = v;
-        }
-        return;
-    }
-    b -= a.nb_x4;
-    if (b < a.nb_thin) {                                 // w1b[f][k] = k<3 ? W_1[f][k] : b_1[f];  w1t16[r][f] = r<3 ? W_1[f][r] : 0;  zeros
-        const int n_thin = 16 * H > a.L * H ? 16 * H : a.L * H;
-        for (int gid = b * 256 + threadIdx.x; gid < n_thin; gid += a.nb_thin * 256) {
-            if (gid < 4 * H) {
-                const int f = gid / 4, k = gid % 4;
-                a.w1b[gid] = a.rho * (k < 3 ? a.theta[f * 3 + k] : a.theta[3 * H + f]);
-                if (k == 3) a.b1s[f] = a.rho * a.theta[3 * H + f];
-            }
-            if (gid >= H && gid < a.L * H) {                 // b1s rows 1 .. L-1 = b_2 .. b_L (16 H >= L H is not guaranteed: see the loop bound)
-                const int layer = gid / H, f = gid % H;
-                a.b1s[gid] = a.theta[a.off_hid + (int64_t)(layer - 1) * a.hid_stride + (int64_t)H * H + f];
-            }
-            if (gid < 16 * H) {
-                const int r = gid / H, f = gid % H;
-                a.w1t16[gid] = r < 3 ? a.rho * a.theta[f * 3 + r] : 0.f;
-            }
-        }
-        if (b == 0) {
-            for (int i = threadIdx.x; i < a.nzero; i += 256) a.zero[i] = 0u;
-            for (int i = threadIdx.x; i < a.nzero2; i += 256) a.zero2[i] = 0u;
-        }
-        return;
-    }
-    b -= a.nb_thin;
-    {                                                    // wt[j][i][o] = W_{j+2}[o][i] (f32-input reverse sweeps)
-        const int64_t n_wt = (int64_t)nhid * H * H;
-        for (int64_t gid = (int64_t)b * 256 + threadIdx.x; gid < n_wt; gid += (int64_t)a.nb_wt * 256) {
-            const int64_t j = gid / ((int64_t)H * H), rem = gid % ((int64_t)H * H);
-            const int i = (int)(rem / H), o = (int)(rem % H);
-            a.wt[gid] = a.theta[a.off_hid + j * a.hid_stride + (int64_t)o * H + i];
-        }
-    }
-}
-
 // the instantiation of a family: the forward, Hessian-quad and jet sweeps are the builds without packed fp32 instructions
 template <int H, int FAM, int SW, int FL>
 constexpr auto sweep_kernel_of() {
@@ -1229,379 +877,6 @@ int launch_b(const SweepChoice& c, const SweepArgs& a, hipStream_t st) {
     });
 }
 
-
-// ====================================================================================================================
-// 512-wide layers (BASELINE.json configs[2]: SIREN 8x512), plain columns, training variants.
-// The scheme above keeps this layer's AND the previous layer's accumulators in registers (2 x NT x 4): at H = 512 that
-// is 256 registers before anything else, i.e. one wave per SIMD and 64-column workgroups, which the weight stream cannot
-// feed.  Here a wave keeps only THIS layer's 32 accumulator tiles (128 registers, two waves per SIMD, 128-column
-// workgroups as above) and the previous layer's outputs travel through the stash arrays the sweep writes anyway:
-//   * when a layer's accumulators are final its elementwise tails run in one burst (same `epilogue` as everywhere: bias,
-//     sin/cos or adjoint formulas, stash stores) — the post-tail value of every tile is exactly what one of those stores
-//     leaves behind (forward: h_l in S; reverse: q_l in Q; adjoint forward: A_l; adjoint reverse: zbar_l in Z);
-//   * the next layer reads its B operand back, one k-block (two 16-byte loads per lane) ahead of its use — this wave's
-//     own 2 KB per column, written a moment ago — splits it into the three bf16 pieces, and uses it for the 32 output
-//     tiles in two half-steps of 16 tiles: a weight chunk stays 48 KiB ([k-block][half]: the image of a k-block is
-//     [tile][piece], so a half is contiguous) and the three-buffer LDS-DMA stream is the one above;
-//   * the read-back loads are inline asm like the DMA: inside the k-loop the compiler sees no vector-memory operation,
-//     every wait is hand-counted (derivation at the waits); around a tail burst everything is drained once per layer.
-// Cost against the register-resident scheme: one more stash unit READ per layer and sweep (largely served by L2 / the
-// Infinity Cache: it is the unit just written), and the burst is not overlapped with this wave's own MFMAs.
-// which stash array carries the post-tail values of sweep SW to the next layer.  Where the tail does not store them itself
-// (queries: the reverse sweep without its training stores, the jets) the kernel stores them into S, which no later tail of
-// the same sweep reads.
-template <int SW, int FL>
-__device__ __forceinline__ const float* wide_in(const SweepArgs& a) {
-    constexpr int BS = base_of(SW);
-    if constexpr (BS == SWEEP_FWD) return a.S;
-    else if constexpr (BS == SWEEP_REV) return (FL & 1) ? a.Q : a.S;
-    else if constexpr (BS == SWEEP_ADJ_FWD) return a.A;
-    else return a.Z;
-}
-template <int SW, int FL>
-constexpr bool wide_relay_store() { return (base_of(SW) == SWEEP_REV && !(FL & 1)) || SW == SWEEP_FWD_J; }
-
-template <int SP>
-struct GeoWT {
-    static constexpr int NPC = SP ? 2 : 3;              // pieces per operand (fp16 hi | lo, or bf16 h | m | l)
-    static constexpr int H = 512, NT = 32, NKB = 16, FRAG = 1024;
-    static constexpr int HALFT = 16;                    // tiles per half-step
-    static constexpr int CHUNKB = HALFT * NPC * FRAG;   // 48 (32) KiB: one (k-block, half) of a matrix
-    static constexpr int IMGB = NKB * 2 * CHUNKB;       // one matrix (= GeoB<512, SP>::IMGB)
-    static constexpr int NDMA = HALFT * NPC / NWB;      // 6 (4) LDS-DMA wave-instructions per wave and chunk
-    static constexpr int NTHR = 64 * NWB;
-};
-using GeoW = GeoWT<0>;
-
-// SP = 1: fp16x3 (see GeoB).  The B operand of a layer is read back from the stash AFTER the whole previous layer has been
-// written, so its per-column scale is exact here: 2^15 over the column's largest |output| of the tail burst.
-// P24 (0 or 6): R, E as 24-bit floats and C as 24-bit fixed point, tile-major (dudf_internal.h) — the arrays that are NOT the relay.
-template <int SW, int FL, int SP = 0, int P24 = 0>
-__device__ __forceinline__ void sweep_tile_w(const SweepArgs& a, const int g_first, const int nact, char* lds, unsigned& gc) {
-    static_assert(P24 == 0 || (P24 == 6 && SP != 0 && !is_jet(SW)), "24-bit stash arrays in the 512-wide kernel: R, E, C of the fp16x3 training variants");
-    using G = GeoWT<SP>;
-    constexpr int H = G::H;
-    constexpr int NPC = G::NPC;
-    constexpr int BS = base_of(SW);
-    constexpr bool HS = is_hess(SW);                   // Hessian quads / jets: the tails couple lanes (dudf_sweep_common.h)
-    constexpr bool kColScale = SP != 0 && SW != SWEEP_FWD;   // (the quads' forward tangents are not bounded by 1)
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, q = lane >> 4;
-    const bool isv = !HS || (is_jet(SW) ? li == 0 : (lane & 3) == 0);
-    const int nhid = a.L - 1;
-    constexpr bool kFwdDir = (BS == SWEEP_FWD || BS == SWEEP_ADJ_FWD);
-    const int64_t p = (int64_t)(g_first + wave) * 16 + li;
-    auto image = [&](int j) -> const char* {
-        if constexpr (SP) return kFwdDir ? a.wimg16_f + (size_t)j * G::IMGB : a.wimg16_t + (size_t)(nhid - 1 - j) * G::IMGB;
-        return kFwdDir ? a.wimg_f + (size_t)j * G::IMGB : a.wimg_t + (size_t)(nhid - 1 - j) * G::IMGB;
-    };
-    auto unscale_of = [&](int j) -> float { return a.wsc[kFwdDir ? j : nhid - 1 - j]; };
-    float unscale = 1.f, sb = 1.f, inv_sb = 1.f;        // accumulators -> true values | scale of the B operand being read back
-    auto in_layer = [&](int j) -> int { return kFwdDir ? j : a.L - 1 - j; };
-    auto bias_ptr = [&](int layer) -> const float* {
-        return a.b1s + (size_t)layer * H;              // [L][H] biases as packed (row 0 = rho b_1)
-    };
-    auto stash_base = [&](int layer, int T) -> int64_t {
-        const int64_t v = (int64_t)layer * a.stash_layer + (int64_t)(16 * T) * a.np;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return (int64_t)(((uint64_t)hi << 32) | lo);
-    };
-    const unsigned vo = (unsigned)(((int64_t)q * a.np + p) * 16);
-    const LaneOff vl(vo, (is_hess(SW) && !is_jet(SW)) ? (unsigned)(((int64_t)q * a.np + (p >> 2)) * 16) : vo,   // C: one copy per quad
-                     P24 ? (unsigned)(((p >> 4) * 64 + lane) * 12) : 0u,                                          // 24-bit tile-major arrays
-                     !P24 ? 0u : (is_hess(SW) && !is_jet(SW)) ? (unsigned)(((p >> 6) * 64 + 16 * q + ((p >> 2) & 15)) * 12)
-                                                              : (unsigned)(((p >> 4) * 64 + lane) * 12));
-    const int total2 = nhid * G::NKB * 2;
-    auto chunk_src = [&](int c2) -> const char* {       // c2 = (matrix, k-block, half), wave-uniform
-        const int j = c2 / (G::NKB * 2);
-        return image(j) + (size_t)(c2 - j * G::NKB * 2) * G::CHUNKB;
-    };
-    auto dma = [&](int c2, unsigned buf) {
-        // GeoB<256, SP> has the same chunk geometry (16 tiles x NPC pieces): reuse its issue code
-        dma_issue<256, SP>(chunk_src(c2), (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds + buf * G::CHUNKB,
-                       (unsigned)lane * 16u, wave);
-    };
-    __syncthreads();                                   // every wave is past its last LDS read of the previous pass
-    dma(0, gc);
-    dma(1, (gc + 1) % 3);
-    if (wave >= nact) {                                // idle waves of a partial pass: same DMA pieces, same barriers
-        dma_wait_b<0>();
-        __syncthreads();
-        for (int j = 0; j < nhid; ++j) {
-            for (int hs = 0; hs < G::NKB * 2; ++hs) {
-                const int c2 = j * G::NKB * 2 + hs;
-                const bool more = c2 + 2 < total2;
-                if (more) dma(c2 + 2, (gc + 2) % 3);
-                gc = (gc + 1) % 3;
-                if (more) dma_wait_b<G::NDMA>(); else dma_wait_b<0>();
-                __syncthreads();
-            }
-            dma_wait_b<0>();
-            __syncthreads();                           // the barrier behind the active waves' tail burst
-        }
-        return;
-    }
-
-    f32x4 acc[G::NT];
-    float part = 0.f;                                  // forward: y partial sums; reverse: df/dx accumulator
-    f32x4 accg = {0, 0, 0, 0};
-    // ---- the elementwise tails of all 32 tiles of `layer` (operands one pair ahead), stash stores, output stage ----
-    constexpr int kRow = amax_row<SW, FL>();
-    unsigned* lds_amax = reinterpret_cast<unsigned*>(lds + 3 * G::CHUNKB);
-    auto tail_burst = [&](int layer, bool last) {
-        TailTrack tmax;
-        // operand ring: the stash operands of tile T + PD are requested when tile T has been consumed.  One tile of tail is
-        // ~100 instructions, an HBM round trip ~2 us: with the operands only one tile ahead the burst waited for memory at
-        // every tile (it took about as long as the layer's whole k-loop); the forward sweep only reads its bias (cached).
-        // (three-operand tails — the quads' adjoint sweeps — get a ring of four: 128 accumulator registers leave no more)
-        constexpr int PD = (BS == SWEEP_FWD) ? 2 : ((SW == SWEEP_ADJ_FWD_H || SW == SWEEP_ADJ_REV_H) ? 4 : 8);
-        f32x4 o1[PD], o2[PD], o3[PD], bs[PD];
-        auto ld = [&](int T, int s) {
-            epilogue_loads<SW, FL, P24>(a, stash_base(layer, T), vl, o1[s], o2[s], o3[s]);
-            if constexpr (BS == SWEEP_FWD) bs[s] = *reinterpret_cast<const f32x4*>(bias_ptr(layer) + 16 * T + 4 * q);
-        };
-        float cmax = 0.f;                              // fp16x3: largest |output| of this lane's rows of the column
-#pragma unroll
-        for (int T = 0; T < PD; ++T) ld(T, T);
-        // (two halves of 16 tiles, each its own fully unrolled loop: as ONE loop of 32 the larger tails — the quads' adjoint forward
-        //  sweep with 24-bit arrays — exceed hipcc's size limit for a forced unroll, and the rolled loop indexes acc[] dynamically)
-        //  The jets' tail is too large even so; their loop stays the single rolled one it has been since round 3.)
-        auto burst_range = [&](auto t0c, auto t1c) {
-        constexpr int T0 = decltype(t0c)::value, T1 = decltype(t1c)::value;
-#pragma unroll
-        for (int T = T0; T < T1; ++T) {
-            const int s = T % PD;
-            f32x4 z = acc[T];
-            const f32x4 zero4 = {0, 0, 0, 0};
-            if constexpr (SP != 0 && SW == SWEEP_FWD) z = __builtin_elementwise_fma(z, f32x4{unscale, unscale, unscale, unscale}, bs[s]);
-            else if constexpr (SW == SWEEP_FWD) z += bs[s];
-            else if constexpr (BS == SWEEP_FWD) z = (SP != 0 ? z * unscale : z) + (isv ? bs[s] : zero4);   // the bias: value channel only
-            else if constexpr (SP != 0) z *= unscale;
-            // (RL: the array the next layer reads its operand back from keeps the default cache policy)
-            const f32x4 e = epilogue<SW, FL, false, P24, true>(a, z, o1[s], o2[s], o3[s], stash_base(layer, T), vl, isv, tmax);
-            if constexpr (wide_relay_store<SW, FL>()) DUDF_ST_CACHED(a.S, stash_base(layer, T), vo, e);
-            if constexpr (kColScale) dudf_track(cmax, e);
-            if (T + PD < G::NT) ld(T + PD, s);
-            if (last) {
-                if constexpr (BS == SWEEP_FWD) {
-                    const f32x4 wv = *reinterpret_cast<const f32x4*>(a.theta + a.off_wo + 16 * T + 4 * q);
-                    part += e[0] * wv[0] + e[1] * wv[1] + e[2] * wv[2] + e[3] * wv[3];
-                } else if constexpr (BS == SWEEP_REV) {
-                    const f32x4 wv = *reinterpret_cast<const f32x4*>(a.w1t16 + li * H + 16 * T + 4 * q);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) accg = mfma16(wv[t], e[t], accg);
-                }
-            }
-            acc[T] = f32x4{0, 0, 0, 0};
-        }
-        };
-        if constexpr (is_jet(SW)) {
-            burst_range(std::integral_constant<int, 0>{}, std::integral_constant<int, G::NT>{});
-        } else {
-            burst_range(std::integral_constant<int, 0>{}, std::integral_constant<int, G::NT / 2>{});
-            burst_range(std::integral_constant<int, G::NT / 2>{}, std::integral_constant<int, G::NT>{});
-        }
-        if constexpr (kRow >= 0) { if (layer < kMaxAmaxLayers) lds_max_wave(lds_amax + layer, tmax.t); }
-        if constexpr (kColScale) {                     // the next layer's B operand = these outputs: scale the column below 2^15
-            cmax = fmaxf(cmax, __shfl_xor(cmax, 16));
-            cmax = fmaxf(cmax, __shfl_xor(cmax, 32));
-            col_scale(cmax, sb, inv_sb);
-        }
-    };
-    // ---- first layer (fp32, K = 3): pre-activations / incoming adjoints of the 32 tiles, then their tails ----
-    {
-        float b = 0.f, yb = 1.f;
-        if constexpr (BS == SWEEP_FWD) b = (q < 3) ? a.x4[p * 4 + q] : 0.f;
-        if constexpr (BS == SWEEP_ADJ_FWD) b = (q < 3) ? a.gbar[p * 4 + q] : 0.f;
-        if constexpr (BS == SWEEP_ADJ_REV) yb = a.ybar[p];
-        if constexpr (SW == SWEEP_REV_H) yb = isv ? 1.f : 0.f;                         // adot_L^k = 0
-#pragma unroll
-        for (int T = 0; T < G::NT; ++T) {
-            if constexpr (kFwdDir) acc[T] = mfma16(a.w1b[(16 * T + li) * 4 + q], b, f32x4{0, 0, 0, 0});
-            else acc[T] = *reinterpret_cast<const f32x4*>(a.theta + a.off_wo + 16 * T + 4 * q) * yb;
-        }
-        tail_burst(in_layer(0), false);
-    }
-    dma_wait_b<0>();                                   // chunks 0 and 1, and the burst's stores (read back below)
-    __syncthreads();
-
-    // read-back of the post-tail values of tiles 2kb, 2kb+1 of `layer`: two asm loads, scalar base + lane offset
-    auto ld_in = [&](int layer, int kb, f32x4& x0, f32x4& x1) {
-        const float* b0 = wide_in<SW, FL>(a) + stash_base(layer, 2 * kb);
-        const float* b1 = b0 + 16 * a.np;              // next tile: 16 feature rows further (stash_base is linear in T)
-        const uint64_t g0 = (uint64_t)(size_t)b0, g1 = (uint64_t)(size_t)b1;
-        // (readfirstlane returns int: go through unsigned, or a low word with its top bit set sign-extends into the high word)
-        const unsigned l0 = __builtin_amdgcn_readfirstlane((unsigned)g0), h0 = __builtin_amdgcn_readfirstlane((unsigned)(g0 >> 32));
-        const unsigned l1 = __builtin_amdgcn_readfirstlane((unsigned)g1), h1 = __builtin_amdgcn_readfirstlane((unsigned)(g1 >> 32));
-        const uint64_t s0 = ((uint64_t)h0 << 32) | l0, s1 = ((uint64_t)h1 << 32) | l1;
-        asm volatile("global_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx4 %1, %2, %4"
-                     : "=&v"(x0), "=&v"(x1) : "v"(vo), "s"(s0), "s"(s1) : "memory");
-    };
-    u32x4 bq[NPC];                                     // B operand of the current k-block
-    for (int j = 0; j < nhid; ++j) {
-        const int lin = in_layer(j);
-        if constexpr (SP != 0) unscale = unscale_of(j) * inv_sb;     // what turns THIS matrix's accumulators into true values
-        // read-back registers: `xa` carries the even k-blocks, `xb` the odd ones — the loop is unrolled by two so that a set
-        // is never copied while its asm loads are in flight (a rolled loop would rotate them with v_mov at the back edge)
-        f32x4 xa0, xa1, xb0, xb1;
-#if DUDF_SWEEP_DBG & 128
-        const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
-#endif
-        ld_in(lin, 0, xa0, xa1);
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(xa0), "+v"(xa1));      // k-block 0: nothing to overlap it with yet
-        auto kstep = [&](int kb, f32x4& c0, f32x4& c1, f32x4& n0, f32x4& n1, auto steady) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int c2 = (j * G::NKB + kb) * 2 + h;
-                const bool more = decltype(steady)::value || c2 + 2 < total2;    // compile-time in the steady loop: one basic block
-                if (h == 0) {
-                    // the read-back of this k-block was issued one k-block ago; younger than it: the 6 DMA pieces of the
-                    // half-step in between
-                    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(c0), "+v"(c1) : "n"(G::NDMA));
-                    if constexpr (kColScale) split8h(c0 * sb, c1 * sb, bq[0], bq[1]);
-                    else if constexpr (SP != 0) split8h(c0, c1, bq[0], bq[1]);
-                    else split8(c0, c1, bq[0], bq[1], bq[2]);
-                }
-                if (more) dma(c2 + 2, (gc + 2) % 3);
-                if (h == 0) ld_in(lin, kb + 1 < G::NKB ? kb + 1 : kb, n0, n1);   // the last one re-reads its own: uniform counts
-                __builtin_amdgcn_sched_barrier(0);
-                const char* bp = lds + gc * G::CHUNKB + lane * 16;
-                auto frag = [&](int T, int pc) -> u32x4 {
-                    return *reinterpret_cast<const u32x4*>(bp + (T * NPC + pc) * G::FRAG);
-                };
-                u32x4 an[2][NPC];
-#pragma unroll
-                for (int T = 0; T < 2; ++T)
-#pragma unroll
-                    for (int pc = 0; pc < NPC; ++pc) an[T][pc] = frag(T, pc);
-#pragma unroll
-                for (int T = 0; T < G::HALFT; ++T) {
-                    u32x4 af[NPC];
-#pragma unroll
-                    for (int pc = 0; pc < NPC; ++pc) af[pc] = an[T & 1][pc];
-                    if (T + 2 < G::HALFT) {
-#pragma unroll
-                        for (int pc = 0; pc < NPC; ++pc) an[T & 1][pc] = frag(T + 2, pc);
-                        __builtin_amdgcn_sched_barrier(0x76);
-                    }
-                    f32x4 cc = acc[G::HALFT * h + T];
-                    if constexpr (SP != 0) {                    // smallest terms first: lo*hi, hi*lo, hi*hi
-                        cc = mfma_h(as_h(af[1]), as_h(bq[0]), cc);
-                        cc = mfma_h(as_h(af[0]), as_h(bq[1]), cc);
-                        cc = mfma_h(as_h(af[0]), as_h(bq[0]), cc);
-                    } else {
-                        const bf16x8 ah = as_bf(af[0]), am = as_bf(af[1]), al = as_bf(af[NPC - 1]);
-                        cc = mfma_b(am, as_bf(bq[1]), cc);          // smallest terms first
-                        cc = mfma_b(al, as_bf(bq[0]), cc);
-                        cc = mfma_b(ah, as_bf(bq[NPC - 1]), cc);
-                        cc = mfma_b(am, as_bf(bq[0]), cc);
-                        cc = mfma_b(ah, as_bf(bq[1]), cc);
-                        cc = mfma_b(ah, as_bf(bq[0]), cc);
-                    }
-                    acc[G::HALFT * h + T] = cc;
-                }
-                gc = (gc + 1) % 3;
-                // chunk c2+1 has landed.  Issued after its DMA: h == 0: [this step: NDMA pieces + 2 read-back]; h == 1: [previous
-                // step: 2 read-back] + [this step: NDMA pieces]  ->  NDMA + 2 younger operations either way
-                if (more) dma_wait_b<G::NDMA + 2>(); else dma_wait_b<0>();
-                __syncthreads();
-            }
-        };
-        const int kb_steady = (j + 1 == nhid) ? G::NKB - 2 : G::NKB;   // the stream's last two half-chunks have no successor
-#pragma unroll 1                                        // 384 MFMAs per iteration: the body stays inside the instruction cache
-        for (int kb = 0; kb < kb_steady; kb += 2) {
-            kstep(kb, xa0, xa1, xb0, xb1, std::true_type{});
-            kstep(kb + 1, xb0, xb1, xa0, xa1, std::true_type{});
-        }
-        if (j + 1 == nhid) {
-            kstep(G::NKB - 2, xa0, xa1, xb0, xb1, std::false_type{});
-            kstep(G::NKB - 1, xb0, xb1, xa0, xa1, std::false_type{});
-        }
-        // the last k-block's (dummy) read-back is still in flight and nothing will consume it: keep its registers until it
-        // has landed, or hipcc hands them to the burst below while the load is still writing them
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(xa0), "+v"(xa1), "+v"(xb0), "+v"(xb1));
-#if DUDF_SWEEP_DBG & 128
-        const unsigned long long tw1 = __builtin_amdgcn_s_memtime();
-#endif
-        tail_burst(in_layer(j + 1), j + 1 == nhid);
-#if DUDF_SWEEP_DBG & 128
-        const unsigned long long tw2 = __builtin_amdgcn_s_memtime();
-#endif
-        dma_wait_b<0>();
-        __syncthreads();
-#if DUDF_SWEEP_DBG & 128
-        if ((blockIdx.x == 100 || blockIdx.x == 101) && lane == 0 && (wave == 0 || wave == 4) && j < 8) {
-            const unsigned long long tw3 = __builtin_amdgcn_s_memtime();
-            unsigned long long* o = &g_stamp[SW & 3][(blockIdx.x - 100) * 2 + (wave >> 2)][j][0];
-            o[0] = tw0; o[1] = tw1; o[2] = tw2; o[3] = tw3;
-        }
-#endif
-    }
-    if constexpr (BS == SWEEP_FWD) {
-        part += __shfl_xor(part, 16);
-        part += __shfl_xor(part, 32);
-        if (isv) part += a.theta[a.off_bo];             // tangent / jet columns are derivatives: no constant term
-        if (q == 0) a.y[p] = part;
-    } else if constexpr (BS == SWEEP_REV) {
-        if (q == 0) *reinterpret_cast<f32x4*>(a.g + p * 4) = f32x4{accg[0], accg[1], accg[2], 0.f};
-    }
-}
-
-template <int SW, int FL, int SP, int P24 = 0>
-__device__ __forceinline__ void sweep_w_body(const SweepArgs& a) {
-    extern __shared__ __attribute__((aligned(16))) char lds_w[];
-    unsigned gc = 0;
-    const bool clk_on = a.clk != nullptr && blockIdx.x == 0;
-    const unsigned long long clk_t0 = clk_on ? __builtin_amdgcn_s_memtime() : 0ull, clk_r0 = clk_on ? __builtin_amdgcn_s_memrealtime() : 0ull;
-    constexpr int kRow = amax_row<SW, FL>();
-    unsigned* lds_amax = reinterpret_cast<unsigned*>(lds_w + 3 * GeoWT<SP>::CHUNKB);
-    if constexpr (kRow >= 0) { if (threadIdx.x < kMaxAmaxLayers) lds_amax[threadIdx.x] = 0u; }
-    // (measured and dropped: odd workgroups starting half a layer late, so that one half of the chip is in its compute phase
-    //  — the k-loop — while the other is in its memory phase — the tail burst: +1.3 %)
-    const int ng = a.ntiles * (TILE / 16), gbase = a.tile0 * (TILE / 16);
-    const int g0 = (int)((int64_t)blockIdx.x * ng / gridDim.x), g1 = (int)((int64_t)(blockIdx.x + 1) * ng / gridDim.x);
-    for (int g = g0; g < g1; g += NWB)
-        sweep_tile_w<SW, FL, SP, P24>(a, gbase + g, (g1 - g < NWB) ? g1 - g : NWB, lds_w, gc);
-    if constexpr (kRow >= 0) {
-        __syncthreads();
-        if ((int)threadIdx.x < a.L && (int)threadIdx.x < kMaxAmaxLayers && a.amax) {
-            const unsigned v = lds_amax[threadIdx.x];
-            if (v) atomicMax(a.amax + kRow * a.L + threadIdx.x, v);
-        }
-    }
-    if (clk_on && threadIdx.x == 0) {
-        a.clk[0] = __builtin_amdgcn_s_memtime() - clk_t0;
-        a.clk[1] = __builtin_amdgcn_s_memrealtime() - clk_r0;
-    }
-}
-template <int SW, int FL>
-__global__ __launch_bounds__(64 * NWB) void sweep_w_kernel(SweepArgs a) { sweep_w_body<SW, FL, 0>(a); }
-template <int SW, int FL>
-__global__ __launch_bounds__(64 * NWB) void sweep_w16_kernel(SweepArgs a) { sweep_w_body<SW, FL, 1>(a); }
-// ... with R, E, C at 24 bits (stash mask 6: the training variants of a default training workspace)
-template <int SW, int FL>
-__global__ __launch_bounds__(64 * NWB) void sweep_w16r_kernel(SweepArgs a) { sweep_w_body<SW, FL, 1, 6>(a); }
-
-static_assert(dudf_wide_chunk_bytes(3) == GeoWT<0>::CHUNKB && dudf_wide_chunk_bytes(2) == GeoWT<1>::CHUNKB, "dudf_variants.h: LDS sizes");
-int launch_w(const SweepChoice& c, const SweepArgs& a, hipStream_t st) {
-    if (a.ntiles <= 0) return 0;
-    const int ntb = (a.ntiles * TILE + TILEB - 1) / TILEB;
-    const dim3 grid(ntb < 256 ? ntb : 256), block(GeoW::NTHR);
-    return dudf_with_variant(kWideVariants, c.sw, c.fl, [&](auto i) {
-        constexpr DudfVariant v = kWideVariants[decltype(i)::value];
-        if (c.family == DUDF_FAM_W) return dudf_launch_kernel<&sweep_w_kernel<v.sw, v.fl>>(grid, block, c.lds, c.lds_max, st, a);
-        if (c.family == DUDF_FAM_W16) return dudf_launch_kernel<&sweep_w16_kernel<v.sw, v.fl>>(grid, block, c.lds, c.lds_max, st, a);
-        if constexpr (v.p24 != 0) {
-            if (c.family == DUDF_FAM_W16R) return dudf_launch_kernel<&sweep_w16r_kernel<v.sw, v.fl>>(grid, block, c.lds, c.lds_max, st, a);
-        }
-        return (int)DUDF_E_UNSUPPORTED;
-    });
-}
-
-}  // namespace
-
-namespace {
 // Estimated duration of one part of a pair launch, in full plain-column passes: every workgroup walks ceil(ng / nb) groups of 16
 // columns in passes of 8 (one per wave); a partial pass with up to one wave per SIMD costs about half a full one (measured: a
 // lone wave 0.68, the passes are bound by latency, not by issue), more waves in proportion.  `c` = a pass of this variant
@@ -1648,79 +923,18 @@ int dudf_launch_sweep_bf16(const SweepChoice& c, const SweepArgs& a, hipStream_t
     switch (c.H) {
         case 256: return launch_b<256>(c, a, st);
         case 128: return launch_b<128>(c, a, st);
-        case 512: return launch_w(c, a, st);
+        case 512: return dudf_launch_sweep_wide(c, a, st);
         default: return DUDF_E_UNSUPPORTED;
     }
 }
 
-namespace {
-template <int H>
-int pack_b(const DudfLayout& lo, const float* theta, float* ws, hipStream_t st) {
-    using G = GeoB<H>;
-    char* img_f = reinterpret_cast<char*>(ws + lo.ws_wimg);
-    char* img_t = img_f + (size_t)(lo.L - 1) * G::IMGB;
-    const int64_t total = (int64_t)2 * (lo.L - 1) * G::NKB * G::NT * 64;
-    hipLaunchKernelGGL(pack_bf16_kernel<H>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, theta, img_f, img_t,
-                       lo.L - 1, lo.off_hid, lo.hid_stride);
-    if (dudf_split_fp16()) {
-        using G1 = GeoB<H, 1>;
-        char* i16_f = reinterpret_cast<char*>(ws + lo.ws_wimg16);
-        char* i16_t = i16_f + (size_t)(lo.L - 1) * G1::IMGB;
-        hipLaunchKernelGGL(pack_f16_kernel<H>, dim3(H >= 256 ? 16 : 4, lo.L - 1), dim3(256), 0, st, theta, i16_f, i16_t,
-                           ws + lo.ws_wsc, lo.L - 1, lo.off_hid, lo.hid_stride);
-    }
-    return (int)hipGetLastError();
-}
-}  // namespace
-
-namespace {
-template <int H>
-int prep_b(const DudfLayout& lo, const float* theta, const float* x, float* ws, int need, hipStream_t st) {
-    PrepArgs a;
-    a.theta = theta; a.x = x;
-    a.w1b = ws + lo.ws_w1b; a.b1s = ws + lo.ws_b1s; a.rho = lo.rho; a.w1t16 = ws + lo.ws_w1t16; a.wt = ws + lo.ws_wt; a.x4 = ws + lo.ws_x4; a.wsc = ws + lo.ws_wsc;
-    a.img_f = reinterpret_cast<char*>(ws + lo.ws_wimg); a.img_t = a.img_f + (size_t)(lo.L - 1) * GeoB<H>::IMGB;
-    a.img16_f = reinterpret_cast<char*>(ws + lo.ws_wimg16); a.img16_t = a.img16_f + (size_t)(lo.L - 1) * GeoB<H, 1>::IMGB;
-    a.zero = reinterpret_cast<unsigned*>(ws + lo.ws_acc); a.nzero = 2 * DUDF_NACC;
-    a.zero2 = reinterpret_cast<unsigned*>(ws + lo.ws_amax); a.nzero2 = 4 * lo.L;
-    a.L = lo.L; a.off_hid = lo.off_hid; a.hid_stride = lo.hid_stride;
-    a.n = lo.n; a.n_h = lo.n_h; a.ncol_h = lo.ncol_h; a.np = lo.np;
-    const int nhid = lo.L - 1;
-    a.nsub = H >= 256 ? 16 : 4;
-    a.nb_f16 = (dudf_split_fp16() && nhid > 0) ? nhid * a.nsub : 0;
-    a.nb_bf16 = ((need & 1) && nhid > 0) ? (int)(((int64_t)2 * nhid * GeoB<H>::NKB * GeoB<H>::NT * 64 + 255) / 256) : 0;
-    a.nb_x4 = x ? (int)((lo.np + 255) / 256 < 1024 ? (lo.np + 255) / 256 : 1024) : 0;
-    a.nb_thin = 2;
-    a.nb_wt = ((need & 2) && nhid > 0) ? (int)(((int64_t)nhid * H * H + 255) / 256 < 2048 ? ((int64_t)nhid * H * H + 255) / 256 : 2048) : 0;
-    const int grid = a.nb_f16 + a.nb_bf16 + a.nb_x4 + a.nb_thin + a.nb_wt;
-    hipLaunchKernelGGL(prep_kernel<H>, dim3(grid), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
-}
-}  // namespace
-
-// Returns DUDF_E_UNSUPPORTED for widths without 16-bit weight images (the caller then packs with the separate kernels).
-int dudf_launch_prep(const DudfLayout& lo, const float* theta, const float* x, float* ws, int need, hipStream_t st) {
-    DudfProfScope prof(PROF_PACK, st);
-    if (lo.H == 256) return prep_b<256>(lo, theta, x, ws, need, st);
-    if (lo.H == 128) return prep_b<128>(lo, theta, x, ws, need, st);
-    if (lo.H == 512) return prep_b<512>(lo, theta, x, ws, need, st);
-    return DUDF_E_UNSUPPORTED;
-}
-
-int dudf_launch_pack_bf16(const DudfLayout& lo, const float* theta, float* ws, hipStream_t st) {
-    if (lo.L < 2) return 0;
-    DudfProfScope prof(PROF_PACK, st);
-    if (lo.H == 256) return pack_b<256>(lo, theta, ws, st);
-    if (lo.H == 128) return pack_b<128>(lo, theta, ws, st);
-    if (lo.H == 512) return pack_b<512>(lo, theta, ws, st);
-    return 0;
-}
-
 #if DUDF_FX_CHECK
-// debug build only (not part of the C ABI): granules the fixed-point packers would have wrapped since the last reset — [0] S/Q/A/Z, [1] C
+// debug build only (not part of the C ABI): granules the fixed-point packers would have wrapped since the last reset — [0] S/Q/A/Z, [1] C.
+// The packers that count are the sweeps' tails, so the counters live in this unit and in dudf_sweep_wide.hip: build both with the flag.
+int dudf_fx_read_wide(unsigned* out2, int reset);
 extern "C" int dudf_dbg_fx_violations(unsigned* out2, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out2, HIP_SYMBOL(g_dudf_fx_bad), 2 * sizeof(unsigned));
-    if (e == hipSuccess && reset) { const unsigned z[2] = {0u, 0u}; e = hipMemcpyToSymbol(HIP_SYMBOL(g_dudf_fx_bad), z, sizeof(z)); }
-    return (int)e;
+    out2[0] = out2[1] = 0u;
+    const int e = dudf_fx_read(out2, reset);
+    return e ? e : dudf_fx_read_wide(out2, reset);
 }
 #endif

@@ -1,4 +1,4 @@
-// Pieces shared by the two sweep kernels (dudf_sweep.hip: f32-input MFMA; dudf_sweep_bf16.hip: bf16x6 MFMA): stash
+// Pieces shared by the two sweep kernels (dudf_sweep.hip: f32-input MFMA; dudf_sweep_bf16.hip, dudf_sweep_wide.hip: bf16x6 MFMA): stash
 // addressing, the elementwise tails of every sweep variant, and the vector-memory bookkeeping of a chunk.
 // Both kernels produce the 16x16 accumulator tile in the same register layout (row = 4*(lane>>4)+reg = feature,
 // col = lane&15 = column), so the tails are identical.
@@ -128,7 +128,7 @@ __device__ __forceinline__ f32x4 p24_unpack_raw(const f32x4 r) { return p24_unpa
 // trajectory does not see it (profiles/r04_cround.txt: 2^-22 and 2^-23 grids both within 5e-7, like fp32).
 // Debug build (-DDUDF_FX_CHECK=1, tools/fx_check.py): count the granules whose values the two fixed-point packers would WRAP
 // (a value outside [-1, 1] of its grid reads back as ~ +5) — the precondition `set_scale`'s bound and |cos| <= 1 have to guarantee.  The counter is
-// read by dudf_dbg_fx_violations (dudf_sweep_bf16.hip, debug build only); the branch is never taken unless the invariant breaks.
+// read by dudf_dbg_fx_violations (dudf_sweep_bf16.hip, per unit: dudf_sweep16.h; debug build only); the branch is never taken unless the invariant breaks.
 #ifndef DUDF_FX_CHECK
 #define DUDF_FX_CHECK 0
 #endif

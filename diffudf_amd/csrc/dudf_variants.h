@@ -31,7 +31,7 @@ constexpr DudfVariant kF32Variants[] = {{0, 3, 0}, {1, 1, 0}, {1, 0, 0}, {2, 0, 
 // sweep_f16r[_np]_kernel (stash mask 6) and sweep_f16p[_np]_kernel (mask 7)
 constexpr DudfVariant kSweepVariants[] = {{0, 3, 1}, {0, 2, 0}, {0, 0, 0}, {1, 1, 1}, {1, 0, 0}, {2, 0, 1}, {3, 1, 1}, {3, 0, 1},
                                           {4, 1, 1}, {4, 0, 0}, {5, 1, 1}, {5, 0, 0}, {6, 0, 1}, {7, 0, 1}, {8, 0, 0}};
-// dudf_sweep_bf16.hip, H = 512: sweep_w_kernel and sweep_w16_kernel<SW, FL>; p24: sweep_w16r_kernel (mask 6).  The stash array
+// dudf_sweep_wide.hip, H = 512: sweep_w_kernel and sweep_w16_kernel<SW, FL>; p24: sweep_w16r_kernel (mask 6).  The stash array
 // a layer's outputs travel through is written in every variant: the forward sweeps always store h_l
 constexpr DudfVariant kWideVariants[] = {{0, 3, 1}, {0, 1, 0}, {1, 1, 1}, {1, 0, 0}, {2, 0, 1}, {3, 1, 1}, {3, 0, 1},
                                          {4, 1, 1}, {5, 1, 1}, {5, 0, 0}, {6, 0, 1}, {7, 0, 1}, {8, 0, 0}};
@@ -56,8 +56,8 @@ constexpr int kMaxAmaxLayers = 64;         // LDS words of the per-layer running
 constexpr size_t kLdsCu = 160 * 1024;
 constexpr size_t kAmaxBytes = kMaxAmaxLayers * sizeof(unsigned);
 constexpr size_t kOctBytes = 8 * 2 * 1024 + 1024 + 8 * 64 * 16;      // B fragments | column maxima (2 x 128 floats) | output-stage partials
-constexpr size_t dudf_chunk_bytes(int H, int pieces) { return (size_t)(H / 16) * pieces * 1024; }   // GeoB<H, SP>::CHUNKB
-constexpr size_t dudf_wide_chunk_bytes(int pieces) { return (size_t)16 * pieces * 1024; }            // GeoWT<SP>::CHUNKB
+constexpr size_t dudf_chunk_bytes(int H, int pieces) { return (size_t)(H / 16) * pieces * 1024; }   // dudf_sweep16.h GeoB<H, SP>::CHUNKB
+constexpr size_t dudf_wide_chunk_bytes(int pieces) { return (size_t)16 * pieces * 1024; }            // dudf_sweep_wide.hip GeoWT<SP>::CHUNKB
 constexpr size_t dudf_bias_bytes(int L, int H) { return (size_t)L * H * sizeof(float); }
 
 enum { DUDF_FAM_F32 = 0, DUDF_FAM_BF16, DUDF_FAM_F16, DUDF_FAM_F16R, DUDF_FAM_F16P,     // sweeps, H <= 256 (F32: every width)

@@ -244,7 +244,7 @@ def test_unsupported_configs_fail_loudly(hip):
 
 def test_f32_and_bf16x6_sweeps_agree(hip):
     """The 256-wide plain path runs its hidden matmuls on the 16-bit matrix cores — fp16 hi/lo split, three products
-    (default since round 3) or the exact 3-way bf16 split, six products (option split = 0; csrc/dudf_sweep_bf16.hip) —;
+    (default since round 3) or the exact 3-way bf16 split, six products (option split = 0; csrc/dudf_sweep_bf16.hip, csrc/dudf_sweep16.h) —;
     options sweep_family = 0 / wgrad_family = 1 select the f32-input MFMA kernels.  All three must meet the SAME oracle
     tolerances, and agree with each other far inside them.  The modes are switched IN-PROCESS through dudf_set_option
     (rounds 1-4 read environment variables once per process and needed a child process per mode)."""

@@ -20,7 +20,8 @@ P24_KEYS = {(sw, fl) for sw, fl, p24 in variant_table("kSweepVariants") if p24}
 
 @pytest.fixture(scope="module")
 def bf16_asm(tmp_path_factory):
-    """Assembly of dudf_sweep_bf16.hip per flag set, emitted once per test session (three builds, in parallel)."""
+    """Assembly of dudf_sweep_bf16.hip (the 128- and 256-wide kernels: the unit holds what the analysers below read, the 512-wide
+    kernels and the packing kernels are units of their own) per flag set, emitted once per test session (three builds, in parallel)."""
     from concurrent.futures import ThreadPoolExecutor
     d = tmp_path_factory.mktemp("sweep_bf16_asm")
     builds = {"late0": ("-DDUDF_LATE_FORCE=0",), "late1": ("-DDUDF_LATE_FORCE=1",), "ship": ()}

@@ -25,7 +25,7 @@ ALL = S | C | TRAIN | HAVE_E
 STEP = ((0, ALL), (1, ALL), (2, TRAIN | HAVE_E), (3, TRAIN | HAVE_E), (3, TRAIN))
 # query launches (flags | QUERY): value, value + gradient / Hessian, jets
 QUERIES = ((0, HAVE_E), (0, C | HAVE_E), (1, HAVE_E), (8, HAVE_E))
-# kernels of dudf_sweep.hip / dudf_sweep_bf16.hip / dudf_wgrad.hip that no request of the enumeration reaches — reported, not removed
+# kernels of dudf_sweep.hip / dudf_sweep_bf16.hip / dudf_sweep_wide.hip / dudf_wgrad.hip that no request of the enumeration reaches — reported, not removed
 UNREACHED = {}          # name: reason (none at present)
 # ... and the kernels of those files that are not subject to a choice (packing, thin layers): one per width
 FIXED = ("pack_bf16_kernel", "pack_f16_kernel", "prep_kernel", "wgrad_small_kernel", "wgrad_small_p24_kernel")
@@ -101,7 +101,7 @@ def test_every_promised_stash_mask_has_its_kernels_and_every_kernel_is_reachable
     built = library_kernels()
     assert chosen <= built, sorted(chosen - built)
     ours = {k for k in built if k.startswith(("sweep_", "wgrad_hidden_"))}
-    assert len(ours) == 60 + 129 + 13                   # dudf_sweep.hip, dudf_sweep_bf16.hip (138 with its 9 packing kernels), dudf_wgrad.hip
+    assert len(ours) == 60 + 129 + 13                   # dudf_sweep.hip, dudf_sweep_bf16.hip + dudf_sweep_wide.hip (138 with the 9 packing kernels of dudf_prep.hip), dudf_wgrad.hip
     assert {k.split("<")[0] for k in built - ours if k.split("<")[0] in FIXED} == set(FIXED)
     assert ours - chosen == set(UNREACHED), sorted((ours - chosen) ^ set(UNREACHED))
 
@@ -113,7 +113,7 @@ def test_instantiation_tables_are_what_the_isa_contract_pins():
                                              (4, 1), (4, 0), (5, 1), (5, 0), (6, 0), (7, 0), (8, 0)}
     assert {(s, f) for s, f, p in sweep if p} == {(0, 3), (1, 1), (2, 0), (3, 1), (3, 0), (4, 1), (5, 1), (6, 0), (7, 0)}
     assert len(sweep) == 15 and len(variant_table("kWideVariants")) == 13 and len(variant_table("kF32Variants")) == 12
-    # 138 kernels of dudf_sweep_bf16.hip: two widths x two families x 15, 2 x 9 for the 24-bit stash, 2 x 13 + 9 at 512, 16 pair
+    # 138 kernels of dudf_sweep_bf16.hip, dudf_sweep_wide.hip and dudf_prep.hip: two widths x two families x 15, 2 x 9 for the 24-bit stash, 2 x 13 + 9 at 512, 16 pair
     # kernels (4 sweeps x {bf16x6 quads, fp16x3 quads, masks 6 and 7}), and the 3 x 3 packing kernels
     assert 2 * 2 * 15 + 2 * 9 + 2 * 13 + 9 + 4 * len(variant_table("kPairVariants")) + 9 == 138
 

@@ -2,7 +2,7 @@
 """GPU: a 12-step training trajectory of a 512-WIDE network (BASELINE configs[2]'s width) against the fp64 oracle, in its stash formats.
 
 "The trajectory, not single-step parity, is what catches a bad format"  — and it did again in round 5: the 512-wide
-kernel's relay (the stash array a layer's outputs travel through to the next layer, csrc/dudf_sweep_bf16.hip::sweep_tile_w) was
+kernel's relay (the stash array a layer's outputs travel through to the next layer, csrc/dudf_sweep_wide.hip::sweep_tile_w) was
 built as the 24-bit fixed-point array of stash mask 7.  Every single-step tolerance held (tests/test_hip_parity.py, the full-size
 oracle comparison: d(theta) 5.8e-7), config 3 ran 2.7 % faster — and THIS test, written afterwards, showed the 12-step curve leaving
 the fp64 oracle's by 1.3e-5 at step 2 and 6e-4 at step 10, where the fp32 relay (masks 6 and 0) stays within 7e-7: at width 256 the

@@ -4,7 +4,7 @@
 fma(v, 2^-E, 3): a value a grid step outside [-1, 1] 2^E would read back as ~ +5 2^E, silently.)  Runs training steps of every kind on a DEBUG build
 that counts such granules inside the packers and prints the counters:
 
-    bash tools/build_dbg.sh fxcheck sweep_bf16 "-DDUDF_FX_CHECK=1"
+    bash tools/build_dbg.sh fxcheck "sweep_bf16 sweep_wide" "-DDUDF_FX_CHECK=1"
     DUDF_LIB=dbg/libdudf_fxcheck.so python tools/fx_check.py [trajectory repeats]
 
 Workloads: the g12 fixtures (beetle x50 on the oracle sampler's batches; synthetic s1 x40 -> s2 x10) R times, the 100 000-point headline step,
