@@ -12,7 +12,7 @@
 //     distances the smallest index wins, whatever the launch geometry or the order in which workgroups arrive;
 //   - a finishing kernel unpacks the keys.
 // Every pair is evaluated by the same expression, so the result is a pure function of the inputs: repeated calls are bit-identical.
-#include "dudf_internal.h"
+#include "dudf_context.h"
 
 namespace {
 
@@ -174,9 +174,6 @@ __global__ __launch_bounds__(256) void vertex_normalize_kernel(const double* __r
 }
 
 inline size_t round256(size_t b) { return b < 256 ? 256 : (b + 255) / 256 * 256; }
-inline bool bad_workspace(const void* ws, size_t have, size_t need) {
-    return !ws || have < need || (reinterpret_cast<uintptr_t>(ws) & 255);
-}
 inline int terms_groups(int64_t n) { return grid_for(n, kTermsBlock, kTermsMaxGroups); }
 
 }  // namespace
@@ -192,7 +189,7 @@ int dudf_nearest_points(const float* x, int64_t n, const float* y, int64_t m, in
     if (n >= ((int64_t)1 << 31) || m >= ((int64_t)1 << 31)) return DUDF_E_UNSUPPORTED;
     if (n == 0) return 0;
     if (m <= 0 || !x || !y) return DUDF_E_BADCFG;
-    if (bad_workspace(workspace, workspace_bytes, dudf_nearest_workspace_bytes(n))) return DUDF_E_WORKSPACE;
+    if (int rc = dudf_check_buffer(workspace, workspace_bytes, dudf_nearest_workspace_bytes(n))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(workspace);
@@ -226,7 +223,7 @@ int dudf_chamfer_terms(const float* dist, const int64_t* idx, int64_t n, const f
     if (n < 0 || !out_sums || (n > 0 && !dist)) return DUDF_E_BADCFG;
     if ((x_normals == nullptr) != (y_normals == nullptr)) return DUDF_E_BADCFG;
     if (x_normals && n > 0 && (!idx || m <= 0)) return DUDF_E_BADCFG;
-    if (bad_workspace(workspace, workspace_bytes, dudf_chamfer_terms_workspace_bytes(n))) return DUDF_E_WORKSPACE;
+    if (int rc = dudf_check_buffer(workspace, workspace_bytes, dudf_chamfer_terms_workspace_bytes(n))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     double* partials = reinterpret_cast<double*>(workspace);
@@ -249,7 +246,7 @@ int dudf_vertex_normals(const double* vertices, int64_t n_vertices, const int64_
     if (n_vertices < 0 || n_faces < 0) return DUDF_E_BADCFG;
     if (n_vertices == 0) return 0;
     if (!vertices || !out_normals || (n_faces > 0 && !faces)) return DUDF_E_BADCFG;
-    if (bad_workspace(workspace, workspace_bytes, dudf_vertex_normals_workspace_bytes(n_vertices))) return DUDF_E_WORKSPACE;
+    if (int rc = dudf_check_buffer(workspace, workspace_bytes, dudf_vertex_normals_workspace_bytes(n_vertices))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     double* acc = reinterpret_cast<double*>(workspace);

@@ -99,8 +99,14 @@ struct DudfLayout {
     size_t total_bytes;
 };
 
-// the current run-time options (dudf_set_option in the C ABI; dudf_api.hip holds them)
+// the current run-time options (dudf_set_option in the C ABI; dudf_runtime.hip holds them, dudf_variants.h lists them)
 DudfOptions dudf_options();
+inline bool dudf_deterministic() { return dudf_options().deterministic != 0; }
+inline bool dudf_split_fp16() { return dudf_options().split != 0; }
+inline int dudf_wgrad_max_workgroups() { return dudf_options().wgrad_max_workgroups; }
+
+// carves arrays out of a buffer of floats: every array starts on a 64-float (256-byte) granule
+struct DudfCarver { int64_t o; int64_t take(int64_t cnt) { const int64_t r = o; o += (cnt + 63) / 64 * 64; return r; } };
 
 static inline int dudf_make_layout(const dudf_net_cfg* cfg, int64_t n, int64_t n_h, DudfLayout* lo, int query_only = 0) {
     if (!cfg || cfg->n_in != 3 || cfg->n_hidden_layers < 1) return DUDF_E_BADCFG;
@@ -128,43 +134,42 @@ static inline int dudf_make_layout(const dudf_net_cfg* cfg, int64_t n, int64_t n
     lo->off_hid = 4 * (int64_t)H; lo->hid_stride = (int64_t)H * H + H;
     lo->off_wo = lo->off_hid + (L - 1) * lo->hid_stride; lo->off_bo = lo->off_wo + H;
     lo->n_theta = lo->off_bo + 1;
-    int64_t o = 0;
     // every array starts on a 256-byte boundary of the workspace (whose base the caller aligns to 256 B): a lane quarter's
     // 256-byte segment of a stash row is then exactly two 128-byte lines.  (Round 3 first put two small arrays of 64 + 128 bytes
     // in front of the stash: every segment straddled three lines, and FETCH_SIZE / WRITE_SIZE of all four sweeps read 9-12 %
     // above the algorithmic bytes until this was noticed — profiles/r03_a, r03_b against r02_c.)
-    auto take = [&](int64_t cnt) { int64_t r = o; o += (cnt + 63) / 64 * 64; return r; };
-    lo->ws_w1b = take(4 * (int64_t)H);
-    lo->ws_b1s = take((int64_t)L * H);                             // rho b_1 | b_2 .. b_L (the forward tails' biases, one row per layer)
-    lo->ws_w1t16 = take(16 * (int64_t)H);
-    lo->ws_wt = take((int64_t)(L - 1) * H * H);
-    lo->ws_wimg = take((int64_t)(L - 1) * H * H * 3);      // bf16x3 images of W_l and W_l^T: 2 x 6 bytes per weight
-    lo->ws_wimg16 = take((int64_t)(L - 1) * H * H * 2);    // fp16 hi/lo images of W_l and W_l^T: 2 x 4 bytes per weight
-    lo->ws_wsc = take(2 * (int64_t)(L > 1 ? L - 1 : 1));
-    lo->ws_amax = take(4 * (int64_t)L);
-    lo->ws_ebound = query_only ? lo->ws_amax : take((int64_t)L * lo->np);   // [L][np]: max_f |e_l[f][column]| (fp16x3 adjoint reverse sweep)
+    DudfCarver cv = {0};
+    lo->ws_w1b = cv.take(4 * (int64_t)H);
+    lo->ws_b1s = cv.take((int64_t)L * H);                             // rho b_1 | b_2 .. b_L (the forward tails' biases, one row per layer)
+    lo->ws_w1t16 = cv.take(16 * (int64_t)H);
+    lo->ws_wt = cv.take((int64_t)(L - 1) * H * H);
+    lo->ws_wimg = cv.take((int64_t)(L - 1) * H * H * 3);      // bf16x3 images of W_l and W_l^T: 2 x 6 bytes per weight
+    lo->ws_wimg16 = cv.take((int64_t)(L - 1) * H * H * 2);    // fp16 hi/lo images of W_l and W_l^T: 2 x 4 bytes per weight
+    lo->ws_wsc = cv.take(2 * (int64_t)(L > 1 ? L - 1 : 1));
+    lo->ws_amax = cv.take(4 * (int64_t)L);
+    lo->ws_ebound = query_only ? lo->ws_amax : cv.take((int64_t)L * lo->np);   // [L][np]: max_f |e_l[f][column]| (fp16x3 adjoint reverse sweep)
     // [L][np]: max_f |zdot_l[f][column]| of the tangent columns of the Hessian quads (left by the fp16x3 forward sweep of the
     // quads for the column scales of the sweeps behind it); every workspace with Hessian-path points has it (training and queries)
-    lo->ws_zbound = (n_h == 0) ? lo->ws_amax : take((int64_t)L * lo->ncol_h);
-    lo->ws_x4 = take(4 * lo->np);
-    lo->ws_y = take(lo->np); lo->ws_g = take(4 * lo->np);
-    lo->ws_ybar = take(lo->np); lo->ws_gbar = take(4 * lo->np);
+    lo->ws_zbound = (n_h == 0) ? lo->ws_amax : cv.take((int64_t)L * lo->ncol_h);
+    lo->ws_x4 = cv.take(4 * lo->np);
+    lo->ws_y = cv.take(lo->np); lo->ws_g = cv.take(4 * lo->np);
+    lo->ws_ybar = cv.take(lo->np); lo->ws_gbar = cv.take(4 * lo->np);
     lo->stash_layer = (int64_t)H * lo->np;
     const int64_t stash = (int64_t)L * lo->stash_layer;
     const int64_t stash_b = (lo->p24 & 1) ? stash / 4 * 3 : stash;   // S, Q, A, Z: 12 instead of 16 bytes per granule
     const int64_t stash_r = (lo->p24 & 2) ? stash / 4 * 3 : stash;   // R, E
     const int64_t stash_c = (lo->p24 & 4) ? stash / 4 * 3 : stash;   // C (fixed point)
-    lo->ws_S = take(stash_b); lo->ws_C = take(stash_c);
-    lo->ws_ZS = n_h > 0 ? take(stash) : lo->ws_S;
+    lo->ws_S = cv.take(stash_b); lo->ws_C = cv.take(stash_c);
+    lo->ws_ZS = n_h > 0 ? cv.take(stash) : lo->ws_S;
     if (query_only) {        // value / df/dx / Hessian queries only ever touch S, C, ZS: 16-24 KB per column instead of 56-64
         lo->ws_Q = lo->ws_R = lo->ws_E = lo->ws_A = lo->ws_Z = lo->ws_S;
     } else {
-        lo->ws_Q = take(stash_b); lo->ws_R = take(stash_r); lo->ws_E = take(stash_r); lo->ws_A = take(stash_b);
-        lo->ws_Z = take(stash_b);
+        lo->ws_Q = cv.take(stash_b); lo->ws_R = cv.take(stash_r); lo->ws_E = cv.take(stash_r); lo->ws_A = cv.take(stash_b);
+        lo->ws_Z = cv.take(stash_b);
     }
-    for (int i = 0; i < 4; ++i) lo->ws_fx[i] = (lo->p24 & 1) ? take((int64_t)L * lo->np) : lo->ws_amax;
-    lo->ws_acc = take(2 * DUDF_NACC);
-    lo->total_bytes = (size_t)o * sizeof(float);
+    for (int i = 0; i < 4; ++i) lo->ws_fx[i] = (lo->p24 & 1) ? cv.take((int64_t)L * lo->np) : lo->ws_amax;
+    lo->ws_acc = cv.take(2 * DUDF_NACC);
+    lo->total_bytes = (size_t)cv.o * sizeof(float);
     return 0;
 }
 
@@ -230,7 +235,6 @@ int dudf_launch_pack(const DudfLayout& lo, const float* theta, float* ws, hipStr
 int dudf_launch_wgrad(const DudfLayout& lo, float* ws, float* dtheta, int have_g, hipStream_t st, int layer_begin = 0,
                       int layer_end = 1 << 30);
 int dudf_launch_make_x4(const DudfLayout& lo, const float* x, float* ws, hipStream_t st);
-int dudf_launch_make_x4_grid(const DudfLayout& lo, int64_t grid_n, int64_t start, float* ws, hipStream_t st);
 int dudf_launch_field_features(const DudfLayout& lo, const float* ws, int inverse_mode, double alpha, float* out_df,
                                float* out_vec, int* out_flag_count, float* out_lam, float* out_V, hipStream_t st);
 int dudf_launch_loss_fwd(const DudfLayout& lo, int mode, const float* normals, const float* sdf, int64_t n_global,
@@ -255,58 +259,15 @@ int dudf_launch_read_stash(const DudfLayout& lo, const float* src, int layer, in
 int dudf_launch_copy_in(const DudfLayout& lo, const float* ybar, const float* gbar, float* ws, hipStream_t st);
 int dudf_launch_copy_out(const DudfLayout& lo, const float* ws, float* out_f, float* out_g, float* out_h,
                          hipStream_t st);
-// sphere tracing (reference src/render_st.py:136-172): x4 from double positions, one marching / descent iteration
+// x4 from double positions (sphere tracing, point projection; dudf_query.hip)
 int dudf_launch_rays_x4(const DudfLayout& lo, const double* t0, float* ws, hipStream_t st);
-int dudf_launch_rays_step(const DudfLayout& lo, const float* ws, const double* rays, double* t0, unsigned char* mask,
-                          unsigned char* hits, int inverse_mode, double alpha, double min_step, double threshold,
-                          int* active, hipStream_t st);
-int dudf_launch_rays_descend(const DudfLayout& lo, const float* ws, double* t0, const unsigned char* hits,
-                             int inverse_mode, double alpha, double min_step, hipStream_t st);
-// dense point cloud (reference src/render_pc.py:26-73; dudf_pointcloud.hip): proposals (double rows + x4), one projection step
-// behind the sweeps (writes the next x4; the last one the accept flags), ordered compaction / append behind a device row
-// counter (scratch: 2 * dudf_pc_tiles(n) ints), normals from the frame query's eigenvectors
+// dudf_pointcloud.hip: ordered compaction / append behind a device row counter (scratch: 2 * dudf_pc_tiles(n) ints); dudf_render_gather
+// gathers its hits through it
 int64_t dudf_pc_tiles(int64_t n);
-int dudf_launch_pc_propose(const DudfLayout& lo, const double* rand, int64_t rand_count, uint64_t seed, int64_t round, const double* surface,
-                           const int64_t* counter, int64_t quota, double* samples, double* proposals, float* ws, hipStream_t st);
-int dudf_launch_pc_step(const DudfLayout& lo, float* ws, double* samples, int inverse_mode, double alpha, double thresh,
-                        int last, double* out_step, double* out_unit, float* out_pre, unsigned char* out_accept,
-                        const int64_t* counter, int64_t quota, hipStream_t st);
 int dudf_launch_pc_append(const unsigned char* flags, int64_t n, const double* src_a, const double* src_b, const float* src_f,
                           double* dst_a, double* dst_b, float* out_f, int64_t capacity, int64_t quota, int64_t* counter,
                           int* scratch, hipStream_t st);
-int dudf_launch_pc_normals(const float* V, int64_t m, double* normals, hipStream_t st);
-// sphere-traced images (dudf_render.hip): camera rays, the image row of every gathered hit (from the tile offsets
-// dudf_launch_pc_append left in `scratch`), normals, colour map, reflection models + scatter, 8-bit image
-int dudf_launch_render_setup(int64_t width, int64_t height, double fov, double noise, const double* R, const double* cam,
-                             const double* planes, double* rays, double* t0, unsigned char* mask, hipStream_t st);
-int dudf_launch_render_rows(const unsigned char* flags, int64_t n, const int64_t* counter, const int* scratch, int* rows, hipStream_t st);
-int dudf_launch_render_orient(const float* frame, const float* grad, const double* rays, int64_t k, double* normals, double* pc1,
-                              double* pc2, float* mean, hipStream_t st);
-int dudf_launch_render_colormap(const float* curv, int64_t k, const float* bounds, const double* lut, double* out, hipStream_t st);
-int dudf_launch_render_shade(int model, const unsigned char* hits, int64_t m, const int* rows, int64_t k, const double* pos,
-                             const double* normals, const double* pc1, const double* pc2, const double* cmap, const double* light,
-                             const double* camera, double shininess, double alpha1, double alpha2, double* acc, hipStream_t st);
-int dudf_launch_render_finish(const double* acc, int64_t count, double sample_rate, unsigned char* out, hipStream_t st);
-// third-order jets: x4 of n points x one 16-column tile (value + the eigen-frame V as three directions), and the
-// epilogue that turns the jets' mixed third-order coefficients into curvature
-int dudf_launch_make_x4_jet(const float* x, const float* V, int64_t n, int64_t npj, float* x4j, hipStream_t st);
-int dudf_launch_curvature(const float* yj, const float* lam, const float* V, int64_t n, float* out_mean,
-                          float* out_gauss, float* out_shape, hipStream_t st);
 
-// Run-time options (dudf_set_option in the C ABI; dudf_api.hip holds them).
-#ifndef DUDF_STASH_DEFAULT
-#define DUDF_STASH_DEFAULT 7          // requested stash mask of a fresh process: all seven arrays at 24 bits (R, E floats; C, S, Q, A, Z fixed point)
-#endif
-// option "deterministic": every cross-workgroup sum of the training path — loss terms, loss_s2 statistics, dW, db —
-// is formed by ONE workgroup per output element (a single block for the loss sums, one column split per weight tile,
-// one block for the thin layers), so repeated launches give bit-identical results.  A test mode: the weight-gradient
-// GEMM then runs on 7 CUs.
-bool dudf_deterministic();
-// option "split" = 0 keeps every hidden matmul on the exact three-piece bf16 split (six products); default: the fp16 hi/lo
-// split (three products) where it is built.
-bool dudf_split_fp16();
-// cap of the weight-gradient GEMM's grid (option "wgrad_max_workgroups"; 256 = one workgroup per CU)
-int dudf_wgrad_max_workgroups();
 // products per algorithmic multiply of the kernel a launcher is about to start in profile slot `slot`: 1 = f32-input MFMA,
 // 3 = fp16 hi/lo split, 6 = three-piece bf16 split (bench.py labels and prices its roofline from THIS, not from a table)
 void dudf_note_products(int slot, int products);

@@ -1,6 +1,7 @@
-// Small kernels around the sweeps: parameter packing, the per-point loss terms and their
-// cotangents, loss_s2 statistics, Adam, and copy-out helpers.  All bandwidth-trivial.
+// The training step's small kernels: parameter packing, the per-point loss terms and their cotangents, loss_s2
+// statistics, x4, copy-in, Adam, stash reads; with their launchers.  All bandwidth-trivial.
 #include "dudf_internal.h"
+#include "dudf_eigh3.h"
 
 namespace {
 
@@ -85,50 +86,6 @@ __device__ __forceinline__ void s1_point(float y, const f32x4 g, float u, float 
     gn = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
     tau = fabsf(tn + u * alpha * (1.f - tn * tn));
     t_g = fabsf(gn - tau);
-}
-
-// Symmetric 3x3 eigen-decomposition of the LOWER triangle (as torch.linalg.eigh reads it, reference
-// src/loss_functions.py:142), cyclic Jacobi in fp64, eigenvalues ascending.  V[i][j] = component i of v_j.
-__device__ __forceinline__ void eigh3(const double (&Hm)[3][3], double (&lam)[3], double (&V)[3][3]) {
-    double A[3][3] = {{Hm[0][0], Hm[1][0], Hm[2][0]}, {Hm[1][0], Hm[1][1], Hm[2][1]}, {Hm[2][0], Hm[2][1], Hm[2][2]}};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 10; ++sweep) {
-        const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-        const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-        if (off <= 1e-34 * dia || off == 0.0) break;
-#pragma unroll
-        for (int pq = 0; pq < 3; ++pq) {
-            const int p = (pq == 2) ? 1 : 0, q = (pq == 0) ? 1 : 2;
-            const double apq = A[p][q];
-            if (apq == 0.0) continue;
-            const double th = (A[q][q] - A[p][p]) / (2.0 * apq);
-            const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-            const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-            const int r = 3 - p - q;
-            const double app = A[p][p], aqq = A[q][q], arp = A[r][p], arq = A[r][q];
-            A[p][p] = app - t * apq; A[q][q] = aqq + t * apq; A[p][q] = A[q][p] = 0.0;
-            A[r][p] = A[p][r] = c * arp - sn * arq;
-            A[r][q] = A[q][r] = sn * arp + c * arq;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const double vip = V[i][p], viq = V[i][q];
-                V[i][p] = c * vip - sn * viq;
-                V[i][q] = sn * vip + c * viq;
-            }
-        }
-    }
-    lam[0] = A[0][0]; lam[1] = A[1][1]; lam[2] = A[2][2];
-    auto swp = [&](int i, int j) {
-        if (lam[i] > lam[j]) {
-            const double t = lam[i]; lam[i] = lam[j]; lam[j] = t;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { const double u = V[k][i]; V[k][i] = V[k][j]; V[k][j] = u; }
-        }
-    };
-    swp(0, 1); swp(1, 2); swp(0, 1);
 }
 
 // Hessian of a quad: H[i][k] = (adot_0^k)_i = g[(4p+1+k)*4 + i]
@@ -441,23 +398,6 @@ __global__ __launch_bounds__(256) void read_stash_kernel(const float* __restrict
     }
 }
 
-// out_f (n), out_g (n,3), out_h (n,3,3) [Hessian points first n_h only meaningful], any may be null
-__global__ __launch_bounds__(256) void copy_out_kernel(const float* __restrict__ y, const float* __restrict__ g,
-                                                       float* __restrict__ of, float* __restrict__ og,
-                                                       float* __restrict__ oh, int64_t n, int64_t n_h, int64_t ncol_h) {
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t c = p < n_h ? 4 * p : ncol_h + (p - n_h);
-        if (of) of[p] = y[c];
-        if (og) { og[p * 3] = g[c * 4]; og[p * 3 + 1] = g[c * 4 + 1]; og[p * 3 + 2] = g[c * 4 + 2]; }
-        if (oh && p < n_h) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int i = 0; i < 3; ++i) oh[p * 9 + i * 3 + k] = g[(c + 1 + k) * 4 + i];
-        }
-    }
-}
-
 // ybar (n) / gbar (n,3) given per POINT by the caller -> per column (tangent channels and padding zero)
 __global__ __launch_bounds__(256) void copy_in_kernel(const float* __restrict__ ybar, const float* __restrict__ gbar,
                                                       float* __restrict__ wy, float* __restrict__ wg, int64_t n,
@@ -470,193 +410,6 @@ __global__ __launch_bounds__(256) void copy_in_kernel(const float* __restrict__ 
         f32x4 gv = {0, 0, 0, 0};
         if (p >= 0 && gbar) gv = f32x4{gbar[p * 3], gbar[p * 3 + 1], gbar[p * 3 + 2], 0.f};
         *reinterpret_cast<f32x4*>(wg + c * 4) = gv;
-    }
-}
-
-// x4 of a regular N^3 grid on [-1,1]^3, linear index start+c, first axis slowest — the sample order of reference
-// src/render_mc.py:36-49 (`extract_fields`); coordinates are index-derived, nothing is read from HBM.
-__global__ __launch_bounds__(256) void make_x4_grid_kernel(float* __restrict__ x4, int64_t n, int64_t np, int64_t N,
-                                                           int64_t start) {
-    const float voxel = 2.0f / (float)(N - 1);
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < np; c += (int64_t)gridDim.x * blockDim.x) {
-        f32x4 v = {0, 0, 0, 0};
-        if (c < n) {
-            const int64_t i = start + c;
-            const int64_t i2 = i % N, i1 = (i / N) % N, i0 = (i / N / N) % N;
-            v = f32x4{(float)i0 * voxel - 1.0f, (float)i1 * voxel - 1.0f, (float)i2 * voxel - 1.0f, 1.f};
-        }
-        *reinterpret_cast<f32x4*>(x4 + c * 4) = v;
-    }
-}
-
-// Per-point features the renderers derive from (f, df/dx, Hessian):
-//   out_df  = inverse(gt_mode, |f|, alpha)                    reference src/inverses.py:3-21 via src/render_mc.py:71
-//   out_vec = -normalize(df/dx) (eps 1e-12)                    reference src/render_mc.py:74-75
-//   flags   : points whose NORMALISED gradient has norm < 0.04 (only a vanishing gradient does, :86-93): the caller
-//             re-queries those with the Hessian path for the eigenvector fallback
-//   out_lam / out_V (Hessian points): eigenvalues ascending and eigenvectors (columns) of the Hessian's lower triangle,
-//             reference src/render_st.py:57-62 `compute_normals_and_cd` (normal = V[:,2])
-__global__ __launch_bounds__(256) void field_features_kernel(const float* __restrict__ y, const float* __restrict__ g,
-                                                             int64_t n, int64_t n_h, int64_t ncol_h, int inverse_mode,
-                                                             float alpha, float* __restrict__ out_df,
-                                                             float* __restrict__ out_vec, int* __restrict__ flag_count,
-                                                             float* __restrict__ out_lam, float* __restrict__ out_V) {
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t c = p < n_h ? 4 * p : ncol_h + (p - n_h);
-        if (out_df) {
-            const float f = fabsf(y[c]);
-            float d;
-            if (inverse_mode == 0) d = (f < 1.0f / alpha) ? sqrtf(f / alpha) : f;          // 'tanh'
-            else if (inverse_mode == 1) d = (f > 0.f) ? f : 0.01f;                        // 'siren' (min_step 0.01)
-            else d = ((f > 0.f) ? sqrtf(f) : 0.01f) / sqrtf(alpha);                       // 'squared'
-            out_df[p] = d;
-        }
-        if (out_vec) {
-            const float gx = g[c * 4], gy = g[c * 4 + 1], gz = g[c * 4 + 2];
-            const float nrm = sqrtf(gx * gx + gy * gy + gz * gz);
-            const float inv = -1.0f / fmaxf(nrm, 1e-12f);
-            const float vx = gx * inv, vy = gy * inv, vz = gz * inv;
-            out_vec[p * 3] = vx; out_vec[p * 3 + 1] = vy; out_vec[p * 3 + 2] = vz;
-            if (flag_count && sqrtf(vx * vx + vy * vy + vz * vz) < 0.04f) atomicAdd(flag_count, 1);
-        }
-        if ((out_lam || out_V) && p < n_h) {
-            double Hm[3][3], lam[3], V[3][3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                Hm[0][k] = g[(c + 1 + k) * 4]; Hm[1][k] = g[(c + 1 + k) * 4 + 1]; Hm[2][k] = g[(c + 1 + k) * 4 + 2];
-            }
-            eigh3(Hm, lam, V);
-            if (out_lam) { out_lam[p * 3] = (float)lam[0]; out_lam[p * 3 + 1] = (float)lam[1]; out_lam[p * 3 + 2] = (float)lam[2]; }
-            if (out_V)
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) out_V[p * 9 + i * 3 + j] = (float)V[i][j];
-        }
-    }
-}
-
-// ---- third-order jets for the curvature query (reference src/render_st.py:42-55) ------------------------------------
-// One 16-column tile per point: column 0 = (x, 1), columns 1..3 = the eigen-frame A = v_0, B = v_1, C = v_2 = n of the
-// Hessian as directions, the rest zero; SWEEP_FWD_J (dudf_sweep.hip) turns them into the Taylor coefficients y_m of
-// f(x + sA + rB + tC) for the monomials listed there.  Mixed third derivatives in the frame:
-//   T(A,A,C) = 2 y_sst, T(B,B,C) = 2 y_rrt, T(A,B,C) = y_srt, T(A,C,C) = 2 y_stt, T(B,C,C) = 2 y_rtt
-// and the shape operator  J_ik = dn_i/dx_k = sum_{j<2} (v_j)_i T(v_j, n, e_k) / (lam_2 - lam_j)  (first-order perturbation
-// of the top eigenvector of the Hessian — what autograd through torch.linalg.eigh returns), e_k expanded in the frame.
-// mean = tr J / 2 = [T(A,A,C)/(lam_2-lam_0) + T(B,B,C)/(lam_2-lam_1)]/2.
-__global__ __launch_bounds__(256) void make_x4_jet_kernel(const float* __restrict__ x, const float* __restrict__ V,
-                                                          int64_t n, int64_t npj, float* __restrict__ x4j) {
-    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < npj; c += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t p = c >> 4;
-        const int li = (int)(c & 15);
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (p < n) {
-            if (li == 0) v = f32x4{x[p * 3], x[p * 3 + 1], x[p * 3 + 2], 1.f};
-            else if (li <= 3) v = f32x4{V[p * 9 + li - 1], V[p * 9 + 3 + li - 1], V[p * 9 + 6 + li - 1], 0.f};
-        }
-        *reinterpret_cast<f32x4*>(x4j + c * 4) = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void curvature_kernel(const float* __restrict__ yj, const float* __restrict__ lam,
-                                                        const float* __restrict__ V, int64_t n,
-                                                        float* __restrict__ out_mean, float* __restrict__ out_gauss,
-                                                        float* __restrict__ out_shape) {
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
-        const float* yp = yj + p * 16;
-        const double g0 = (double)lam[p * 3 + 2] - (double)lam[p * 3], g1 = (double)lam[p * 3 + 2] - (double)lam[p * 3 + 1];
-        const double Taac = 2.0 * yp[10], Tbbc = 2.0 * yp[11], Tabc = yp[12], Tacc = 2.0 * yp[13], Tbcc = 2.0 * yp[14];
-        if (out_mean) out_mean[p] = (float)(0.5 * (Taac / g0 + Tbbc / g1));
-        if (out_shape || out_gauss) {
-            double J[3][3], A[3], B[3], C[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { A[i] = V[p * 9 + i * 3]; B[i] = V[p * 9 + i * 3 + 1]; C[i] = V[p * 9 + i * 3 + 2]; }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double w0k = (A[k] * Taac + B[k] * Tabc + C[k] * Tacc) / g0;
-                const double w1k = (A[k] * Tabc + B[k] * Tbbc + C[k] * Tbcc) / g1;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) J[i][k] = A[i] * w0k + B[i] * w1k;
-            }
-            if (out_shape)
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) out_shape[p * 9 + i * 3 + k] = (float)J[i][k];
-            if (out_gauss) {
-                // -det [[J, n], [n^T, 0]]  (reference src/render_st.py:48-53) = sum_ik n_i n_k cof(J)_ik
-                double acc = 0.0;
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, k1 = (k + 1) % 3, k2 = (k + 2) % 3;
-                        acc += C[i] * C[k] * (J[i1][k1] * J[i2][k2] - J[i1][k2] * J[i2][k1]);
-                    }
-                out_gauss[p] = (float)acc;
-            }
-        }
-    }
-}
-
-// ---- sphere tracing on the device (reference src/render_st.py:136-172 `propagate_rays`, `grad_descent`) ----------------
-// The reference keeps ray positions in float64 numpy, feeds float32 copies to the network, takes the step in float32
-// (`inverse`, src/inverses.py:3-21) and adds it in float64.  Same here: t0 is double, x4 = (float)t0, the step float.
-__device__ __forceinline__ float inverse_step(float f, int inverse_mode, float alpha, float min_step) {
-    if (inverse_mode == 0) return (f < 1.0f / alpha) ? sqrtf(f / alpha) : f;               // 'tanh'
-    if (inverse_mode == 1) return (f > 0.f) ? f : min_step;                               // 'siren'
-    return ((f > 0.f) ? sqrtf(f) : min_step) / sqrtf(alpha);                              // 'squared'
-}
-
-__global__ __launch_bounds__(256) void rays_x4_kernel(const double* __restrict__ t0, int64_t m, int64_t np,
-                                                      float* __restrict__ x4) {
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < np; p += (int64_t)gridDim.x * blockDim.x) {
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (p < m) v = f32x4{(float)t0[p * 3], (float)t0[p * 3 + 1], (float)t0[p * 3 + 2], 1.f};
-        *reinterpret_cast<f32x4*>(x4 + p * 4) = v;
-    }
-}
-
-// one marching iteration for the rays still active: step along the ray, record hits, retire rays (:141-156)
-__global__ __launch_bounds__(256) void rays_step_kernel(const float* __restrict__ y, const double* __restrict__ rays,
-                                                        double* __restrict__ t0, unsigned char* __restrict__ mask,
-                                                        unsigned char* __restrict__ hits, int64_t m, int inverse_mode,
-                                                        float alpha, float min_step, float threshold,
-                                                        int* __restrict__ active) {
-    int mine = 0;
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += (int64_t)gridDim.x * blockDim.x) {
-        if (!mask[p]) continue;
-        const float udf = y[p];
-        const float step = inverse_step(fabsf(udf), inverse_mode, alpha, min_step);
-        double q[3];
-        bool inside = true;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            q[k] = t0[p * 3 + k] + rays[p * 3 + k] * (double)step;
-            t0[p * 3 + k] = q[k];
-            inside = inside && q[k] > -1.0 && q[k] < 1.0;
-        }
-        const bool close = (inverse_mode == 1) ? (udf < threshold) : (fabsf(step) < threshold);
-        if (close && inside) hits[p] = 1;
-        const bool go_on = !close && inside;
-        mask[p] = go_on ? 1 : 0;
-        mine += go_on ? 1 : 0;
-    }
-    if (mine) atomicAdd(active, mine);
-}
-
-// one descent step for the hit rays: t0 -= normalize(grad f) * inverse(|f|)  (:163-172; src/util.py:35-40 `normalize`)
-__global__ __launch_bounds__(256) void rays_descend_kernel(const float* __restrict__ y, const float* __restrict__ g,
-                                                           double* __restrict__ t0, const unsigned char* __restrict__ hits,
-                                                           int64_t m, int inverse_mode, float alpha, float min_step) {
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += (int64_t)gridDim.x * blockDim.x) {
-        if (!hits[p]) continue;
-        const float gx = g[p * 4], gy = g[p * 4 + 1], gz = g[p * 4 + 2];
-        const float nrm = sqrtf(gx * gx + gy * gy + gz * gz);
-        const float step = inverse_step(fabsf(y[p]), inverse_mode, alpha, min_step);
-        t0[p * 3] -= (double)((gx / nrm) * step);
-        t0[p * 3 + 1] -= (double)((gy / nrm) * step);
-        t0[p * 3 + 2] -= (double)((gz / nrm) * step);
     }
 }
 
@@ -774,13 +527,6 @@ int dudf_launch_read_stash(const DudfLayout& lo, const float* src, int layer, in
     return (int)hipGetLastError();
 }
 
-int dudf_launch_copy_out(const DudfLayout& lo, const float* ws, float* out_f, float* out_g, float* out_h,
-                         hipStream_t st) {
-    hipLaunchKernelGGL(copy_out_kernel, dim3(grid_for(lo.n)), dim3(256), 0, st, ws + lo.ws_y, ws + lo.ws_g, out_f,
-                       out_g, out_h, lo.n, lo.n_h, lo.ncol_h);
-    return (int)hipGetLastError();
-}
-
 int dudf_launch_copy_in(const DudfLayout& lo, const float* ybar, const float* gbar, float* ws, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
     hipLaunchKernelGGL(copy_in_kernel, dim3(grid_for(lo.np)), dim3(256), 0, st, ybar, gbar, ws + lo.ws_ybar,
@@ -792,63 +538,5 @@ int dudf_launch_make_x4(const DudfLayout& lo, const float* x, float* ws, hipStre
     DudfProfScope prof(PROF_OTHER, st);
     hipLaunchKernelGGL(make_x4_kernel, dim3(grid_for(lo.np)), dim3(256), 0, st, x, ws + lo.ws_x4, lo.n, lo.n_h,
                        lo.ncol_h, lo.np);
-    return (int)hipGetLastError();
-}
-
-int dudf_launch_make_x4_jet(const float* x, const float* V, int64_t n, int64_t npj, float* x4j, hipStream_t st) {
-    DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(make_x4_jet_kernel, dim3(grid_for(npj)), dim3(256), 0, st, x, V, n, npj, x4j);
-    return (int)hipGetLastError();
-}
-
-int dudf_launch_curvature(const float* yj, const float* lam, const float* V, int64_t n, float* out_mean,
-                          float* out_gauss, float* out_shape, hipStream_t st) {
-    DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(curvature_kernel, dim3(grid_for(n)), dim3(256), 0, st, yj, lam, V, n, out_mean, out_gauss,
-                       out_shape);
-    return (int)hipGetLastError();
-}
-
-int dudf_launch_rays_x4(const DudfLayout& lo, const double* t0, float* ws, hipStream_t st) {
-    DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(rays_x4_kernel, dim3(grid_for(lo.np)), dim3(256), 0, st, t0, lo.n, lo.np, ws + lo.ws_x4);
-    return (int)hipGetLastError();
-}
-
-int dudf_launch_rays_step(const DudfLayout& lo, const float* ws, const double* rays, double* t0, unsigned char* mask,
-                          unsigned char* hits, int inverse_mode, double alpha, double min_step, double threshold,
-                          int* active, hipStream_t st) {
-    DudfProfScope prof(PROF_OTHER, st);
-    hipError_t e = hipMemsetAsync(active, 0, sizeof(int), st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(rays_step_kernel, dim3(grid_for(lo.n)), dim3(256), 0, st, ws + lo.ws_y, rays, t0, mask, hits, lo.n,
-                       inverse_mode, (float)alpha, (float)min_step, (float)threshold, active);
-    return (int)hipGetLastError();
-}
-
-int dudf_launch_rays_descend(const DudfLayout& lo, const float* ws, double* t0, const unsigned char* hits,
-                             int inverse_mode, double alpha, double min_step, hipStream_t st) {
-    DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(rays_descend_kernel, dim3(grid_for(lo.n)), dim3(256), 0, st, ws + lo.ws_y, ws + lo.ws_g, t0, hits,
-                       lo.n, inverse_mode, (float)alpha, (float)min_step);
-    return (int)hipGetLastError();
-}
-
-int dudf_launch_make_x4_grid(const DudfLayout& lo, int64_t grid_n, int64_t start, float* ws, hipStream_t st) {
-    DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(make_x4_grid_kernel, dim3(grid_for(lo.np)), dim3(256), 0, st, ws + lo.ws_x4, lo.n, lo.np, grid_n,
-                       start);
-    return (int)hipGetLastError();
-}
-
-int dudf_launch_field_features(const DudfLayout& lo, const float* ws, int inverse_mode, double alpha, float* out_df,
-                               float* out_vec, int* out_flag_count, float* out_lam, float* out_V, hipStream_t st) {
-    DudfProfScope prof(PROF_OTHER, st);
-    if (out_flag_count) {
-        hipError_t e = hipMemsetAsync(out_flag_count, 0, sizeof(int), st);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(field_features_kernel, dim3(grid_for(lo.n)), dim3(256), 0, st, ws + lo.ws_y, ws + lo.ws_g, lo.n,
-                       lo.n_h, lo.ncol_h, inverse_mode, (float)alpha, out_df, out_vec, out_flag_count, out_lam, out_V);
     return (int)hipGetLastError();
 }

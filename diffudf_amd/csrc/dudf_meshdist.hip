@@ -19,7 +19,7 @@
 //   Every triangle evaluation is the fp64 Voronoi-region arithmetic of dudf_tridist.h, called through ONE non-inlined function by
 //   the indexed and the brute-force kernel alike: the same machine code, hence the same bits.  The answer is the minimum of those
 //   values over a set that contains every minimiser, so the index changes what is skipped, never what is returned.
-#include "dudf_internal.h"
+#include "dudf_context.h"
 #include "dudf_tridist.h"
 
 namespace {
@@ -297,14 +297,12 @@ static hipError_t launch_bounds(const float* tri, int64_t T, unsigned* hdr, hipS
     return hipGetLastError();
 }
 
-static int bad_index(const void* index, size_t index_bytes, int64_t T) {
-    return !index || (reinterpret_cast<uintptr_t>(index) & 255) || index_bytes < layout_of(T).total;
-}
+static int check_index(const void* index, size_t index_bytes, int64_t T) { return dudf_check_buffer(index, index_bytes, layout_of(T).total); }
 
 int dudf_mesh_morton_codes(const float* tri, int64_t n_tri, void* index, size_t index_bytes, int64_t* codes, void* stream) {
     if (n_tri <= 0 || !tri || !codes) return DUDF_E_BADCFG;
     if (n_tri >= ((int64_t)1 << 31)) return DUDF_E_UNSUPPORTED;
-    if (bad_index(index, index_bytes, n_tri)) return DUDF_E_WORKSPACE;
+    if (int rc = check_index(index, index_bytes, n_tri)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     unsigned* hdr = reinterpret_cast<unsigned*>(index);
@@ -317,7 +315,7 @@ int dudf_mesh_morton_codes(const float* tri, int64_t n_tri, void* index, size_t 
 int dudf_mesh_index_build(const float* tri, int64_t n_tri, const int64_t* order, void* index, size_t index_bytes, void* stream) {
     if (n_tri <= 0 || !tri || !order) return DUDF_E_BADCFG;
     if (n_tri >= ((int64_t)1 << 31)) return DUDF_E_UNSUPPORTED;
-    if (bad_index(index, index_bytes, n_tri)) return DUDF_E_WORKSPACE;
+    if (int rc = check_index(index, index_bytes, n_tri)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     const Layout y = layout_of(n_tri);
@@ -346,7 +344,7 @@ int dudf_mesh_distance(const float* tri, int64_t n_tri, const void* index, size_
     if (n_pts == 0) return 0;
     if (n_tri <= 0 || !tri || !pts) return DUDF_E_BADCFG;
     if (n_tri >= ((int64_t)1 << 31)) return DUDF_E_UNSUPPORTED;
-    if (index && bad_index(index, index_bytes, n_tri)) return DUDF_E_WORKSPACE;
+    if (index && check_index(index, index_bytes, n_tri)) return DUDF_E_WORKSPACE;
     if ((n_pts + kBlock - 1) / kBlock >= ((int64_t)1 << 31)) return DUDF_E_UNSUPPORTED;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);

@@ -1,11 +1,11 @@
 // Dense point-cloud extraction on the device — the kernels around the value+gradient sweeps and the frame query that replace
 // the host loop of reference src/render_pc.py:26-73 (`Sampler.generate_point_cloud`): propose, project step, ordered
-// compaction / append, normals.  Sequencing: dudf_api.hip (dudf_project_points, dudf_pointcloud_append, dudf_pointcloud_round).
+// compaction / append, normals; and the entry points that sequence them (dudf_project_points, dudf_pointcloud_*).
 //
 // The reference keeps the samples in float64 numpy, feeds float32 copies to the network (src/evaluate.py:18), forms the step
 // with `inverse` in float64 on the float32 value WITHOUT abs (:51) and moves in float64 (:53).  Same here, operation by
 // operation (no contraction: numpy rounds every product and sum).
-#include "dudf_internal.h"
+#include "dudf_context.h"
 
 namespace {
 
@@ -195,10 +195,6 @@ __global__ __launch_bounds__(256) void pc_normals_kernel(const float* __restrict
     }
 }
 
-}  // namespace
-
-int64_t dudf_pc_tiles(int64_t n) { return (n + kTile - 1) / kTile; }
-
 int dudf_launch_pc_propose(const DudfLayout& lo, const double* rand, int64_t rand_count, uint64_t seed, int64_t round, const double* surface,
                            const int64_t* counter, int64_t quota, double* samples, double* proposals, float* ws, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
@@ -221,6 +217,59 @@ int dudf_launch_pc_step(const DudfLayout& lo, float* ws, double* samples, int in
     return (int)hipGetLastError();
 }
 
+int dudf_launch_pc_normals(const float* V, int64_t m, double* normals, hipStream_t st) {
+    DudfProfScope prof(PROF_OTHER, st);
+    hipLaunchKernelGGL(pc_normals_kernel, dim3(grid_for(m)), dim3(256), 0, st, V, m, normals);
+    return (int)hipGetLastError();
+}
+
+// the projection loop of reference src/render_pc.py:43-56 on a context whose x4 already holds the float32 copies of `samples`:
+// per step the value+gradient sweeps and ONE kernel (step in double, move, next x4).  The first step packs theta (dudf_forward_common);
+// the later ones find the A-operand forms where it left them.  counter / quota: round mode (nothing moves once the quota is reached).
+int project_steps(DudfCtx& c, const float* theta, double* samples, int num_steps, int inverse_mode, double alpha, double thresh,
+                  double* out_step, double* out_unit, float* out_pre, unsigned char* out_accept, const int64_t* counter,
+                  int64_t quota) {
+    int rc;
+    SweepArgs a = dudf_make_sweep_args(c.lo, theta, c.ws);
+    a.store_c = 1;
+    for (int s = 0; s < num_steps; ++s) {
+        if (s == 0) {
+            if ((rc = dudf_forward_common(c, theta, nullptr, 0, true))) return rc;
+        } else {
+            if ((rc = dudf_run_sweep(SWEEP_FWD, c.lo, a, c.st))) return rc;
+            if ((rc = dudf_run_sweep(SWEEP_REV, c.lo, a, c.st))) return rc;
+        }
+        const int last = s + 1 == num_steps;
+        if ((rc = dudf_launch_pc_step(c.lo, c.ws, samples, inverse_mode, alpha, thresh, last, out_step, out_unit, out_pre,
+                                      out_accept, counter, quota, c.st))) return rc;
+    }
+    return 0;
+}
+
+// round workspace = [value+gradient query layout of n points][samples 3n doubles][proposals 3n doubles][unit gradient 3n doubles][pre-move position 3n]
+// [the same, compacted 3n][accept flags n bytes][tile counts + offsets][V 9 chunk][frame-query layout of `chunk` points]
+constexpr int64_t kPcFrameChunk = 32768;
+struct PcLayout { DudfLayout q; int64_t chunk, o_samples, o_prop, o_unit, o_pre, o_prec, o_accept, o_tiles, o_V, o_frame; size_t frame_bytes, total_bytes; };
+int make_pc_layout(const dudf_net_cfg* cfg, int64_t n, PcLayout* pl) {
+    int rc = dudf_make_layout(cfg, n, 0, &pl->q, 1);
+    if (rc) return rc;
+    if (pl->q.np > (1ll << 25)) return DUDF_E_BADCFG;
+    pl->chunk = n < kPcFrameChunk ? (n > 0 ? n : 1) : kPcFrameChunk;
+    DudfLayout f;
+    if ((rc = dudf_make_layout(cfg, pl->chunk, pl->chunk, &f, 1))) return rc;
+    pl->frame_bytes = f.total_bytes;
+    DudfCarver cv = {(int64_t)(pl->q.total_bytes / sizeof(float))};
+    pl->o_samples = cv.take(6 * n); pl->o_prop = cv.take(6 * n); pl->o_unit = cv.take(6 * n); pl->o_pre = cv.take(3 * n); pl->o_prec = cv.take(3 * n);
+    pl->o_accept = cv.take((n + 3) / 4); pl->o_tiles = cv.take(2 * dudf_pc_tiles(n)); pl->o_V = cv.take(9 * pl->chunk);
+    pl->o_frame = cv.take((int64_t)(f.total_bytes / sizeof(float)));
+    pl->total_bytes = (size_t)cv.o * sizeof(float);
+    return 0;
+}
+
+}  // namespace
+
+int64_t dudf_pc_tiles(int64_t n) { return (n + kTile - 1) / kTile; }
+
 // scratch: [tile counts | tile offsets], dudf_pc_tiles(n) ints each
 int dudf_launch_pc_append(const unsigned char* flags, int64_t n, const double* src_a, const double* src_b, const float* src_f,
                           double* dst_a, double* dst_b, float* out_f, int64_t capacity, int64_t quota, int64_t* counter,
@@ -237,8 +286,109 @@ int dudf_launch_pc_append(const unsigned char* flags, int64_t n, const double* s
     return (int)hipGetLastError();
 }
 
-int dudf_launch_pc_normals(const float* V, int64_t m, double* normals, hipStream_t st) {
-    DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(pc_normals_kernel, dim3(grid_for(m)), dim3(256), 0, st, V, m, normals);
-    return (int)hipGetLastError();
+extern "C" {
+
+int dudf_project_points(const dudf_net_cfg* cfg, const float* theta, double* points, int64_t n, int num_steps,
+                        int inverse_mode, double alpha, double surf_thresh, double* out_last_step, double* out_unit_grad,
+                        float* out_pre_pos, unsigned char* out_accept, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!dudf_valid_inverse_mode(inverse_mode) || num_steps < 1) return DUDF_E_BADMODE;
+    DudfCtx c;
+    int rc = dudf_open_ctx(cfg, n, 0, workspace, workspace_bytes, stream, &c, 1);
+    if (rc) return rc;
+    if (n <= 0) return 0;
+    if ((rc = dudf_launch_rays_x4(c.lo, points, c.ws, c.st))) return rc;
+    return project_steps(c, theta, points, num_steps, inverse_mode, alpha, surf_thresh, out_last_step, out_unit_grad,
+                         out_pre_pos, out_accept, nullptr, 0);
 }
+
+size_t dudf_pointcloud_append_workspace_bytes(int64_t n) {
+    if (n < 0) return 0;
+    return (size_t)((2 * dudf_pc_tiles(n) * (int64_t)sizeof(int) + 255) / 256 * 256 + 256);
+}
+
+int dudf_pointcloud_append(const unsigned char* flags, int64_t n, const double* src_a, const double* src_b, const float* src_f,
+                           double* dst_a, double* dst_b, float* out_f, int64_t capacity, int64_t quota, int64_t* counter,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    if (n < 0 || capacity < 0 || !counter || n > (1ll << 30)) return DUDF_E_BADCFG;
+    if (int rc = dudf_check_buffer(workspace, workspace_bytes, dudf_pointcloud_append_workspace_bytes(n))) return rc;
+    if (n == 0) return 0;
+    if (!flags || !src_a || !dst_a) return DUDF_E_BADCFG;
+    return dudf_launch_pc_append(flags, n, src_a, src_b, src_f, dst_a, dst_b, out_f, capacity, quota, counter,
+                                 reinterpret_cast<int*>(workspace), reinterpret_cast<hipStream_t>(stream));
+}
+
+int dudf_pointcloud_read_proposals(const dudf_net_cfg* cfg, int64_t num_points, double* out, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    PcLayout pl;
+    int rc = make_pc_layout(cfg, num_points, &pl);
+    if (rc) return rc;
+    if ((rc = dudf_check_buffer(workspace, workspace_bytes, pl.total_bytes))) return rc;
+    if (num_points <= 0) return 0;
+    if (!out) return DUDF_E_BADCFG;
+    return (int)hipMemcpyAsync(out, reinterpret_cast<float*>(workspace) + pl.o_prop, (size_t)num_points * 3 * sizeof(double),
+                               hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t dudf_pointcloud_workspace_bytes(const dudf_net_cfg* cfg, int64_t num_points) {
+    PcLayout pl;
+    if (make_pc_layout(cfg, num_points, &pl)) return 0;
+    return pl.total_bytes;
+}
+
+int dudf_pointcloud_round(const dudf_net_cfg* cfg, const float* theta, int64_t num_points, int num_steps, int inverse_mode,
+                          double alpha, double surf_thresh, const double* rand, int64_t rand_count, uint64_t seed, int64_t round,
+                          double* surface_points, double* normals, int64_t capacity, int64_t* counter, int64_t* host_counter,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (!dudf_valid_inverse_mode(inverse_mode) || num_steps < 1) return DUDF_E_BADMODE;
+    PcLayout pl;
+    int rc = make_pc_layout(cfg, num_points, &pl);
+    if (rc) return rc;
+    const int64_t n = num_points;
+    if ((rc = dudf_check_buffer(workspace, workspace_bytes, pl.total_bytes))) return rc;
+    if (!counter || !surface_points || !normals || capacity < 2 * n) return DUDF_E_BADCFG;
+    DudfCtx c = dudf_ctx_at(pl.q, reinterpret_cast<float*>(workspace), reinterpret_cast<hipStream_t>(stream));
+    hipError_t e;
+    if (n > 0) {
+        double* samples = reinterpret_cast<double*>(c.ws + pl.o_samples);
+        double* unit = reinterpret_cast<double*>(c.ws + pl.o_unit);
+        float* pre = c.ws + pl.o_pre; float* prec = c.ws + pl.o_prec;
+        unsigned char* accept = reinterpret_cast<unsigned char*>(c.ws + pl.o_accept);
+        const bool siren = inverse_mode == 1;
+        if ((rc = dudf_launch_pc_propose(c.lo, rand, rand_count, seed, round, surface_points, counter, n, samples,
+                                         reinterpret_cast<double*>(c.ws + pl.o_prop), c.ws, c.st))) return rc;
+        if ((rc = project_steps(c, theta, samples, num_steps, inverse_mode, alpha, surf_thresh, nullptr, siren ? unit : nullptr,
+                                siren ? nullptr : pre, accept, counter, n))) return rc;
+        // accepted rows in their order behind the counter; 'siren': the unit gradients with them, otherwise the float32 pre-move
+        // positions compacted as the input of the frame query
+        if ((rc = dudf_launch_pc_append(accept, n, samples, siren ? unit : nullptr, siren ? nullptr : pre, surface_points,
+                                        siren ? normals : nullptr, siren ? nullptr : prec, capacity, n, counter,
+                                        reinterpret_cast<int*>(c.ws + pl.o_tiles), c.st))) return rc;
+        if (!siren) {
+            int64_t hc[4];
+            if ((e = hipMemcpyAsync(hc, counter, sizeof(hc), hipMemcpyDeviceToHost, c.st)) != hipSuccess) return (int)e;
+            if ((e = hipStreamSynchronize(c.st)) != hipSuccess) return (int)e;
+            const int64_t added = hc[1], base = hc[2];
+            if (added < 0 || base < 0 || base + added > capacity || added > n) return DUDF_E_BADCFG;
+            float* V = c.ws + pl.o_V;
+            for (int64_t s = 0; s < added; s += pl.chunk) {        // the Hessian sweeps run on accepted rows only
+                const int64_t m = added - s < pl.chunk ? added - s : pl.chunk;
+                DudfLayout fl;
+                if ((rc = dudf_make_layout(cfg, m, m, &fl, 1))) return rc;
+                if (fl.total_bytes > pl.frame_bytes) return DUDF_E_WORKSPACE;
+                DudfCtx f = dudf_ctx_at(fl, c.ws + pl.o_frame, c.st);
+                if ((rc = dudf_forward_common(f, theta, prec + 3 * s, 0, true))) return rc;
+                if ((rc = dudf_launch_field_features(f.lo, f.ws, 0, 1.0, nullptr, nullptr, nullptr, nullptr, V, f.st))) return rc;
+                if ((rc = dudf_launch_pc_normals(V, m, normals + 3 * (base + s), f.st))) return rc;
+            }
+            if (host_counter) for (int i = 0; i < 4; ++i) host_counter[i] = hc[i];
+            return 0;
+        }
+    }
+    if (host_counter) {
+        if ((e = hipMemcpyAsync(host_counter, counter, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, c.st)) != hipSuccess) return (int)e;
+        if ((e = hipStreamSynchronize(c.st)) != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
     b -= a.nb_bf16;
     if (b < a.nb_x4) {
         // x4: the layer-1 B operand of every column.  plain column: (x0,x1,x2,1); Hessian quad: channel 0 the same, channel
-        // 1+k = (e_k, 0); padding: zeros (as make_x4_kernel, dudf_misc.hip)
+        // 1+k = (e_k, 0); padding: zeros (as make_x4_kernel, dudf_loss.hip)
         for (int64_t c = (int64_t)b * 256 + threadIdx.x; c < a.np; c += (int64_t)a.nb_x4 * 256) {
             f32x4 v = {0, 0, 0, 0};
             if (c < a.ncol_h) {

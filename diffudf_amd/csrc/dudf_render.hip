@@ -1,12 +1,12 @@
 // Sphere-traced images on the device — the kernels around the marching loop (dudf_trace_rays / dudf_descend_rays) and the frame /
 // curvature queries that replace the numpy glue of reference generate_st.py:41-101, :139 and src/render_st.py:104-114, :174-245:
 // camera rays against the six box planes, the row index of the gathered hits, orientation of the normals, the curvature colour
-// map, the two reflection models with the scatter into the image, and the final 8-bit image.  Entry points: dudf_api.hip.
+// map, the two reflection models with the scatter into the image, and the final 8-bit image; with the dudf_render_* entry points.
 //
 // The reference does all of this in float64 numpy (normals, principal directions and curvatures arrive as float32 from torch and
 // are promoted where they meet a float64 operand).  Same here, operation by operation and in its order; no contraction: numpy
 // rounds every product and sum.  One thread per ray or hit, rows of three consecutive values.
-#include "dudf_internal.h"
+#include "dudf_context.h"
 
 #include <cfloat>
 
@@ -231,8 +231,6 @@ __global__ __launch_bounds__(256) void render_finish_kernel(const double* __rest
     }
 }
 
-}  // namespace
-
 int dudf_launch_render_setup(int64_t width, int64_t height, double fov, double noise, const double* R, const double* cam,
                              const double* planes, double* rays, double* t0, unsigned char* mask, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
@@ -289,3 +287,65 @@ int dudf_launch_render_finish(const double* acc, int64_t count, double sample_ra
     hipLaunchKernelGGL(render_finish_kernel, dim3(grid_for(count)), dim3(256), 0, st, acc, count, sample_rate, out);
     return (int)hipGetLastError();
 }
+
+}  // namespace
+
+// ---- the entry points around dudf_trace_rays / dudf_descend_rays and the frame / curvature queries (dudf_query.hip) -------------
+extern "C" {
+
+int dudf_render_setup_rays(int64_t width, int64_t height, double fov, double noise, const double* rotation, const double* camera_position,
+                           const double* planes, double* rays, double* t0, unsigned char* mask, void* stream) {
+    if (width < 1 || height < 1 || width * height > (1ll << 30) || !rotation || !camera_position || !planes) return DUDF_E_BADCFG;
+    if (!rays || !t0 || !mask) return DUDF_E_BADCFG;
+    return dudf_launch_render_setup(width, height, fov, noise, rotation, camera_position, planes, rays, t0, mask,
+                                    reinterpret_cast<hipStream_t>(stream));
+}
+
+int dudf_render_gather(const unsigned char* hits, int64_t m, const double* t0, const double* rays, double* out_pos, double* out_rays,
+                       int32_t* out_rows, int64_t* counter, void* workspace, size_t workspace_bytes, void* stream) {
+    if (m < 0 || m > (1ll << 30) || !counter) return DUDF_E_BADCFG;
+    if (int rc = dudf_check_buffer(workspace, workspace_bytes, dudf_pointcloud_append_workspace_bytes(m))) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipError_t e = hipMemsetAsync(counter, 0, 4 * sizeof(int64_t), st);
+    if (e != hipSuccess) return (int)e;
+    if (m == 0) return 0;
+    if (!hits || !t0 || !out_pos || !out_rows || (rays && !out_rays)) return DUDF_E_BADCFG;
+    int rc = dudf_launch_pc_append(hits, m, t0, rays, nullptr, out_pos, rays ? out_rays : nullptr, nullptr, m, (int64_t)1 << 62, counter,
+                                   reinterpret_cast<int*>(workspace), st);
+    if (rc) return rc;
+    return dudf_launch_render_rows(hits, m, counter, reinterpret_cast<const int*>(workspace), out_rows, st);
+}
+
+int dudf_render_orient(const float* frame_v, const float* grad, const double* hit_rays, int64_t k, double* out_normals,
+                       double* out_pc1, double* out_pc2, float* mean, void* stream) {
+    if (k < 0 || (frame_v != nullptr) == (grad != nullptr) || !out_normals || (frame_v && !hit_rays)) return DUDF_E_BADCFG;
+    if (k == 0) return 0;
+    return dudf_launch_render_orient(frame_v, grad, hit_rays, k, out_normals, out_pc1, out_pc2, grad ? nullptr : mean,
+                                     reinterpret_cast<hipStream_t>(stream));
+}
+
+int dudf_render_colormap(const float* curvatures, int64_t k, const float* bounds, const double* lut, double* out_colors, void* stream) {
+    if (k < 0 || !bounds || !lut || (k > 0 && (!curvatures || !out_colors))) return DUDF_E_BADCFG;
+    if (k == 0) return 0;
+    return dudf_launch_render_colormap(curvatures, k, bounds, lut, out_colors, reinterpret_cast<hipStream_t>(stream));
+}
+
+int dudf_render_shade(int model, const unsigned char* hits, int64_t m, const int32_t* rows, int64_t k, const double* hit_pos,
+                      const double* normals, const double* pc1, const double* pc2, const double* color_map, const double* light_position,
+                      const double* camera_position, double shininess, double alpha1, double alpha2, double* accumulator, void* stream) {
+    if (model != DUDF_SHADE_PHONG && model != DUDF_SHADE_WARD) return DUDF_E_BADMODE;
+    if (m < 0 || k < 0 || k > m || !light_position || !accumulator || (m > 0 && !hits)) return DUDF_E_BADCFG;
+    if (k > 0 && (!rows || !hit_pos || !normals)) return DUDF_E_BADCFG;
+    if (model == DUDF_SHADE_WARD && (!camera_position || (k > 0 && (!pc1 || !pc2)))) return DUDF_E_BADCFG;
+    if (m == 0) return 0;
+    return dudf_launch_render_shade(model, hits, m, rows, k, hit_pos, normals, pc1, pc2, color_map, light_position, camera_position,
+                                    shininess, alpha1, alpha2, accumulator, reinterpret_cast<hipStream_t>(stream));
+}
+
+int dudf_render_finish(const double* accumulator, int64_t count, double sample_rate, unsigned char* out_image, void* stream) {
+    if (count < 0 || !(sample_rate > 0.0) || (count > 0 && (!accumulator || !out_image))) return DUDF_E_BADCFG;
+    if (count == 0) return 0;
+    return dudf_launch_render_finish(accumulator, count, sample_rate, out_image, reinterpret_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

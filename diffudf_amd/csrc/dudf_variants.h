@@ -13,9 +13,34 @@ enum { SWEEP_FWD = 0, SWEEP_REV = 1, SWEEP_ADJ_FWD = 2, SWEEP_ADJ_REV = 3,
        SWEEP_FWD_H = 4, SWEEP_REV_H = 5, SWEEP_ADJ_FWD_H = 6, SWEEP_ADJ_REV_H = 7,     // Hessian-quad variants
        SWEEP_FWD_J = 8 };                                                              // third-order jets (query)
 
-// snapshot of the run-time options (dudf_set_option; dudf_api.hip holds them): the choosers read no globals
+// ---- the run-time options, ONCE: X(name, lowest, highest, default of a fresh process).  dudf_set_option / dudf_get_option take the
+// names; struct DudfOptions, the table of dudf_runtime.hip, the defaults and the current values all come from this list
+#ifndef DUDF_STASH_DEFAULT
+#define DUDF_STASH_DEFAULT 7          // requested stash mask of a fresh process: all seven arrays at 24 bits (R, E floats; C, S, Q, A, Z fixed point)
+#endif
+#ifndef DUDF_WGRAD_BUFFERS_DEFAULT
+#define DUDF_WGRAD_BUFFERS_DEFAULT 4
+#endif
+#define DUDF_OPTION_LIST(X)                                                                                                            \
+    X(deterministic, 0, 1, 0)              /* 1: every cross-workgroup sum of the training path — loss terms, loss_s2 statistics, dW, db — */ \
+                                           /* has ONE owner (a single block for the loss sums, one column split per weight tile, one */ \
+                                           /* block for the thin layers): bit-reproducible; slow (the weight-gradient GEMM runs on 7 CUs) */ \
+    X(split, 0, 1, 1)                      /* operand split of the 16-bit matrix cores: 1 = fp16 hi/lo, three products, where it is */ \
+                                           /* built; 0 = bf16x3, six, for every hidden matmul */                                       \
+    X(split_quads, 0, 1, 1)                /* the Hessian quads / jets on fp16x3 as well (0: bf16x6) */                                \
+    X(sweep_family, 0, 1, 1)               /* 1 = the 16-bit-core sweeps where built; 0 = the f32-input MFMA kernel everywhere (A/B reference) */ \
+    X(stash, 0, 15, DUDF_STASH_DEFAULT)    /* REQUESTED stash mask, only 0, 6 or 7 (dudf_stash_mode reports what a workspace gets) */ \
+    X(wgrad_family, 0, 2, 0)               /* weight-gradient GEMM: 0 = cooperative split (default), 1 = f32-input MFMA, 2 = bf16x6 per-wave split */ \
+    X(wgrad_tr, 0, 1, 0)                   /* fp32 rows staged through the [column][feature] image + transposed fragment reads */      \
+    X(pair_launch, 0, 1, 1)                /* quads + plain columns of a training sweep in ONE grid */                                 \
+    X(wgrad_max_workgroups, 8, 256, 256)   /* cap of the weight-gradient GEMM's grid (256 = one workgroup per CU; a multi-GPU step leaves CUs to RCCL) */ \
+    X(wgrad_buffers, 3, 4, DUDF_WGRAD_BUFFERS_DEFAULT)   /* LDS image buffers of the 24-bit-operand weight-gradient GEMM (4: one poll per stage instead of two) */
+
+// snapshot of the run-time options (dudf_runtime.hip holds the current ones): the choosers read no globals.  A fresh one holds the defaults
 struct DudfOptions {
-    int deterministic, split, split_quads, sweep_family, stash, wgrad_family, wgrad_tr, pair_launch, wgrad_max_workgroups, wgrad_buffers;
+#define X(name, lo, hi, def) int name = def;
+    DUDF_OPTION_LIST(X)
+#undef X
 };
 // which sweeps run fp16x3: bits 0-3 the plain columns' four sweeps (all or none: the adjoint reverse sweep's column scale
 // comes from the fp16x3 adjoint forward sweep), bit 5 the Hessian quads / jets as well (option split_quads = 0: bf16x6)

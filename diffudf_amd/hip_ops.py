@@ -62,19 +62,19 @@ OPTIONS = ("deterministic", "split", "split_quads", "sweep_family", "stash", "wg
 def set_option(name, value):
     """dudf_set_option: a process-wide run-time option of the library (include/dudf_hip.h lists names and values).  Options that
     change the stash format or the kernel family invalidate cached workspaces (their size and layout depend on them)."""
-    _lib.check(_lib.load().dudf_set_option(str(name).encode(), int(value)), f"dudf_set_option({name!r}, {value})")
+    _call("dudf_set_option", str(name).encode(), int(value), stream=False, what=f"dudf_set_option({name!r}, {value})")
     if name != "wgrad_max_workgroups":
         _ws_cache.clear(); _qws_cache.clear()
 
 
 def get_option(name):
     v = ctypes.c_int(0)
-    _lib.check(_lib.load().dudf_get_option(str(name).encode(), ctypes.byref(v)), f"dudf_get_option({name!r})")
+    _call("dudf_get_option", str(name).encode(), ctypes.byref(v), stream=False, what=f"dudf_get_option({name!r})")
     return int(v.value)
 
 
 def reset_options():
-    _lib.check(_lib.load().dudf_reset_options(), "dudf_reset_options")
+    _call("dudf_reset_options", stream=False)
     _ws_cache.clear(); _qws_cache.clear()
 
 
@@ -96,13 +96,6 @@ class options:
         return False
 
 
-def theta_count(cfg):
-    n = _lib.load().dudf_theta_count(ctypes.byref(cfg))
-    if n < 0:
-        _lib.check(-1, "dudf_theta_count")
-    return int(n)
-
-
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
@@ -111,18 +104,62 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _f32(t, what):
-    if t.device.type != "cuda":
-        raise _lib.DudfError(f"{what} must live on the GPU (got {t.device}); the HIP path has no CPU fallback")
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
+def _call(name, *args, dev=None, stream=True, what=None):
+    """One C-ABI call: `name(*args[, current stream])` under the device guard of `dev` (None: no guard); a non-zero return raises,
+    named after the symbol (or `what`)."""
+    fn = getattr(_lib.load(), name)
+    if stream:
+        args += (_stream(),)
+    if dev is None:
+        rc = fn(*args)
+    else:
+        with torch.cuda.device(dev):
+            rc = fn(*args)
+    _lib.check(rc, what or name)
+
+
+def _bytes(name, *args, err=-1):
+    """A byte (or element) count of the library; it answers 0 (or less) for arguments it refuses."""
+    n = int(getattr(_lib.load(), name)(*args))
+    if n <= 0:
+        _lib.check(err, name)
+    return n
+
+
+def _scratch(nbytes, device):
+    """256-byte-aligned device scratch of the C ABI's (workspace, bytes) pairs."""
+    buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    assert buf.data_ptr() % 256 == 0
+    return buf
+
+
+def _tensor(t, what, dtype, shape=None, convert=False):
+    """`t` as the C ABI reads it: a contiguous CUDA tensor of `dtype` whose dimensions behind the first are `shape` (None: any
+    shape).  convert: another dtype or stride is converted, otherwise it is refused."""
+    if not torch.is_tensor(t) or t.device.type != "cuda":
+        raise _lib.DudfError(f"{what} must be a CUDA tensor (got {getattr(t, 'device', type(t).__name__)}); the HIP path has no CPU fallback")
+    if shape is not None and (t.dim() != 1 + len(shape) or tuple(t.shape[1:]) != tuple(shape)):
+        raise _lib.DudfError(f"{what} must have shape (n,{','.join(str(d) for d in shape or ())}); got {tuple(t.shape)}")
+    if convert:
+        return t.to(dtype).contiguous()
+    if t.dtype != dtype or not t.is_contiguous():
+        raise _lib.DudfError(f"{what} must be a contiguous {str(dtype).replace('torch.', '')} tensor; got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def theta_count(cfg):
+    return _bytes("dudf_theta_count", ctypes.byref(cfg))
 
 
 _theta_counts = {}
 
 
-def _check_theta(cfg, theta):
+def _theta(cfg, theta, convert=True):
+    """theta as the C ABI takes it: flat fp32 on the GPU with exactly this network's (padded) parameter count — the library
+    indexes it by the layout of `cfg` and cannot know the length of the buffer behind a pointer.  convert=False (the training
+    path): checked only."""
+    if convert:
+        theta = _tensor(theta, "theta", torch.float32, convert=True)
     key = (cfg.n_hidden_layers, cfg.hidden)
     n = _theta_counts.get(key)
     if n is None:
@@ -130,42 +167,22 @@ def _check_theta(cfg, theta):
     if theta.numel() != n or theta.dtype != torch.float32 or theta.device.type != "cuda":
         raise _lib.DudfError(f"theta must be {n} fp32 elements on the GPU for SIREN(3, 1, [{cfg.hidden}]*{cfg.n_hidden_layers}); got "
                              f"{theta.numel()} x {theta.dtype} on {theta.device}")
-
-
-def _theta(cfg, theta):
-    """theta as the C ABI takes it: flat fp32 on the GPU with exactly this network's (padded) parameter count — the library
-    indexes it by the layout of `cfg` and cannot know the length of the buffer behind a pointer."""
-    theta = _f32(theta, "theta")
-    key = (cfg.n_hidden_layers, cfg.hidden)
-    n = _theta_counts.get(key)
-    if n is None:
-        n = _theta_counts[key] = theta_count(cfg)
-    if theta.numel() != n:
-        raise _lib.DudfError(f"theta has {theta.numel()} elements; SIREN(3, 1, [{cfg.hidden}]*{cfg.n_hidden_layers}) takes {n}")
     return theta
 
 
 class Workspace:
     """Caller-owned scratch for one (cfg, n_points, n_hess).  Holds the stash between forward and backward."""
+    _bytes_symbol = "dudf_workspace_bytes_hess"
 
     def __init__(self, cfg, n, device, n_hess=0):
         self.cfg, self.n, self.n_hess = cfg, int(n), int(n_hess)
-        self.nbytes = int(_lib.load().dudf_workspace_bytes_hess(ctypes.byref(cfg), self.n, self.n_hess))
-        if self.nbytes == 0:
-            _lib.check(-1, "dudf_workspace_bytes")
-        self.buf = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
-        assert self.buf.data_ptr() % 256 == 0
+        self.nbytes = _bytes(self._bytes_symbol, ctypes.byref(cfg), self.n, self.n_hess)
+        self.buf = _scratch(self.nbytes, device)
 
 
 class QueryWorkspace(Workspace):
     """The smaller scratch the value / df/dx / Hessian queries need (no adjoint stash)."""
-
-    def __init__(self, cfg, n, device, n_hess=0):
-        self.cfg, self.n, self.n_hess = cfg, int(n), int(n_hess)
-        self.nbytes = int(_lib.load().dudf_workspace_bytes_query(ctypes.byref(cfg), self.n, self.n_hess))
-        if self.nbytes == 0:
-            _lib.check(-1, "dudf_workspace_bytes_query")
-        self.buf = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
+    _bytes_symbol = "dudf_workspace_bytes_query"
 
 
 _ws_cache = {}
@@ -193,40 +210,33 @@ def workspace_for(cfg, n, device, n_hess=0):
 
 def query(cfg, theta, x, want_grad=True, ws=None):
     """f (n,), df/dx (n,3) or None.  Reference: src/evaluate.py:26-32 per chunk."""
-    lib = _lib.load()
-    x = _f32(x, "x").view(-1, 3)
+    x = _tensor(x, "x", torch.float32, convert=True).view(-1, 3)
     theta = _theta(cfg, theta)
     n = x.shape[0]
     ws = ws or query_workspace_for(cfg, n, x.device)
     f = torch.empty(n, dtype=torch.float32, device=x.device)
     g = torch.empty(n, 3, dtype=torch.float32, device=x.device) if want_grad else None
-    rc = lib.dudf_query(ctypes.byref(cfg), _ptr(theta), _ptr(x), n, _ptr(f), _ptr(g), _ptr(ws.buf), ws.nbytes,
-                        _stream())
-    _lib.check(rc, "dudf_query")
+    _call("dudf_query", ctypes.byref(cfg), _ptr(theta), _ptr(x), n, _ptr(f), _ptr(g), _ptr(ws.buf), ws.nbytes)
     return f, g
 
 
 def query_hessian(cfg, theta, x, ws=None):
     """f (n,), df/dx (n,3), Hessian (n,3,3) [i][k] = d(df/dx_i)/dx_k.  Reference: src/evaluate.py:26-35."""
-    lib = _lib.load()
-    x = _f32(x, "x").view(-1, 3)
+    x = _tensor(x, "x", torch.float32, convert=True).view(-1, 3)
     theta = _theta(cfg, theta)
     n = x.shape[0]
     ws = ws or query_workspace_for(cfg, n, x.device, n_hess=n)
     f = torch.empty(n, dtype=torch.float32, device=x.device)
     g = torch.empty(n, 3, dtype=torch.float32, device=x.device)
     h = torch.empty(n, 3, 3, dtype=torch.float32, device=x.device)
-    rc = lib.dudf_query_hessian(ctypes.byref(cfg), _ptr(theta), _ptr(x), n, _ptr(f), _ptr(g), _ptr(h), _ptr(ws.buf),
-                                ws.nbytes, _stream())
-    _lib.check(rc, "dudf_query_hessian")
+    _call("dudf_query_hessian", ctypes.byref(cfg), _ptr(theta), _ptr(x), n, _ptr(f), _ptr(g), _ptr(h), _ptr(ws.buf), ws.nbytes)
     return f, g, h
 
 
 def query_frame(cfg, theta, x, ws=None):
     """f, df/dx, Hessian, eigenvalues (n,3) ascending, eigenvectors (n,3,3) as columns — eigh of the Hessian's
     lower triangle (reference src/render_st.py:57-62)."""
-    lib = _lib.load()
-    x = _f32(x, "x").view(-1, 3)
+    x = _tensor(x, "x", torch.float32, convert=True).view(-1, 3)
     theta = _theta(cfg, theta)
     n = x.shape[0]
     ws = ws or query_workspace_for(cfg, n, x.device, n_hess=n)
@@ -234,9 +244,8 @@ def query_frame(cfg, theta, x, ws=None):
     f = torch.empty(n, dtype=torch.float32, device=dev); g = torch.empty(n, 3, dtype=torch.float32, device=dev)
     h = torch.empty(n, 3, 3, dtype=torch.float32, device=dev); lam = torch.empty(n, 3, dtype=torch.float32, device=dev)
     v = torch.empty(n, 3, 3, dtype=torch.float32, device=dev)
-    rc = lib.dudf_query_frame(ctypes.byref(cfg), _ptr(theta), _ptr(x), n, _ptr(f), _ptr(g), _ptr(h), _ptr(lam), _ptr(v),
-                              _ptr(ws.buf), ws.nbytes, _stream())
-    _lib.check(rc, "dudf_query_frame")
+    _call("dudf_query_frame", ctypes.byref(cfg), _ptr(theta), _ptr(x), n, _ptr(f), _ptr(g), _ptr(h), _ptr(lam), _ptr(v),
+          _ptr(ws.buf), ws.nbytes)
     return f, g, h, lam, v
 
 
@@ -244,8 +253,7 @@ def query_curvature(cfg, theta, x, want_shape=False, chunk=65536):
     """Eigen-frame of the Hessian and the curvature of its top-eigenvector field (reference src/render_st.py:42-62):
     lam (n,3), V (n,3,3) [normal = V[:,:,2]], mean (n,), and with want_shape also gaussian (n,) and the shape operator
     J (n,3,3) = d normal_i / d x_k; (None, None) otherwise.  Runs in chunks so the scratch stays a few GB."""
-    lib = _lib.load()
-    x = _f32(x, "x").view(-1, 3)
+    x = _tensor(x, "x", torch.float32, convert=True).view(-1, 3)
     theta = _theta(cfg, theta)
     n, dev = x.shape[0], x.device
     lam = torch.empty(n, 3, dtype=torch.float32, device=dev); v = torch.empty(n, 3, 3, dtype=torch.float32, device=dev)
@@ -253,17 +261,13 @@ def query_curvature(cfg, theta, x, want_shape=False, chunk=65536):
     gauss = torch.empty(n, dtype=torch.float32, device=dev) if want_shape else None
     shape = torch.empty(n, 3, 3, dtype=torch.float32, device=dev) if want_shape else None
     m = min(max(n, 1), int(chunk))
-    nbytes = int(lib.dudf_workspace_bytes_curvature(ctypes.byref(cfg), m))
-    if nbytes == 0:
-        _lib.check(-1, "dudf_workspace_bytes_curvature")
-    buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    nbytes = _bytes("dudf_workspace_bytes_curvature", ctypes.byref(cfg), m)
+    buf = _scratch(nbytes, dev)
     for s in range(0, n, m):
         e = min(s + m, n)
-        rc = lib.dudf_query_curvature(ctypes.byref(cfg), _ptr(theta), _ptr(x[s:e]), e - s,
-                                      _ptr(lam[s:e]), _ptr(v[s:e]), _ptr(mean[s:e]),
-                                      _ptr(gauss[s:e]) if want_shape else None,
-                                      _ptr(shape[s:e]) if want_shape else None, _ptr(buf), nbytes, _stream())
-        _lib.check(rc, "dudf_query_curvature")
+        _call("dudf_query_curvature", ctypes.byref(cfg), _ptr(theta), _ptr(x[s:e]), e - s, _ptr(lam[s:e]), _ptr(v[s:e]),
+              _ptr(mean[s:e]), _ptr(gauss[s:e]) if want_shape else None, _ptr(shape[s:e]) if want_shape else None, _ptr(buf),
+              nbytes)
     return lam, v, mean, gauss, shape
 
 
@@ -273,39 +277,26 @@ INVERSE_MODES = {"tanh": 0, "siren": 1, "squared": 2}
 def trace_rays(cfg, theta, rays, t0, mask, gt_mode, alpha, surface_threshold, max_iterations, check_every=8, min_step=0.01):
     """The marching loop of reference src/render_st.py:136-161 on the device.  rays (m,3), t0 (m,3) float64 CUDA tensors,
     mask (m,) uint8; t0 and mask are updated in place.  Returns (hits (m,) uint8, iterations executed)."""
-    lib = _lib.load()
     theta = _theta(cfg, theta)
     m = t0.shape[0]
-    for t, dt in ((rays, torch.float64), (t0, torch.float64), (mask, torch.uint8)):
-        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
-            raise _lib.DudfError("trace_rays: rays/t0 must be contiguous float64 CUDA tensors, mask uint8")
+    for name, t, dt in (("rays", rays, torch.float64), ("t0", t0, torch.float64), ("mask", mask, torch.uint8)):
+        _tensor(t, f"trace_rays: {name}", dt)
     hits = torch.empty(m, dtype=torch.uint8, device=t0.device)
     ws = query_workspace_for(cfg, m, t0.device)
     done = ctypes.c_int(0)
-    rc = lib.dudf_trace_rays(ctypes.byref(cfg), _ptr(theta), _ptr(rays), _ptr(t0), _ptr(mask), _ptr(hits), m,
-                             INVERSE_MODES[gt_mode], float(alpha), float(min_step), float(surface_threshold),
-                             int(max_iterations), int(check_every), ctypes.byref(done), _ptr(ws.buf), ws.nbytes, _stream())
-    _lib.check(rc, "dudf_trace_rays")
+    _call("dudf_trace_rays", ctypes.byref(cfg), _ptr(theta), _ptr(rays), _ptr(t0), _ptr(mask), _ptr(hits), m,
+          INVERSE_MODES[gt_mode], float(alpha), float(min_step), float(surface_threshold), int(max_iterations), int(check_every),
+          ctypes.byref(done), _ptr(ws.buf), ws.nbytes)
     return hits, done.value
 
 
 def descend_rays(cfg, theta, t0, hits, gt_mode, alpha, gd_steps, min_step=0.01):
     """`grad_descent` of reference src/render_st.py:163-172 on the device; t0 (m,3) float64 updated in place."""
-    lib = _lib.load()
     theta = _theta(cfg, theta)
     m = t0.shape[0]
     ws = query_workspace_for(cfg, m, t0.device)
-    rc = lib.dudf_descend_rays(ctypes.byref(cfg), _ptr(theta), _ptr(t0), _ptr(hits), m, INVERSE_MODES[gt_mode],
-                               float(alpha), float(min_step), int(gd_steps), _ptr(ws.buf), ws.nbytes, _stream())
-    _lib.check(rc, "dudf_descend_rays")
-
-
-def _f64_dev(t, what, cols=3):
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise _lib.DudfError(f"{what} must be a CUDA tensor (got {getattr(t, 'device', type(t).__name__)}); the HIP path has no CPU fallback")
-    if t.dtype != torch.float64 or not t.is_contiguous() or (cols and (t.dim() != 2 or t.shape[1] != cols)):
-        raise _lib.DudfError(f"{what} must be a contiguous float64 (n,{cols}) tensor; got {t.dtype} {tuple(t.shape)}")
-    return t
+    _call("dudf_descend_rays", ctypes.byref(cfg), _ptr(theta), _ptr(t0), _ptr(hits), m, INVERSE_MODES[gt_mode], float(alpha),
+          float(min_step), int(gd_steps), _ptr(ws.buf), ws.nbytes)
 
 
 def project_points(cfg, theta, points, gt_mode, alpha, num_steps=5, surf_thresh=0.01):
@@ -313,18 +304,14 @@ def project_points(cfg, theta, points, gt_mode, alpha, num_steps=5, surf_thresh=
     `num_steps` projection steps.  Returns (last_step (n,) float64, unit_grad (n,3) float64 = normalize(grad) before the last move,
     pre_pos (n,3) float32 = the position the network saw at the last step, accept (n,) uint8 = in the closed domain after the
     move and last step < surf_thresh)."""
-    lib = _lib.load()
     theta = _theta(cfg, theta)
-    points = _f64_dev(points, "project_points: points")
+    points = _tensor(points, "project_points: points", torch.float64, (3,))
     n, dev = points.shape[0], points.device
     last = torch.empty(n, dtype=torch.float64, device=dev); unit = torch.empty(n, 3, dtype=torch.float64, device=dev)
     pre = torch.empty(n, 3, dtype=torch.float32, device=dev); acc = torch.empty(n, dtype=torch.uint8, device=dev)
     ws = query_workspace_for(cfg, n, dev)
-    with torch.cuda.device(dev):
-        rc = lib.dudf_project_points(ctypes.byref(cfg), _ptr(theta), _ptr(points), n, int(num_steps), INVERSE_MODES[gt_mode],
-                                     float(alpha), float(surf_thresh), _ptr(last), _ptr(unit), _ptr(pre), _ptr(acc), _ptr(ws.buf),
-                                     ws.nbytes, _stream())
-    _lib.check(rc, "dudf_project_points")
+    _call("dudf_project_points", ctypes.byref(cfg), _ptr(theta), _ptr(points), n, int(num_steps), INVERSE_MODES[gt_mode],
+          float(alpha), float(surf_thresh), _ptr(last), _ptr(unit), _ptr(pre), _ptr(acc), _ptr(ws.buf), ws.nbytes, dev=dev)
     return last, unit, pre, acc
 
 
@@ -333,30 +320,28 @@ def pointcloud_append(flags, src_a, dst_a, counter, src_b=None, dst_b=None, src_
     src_b) (n,3) float64 go, in their order, behind row counter[0] of dst_a (dst_b); the flagged rows of src_f (n,3) float32 to
     out_f from row 0.  counter: int64 CUDA tensor of 4 — [0] rows held (advanced), [1] rows added by this call, [2] rows held
     before it.  Nothing is added once counter[0] >= quota (default: never) or when the rows would not fit into dst_a."""
-    lib = _lib.load()
-    if flags.dtype != torch.uint8 or not flags.is_cuda or not flags.is_contiguous():
-        raise _lib.DudfError("pointcloud_append: flags must be a contiguous uint8 CUDA tensor")
+    flags = _tensor(flags, "pointcloud_append: flags", torch.uint8)
     n, dev = flags.shape[0], flags.device
-    src_a = _f64_dev(src_a, "pointcloud_append: src_a"); dst_a = _f64_dev(dst_a, "pointcloud_append: dst_a")
+    src_a = _tensor(src_a, "pointcloud_append: src_a", torch.float64, (3,))
+    dst_a = _tensor(dst_a, "pointcloud_append: dst_a", torch.float64, (3,))
     if (src_b is None) != (dst_b is None) or (src_f is None) != (out_f is None):
         raise _lib.DudfError("pointcloud_append: src_b / dst_b and src_f / out_f come in pairs")
     if src_b is not None:
-        src_b = _f64_dev(src_b, "pointcloud_append: src_b"); dst_b = _f64_dev(dst_b, "pointcloud_append: dst_b")
-    if src_f is not None and (src_f.dtype != torch.float32 or out_f.dtype != torch.float32 or not src_f.is_contiguous()
-                              or not out_f.is_contiguous() or out_f.shape[0] < n or not src_f.is_cuda or not out_f.is_cuda):
-        raise _lib.DudfError("pointcloud_append: src_f / out_f must be contiguous float32 (n,3) CUDA tensors")
-    if counter.dtype != torch.int64 or counter.numel() != 4 or not counter.is_cuda:
+        src_b = _tensor(src_b, "pointcloud_append: src_b", torch.float64, (3,))
+        dst_b = _tensor(dst_b, "pointcloud_append: dst_b", torch.float64, (3,))
+    if src_f is not None:
+        _tensor(src_f, "pointcloud_append: src_f", torch.float32); _tensor(out_f, "pointcloud_append: out_f", torch.float32)
+        if out_f.shape[0] < n:
+            raise _lib.DudfError("pointcloud_append: out_f must have a row for every source row")
+    if _tensor(counter, "pointcloud_append: counter", torch.int64).numel() != 4:
         raise _lib.DudfError("pointcloud_append: counter must be an int64 CUDA tensor of 4")
     if src_a.shape[0] != n or (src_b is not None and (src_b.shape[0] != n or dst_b.shape[0] != dst_a.shape[0])) or \
             (src_f is not None and src_f.shape[0] != n):
         raise _lib.DudfError("pointcloud_append: row counts of flags and sources differ")
-    nbytes = int(lib.dudf_pointcloud_append_workspace_bytes(n))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.dudf_pointcloud_append(_ptr(flags), n, _ptr(src_a), _ptr(src_b), _ptr(src_f), _ptr(dst_a), _ptr(dst_b), _ptr(out_f),
-                                        dst_a.shape[0], (1 << 62) if quota is None else int(quota), _ptr(counter), _ptr(ws), nbytes,
-                                        _stream())
-    _lib.check(rc, "dudf_pointcloud_append")
+    nbytes = _bytes("dudf_pointcloud_append_workspace_bytes", n)
+    ws = _scratch(nbytes, dev)
+    _call("dudf_pointcloud_append", _ptr(flags), n, _ptr(src_a), _ptr(src_b), _ptr(src_f), _ptr(dst_a), _ptr(dst_b), _ptr(out_f),
+          dst_a.shape[0], (1 << 62) if quota is None else int(quota), _ptr(counter), _ptr(ws), nbytes, dev=dev)
 
 
 class PointCloudState:
@@ -364,16 +349,13 @@ class PointCloudState:
     counter and the round workspace."""
 
     def __init__(self, cfg, num_points, device):
-        lib = _lib.load()
         self.cfg, self.num_points = cfg, int(num_points)
         self.capacity = max(2 * self.num_points, 1)
         self.points = torch.zeros(self.capacity, 3, dtype=torch.float64, device=device)
         self.normals = torch.zeros(self.capacity, 3, dtype=torch.float64, device=device)
         self.counter = torch.zeros(4, dtype=torch.int64, device=device)
-        self.nbytes = int(lib.dudf_pointcloud_workspace_bytes(ctypes.byref(cfg), self.num_points))
-        if self.nbytes == 0:
-            _lib.check(-1, "dudf_pointcloud_workspace_bytes")
-        self.buf = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
+        self.nbytes = _bytes("dudf_pointcloud_workspace_bytes", ctypes.byref(cfg), self.num_points)
+        self.buf = _scratch(self.nbytes, device)
         self.rounds = 0
 
     def count(self):
@@ -382,10 +364,8 @@ class PointCloudState:
     def proposals(self):
         """(num_points,3) float64: the rows the last round proposed, before any move (diagnostic; reference :36-39)."""
         out = torch.empty(self.num_points, 3, dtype=torch.float64, device=self.points.device)
-        with torch.cuda.device(self.points.device):
-            rc = _lib.load().dudf_pointcloud_read_proposals(ctypes.byref(self.cfg), self.num_points, _ptr(out), _ptr(self.buf),
-                                                            self.nbytes, _stream())
-        _lib.check(rc, "dudf_pointcloud_read_proposals")
+        _call("dudf_pointcloud_read_proposals", ctypes.byref(self.cfg), self.num_points, _ptr(out), _ptr(self.buf), self.nbytes,
+              dev=self.points.device)
         return out
 
 
@@ -393,23 +373,18 @@ def pointcloud_round(cfg, theta, state, gt_mode, alpha, num_steps=5, surf_thresh
     """One round of reference src/render_pc.py:33-68 on `state` (propose -> project -> ordered append -> normals).  rand: float64
     CUDA tensor with the host-drawn numbers of this round (layout: include/dudf_hip.h) or None for the in-kernel generator keyed by
     (seed, round).  Returns the host copy of the counter [rows held, rows added, rows held before] or None (want_count=False)."""
-    lib = _lib.load()
     theta = _theta(cfg, theta)
     if rand is not None:
-        if rand.dtype != torch.float64 or not rand.is_cuda or not rand.is_contiguous():
-            raise _lib.DudfError("pointcloud_round: rand must be a contiguous float64 CUDA tensor")
+        _tensor(rand, "pointcloud_round: rand", torch.float64)
         half = state.num_points // 2
         if rand.numel() not in (3 * state.num_points, 7 * half):
             raise _lib.DudfError(f"pointcloud_round: rand has {rand.numel()} numbers; a round of {state.num_points} points takes "
                                  f"{3 * state.num_points} (first form) or {7 * half}")
     hc = (ctypes.c_int64 * 4)() if want_count else None
-    with torch.cuda.device(state.points.device):
-        rc = lib.dudf_pointcloud_round(ctypes.byref(cfg), _ptr(theta), state.num_points, int(num_steps), INVERSE_MODES[gt_mode],
-                                       float(alpha), float(surf_thresh), _ptr(rand), 0 if rand is None else rand.numel(), int(seed) & ((1 << 64) - 1),
-                                       state.rounds,
-                                       _ptr(state.points), _ptr(state.normals), state.capacity, _ptr(state.counter), hc,
-                                       _ptr(state.buf), state.nbytes, _stream())
-    _lib.check(rc, "dudf_pointcloud_round")
+    _call("dudf_pointcloud_round", ctypes.byref(cfg), _ptr(theta), state.num_points, int(num_steps), INVERSE_MODES[gt_mode],
+          float(alpha), float(surf_thresh), _ptr(rand), 0 if rand is None else rand.numel(), int(seed) & ((1 << 64) - 1),
+          state.rounds, _ptr(state.points), _ptr(state.normals), state.capacity, _ptr(state.counter), hc, _ptr(state.buf),
+          state.nbytes, dev=state.points.device)
     state.rounds += 1
     return list(hc)[:3] if want_count else None
 
@@ -417,16 +392,13 @@ def pointcloud_round(cfg, theta, state, gt_mode, alpha, num_steps=5, surf_thresh
 def grid_fields(cfg, theta, grid_n, start, count, gt_mode, alpha, out_df, out_vec, ws=None):
     """Fills out_df[start:start+count], out_vec[start:start+count] (device tensors over the flattened N^3 grid);
     returns the device int32 counter of points that need the Hessian-eigenvector fallback."""
-    lib = _lib.load()
     theta = _theta(cfg, theta)
     ws = ws or query_workspace_for(cfg, count, theta.device)
     flag = torch.zeros(1, dtype=torch.int32, device=theta.device)
     df = out_df[start:start + count]
     vec = out_vec[start:start + count]
-    rc = lib.dudf_grid_fields(ctypes.byref(cfg), _ptr(theta), int(grid_n), int(start), int(count),
-                              INVERSE_MODES[gt_mode], float(alpha), _ptr(df), _ptr(vec), _ptr(flag), _ptr(ws.buf),
-                              ws.nbytes, _stream())
-    _lib.check(rc, "dudf_grid_fields")
+    _call("dudf_grid_fields", ctypes.byref(cfg), _ptr(theta), int(grid_n), int(start), int(count), INVERSE_MODES[gt_mode],
+          float(alpha), _ptr(df), _ptr(vec), _ptr(flag), _ptr(ws.buf), ws.nbytes)
     return flag
 
 
@@ -434,28 +406,23 @@ def capudf_extract(ndf, grad, threshold=0.008, want_cells=False):
     """CAP-UDF cell extraction (reference src/render_mc.py:201-256) on device fields ndf (N,N,N), grad (N,N,N,3):
     (vertices (V,3) float64 in [-1,1]^3, triangles (T,3) int64[, cells (C,3) int64]) device tensors.  One host sync
     for the three output sizes."""
-    lib = _lib.load()
-    ndf = _f32(ndf, "ndf"); grad = _f32(grad, "grad")
+    ndf = _tensor(ndf, "ndf", torch.float32, convert=True); grad = _tensor(grad, "grad", torch.float32, convert=True)
     n = ndf.shape[0]
     if ndf.shape != (n, n, n) or grad.shape != (n, n, n, 3):
         raise _lib.DudfError(f"capudf_extract: ndf (N,N,N) and grad (N,N,N,3) expected, got {tuple(ndf.shape)}, {tuple(grad.shape)}")
     dev = ndf.device
-    nbytes = int(lib.dudf_capudf_workspace_bytes(n))
-    if nbytes == 0:
-        _lib.check(-1, "dudf_capudf_workspace_bytes")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    nbytes = _bytes("dudf_capudf_workspace_bytes", n)
+    ws = _scratch(nbytes, dev)
     counts = torch.zeros(3, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.dudf_capudf_count(_ptr(ndf), _ptr(grad), n, float(threshold), _ptr(counts), _ptr(ws), nbytes, _stream())
-        _lib.check(rc, "dudf_capudf_count")
+        _call("dudf_capudf_count", _ptr(ndf), _ptr(grad), n, float(threshold), _ptr(counts), _ptr(ws), nbytes)
         nc, nv, nt = [int(v) for v in counts.tolist()]
         verts = torch.empty(nv, 3, dtype=torch.float64, device=dev)
         tris = torch.empty(nt, 3, dtype=torch.int64, device=dev)
         cells = torch.empty(nc, 3, dtype=torch.int64, device=dev) if want_cells else None
         if nc:
-            rc = lib.dudf_capudf_emit(_ptr(ndf), _ptr(grad), n, float(threshold), _ptr(verts), _ptr(tris), _ptr(cells),
-                                      _ptr(ws), nbytes, _stream())
-            _lib.check(rc, "dudf_capudf_emit")
+            _call("dudf_capudf_emit", _ptr(ndf), _ptr(grad), n, float(threshold), _ptr(verts), _ptr(tris), _ptr(cells), _ptr(ws),
+                  nbytes)
     return (verts, tris, cells) if want_cells else (verts, tris)
 
 
@@ -467,56 +434,44 @@ def _w4(weights):
 def loss_forward(cfg, mode, theta, x, normals, sdf, n_global, weights, alpha, ws, n_hess=0, out=None):
     """n_hess > 0 (loss_s1 with a Hessian weight): the first n_hess points must be exactly the on-surface ones.
     `out`: a contiguous float32 tensor of 4 to receive the terms (no extra copy kernel in the training loop)."""
-    lib = _lib.load()
-    _check_theta(cfg, theta)
+    _theta(cfg, theta, convert=False)
     n = x.shape[0]
     terms = out if out is not None else torch.empty(4, dtype=torch.float32, device=x.device)
-    rc = lib.dudf_loss_forward(ctypes.byref(cfg), mode, _ptr(theta), _ptr(x), _ptr(normals), _ptr(sdf), n,
-                               int(n_global), int(n_hess), _w4(weights), float(alpha), _ptr(terms), _ptr(ws.buf),
-                               ws.nbytes, _stream())
-    _lib.check(rc, "dudf_loss_forward")
+    _call("dudf_loss_forward", ctypes.byref(cfg), mode, _ptr(theta), _ptr(x), _ptr(normals), _ptr(sdf), n, int(n_global),
+          int(n_hess), _w4(weights), float(alpha), _ptr(terms), _ptr(ws.buf), ws.nbytes)
     return terms
 
 
 def s2_forward_stats(cfg, theta, x, sdf, ws):
-    lib = _lib.load()
-    _check_theta(cfg, theta)
+    _theta(cfg, theta, convert=False)
     stats = torch.empty(3, dtype=torch.float64, device=x.device)
-    rc = lib.dudf_s2_forward_stats(ctypes.byref(cfg), _ptr(theta), _ptr(x), _ptr(sdf), x.shape[0], _ptr(stats),
-                                   _ptr(ws.buf), ws.nbytes, _stream())
-    _lib.check(rc, "dudf_s2_forward_stats")
+    _call("dudf_s2_forward_stats", ctypes.byref(cfg), _ptr(theta), _ptr(x), _ptr(sdf), x.shape[0], _ptr(stats), _ptr(ws.buf),
+          ws.nbytes)
     return stats
 
 
 def s2_terms(stats, weights):
-    lib = _lib.load()
     terms = torch.empty(2, dtype=torch.float32, device=stats.device)
-    rc = lib.dudf_s2_terms(_ptr(stats), _w4(weights), _ptr(terms), _stream())
-    _lib.check(rc, "dudf_s2_terms")
+    _call("dudf_s2_terms", _ptr(stats), _w4(weights), _ptr(terms))
     return terms
 
 
 def loss_backward(cfg, mode, theta, x, normals, sdf, n_global, weights, alpha, cot, stats, ws, dtheta=None,
                   accumulate=False, n_hess=0):
-    lib = _lib.load()
     if dtheta is None:
         dtheta = torch.empty_like(theta)
         accumulate = False
-    rc = lib.dudf_loss_backward(ctypes.byref(cfg), mode, _ptr(theta), _ptr(x), _ptr(normals), _ptr(sdf), x.shape[0],
-                                int(n_global), int(n_hess), _w4(weights), float(alpha), _ptr(cot), _ptr(stats),
-                                _ptr(dtheta), 1 if accumulate else 0, _ptr(ws.buf), ws.nbytes, _stream())
-    _lib.check(rc, "dudf_loss_backward")
+    _call("dudf_loss_backward", ctypes.byref(cfg), mode, _ptr(theta), _ptr(x), _ptr(normals), _ptr(sdf), x.shape[0], int(n_global),
+          int(n_hess), _w4(weights), float(alpha), _ptr(cot), _ptr(stats), _ptr(dtheta), 1 if accumulate else 0, _ptr(ws.buf),
+          ws.nbytes)
     return dtheta
 
 
 def loss_backward_sweeps(cfg, mode, theta, normals, sdf, n_global, weights, alpha, cot, stats, ws, n_local, n_hess=0):
     """loss cotangents + adjoint sweeps; the weight gradients follow through `weight_gradient` (layer ranges)."""
-    lib = _lib.load()
-    _check_theta(cfg, theta)
-    rc = lib.dudf_loss_backward_sweeps(ctypes.byref(cfg), mode, _ptr(theta), _ptr(normals), _ptr(sdf), int(n_local), int(n_global),
-                                       int(n_hess), _w4(weights), float(alpha), _ptr(cot), _ptr(stats), _ptr(ws.buf), ws.nbytes,
-                                       _stream())
-    _lib.check(rc, "dudf_loss_backward_sweeps")
+    _theta(cfg, theta, convert=False)
+    _call("dudf_loss_backward_sweeps", ctypes.byref(cfg), mode, _ptr(theta), _ptr(normals), _ptr(sdf), int(n_local), int(n_global),
+          int(n_hess), _w4(weights), float(alpha), _ptr(cot), _ptr(stats), _ptr(ws.buf), ws.nbytes)
 
 
 def layer_slices(cfg):
@@ -530,34 +485,27 @@ def layer_slices(cfg):
 
 
 def weight_gradient(cfg, n_local, have_g, layer_begin, layer_end, dtheta, ws, accumulate=False, n_hess=0):
-    lib = _lib.load()
-    rc = lib.dudf_weight_gradient(ctypes.byref(cfg), int(n_local), int(n_hess), 1 if have_g else 0, int(layer_begin),
-                                  int(layer_end), _ptr(dtheta), 1 if accumulate else 0, _ptr(ws.buf), ws.nbytes, _stream())
-    _lib.check(rc, "dudf_weight_gradient")
+    _call("dudf_weight_gradient", ctypes.byref(cfg), int(n_local), int(n_hess), 1 if have_g else 0, int(layer_begin),
+          int(layer_end), _ptr(dtheta), 1 if accumulate else 0, _ptr(ws.buf), ws.nbytes)
 
 
 def fields_forward(cfg, theta, x, ws):
     """(f (n,), df/dx (n,3)) with the training stash kept in ws (for fields_backward)."""
-    lib = _lib.load()
-    _check_theta(cfg, theta)
+    _theta(cfg, theta, convert=False)
     n = x.shape[0]
     f = torch.empty(n, dtype=torch.float32, device=x.device)
     g = torch.empty(n, 3, dtype=torch.float32, device=x.device)
-    rc = lib.dudf_fields_forward(ctypes.byref(cfg), _ptr(theta), _ptr(x), n, _ptr(f), _ptr(g), _ptr(ws.buf),
-                                 ws.nbytes, _stream())
-    _lib.check(rc, "dudf_fields_forward")
+    _call("dudf_fields_forward", ctypes.byref(cfg), _ptr(theta), _ptr(x), n, _ptr(f), _ptr(g), _ptr(ws.buf), ws.nbytes)
     return f, g
 
 
 def fields_backward(cfg, theta, x, ybar, gbar, ws, dtheta=None, accumulate=False):
-    lib = _lib.load()
-    _check_theta(cfg, theta)
+    _theta(cfg, theta, convert=False)
     if dtheta is None:
         dtheta = torch.empty_like(theta)
         accumulate = False
-    rc = lib.dudf_fields_backward(ctypes.byref(cfg), _ptr(theta), _ptr(x), x.shape[0], _ptr(ybar), _ptr(gbar),
-                                  _ptr(dtheta), 1 if accumulate else 0, _ptr(ws.buf), ws.nbytes, _stream())
-    _lib.check(rc, "dudf_fields_backward")
+    _call("dudf_fields_backward", ctypes.byref(cfg), _ptr(theta), _ptr(x), x.shape[0], _ptr(ybar), _ptr(gbar), _ptr(dtheta),
+          1 if accumulate else 0, _ptr(ws.buf), ws.nbytes)
     return dtheta
 
 
@@ -567,44 +515,35 @@ def set_wgrad_max_workgroups(n):
 
 
 def adam_step(theta, dtheta, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
-    lib = _lib.load()
-    rc = lib.dudf_adam_step(_ptr(theta), _ptr(dtheta), _ptr(exp_avg), _ptr(exp_avg_sq), theta.numel(), float(lr),
-                            float(beta1), float(beta2), float(eps), int(step), float(grad_scale), _stream())
-    _lib.check(rc, "dudf_adam_step")
+    _call("dudf_adam_step", _ptr(theta), _ptr(dtheta), _ptr(exp_avg), _ptr(exp_avg_sq), theta.numel(), float(lr), float(beta1),
+          float(beta2), float(eps), int(step), float(grad_scale))
 
 
 def adam_schedule(lrs, first_step=1, beta1=0.9, beta2=0.999):
     """HOST table (len(lrs), 2) float32 of (lr / (1 - beta1^t), sqrt(1 - beta2^t)), t = first_step + i: the two step-dependent
     scalars `adam_step` derives on the host, for `adam_step_scheduled` (dudf_adam_schedule: host only, no GPU work)."""
     import numpy as np
-    lib = _lib.load()
     lr = np.ascontiguousarray(lrs, dtype=np.float64)
     out = np.empty((lr.size, 2), dtype=np.float32)
-    rc = lib.dudf_adam_schedule(lr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), lr.size, int(first_step), float(beta1),
-                                float(beta2), ctypes.c_void_p(out.ctypes.data))
-    _lib.check(rc, "dudf_adam_schedule")
+    _call("dudf_adam_schedule", lr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), lr.size, int(first_step), float(beta1),
+          float(beta2), ctypes.c_void_p(out.ctypes.data), stream=False)
     return out
 
 
 def adam_step_scheduled(theta, dtheta, exp_avg, exp_avg_sq, sched, row, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
     """`adam_step` with (lr, step) replaced by row `row[0]` (device int64, NOT advanced here) of the device table `sched`
     (`adam_schedule(...)` uploaded): graph-replayable."""
-    lib = _lib.load()
     assert sched.dtype == torch.float32 and sched.is_contiguous() and sched.shape[-1] == 2 and row.dtype == torch.int64
-    rc = lib.dudf_adam_step_scheduled(_ptr(theta), _ptr(dtheta), _ptr(exp_avg), _ptr(exp_avg_sq), theta.numel(), float(beta1),
-                                      float(beta2), float(eps), _ptr(sched), sched.shape[0], _ptr(row), float(grad_scale), _stream())
-    _lib.check(rc, "dudf_adam_step_scheduled")
+    _call("dudf_adam_step_scheduled", _ptr(theta), _ptr(dtheta), _ptr(exp_avg), _ptr(exp_avg_sq), theta.numel(), float(beta1),
+          float(beta2), float(eps), _ptr(sched), sched.shape[0], _ptr(row), float(grad_scale))
 
 
 def read_stash(cfg, which, layer, n, ws, channel=0):
     """Diagnostic: (n,H) copy of one stashed quantity of hidden layer `layer` (channel 1..3 = tangent d/dx_k,
     Hessian-path points only)."""
-    lib = _lib.load()
     idx = {"s": 0, "c": 1, "q": 2, "e": 3, "A": 4, "zbar": 5, "r": 6, "zs": 7}[which]
     out = torch.empty(n, cfg.hidden, dtype=torch.float32, device=ws.buf.device)
-    rc = lib.dudf_debug_read_stash(ctypes.byref(cfg), idx, layer, channel, n, ws.n_hess, _ptr(out), _ptr(ws.buf),
-                                   ws.nbytes, _stream())
-    _lib.check(rc, "dudf_debug_read_stash")
+    _call("dudf_debug_read_stash", ctypes.byref(cfg), idx, layer, channel, n, ws.n_hess, _ptr(out), _ptr(ws.buf), ws.nbytes)
     return out
 
 
@@ -622,7 +561,6 @@ def _dbl(values, n, what):
 def render_setup_rays(width, height, fov, noise, rotation, camera_position, planes, device):
     """`dudf_render_setup_rays`: rays (m,3), t0 (m,3) float64 and mask (m,) uint8 on `device` for the width * height pixels of
     `get_pixels_camera(width, height, fov, noise)` — reference generate_st.py:41-101.  rotation: the 3x3 of :49-61 (host)."""
-    lib = _lib.load()
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.DudfError(f"render_setup_rays: device must be a GPU (got {dev}); the HIP path has no CPU fallback")
@@ -630,42 +568,29 @@ def render_setup_rays(width, height, fov, noise, rotation, camera_position, plan
     rays = torch.empty(m, 3, dtype=torch.float64, device=dev); t0 = torch.empty(m, 3, dtype=torch.float64, device=dev)
     mask = torch.empty(m, dtype=torch.uint8, device=dev)
     rot = _dbl([v for row in rotation for v in row], 9, "rotation")
-    with torch.cuda.device(dev):
-        rc = lib.dudf_render_setup_rays(int(width), int(height), float(fov), float(noise), rot, _dbl(camera_position, 3, "camera_position"),
-                                        _dbl(planes, 6, "planes"), _ptr(rays), _ptr(t0), _ptr(mask), _stream())
-    _lib.check(rc, "dudf_render_setup_rays")
+    _call("dudf_render_setup_rays", int(width), int(height), float(fov), float(noise), rot,
+          _dbl(camera_position, 3, "camera_position"), _dbl(planes, 6, "planes"), _ptr(rays), _ptr(t0), _ptr(mask), dev=dev)
     return rays, t0, mask
-
-
-def _u8_dev(t, what):
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise _lib.DudfError(f"{what} must be a CUDA tensor (got {getattr(t, 'device', type(t).__name__)}); the HIP path has no CPU fallback")
-    if t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 1:
-        raise _lib.DudfError(f"{what} must be a contiguous uint8 vector; got {t.dtype} {tuple(t.shape)}")
-    return t
 
 
 def render_gather(hits, t0, rays=None):
     """`t0[hits]`, `rays[hits]` and the ray index of every gathered row (`dudf_render_gather`).  Returns (pos (k,3), rays (k,3) or
     None, rows (k,) int32, k); k is the ONE host read of a pass."""
-    lib = _lib.load()
-    hits = _u8_dev(hits, "render_gather: hits")
-    t0 = _f64_dev(t0, "render_gather: t0")
+    hits = _tensor(hits, "render_gather: hits", torch.uint8, ())
+    t0 = _tensor(t0, "render_gather: t0", torch.float64, (3,))
     m, dev = hits.shape[0], hits.device
     if rays is not None:
-        rays = _f64_dev(rays, "render_gather: rays")
+        rays = _tensor(rays, "render_gather: rays", torch.float64, (3,))
     if t0.shape[0] != m or (rays is not None and rays.shape[0] != m):
         raise _lib.DudfError("render_gather: row counts of hits, t0 and rays differ")
     pos = torch.empty(m, 3, dtype=torch.float64, device=dev)
     hr = torch.empty(m, 3, dtype=torch.float64, device=dev) if rays is not None else None
     rows = torch.empty(m, dtype=torch.int32, device=dev)
     counter = torch.empty(4, dtype=torch.int64, device=dev)
-    nbytes = int(lib.dudf_pointcloud_append_workspace_bytes(m))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.dudf_render_gather(_ptr(hits), m, _ptr(t0), _ptr(rays), _ptr(pos), _ptr(hr), _ptr(rows), _ptr(counter), _ptr(ws), nbytes,
-                                    _stream())
-    _lib.check(rc, "dudf_render_gather")
+    nbytes = _bytes("dudf_pointcloud_append_workspace_bytes", m)
+    ws = _scratch(nbytes, dev)
+    _call("dudf_render_gather", _ptr(hits), m, _ptr(t0), _ptr(rays), _ptr(pos), _ptr(hr), _ptr(rows), _ptr(counter), _ptr(ws),
+          nbytes, dev=dev)
     k = int(counter[1].item())
     return pos[:k], (hr[:k] if hr is not None else None), rows[:k], k
 
@@ -674,28 +599,25 @@ def render_orient(hit_rays, frame_v=None, grad=None, mean=None, want_pc=False):
     """Normals of k hits (`dudf_render_orient`, reference src/render_st.py:80-83, :101-108): from the eigen-frame `frame_v` (k,3,3),
     oriented against the rays (`mean` (k,) float32 is multiplied in place by the same alignment), or from `grad` (k,3) ('siren').
     Returns (normals (k,3) float64, pc1, pc2 (k,3) float64 or None)."""
-    lib = _lib.load()
     src = frame_v if frame_v is not None else grad
     if src is None or (frame_v is not None and grad is not None):
         raise _lib.DudfError("render_orient: exactly one of frame_v / grad")
-    src = _f32(src, "render_orient: frame_v / grad")
+    src = _tensor(src, "render_orient: frame_v / grad", torch.float32, convert=True)
     k, dev = src.shape[0], src.device
     if frame_v is not None:
-        hit_rays = _f64_dev(hit_rays, "render_orient: hit_rays")
+        hit_rays = _tensor(hit_rays, "render_orient: hit_rays", torch.float64, (3,))
         if tuple(src.shape) != (k, 3, 3) or hit_rays.shape[0] != k:
             raise _lib.DudfError(f"render_orient: frame_v must be (k,3,3) with k rays; got {tuple(src.shape)}, {tuple(hit_rays.shape)}")
-        if mean is not None and (mean.dtype != torch.float32 or not mean.is_cuda or not mean.is_contiguous() or mean.numel() != k):
-            raise _lib.DudfError("render_orient: mean must be a contiguous float32 CUDA vector of k")
+        if mean is not None and _tensor(mean, "render_orient: mean", torch.float32).numel() != k:
+            raise _lib.DudfError("render_orient: mean must be a float32 vector of k")
     elif tuple(src.shape) != (k, 3):
         raise _lib.DudfError(f"render_orient: grad must be (k,3); got {tuple(src.shape)}")
     normals = torch.empty(k, 3, dtype=torch.float64, device=dev)
     pc1 = torch.empty(k, 3, dtype=torch.float64, device=dev) if want_pc and frame_v is not None else None
     pc2 = torch.empty(k, 3, dtype=torch.float64, device=dev) if want_pc and frame_v is not None else None
-    with torch.cuda.device(dev):
-        rc = lib.dudf_render_orient(_ptr(src) if frame_v is not None else None, _ptr(src) if frame_v is None else None,
-                                    _ptr(hit_rays) if frame_v is not None else None, k, _ptr(normals), _ptr(pc1), _ptr(pc2),
-                                    _ptr(mean) if frame_v is not None else None, _stream())
-    _lib.check(rc, "dudf_render_orient")
+    _call("dudf_render_orient", _ptr(src) if frame_v is not None else None, _ptr(src) if frame_v is None else None,
+          _ptr(hit_rays) if frame_v is not None else None, k, _ptr(normals), _ptr(pc1), _ptr(pc2),
+          _ptr(mean) if frame_v is not None else None, dev=dev)
     return normals, pc1, pc2
 
 
@@ -719,17 +641,14 @@ def render_percentile_bounds(curvatures, q_low, q_high):
 
 def render_colormap(curvatures, bounds, lut):
     """(k,3) float64 colours of k float32 curvatures (`dudf_render_colormap`, reference src/render_st.py:111-114)."""
-    lib = _lib.load()
-    curvatures = _f32(curvatures, "render_colormap: curvatures").reshape(-1)
-    bounds = _f32(bounds, "render_colormap: bounds")
-    lut = _f64_dev(lut, "render_colormap: lut")
+    curvatures = _tensor(curvatures, "render_colormap: curvatures", torch.float32, convert=True).reshape(-1)
+    bounds = _tensor(bounds, "render_colormap: bounds", torch.float32, convert=True)
+    lut = _tensor(lut, "render_colormap: lut", torch.float64, (3,))
     if tuple(lut.shape) != (256, 3) or bounds.numel() != 2:
         raise _lib.DudfError(f"render_colormap: lut must be (256,3) and bounds 2 floats; got {tuple(lut.shape)}, {bounds.numel()}")
     k = curvatures.shape[0]
     out = torch.empty(k, 3, dtype=torch.float64, device=curvatures.device)
-    with torch.cuda.device(curvatures.device):
-        rc = lib.dudf_render_colormap(_ptr(curvatures), k, _ptr(bounds), _ptr(lut), _ptr(out), _stream())
-    _lib.check(rc, "dudf_render_colormap")
+    _call("dudf_render_colormap", _ptr(curvatures), k, _ptr(bounds), _ptr(lut), _ptr(out), dev=curvatures.device)
     return out
 
 
@@ -737,16 +656,14 @@ def render_shade(model, hits, rows, hit_pos, normals, accumulator, light_positio
                  alpha2=0.0, pc1=None, pc2=None, color_map=None):
     """`dudf_render_shade`: accumulator (m,3) float64 += phong / ward colours of the k hits at their image rows, += 1 elsewhere
     (reference src/render_st.py:174-245)."""
-    lib = _lib.load()
     if model not in SHADE_MODELS:
         raise _lib.DudfError(f"reflection_method must be one of {sorted(SHADE_MODELS)}; got {model!r}")
-    hits = _u8_dev(hits, "render_shade: hits")
-    accumulator = _f64_dev(accumulator, "render_shade: accumulator")
+    hits = _tensor(hits, "render_shade: hits", torch.uint8, ())
+    accumulator = _tensor(accumulator, "render_shade: accumulator", torch.float64, (3,))
     m, k = hits.shape[0], rows.shape[0]
     if accumulator.shape[0] != m:
         raise _lib.DudfError("render_shade: accumulator must have one row per ray")
-    if rows.dtype != torch.int32 or not rows.is_cuda or not rows.is_contiguous():
-        raise _lib.DudfError("render_shade: rows must be a contiguous int32 CUDA vector")
+    _tensor(rows, "render_shade: rows", torch.int32)
     arrs = [("hit_pos", hit_pos), ("normals", normals)]
     if model == "ward":
         if pc1 is None or pc2 is None or camera_position is None:
@@ -755,25 +672,19 @@ def render_shade(model, hits, rows, hit_pos, normals, accumulator, light_positio
     if color_map is not None:
         arrs.append(("color_map", color_map))
     for name, t in arrs:
-        if _f64_dev(t, f"render_shade: {name}").shape[0] != k:
+        if _tensor(t, f"render_shade: {name}", torch.float64, (3,)).shape[0] != k:
             raise _lib.DudfError(f"render_shade: {name} has {t.shape[0]} rows for {k} hits")
-    with torch.cuda.device(hits.device):
-        rc = lib.dudf_render_shade(SHADE_MODELS[model], _ptr(hits), m, _ptr(rows), k, _ptr(hit_pos), _ptr(normals), _ptr(pc1), _ptr(pc2),
-                                   _ptr(color_map), _dbl(light_position, 3, "light_position"),
-                                   _dbl(camera_position, 3, "camera_position") if camera_position is not None else None,
-                                   float(shininess), float(alpha1), float(alpha2), _ptr(accumulator), _stream())
-    _lib.check(rc, "dudf_render_shade")
+    _call("dudf_render_shade", SHADE_MODELS[model], _ptr(hits), m, _ptr(rows), k, _ptr(hit_pos), _ptr(normals), _ptr(pc1),
+          _ptr(pc2), _ptr(color_map), _dbl(light_position, 3, "light_position"),
+          _dbl(camera_position, 3, "camera_position") if camera_position is not None else None, float(shininess), float(alpha1),
+          float(alpha2), _ptr(accumulator), dev=hits.device)
 
 
 def render_finish(accumulator, sample_rate):
     """uint8 tensor of accumulator's shape: `(colores / sample_rate * 255).astype(np.uint8)` (reference generate_st.py:139)."""
-    lib = _lib.load()
-    if not torch.is_tensor(accumulator) or not accumulator.is_cuda or accumulator.dtype != torch.float64 or not accumulator.is_contiguous():
-        raise _lib.DudfError("render_finish: accumulator must be a contiguous float64 CUDA tensor")
+    _tensor(accumulator, "render_finish: accumulator", torch.float64)
     out = torch.empty(accumulator.shape, dtype=torch.uint8, device=accumulator.device)
-    with torch.cuda.device(accumulator.device):
-        rc = lib.dudf_render_finish(_ptr(accumulator), accumulator.numel(), float(sample_rate), _ptr(out), _stream())
-    _lib.check(rc, "dudf_render_finish")
+    _call("dudf_render_finish", _ptr(accumulator), accumulator.numel(), float(sample_rate), _ptr(out), dev=accumulator.device)
     return out
 
 
@@ -835,85 +746,61 @@ def render_pass(cfg, theta, noise, rotation, camera_position, network_config, re
 
 
 # ---- Chamfer distance / normal consistency (reference cuantitative.py:10-19, :99-100; csrc/dudf_chamfer.hip) -------------------
-def _rows3(t, what, dtype):
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise _lib.DudfError(f"{what} must be a CUDA tensor (got {getattr(t, 'device', type(t).__name__)}); the HIP path has no CPU fallback")
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise _lib.DudfError(f"{what} must have shape (n,3); got {tuple(t.shape)}")
-    return t.to(dtype).contiguous()
-
-
-def _scratch(nbytes, device):
-    buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-    assert buf.data_ptr() % 256 == 0
-    return buf
-
-
 def nearest_points(x, y, norm=2, want_dist=True, want_idx=True):
     """For every row of x (n,3) the nearest row of y (m,3) — `knn_points(x, y, norm=norm, K=1)` of pytorch3d: (dist (n,) float32,
     idx (n,) int64).  norm 2: SQUARED Euclidean distance; norm 1: L1 distance.  Smallest index among ties; bit-reproducible."""
-    lib = _lib.load()
-    x = _rows3(x, "nearest_points: x", torch.float32); y = _rows3(y, "nearest_points: y", torch.float32)
+    x = _tensor(x, "nearest_points: x", torch.float32, (3,), convert=True); y = _tensor(y, "nearest_points: y", torch.float32, (3,), convert=True)
     if y.device != x.device:
         raise _lib.DudfError("nearest_points: x and y live on different devices")
     n, m, dev = x.shape[0], y.shape[0], x.device
     dist = torch.empty(n, dtype=torch.float32, device=dev) if want_dist else None
     idx = torch.empty(n, dtype=torch.int64, device=dev) if want_idx else None
-    nbytes = int(lib.dudf_nearest_workspace_bytes(n))
+    nbytes = _bytes("dudf_nearest_workspace_bytes", n)
     ws = _scratch(nbytes, dev)
-    with torch.cuda.device(dev):
-        rc = lib.dudf_nearest_points(_ptr(x), n, _ptr(y), m, int(norm), _ptr(dist), _ptr(idx), _ptr(ws), nbytes, _stream())
-    _lib.check(rc, "dudf_nearest_points")
+    _call("dudf_nearest_points", _ptr(x), n, _ptr(y), m, int(norm), _ptr(dist), _ptr(idx), _ptr(ws), nbytes, dev=dev)
     return dist, idx
 
 
 def chamfer_terms(dist, idx, x_normals=None, y_normals=None, out=None):
     """(2,) float64 CUDA tensor: sum of dist and sum of 1 - |cos(x_normals[p], y_normals[idx[p]])| (the second stays 0 without
     normals).  Double accumulation in a fixed order: bit-reproducible."""
-    lib = _lib.load()
-    if not torch.is_tensor(dist) or not dist.is_cuda or dist.dtype != torch.float32 or dist.dim() != 1 or not dist.is_contiguous():
-        raise _lib.DudfError("chamfer_terms: dist must be a contiguous float32 (n,) CUDA tensor")
+    _tensor(dist, "chamfer_terms: dist", torch.float32, ())
     n, dev, m = dist.shape[0], dist.device, 0
     if (x_normals is None) != (y_normals is None):
         raise _lib.DudfError("chamfer_terms: x_normals and y_normals come together")
     if x_normals is not None:
-        x_normals = _rows3(x_normals, "chamfer_terms: x_normals", torch.float32)
-        y_normals = _rows3(y_normals, "chamfer_terms: y_normals", torch.float32)
-        if idx is None or idx.dtype != torch.int64 or idx.shape != dist.shape or not idx.is_cuda or not idx.is_contiguous():
-            raise _lib.DudfError("chamfer_terms: idx must be a contiguous int64 (n,) CUDA tensor")
+        x_normals = _tensor(x_normals, "chamfer_terms: x_normals", torch.float32, (3,), convert=True)
+        y_normals = _tensor(y_normals, "chamfer_terms: y_normals", torch.float32, (3,), convert=True)
+        if _tensor(idx, "chamfer_terms: idx", torch.int64, ()).shape != dist.shape:
+            raise _lib.DudfError("chamfer_terms: idx must have one entry per distance")
         if x_normals.shape[0] != n:
             raise _lib.DudfError("chamfer_terms: x_normals must have one row per distance")
         m = y_normals.shape[0]
     if out is None:
         out = torch.zeros(2, dtype=torch.float64, device=dev)
-    elif out.dtype != torch.float64 or out.numel() != 2 or not out.is_cuda or not out.is_contiguous():
-        raise _lib.DudfError("chamfer_terms: out must be a contiguous float64 CUDA tensor of 2")
-    nbytes = int(lib.dudf_chamfer_terms_workspace_bytes(n))
+    elif _tensor(out, "chamfer_terms: out", torch.float64).numel() != 2:
+        raise _lib.DudfError("chamfer_terms: out must be a float64 tensor of 2")
+    nbytes = _bytes("dudf_chamfer_terms_workspace_bytes", n)
     ws = _scratch(nbytes, dev)
-    with torch.cuda.device(dev):
-        rc = lib.dudf_chamfer_terms(_ptr(dist), _ptr(idx) if x_normals is not None else _ptr(None), n, _ptr(x_normals), _ptr(y_normals),
-                                    m, _ptr(out), _ptr(ws), nbytes, _stream())
-    _lib.check(rc, "dudf_chamfer_terms")
+    _call("dudf_chamfer_terms", _ptr(dist), _ptr(idx) if x_normals is not None else _ptr(None), n, _ptr(x_normals),
+          _ptr(y_normals), m, _ptr(out), _ptr(ws), nbytes, dev=dev)
     return out
 
 
 def vertex_normals(vertices, faces):
     """(V,3) float32 area-weighted unit vertex normals of a triangle mesh — open3d's `compute_vertex_normals(normalized=True)`
     (reference cuantitative.py:99-100).  vertices (V,3) float64 and faces (F,3) int64 CUDA tensors (other dtypes are converted)."""
-    lib = _lib.load()
-    vertices = _rows3(vertices, "vertex_normals: vertices", torch.float64)
+    vertices = _tensor(vertices, "vertex_normals: vertices", torch.float64, (3,), convert=True)
     if torch.is_tensor(faces) and faces.numel() == 0:
         faces = faces.reshape(0, 3)
-    faces = _rows3(faces, "vertex_normals: faces", torch.int64)
+    faces = _tensor(faces, "vertex_normals: faces", torch.int64, (3,), convert=True)
     if faces.device != vertices.device:
         raise _lib.DudfError("vertex_normals: vertices and faces live on different devices")
     nv, nf, dev = vertices.shape[0], faces.shape[0], vertices.device
     out = torch.empty(nv, 3, dtype=torch.float32, device=dev)
-    nbytes = int(lib.dudf_vertex_normals_workspace_bytes(nv))
+    nbytes = _bytes("dudf_vertex_normals_workspace_bytes", nv)
     ws = _scratch(nbytes, dev)
-    with torch.cuda.device(dev):
-        rc = lib.dudf_vertex_normals(_ptr(vertices), nv, _ptr(faces), nf, _ptr(out), _ptr(ws), nbytes, _stream())
-    _lib.check(rc, "dudf_vertex_normals")
+    _call("dudf_vertex_normals", _ptr(vertices), nv, _ptr(faces), nf, _ptr(out), _ptr(ws), nbytes, dev=dev)
     return out
 
 
@@ -921,38 +808,27 @@ def vertex_normals(vertices, faces):
 MESH_INDEX_FLAGS_OFFSET, MESH_FLAG_NONFINITE, MESH_FLAG_BAD_ORDER = 24, 1, 2       # include/dudf_hip.h
 
 
-def _soup(tri, what):
-    if not torch.is_tensor(tri) or tri.device.type != "cuda":
-        raise _lib.DudfError(f"{what} must be a CUDA tensor (got {getattr(tri, 'device', type(tri).__name__)}); the HIP path has no CPU fallback")
-    if tri.dim() != 2 or tri.shape[1] != 9:
-        raise _lib.DudfError(f"{what} must have shape (T,9); got {tuple(tri.shape)}")
-    return tri.to(torch.float32).contiguous()
-
-
 def mesh_index_build(tri, order=None):
     """Index of a triangle soup tri (T,9) float32 for `mesh_distance`: a uint8 CUDA tensor.  Morton codes on the device, a stable
     `torch.sort`, then the boxes level by level; one host read at the end (the flag word).  ValueError for a NaN / infinite vertex.
     order (T,) int64: a permutation of the triangles to build the leaves from instead of the Morton order (any permutation gives
     the same answers, more slowly)."""
-    lib = _lib.load()
-    tri = _soup(tri, "mesh_index_build: tri")
+    tri = _tensor(tri, "mesh_index_build: tri", torch.float32, (9,), convert=True)
     T, dev = tri.shape[0], tri.device
     if T == 0:
         raise _lib.DudfError("mesh_index_build: a mesh without triangles has no index (DUDF_E_BADCFG)")
-    nbytes = int(lib.dudf_mesh_index_bytes(T))
-    if nbytes == 0:
-        _lib.check(-4, "dudf_mesh_index_bytes")
+    nbytes = _bytes("dudf_mesh_index_bytes", T, err=-4)
     index = torch.zeros(nbytes, dtype=torch.uint8, device=dev)     # zeros: the padding between the sections is part of "same bytes"
     assert index.data_ptr() % 256 == 0
     with torch.cuda.device(dev):
         if order is None:
             codes = torch.empty(T, dtype=torch.int64, device=dev)
-            _lib.check(lib.dudf_mesh_morton_codes(_ptr(tri), T, _ptr(index), nbytes, _ptr(codes), _stream()), "dudf_mesh_morton_codes")
+            _call("dudf_mesh_morton_codes", _ptr(tri), T, _ptr(index), nbytes, _ptr(codes))
             order = torch.sort(codes, stable=True).indices
         elif not torch.is_tensor(order) or order.device != dev or order.dtype != torch.int64 or order.shape != (T,):
             raise _lib.DudfError("mesh_index_build: order must be an int64 (T,) CUDA tensor on the device of tri")
         order = order.contiguous()
-        _lib.check(lib.dudf_mesh_index_build(_ptr(tri), T, _ptr(order), _ptr(index), nbytes, _stream()), "dudf_mesh_index_build")
+        _call("dudf_mesh_index_build", _ptr(tri), T, _ptr(order), _ptr(index), nbytes)
     flags = int(index[MESH_INDEX_FLAGS_OFFSET:MESH_INDEX_FLAGS_OFFSET + 4].view(torch.int32).item())
     if flags & MESH_FLAG_NONFINITE:
         raise ValueError("mesh_index_build: the mesh has a NaN or infinite vertex")
@@ -966,9 +842,8 @@ def mesh_distance(tri, index, points, want_idx=False, want_closest=False, stats=
     the soup tri (T,9), the nearest triangle (smallest index among ties) and the closest point on it.  index: what
     `mesh_index_build(tri)` returned, or None for the brute-force scan (same bits).  stats: int64 CUDA tensor of 1, the number of
     exact triangle evaluations is ADDED to it."""
-    lib = _lib.load()
-    tri = _soup(tri, "mesh_distance: tri")
-    points = _rows3(points, "mesh_distance: points", torch.float32)
+    tri = _tensor(tri, "mesh_distance: tri", torch.float32, (9,), convert=True)
+    points = _tensor(points, "mesh_distance: points", torch.float32, (3,), convert=True)
     if points.device != tri.device:
         raise _lib.DudfError("mesh_distance: tri and points live on different devices")
     T, Q, dev = tri.shape[0], points.shape[0], tri.device
@@ -984,8 +859,6 @@ def mesh_distance(tri, index, points, want_idx=False, want_closest=False, stats=
     closest = torch.empty(Q, 3, dtype=torch.float32, device=dev) if want_closest else None
     if Q and T == 0:
         _lib.check(-1, "dudf_mesh_distance (no triangles)")
-    with torch.cuda.device(dev):
-        rc = lib.dudf_mesh_distance(_ptr(tri), T, _ptr(index), nbytes, _ptr(points), Q, _ptr(dist), _ptr(idx), _ptr(closest),
-                                    _ptr(stats), _stream())
-    _lib.check(rc, "dudf_mesh_distance")
+    _call("dudf_mesh_distance", _ptr(tri), T, _ptr(index), nbytes, _ptr(points), Q, _ptr(dist), _ptr(idx), _ptr(closest),
+          _ptr(stats), dev=dev)
     return dist, idx, closest

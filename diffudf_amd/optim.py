@@ -6,7 +6,7 @@ betas (0.9, 0.999), eps 1e-8, no weight decay) and only ever calls `step()` and 
 IS that optimizer — same constructor, same `param_groups`, and `step()` falls back to torch's implementation whenever its
 fast path does not apply — but when every parameter is a view of the model's flat theta and every `.grad` a view of the
 flat gradient buffer (what `train.py::_zero_flat_grad` sets up), one `dudf_adam_step` launch updates everything: the kernel
-replays torch's CUDA Adam operation by operation (csrc/dudf_misc.hip; tests/test_api_gpu.py holds a 10-step trajectory to
+replays torch's CUDA Adam operation by operation (csrc/dudf_loss.hip; tests/test_api_gpu.py holds a 10-step trajectory to
 2e-7), instead of torch's six foreach launches over 18 tensors and their host-side bookkeeping (0.3 ms of Python a step,
 which is what the stage-2 epochs of the reference recipe are bound by).  The fast path's moments are flat tensors of its
 own; `state_dict()` / `load_state_dict()` convert them to and from torch.optim.Adam's per-parameter layout (`step`,

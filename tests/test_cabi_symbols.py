@@ -60,6 +60,9 @@ def test_host_only_calls():
     assert lib.dudf_get_option(b"wgrad_max_workgroups", ctypes.byref(v)) == 0 and v.value == 240
     assert lib.dudf_reset_options() == 0 and lib.dudf_stash_mode(ctypes.byref(cfg), 29970, 0) == 7
     assert lib.dudf_get_option(b"wgrad_max_workgroups", ctypes.byref(v)) == 0 and v.value == 256
+    from diffudf_amd import hip_ops
+    for name in hip_ops.OPTIONS:                    # the Python mirror of the option list names only what the library knows
+        assert lib.dudf_get_option(name.encode(), ctypes.byref(v)) == 0, name
     bad = _lib.NetCfg(3, 8, 100, 30.0)
     assert lib.dudf_theta_count(ctypes.byref(bad)) == -1
     assert lib.dudf_workspace_bytes(ctypes.byref(bad), 10) == 0
