@@ -3,8 +3,9 @@
 column counts, all-quad batches, 2 ... 34 hidden layers, 256 and 512 wide, `loss_s1` with and without the Hessian term and
 `loss_s2` — must give the same terms and d(theta) with the fp32 stash (option stash = 0), R, E, C at 24 bits (6) and the default:
 all seven arrays at 24 bits (7).  The formats are switched in-process through dudf_set_option.
-(HIP against HIP: the oracle comparisons live in test_hip_parity.py and test_full_size_oracle_gpu.py; this file pins the shapes
-those do not visit.)"""
+(HIP against HIP, over the whole d(theta): a defect all three formats share passes here.  The oracle comparisons of the edge column
+counts, per parameter tensor, are in test_dtheta_edges_gpu.py; this file adds the deep networks and the skewed row stride, which
+cost the oracle too much.)"""
 import importlib.util
 import os
 

@@ -44,7 +44,7 @@ def run(out, stash=None):
         t = hip.loss_forward(cfg, hip.LOSS_S1, th, xd, nd, sd, n, W, 100.0, ws, **kw)
         d = hip.loss_backward(cfg, hip.LOSS_S1, th, xd, nd, sd, n, W, 100.0, torch.ones(4, device="cuda"), None, ws, **kw)
         torch.cuda.synchronize()
-        res[f"t{ci}"] = t.cpu().numpy(); res[f"d{ci}"] = d.cpu().numpy()[::97]; res[f"n{ci}"] = np.array([float(d.double().norm())])
+        res[f"t{ci}"] = t.cpu().numpy(); res[f"d{ci}"] = d.cpu().numpy(); res[f"n{ci}"] = np.array([float(d.double().norm())])
         print(f"case {ci}: {hidden[0]}x{len(hidden)} n={n} n_hess={nh}  mode {hip.stash_mode(cfg, n, nh)}  terms {t.cpu().numpy()}  |dtheta| {float(d.abs().max()):.4e}",
               flush=True)
         modes.add(hip.stash_mode(cfg, n, nh))
@@ -56,22 +56,43 @@ def run(out, stash=None):
             d2 = hip.loss_backward(cfg, hip.LOSS_S2, th, xd, nd, sd2, n, [1e5, 1e5], 100.0, torch.ones(4, device="cuda"), st, ws)
             assert float(d2.abs().max()) > 0
             torch.cuda.synchronize()
-            res[f"s{ci}"] = d2.cpu().numpy()[::97]
+            res[f"s{ci}"] = d2.cpu().numpy()
     np.savez(out, **res)
     return modes
 
 
+def worst_tensor(x, y, hidden):
+    """(name, max|x-y| / max|x|) of the worst (dW_l, db_l) slice of two flat d(theta) of SIREN(3, 1, hidden), state_dict order"""
+    H, L = hidden[0], len(hidden)
+    shapes = [(H, 3)] + [(H, H)] * (L - 1) + [(1, H)]
+    out, o = ("-", 0.0), 0
+    for l, (r, c) in enumerate(shapes):
+        for name, cnt in ((f"dW{l}", r * c), (f"db{l}", r)):
+            m = np.abs(x[o:o + cnt]).max()
+            e = np.abs(x[o:o + cnt] - y[o:o + cnt]).max() / max(m, 1e-300)
+            if e > out[1]:
+                out = (name, e)
+            o += cnt
+    assert o == x.size == y.size
+    return out
+
+
 def compare(a, b):
     A, B = np.load(a), np.load(b)
-    worst = 0.0
+    worst, worst_t = 0.0, (0.0, "-")
     for k in A.files:
         x, y = A[k].astype(np.float64), B[k].astype(np.float64)
         e = np.abs(x - y).max() / max(np.abs(x).max(), 1e-300)
         ok = np.isfinite(y).all() and e < (1e-5 if k[0] == "t" else 3e-4)
         worst = max(worst, e)
-        print(f"{k}: rel diff {e:.2e} {'ok' if ok else 'FAIL'}")
+        per = ""
+        if k[0] in "ds":                                       # a whole d(theta): its worst single tensor, by name
+            name, et = worst_tensor(x, y, CASES[int(k[1:])][0])
+            per = f"  worst tensor {name} {et:.2e}"
+            worst_t = max(worst_t, (et, f"{k} {name}"))
+        print(f"{k}: rel diff {e:.2e}{per} {'ok' if ok else 'FAIL'}")
         assert ok, k
-    print("worst", worst)
+    print("worst", worst, "worst tensor", worst_t[1], "%.2e" % worst_t[0])
 
 
 if __name__ == "__main__":
