@@ -78,6 +78,9 @@ SYMBOLS = {
     "dudf_mesh_morton_codes": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_size_t, _P, _P]),
     "dudf_mesh_index_build": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
     "dudf_mesh_distance": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_size_t, _P, ctypes.c_int64, _P, _P, _P, _P, _P]),
+    "dudf_mesh_occupancy": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_size_t, _P, ctypes.c_int64, _P, _P, _P]),
+    "dudf_mesh_trace_rays": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_size_t, _P, _P, _P, _P, ctypes.c_int64, ctypes.c_double,
+                                            ctypes.c_int, ctypes.c_double, _P]),
     "dudf_grid_fields": (ctypes.c_int, [_CFG, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.c_double, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "dudf_query": (ctypes.c_int, [_CFG, _P, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_size_t, _P]),

@@ -837,6 +837,56 @@ def mesh_index_build(tri, order=None):
     return index
 
 
+def _mesh_args(what, tri, index):
+    """(tri (T,9) float32, index bytes) of a mesh query: the checks `mesh_distance` makes."""
+    tri = _tensor(tri, f"{what}: tri", torch.float32, (9,), convert=True)
+    nbytes = 0
+    if index is not None:
+        if not torch.is_tensor(index) or index.device != tri.device or index.dtype != torch.uint8 or not index.is_contiguous():
+            raise _lib.DudfError(f"{what}: index must be the uint8 CUDA tensor of mesh_index_build on the device of tri")
+        nbytes = index.numel()
+    return tri, nbytes
+
+
+def mesh_occupancy(tri, index, points):
+    """(count (Q,) int32, inside (Q,) uint8) for points (Q,3): how many triangles of the soup tri (T,9) the ray from each point
+    along +x crosses, and its parity — `scene.compute_occupancy(points)` for a closed mesh (`dudf_mesh_occupancy`, whose comment in
+    include/dudf_hip.h states the rule on edges and vertices).  index: what `mesh_index_build(tri)` returned, or None for the scan of
+    every triangle (the same counts).  A NaN point: count -1, inside 0."""
+    tri, nbytes = _mesh_args("mesh_occupancy", tri, index)
+    points = _tensor(points, "mesh_occupancy: points", torch.float32, (3,), convert=True)
+    if points.device != tri.device:
+        raise _lib.DudfError("mesh_occupancy: tri and points live on different devices")
+    T, Q, dev = tri.shape[0], points.shape[0], tri.device
+    count = torch.empty(Q, dtype=torch.int32, device=dev)
+    inside = torch.empty(Q, dtype=torch.uint8, device=dev)
+    if Q and T == 0:
+        _lib.check(-1, "dudf_mesh_occupancy (no triangles)")
+    _call("dudf_mesh_occupancy", _ptr(tri), T, _ptr(index), nbytes, _ptr(points), Q, _ptr(count), _ptr(inside), dev=dev)
+    return count, inside
+
+
+def mesh_trace_rays(tri, index, rays, t0, mask, surface_eps=0.001, max_iterations=30, bound=1.3):
+    """The marching loop of reference src/render_st.py:255-268 against the soup tri (T,9) in one launch (`dudf_mesh_trace_rays`):
+    rays (m,3), t0 (m,3) float64 CUDA tensors, mask (m,) uint8; t0 and mask are updated in place.  Returns hits (m,) uint8.
+    index: what `mesh_index_build(tri)` returned, or None for the scan of every triangle (the same bits)."""
+    tri, nbytes = _mesh_args("mesh_trace_rays", tri, index)
+    for name, t, dt, shape in (("rays", rays, torch.float64, (3,)), ("t0", t0, torch.float64, (3,)), ("mask", mask, torch.uint8, ())):
+        if _tensor(t, f"mesh_trace_rays: {name}", dt, shape).device != tri.device:
+            raise _lib.DudfError(f"mesh_trace_rays: tri and {name} live on different devices")
+    m, dev = t0.shape[0], tri.device
+    if rays.shape[0] != m or mask.shape[0] != m:
+        raise _lib.DudfError("mesh_trace_rays: row counts of rays, t0 and mask differ")
+    if int(max_iterations) < 0:
+        raise _lib.DudfError(f"mesh_trace_rays: max_iterations must not be negative; got {max_iterations}")
+    hits = torch.empty(m, dtype=torch.uint8, device=dev)
+    if m and tri.shape[0] == 0:
+        _lib.check(-1, "dudf_mesh_trace_rays (no triangles)")
+    _call("dudf_mesh_trace_rays", _ptr(tri), tri.shape[0], _ptr(index), nbytes, _ptr(rays), _ptr(t0), _ptr(mask), _ptr(hits), m,
+          float(surface_eps), int(max_iterations), float(bound), dev=dev)
+    return hits
+
+
 def mesh_distance(tri, index, points, want_idx=False, want_closest=False, stats=None):
     """(dist (Q,) float32, idx (Q,) int64 | None, closest (Q,3) float32 | None) for points (Q,3): the exact unsigned distance to
     the soup tri (T,9), the nearest triangle (smallest index among ties) and the closest point on it.  index: what

@@ -7,7 +7,9 @@ there is no CPU path: CPU tensors raise DudfError.
 
 `MeshIndex` / `mesh_distance` stand in for `o3d.t.geometry.RaycastingScene().add_triangles(...)` / `.compute_distance(...)`
 (reference generate_df.py:108-110): the exact unsigned distance from points to a triangle mesh through a bounding-volume
-hierarchy built and walked on the device (csrc/dudf_meshdist.hip)."""
+hierarchy built and walked on the device (csrc/dudf_meshdist.hip).  `MeshIndex.occupancy` / `.signed_distance` are its
+`compute_occupancy` / `compute_signed_distance` (src/dataset.py:35,50, src/render_st.py:275-276) and `.trace_rays` the marching loop
+of src/render_st.py:255-268 as one kernel."""
 import numpy as np
 import torch
 
@@ -114,6 +116,27 @@ class MeshIndex:
         if not (return_index or return_closest):
             return dist
         return (dist,) + ((idx,) if return_index else ()) + ((closest,) if return_closest else ())
+
+    def occupancy(self, points, return_count=False, brute=False):
+        """`scene.compute_occupancy(points)`: inside (Q,) bool of points (Q,3) — the parity of the triangles a ray along +x crosses
+        (exact on shared edges and vertices: every crossing is counted by exactly one of the triangles that meet there); with
+        return_count (inside, count (Q,) int32).  An open mesh has a parity too, it just is not an inside.  A NaN point: False,
+        count -1.  brute=True scans every triangle without the index (the same counts)."""
+        count, inside = hip_ops.mesh_occupancy(self.tri, None if brute else self.index, points)
+        inside = inside.view(torch.bool)
+        return (inside, count) if return_count else inside
+
+    def signed_distance(self, points):
+        """`scene.compute_signed_distance(points)` (Q,) float32: `distance` with the sign of `occupancy`, negative inside (open3d's
+        convention); the magnitude is `distance` bit for bit, a NaN point gives NaN."""
+        dist = self.distance(points)
+        return torch.where(self.occupancy(points), -dist, dist)
+
+    def trace_rays(self, rays, t0, mask, surface_eps=0.001, max_iterations=30, bound=1.3, brute=False):
+        """The sphere-tracing loop of reference src/render_st.py:255-268 against this mesh in ONE launch: rays (m,3) and t0 (m,3)
+        float64 CUDA tensors, mask (m,) uint8; per iteration t0 of the live rays advances by its `distance`, a ray hits when that is
+        below surface_eps and dies outside (-bound, bound)^3.  t0 and mask are updated in place; returns hits (m,) uint8."""
+        return hip_ops.mesh_trace_rays(self.tri, None if brute else self.index, rays, t0, mask, surface_eps, max_iterations, bound)
 
 
 def mesh_distance(points, vertices, faces):

@@ -2,7 +2,9 @@
 """Differential quantities the sphere tracer derives at ray hits — the query half of reference
 src/render_st.py:42-65 (BASELINE config 4).  The marching loop itself (`propagate_rays`, `grad_descent`, :136-172)
 runs on the device too, and so do ray set-up, orientation, colour map and shading
-(`create_projectional_image`, `phong_shading`, `ward_reflectance`, :67-133, :174-245; csrc/dudf_render.hip)."""
+(`create_projectional_image`, `phong_shading`, `ward_reflectance`, :67-133, :174-245; csrc/dudf_render.hip).
+`create_projectional_image_mesh` is the sphere-traced image of the ground-truth mesh (:248-281): the march against the mesh is one
+kernel and the normals come from the signed distance (`MeshIndex.trace_rays`, `.signed_distance`; csrc/dudf_meshdist.hip)."""
 import numpy as np
 import torch
 import weakref
@@ -164,7 +166,87 @@ def ward_reflectance(light_position, camera_position, hits, samples, normals, al
 
 
 def create_projectional_image_gt(*args, **kwargs):
-    """reference src/render_st.py:248-281 casts rays against a triangle mesh with open3d's RaycastingScene; that renderer is not
-    part of this build."""
+    """reference src/render_st.py:248-281 as written calls `phong_shading` with an argument that function no longer has, and reads
+    the mesh with open3d; it keeps raising here.  `create_projectional_image_mesh` is that renderer on the device."""
     raise DudfError("create_projectional_image_gt needs open3d's RaycastingScene (ray casting against the ground-truth mesh); "
-                    "it is outside this build — render the trained network with create_projectional_image")
+                    "it is outside this build — render the trained network with create_projectional_image, or the mesh itself "
+                    "with create_projectional_image_mesh")
+
+
+def load_scene(mesh, device):
+    """`MeshIndex` of `mesh`: one already, (vertices, faces), the path of an OBJ (read as it is, like the reference's
+    `read_triangle_mesh`), or a prefix in the sense of `diffudf_amd.mesh.prepare`: `<prefix>_t.obj`, else `<prefix>.obj` normalised."""
+    import os
+    from . import mesh as dmesh
+    from .metrics import MeshIndex
+    if isinstance(mesh, MeshIndex):
+        return mesh
+    if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
+        return MeshIndex(mesh[0], mesh[1], device=device)
+    path = os.fspath(mesh)
+    if os.path.isfile(path):
+        v, f = dmesh.load_obj(path)
+    elif os.path.isfile(path + "_t.obj"):
+        v, f = dmesh.load_obj(path + "_t.obj")
+    elif os.path.isfile(path + ".obj"):
+        v, f = dmesh.load_obj(path + ".obj")
+        v = dmesh.normalize_vertices(v)
+    else:
+        raise FileNotFoundError(f"no mesh at {path} ({path}_t.obj, {path}.obj)")
+    return MeshIndex(v, f, device=device)
+
+
+GT_GRAD_EPS = 0.0001            # reference src/render_st.py:273
+
+
+def mesh_normals(scene, pos, hit_rays):
+    """Normals (k,3) float64 at the hit positions pos (k,3) float64 — reference src/render_st.py:273-279: central differences of the
+    SIGNED distance at float32(pos +- 1e-4 e_i), the float32 difference divided by 2e-4 as numpy forms it, normalize in float32,
+    flipped where normal . ray > 0."""
+    k, dev = pos.shape[0], pos.device
+    grad = torch.empty(k, 3, dtype=torch.float32, device=dev)
+    two_eps = torch.tensor(2 * GT_GRAD_EPS, dtype=torch.float32, device=dev)              # a tensor: a true division, not * (1 / x)
+    for i in range(3):
+        plus, minus = pos.clone(), pos.clone()
+        plus[:, i] += GT_GRAD_EPS; minus[:, i] -= GT_GRAD_EPS                     # float64, then ONE rounding to float32 (:275-276)
+        grad[:, i] = (scene.signed_distance(plus.float()) - scene.signed_distance(minus.float())) / two_eps
+    normals, _, _ = hip_ops.render_orient(None, grad=grad)                        # normalize in float32
+    n32 = normals.float()                                                         # exact: they are float32 values
+    dot = n32[:, 0] * hit_rays[:, 0] + n32[:, 1] * hit_rays[:, 1] + n32[:, 2] * hit_rays[:, 2]
+    return torch.where((dot > 0)[:, None], -normals, normals)
+
+
+def mesh_pass(scene, rays, t0, mask, light_position, accumulator, specular=False, surface_eps=0.001, max_iterations=30):
+    """One pass of reference src/render_st.py:255-281 on device arrays: the march against the mesh (`MeshIndex.trace_rays`; t0 and
+    mask in place), `mesh_normals` at the hits, Blinn-Phong with shininess 40 (`specular`) or 0 into `accumulator` (m,3) float64
+    (+=).  Returns (hits, k); 0 hits raise the reference's ValueError."""
+    with torch.cuda.device(t0.device):
+        hits = scene.trace_rays(rays, t0, mask, surface_eps=surface_eps, max_iterations=max_iterations)
+        pos, hit_rays, rows, k = hip_ops.render_gather(hits, t0, rays)
+        if k == 0:
+            raise ValueError(f"Ray tracing did not converge in {max_iterations} iterations to any point at distance {surface_eps} "
+                             "or lower from surface.")
+        normals = mesh_normals(scene, pos, hit_rays)
+        hip_ops.render_shade("blinn-phong", hits, rows, pos, normals, accumulator, light_position, shininess=40 if specular else 0)
+    return hits, k
+
+
+def create_projectional_image_mesh(mesh, width, height, rays, t0, mask_rays, light_position, specular=False, surface_eps=0.001,
+                                   max_iterations=30, device=None):
+    """The sphere-traced image of the ground-truth MESH — what reference src/render_st.py:248-281 (`create_projectional_image_gt`)
+    evidently means: its march and normals operation for operation, and Blinn-Phong with shininess 40 with `specular`, 0 without.
+    mesh: a path (see `load_scene`), (vertices, faces) or a `MeshIndex`.  rays (M,3), t0 (M,3) float64 and mask_rays (M,) bool numpy
+    arrays; t0 and mask_rays are updated in place.  Returns the (width, height, 3) float64 image (1.0 where nothing was hit);
+    raises the reference's ValueError when no ray hits."""
+    dev = _gpu(torch.device("cuda:0") if device is None else torch.device(device), "create_projectional_image_mesh")
+    scene = load_scene(mesh, dev)
+    d_rays = torch.from_numpy(np.ascontiguousarray(rays, dtype=np.float64)).to(dev)
+    d_t0 = torch.from_numpy(np.ascontiguousarray(t0, dtype=np.float64)).to(dev)
+    d_mask = torch.from_numpy(np.ascontiguousarray(mask_rays).astype(np.uint8)).to(dev)
+    acc = torch.zeros(d_t0.shape[0], 3, dtype=torch.float64, device=dev)
+    try:
+        mesh_pass(scene, d_rays, d_t0, d_mask, light_position, acc, specular, surface_eps, max_iterations)
+    finally:
+        t0[...] = d_t0.cpu().numpy()
+        mask_rays[...] = d_mask.cpu().numpy().astype(bool)
+    return acc.cpu().numpy().reshape((width, height, 3))

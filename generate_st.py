@@ -16,9 +16,16 @@ the scatter into the image — and the average over `sample_rate` jittered passe
 `generate_st` returns a PIL image as the reference does when PIL is importable, otherwise the (H,W,3) uint8 array (written as PNG
 through zlib; `rotation != 0` needs PIL and is refused without it).  `render` is the array-level entry.  Like the reference, the
 script hands (height, width) to `get_pixels_camera(width, height, ...)` and reshapes by (height, width): images are meant to be
-square, and only square images are tested.  gt_mode 'gt' (open3d ray casting against a mesh) is outside this build."""
+square, and only square images are tested.
+
+gt_mode 'gt' renders the ground-truth MESH instead of a network (reference generate_st.py:103-114, src/render_st.py:248-281):
+"network_config" then holds gt_mode, device and "mesh_path" (an OBJ, or a prefix as the training configs give it: `<prefix>_t.obj`,
+else `<prefix>.obj` normalised), "rendering_config" the keys above it needs — width, height, fov, camera_position, light_position,
+surface_threshold, max_iterations, sample_rate, rotation, output_path, + optional "specular" (Blinn-Phong shininess 40 instead of 0)
+and "planes" (`configs/st_beetle_gt.json`).  The march against the mesh is one kernel per pass (`MeshIndex.trace_rays`)."""
 import argparse
 import json
+import os
 import struct
 import zlib
 
@@ -26,7 +33,8 @@ import numpy as np
 import torch
 
 from src.model import SIREN
-from src.render_st import create_projectional_image, create_projectional_image_gt, default_colormap  # noqa: F401
+from src.render_st import (create_projectional_image, create_projectional_image_gt, create_projectional_image_mesh,  # noqa: F401
+                           default_colormap, load_scene, mesh_pass)
 from diffudf_amd import hip_ops
 from diffudf_amd._lib import DudfError
 
@@ -75,14 +83,14 @@ def render(config_dict, jitter=None, colormap=None, model=None):
     from np.random.normal(0.5, 0.35) in the reference's call order); colormap: (256,3) table (default: matplotlib's RdYlBu, only
     fetched when curvatures are plotted); model: a loaded SIREN on the GPU instead of network_config['model_path']."""
     network_config, rendering_config = config_dict['network_config'], config_dict['rendering_config']
-    if network_config['gt_mode'] == 'gt':
-        create_projectional_image_gt()
     passes = int(rendering_config['sample_rate'])
     if jitter is None:
         jitter = [np.random.normal(0.5, 0.35) for _ in range(passes)]
     jitter = [float(j) for j in np.atleast_1d(jitter)]
     if len(jitter) != passes or passes < 1:
         raise ValueError(f"sample_rate is {passes}; got {len(jitter)} jitter values")
+    if network_config['gt_mode'] == 'gt':
+        return _render_mesh(network_config, rendering_config, jitter)
     if model is None:
         model, dev = _load_model(network_config)
     else:
@@ -104,6 +112,39 @@ def render(config_dict, jitter=None, colormap=None, model=None):
             hip_ops.render_pass(cfg, theta, noise, rotation, rendering_config['camera_position'], network_config, rendering_config,
                                 lut, acc)
         image = hip_ops.render_finish(acc, passes)
+    return image.cpu().numpy().reshape(height, width, 3)
+
+
+def _device(network_config):
+    dev = network_config.get("device", 0)
+    dev = torch.device("cuda", dev) if isinstance(dev, int) else torch.device(dev)
+    if dev.type != "cuda":
+        raise DudfError(f"generate_st: device must be a GPU (got {dev}); the HIP path has no CPU fallback")
+    return dev
+
+
+def _mesh_path(path):
+    """network_config['mesh_path'] as given, or — a relative path that is not there — relative to this script."""
+    if os.path.isabs(path) or any(os.path.isfile(path + ext) for ext in ("", "_t.obj", ".obj")):
+        return path
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), path)
+
+
+def _render_mesh(network_config, rendering_config, jitter):
+    """gt_mode 'gt' — reference generate_st.py:103-114 with the keys every other mode uses: the image of the mesh itself."""
+    dev = _device(network_config)
+    scene = load_scene(_mesh_path(network_config['mesh_path']), dev)
+    height, width = int(rendering_config['height']), int(rendering_config['width'])
+    rotation = camera_rotation(rendering_config['camera_position'])
+    with torch.cuda.device(dev):
+        acc = torch.zeros(height * width, 3, dtype=torch.float64, device=dev)
+        for noise in jitter:
+            rays, t0, mask = hip_ops.render_setup_rays(height, width, rendering_config['fov'], noise, rotation,
+                                                       rendering_config['camera_position'],
+                                                       rendering_config.get('planes', [1, -1, 1, -1, 1, -1]), dev)
+            mesh_pass(scene, rays, t0, mask, rendering_config['light_position'], acc, bool(rendering_config.get('specular', False)),
+                      rendering_config['surface_threshold'], rendering_config['max_iterations'])
+        image = hip_ops.render_finish(acc, len(jitter))
     return image.cpu().numpy().reshape(height, width, 3)
 
 

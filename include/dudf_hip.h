@@ -278,7 +278,25 @@ int dudf_vertex_normals(const double* vertices, int64_t n_vertices, const int64_
  *   closest point on that triangle; *out_stats (device int64, ADDED to) = exact triangle evaluations of the call.
  *   index == NULL: brute force over all triangles — the cross-check; with an index the same bits (a subtree is skipped only on a
  *   safe-side bound STRICTLY above the best exact value).  A point with a NaN coordinate: distance NaN, triangle -1, closest NaN.
- *   n_pts == 0: nothing is launched, 0. */
+ *   n_pts == 0: nothing is launched, 0.
+ * dudf_mesh_occupancy — `scene.compute_occupancy(points)` (behind `compute_signed_distance`, reference src/dataset.py:35,50,
+ *   src/render_st.py:275-276) by ray parity: out_count (n_pts) int32 = how many triangles the ray from the point along +x crosses,
+ *   out_inside (n_pts) bytes = count & 1; either may be NULL.  The ray is axis-aligned, so a crossing is a point-in-triangle test of
+ *   (p.y, p.z) in the triangle's (y, z) projection plus one comparison in x, all on the fp32 inputs: (p.y, p.z) must lie in the
+ *   triangle's closed (y, z) extent with max x >= p.x; a triangle of zero projected area counts 0; each edge function is evaluated
+ *   in fp64 from the edge's lower vertex to its higher one (lexicographic on (y, z, x)) and negated for the triangle that runs the
+ *   edge the other way, so two triangles sharing an edge see exactly opposite values; a zero lies on the left of the edge taken
+ *   from its lower to its higher vertex (a footprint is open at its low-y and high-z borders, closed at its high-y and low-z ones);
+ *   the three sides must agree and the crossing's x, interpolated in fp64, must be > p.x.  index == NULL scans every triangle;
+ *   with an index the same counts (a box is visited iff (p.y, p.z) is in its closed (y, z) extent and its hi.x >= p.x: compares
+ *   of stored floats).  A point with a NaN coordinate: count -1, inside 0.  n_pts == 0: nothing is launched, 0.
+ * dudf_mesh_trace_rays — the marching loop of `create_projectional_image_gt` (reference src/render_st.py:255-268) in one launch, one
+ *   lane per ray: rays (n_rays,3) double; t0 (n_rays,3) double and mask (n_rays) bytes are updated in place; hits (n_rays) bytes is
+ *   written.  Per iteration of a ray whose mask is set: d = the fp32 distance dudf_mesh_distance gives for float32(t0) (same walk,
+ *   same arithmetic, same bits); t0 += ray * (double)d, product and sum rounded separately; d < float32(surface_eps) (numpy's
+ *   comparison of float32 distances with a Python float): hit, mask cleared; otherwise the mask is cleared once a coordinate of t0
+ *   is not inside (-bound, bound) (the reference: 1.3).  A NaN position never hits and clears the mask.  index == NULL: the same with
+ *   the brute-force scan.  max_iterations < 0: DUDF_E_BADCFG; n_rays == 0: nothing is launched, 0. */
 #define DUDF_MESH_INDEX_FLAGS_OFFSET 24
 #define DUDF_MESH_FLAG_NONFINITE 1
 #define DUDF_MESH_FLAG_BAD_ORDER 2
@@ -287,6 +305,11 @@ int dudf_mesh_morton_codes(const float* tri, int64_t n_tri, void* index, size_t 
 int dudf_mesh_index_build(const float* tri, int64_t n_tri, const int64_t* order, void* index, size_t index_bytes, void* stream);
 int dudf_mesh_distance(const float* tri, int64_t n_tri, const void* index, size_t index_bytes, const float* pts, int64_t n_pts,
                        float* out_dist, int64_t* out_tri, float* out_closest, int64_t* out_stats, void* stream);
+int dudf_mesh_occupancy(const float* tri, int64_t n_tri, const void* index, size_t index_bytes, const float* pts, int64_t n_pts,
+                        int32_t* out_count, unsigned char* out_inside, void* stream);
+int dudf_mesh_trace_rays(const float* tri, int64_t n_tri, const void* index, size_t index_bytes, const double* rays, double* t0,
+                         unsigned char* mask, unsigned char* hits, int64_t n_rays, double surface_eps, int max_iterations,
+                         double bound, void* stream);
 
 /* The field part of `extract_fields` (reference src/render_mc.py:20-99) for grid points start .. start+count-1 of the
  * regular grid_n^3 grid on [-1,1]^3 (linear index, first axis slowest, coordinates derived from the index):
