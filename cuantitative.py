@@ -121,6 +121,8 @@ def run(dataset, outfolder, cuda_device, exp_config=None):
         training_time, meshes = setup_train(exp_config, cuda_device)
         if not meshes:
             raise RuntimeError(f"{experiment_name}: training produced no mesh (resolution 0, or no epoch improved on the initial loss)")
+        if not isinstance(meshes, tuple):            # gt_mode 'siren' returns its one signed mesh: there is no MU / CAP pair to compare
+            raise RuntimeError(f"{experiment_name}: the MU / CAP table needs gt_mode 'tanh' (got '{exp_config.get('gt_mode', 'tanh')}')")
         meshMU, meshCAP = meshes
         torch.cuda.empty_cache()
         gc.collect()

@@ -112,6 +112,12 @@ SYMBOLS = {
     "dudf_capudf_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "dudf_capudf_count": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_double, _P, _P, ctypes.c_size_t, _P]),
     "dudf_capudf_emit": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_double, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_grid_values": (ctypes.c_int, [_CFG, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_mc_lewiner_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "dudf_mc_lewiner_count": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _P, _P, _P,
+                                             ctypes.c_int, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_mc_lewiner_emit": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _P, _P, _P,
+                                            ctypes.c_int, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "dudf_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "dudf_split_mode": (ctypes.c_int, []),
     "dudf_profile_dump": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t]),
@@ -151,7 +157,7 @@ def load():
     for name, (res, args) in SYMBOLS.items():
         try:
             fn = getattr(lib, name)
-        except AttributeError:           # calls added without an ABI bump (dudf_render_*, dudf_nearest_points, dudf_mesh_* ..: no existing signature changed)
+        except AttributeError:           # calls added without an ABI bump (dudf_render_*, dudf_nearest_points, dudf_mesh_*, dudf_mc_lewiner_* ..: no existing signature changed)
             raise DudfError(f"{LIB_PATH} does not export {name}: it is older than this package; rebuild it "
                             "(`python -c 'import __graft_entry__ as g; g.build()'`)") from None
         fn.restype = res

@@ -384,6 +384,18 @@ int dudf_grid_fields(const dudf_net_cfg* cfg, const float* theta, int64_t grid_n
                                       nullptr, c.st);
 }
 
+int dudf_grid_values(const dudf_net_cfg* cfg, const float* theta, int64_t grid_n, int64_t start, int64_t count, float* out_f,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (grid_n < 2 || start < 0 || count < 0 || start + count > grid_n * grid_n * grid_n) return DUDF_E_BADCFG;
+    DudfCtx c;
+    int rc = dudf_open_ctx(cfg, count, 0, workspace, workspace_bytes, stream, &c, 1);
+    if (rc) return rc;
+    if (count == 0) return 0;
+    if ((rc = dudf_launch_make_x4_grid(c.lo, grid_n, start, c.ws, c.st))) return rc;
+    if ((rc = dudf_forward_common(c, theta, nullptr, 0, false))) return rc;      // value only: no reverse sweep
+    return dudf_launch_copy_out(c.lo, c.ws, out_f, nullptr, nullptr, c.st);
+}
+
 int dudf_trace_rays(const dudf_net_cfg* cfg, const float* theta, const double* rays, double* t0, unsigned char* mask,
                     unsigned char* hits, int64_t m, int inverse_mode, double alpha, double min_step,
                     double surface_threshold, int max_iterations, int check_every, int* iterations_done,

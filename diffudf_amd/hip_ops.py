@@ -402,6 +402,43 @@ def grid_fields(cfg, theta, grid_n, start, count, gt_mode, alpha, out_df, out_ve
     return flag
 
 
+def grid_values(cfg, theta, grid_n, start, count, out_f, ws=None):
+    """Fills out_f[start:start+count] (a device tensor over the flattened N^3 grid) with the raw network output, sign kept
+    (`dudf_grid_values`: the forward sweep only)."""
+    theta = _theta(cfg, theta)
+    ws = ws or query_workspace_for(cfg, count, theta.device)
+    _call("dudf_grid_values", ctypes.byref(cfg), _ptr(theta), int(grid_n), int(start), int(count), _ptr(out_f[start:start + count]),
+          _ptr(ws.buf), ws.nbytes, dev=theta.device)
+
+
+def mc_lewiner_extract(volume, level, lut_data, lut_offsets, lut_dims):
+    """Lewiner marching cubes of a signed device volume (nz, ny, nx) at `level` (`dudf_mc_lewiner_count` / `_emit`):
+    (vertices (V,3) float32 in x-y-z grid units, faces (T,3) int32, raw normal sums (V,3) float32, values (V,) float32) device
+    tensors, bit for bit what `marching_cubes.marching_cubes_sdf` gives for the same numbers on the host.  lut_data: the packed
+    tables as an int8 device tensor, lut_offsets / lut_dims: their numpy descriptors (`marching_cubes._pack_luts`).  One host
+    sync for the two output sizes; nothing is launched for an empty result."""
+    volume = _tensor(volume, "volume", torch.float32, convert=True)
+    lut_data = _tensor(lut_data, "lut_data", torch.int8)
+    if volume.dim() != 3 or lut_data.device != volume.device:
+        raise _lib.DudfError(f"mc_lewiner_extract: a (nz, ny, nx) volume and tables on its device expected, got {tuple(volume.shape)}")
+    nz, ny, nx = volume.shape
+    dev = volume.device
+    nbytes = _bytes("dudf_mc_lewiner_workspace_bytes", nz, ny, nx)
+    ws = _scratch(nbytes, dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    head = (_ptr(volume), nz, ny, nx, float(level), _ptr(lut_data), ctypes.c_void_p(lut_offsets.ctypes.data),
+            ctypes.c_void_p(lut_dims.ctypes.data), len(lut_offsets))
+    _call("dudf_mc_lewiner_count", *head, _ptr(counts), _ptr(ws), nbytes, dev=dev)
+    nv, nt = [int(v) for v in counts.tolist()]
+    if nv >= 1 << 31:
+        raise _lib.DudfError(f"mc_lewiner_extract: {nv} vertices do not fit int32 faces")
+    verts = torch.empty(nv, 3, dtype=torch.float32, device=dev); faces = torch.empty(nt, 3, dtype=torch.int32, device=dev)
+    normals = torch.empty(nv, 3, dtype=torch.float32, device=dev); values = torch.empty(nv, dtype=torch.float32, device=dev)
+    if nv and nt:
+        _call("dudf_mc_lewiner_emit", *head, _ptr(verts), _ptr(faces), _ptr(normals), _ptr(values), _ptr(ws), nbytes, dev=dev)
+    return verts, faces, normals, values
+
+
 def capudf_extract(ndf, grad, threshold=0.008, want_cells=False):
     """CAP-UDF cell extraction (reference src/render_mc.py:201-256) on device fields ndf (N,N,N), grad (N,N,N,3):
     (vertices (V,3) float64 in [-1,1]^3, triangles (T,3) int64[, cells (C,3) int64]) device tensors.  One host sync

@@ -1,7 +1,9 @@
 # coding: utf-8
 """MeshUDF marching cubes — the wrapper of reference src/marching_cubes/_marching_cubes_lewiner.py:80-141
 (`udf_mc_lewiner`) over the host C++ library `libdudf_meshudf.so` (csrc/dudf_meshudf.cpp) instead of the reference's
-Cython extension.
+Cython extension — and `marching_cubes_lewiner` (:7-76), Lewiner's marching cubes of a SIGNED volume:
+a numpy volume goes through the same host library (`dudf_mc_lewiner_run`), a CUDA tensor through the device kernels
+(csrc/dudf_mcsdf.hip), which give the same bits in the same order.
 
 The Lewiner look-up tables are NOT part of this package: like the reference's extension, the native entry point takes them
 as an argument (`LutProvider` there, a flat int8 buffer + offsets here).  `udf_mc_lewiner(..., luts=...)` accepts
@@ -62,6 +64,9 @@ def _lib():
         lib.dudf_meshudf_run.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
                                          ctypes.c_float]
+        lib.dudf_mc_lewiner_run.restype = ctypes.c_void_p
+        lib.dudf_mc_lewiner_run.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         lib.dudf_meshudf_sizes.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
         lib.dudf_meshudf_sizes.restype = None
         lib.dudf_meshudf_copy.argtypes = [ctypes.c_void_p] * 5
@@ -154,6 +159,11 @@ def marching_cubes_udf(volume, grads, luts, avg_thresh=1.05, max_thresh=1.75):
                              dims.ctypes.data, len(LUT_NAMES), float(avg_thresh), float(max_thresh))
     if not h:
         raise MeshUDFError("dudf_meshudf_run failed (bad arguments or out of memory)")
+    v, f, n, vals = _read_result(lib, h)
+    return v, f, _unit_normals(n), vals
+
+
+def _read_result(lib, h):
     try:
         nv, nf = ctypes.c_longlong(), ctypes.c_longlong()
         lib.dudf_meshudf_sizes(h, ctypes.byref(nv), ctypes.byref(nf))
@@ -162,12 +172,100 @@ def marching_cubes_udf(volume, grads, luts, avg_thresh=1.05, max_thresh=1.75):
         lib.dudf_meshudf_copy(h, v.ctypes.data, f.ctypes.data, n.ctypes.data, vals.ctypes.data)
     finally:
         lib.dudf_meshudf_free(h)
-    # unit normals, computed like the reference's `Cell.get_normals` (:372-390): length in double, product stored as float
+    return v, f, n, vals
+
+
+def _unit_normals(n):
+    """Unit normals of the accumulated sums, computed like the reference's `Cell.get_normals` (:372-390): length in double,
+    product stored as float.  numpy array or tensor."""
+    if not isinstance(n, np.ndarray):
+        import torch
+        nd = n.double()
+        length = nd[:, 0] * nd[:, 0] + nd[:, 1] * nd[:, 1] + nd[:, 2] * nd[:, 2]
+        scale = torch.where(length > 0.0, 1.0 / torch.sqrt(torch.where(length > 0.0, length, torch.ones_like(length))), length)
+        return (nd * scale[:, None]).float()
     nd = n.astype(np.float64)
     length = (nd * nd).sum(axis=1)
     scale = np.where(length > 0.0, 1.0 / np.sqrt(np.where(length > 0.0, length, 1.0)), length)
-    n = (n * scale[:, None]).astype(np.float32)
-    return v, f, n, vals
+    return (n * scale[:, None]).astype(np.float32)
+
+
+def marching_cubes_sdf(volume, level, luts, raw_normals=False):
+    """The native entry point of the signed extraction (what `_marching_cubes_lewiner_cy.marching_cubes(im, level, luts, 1, 0,
+    None)` is to the reference's wrapper): every cube in raster order, corner "inside" where volume - level > 0.  Returns
+    (vertices (n, 3) float32 in x-y-z grid units, faces (3 m,) int32, normals (n, 3) float32 of unit length — the accumulated
+    sums with raw_normals —, values (n,)).  A numpy volume runs in the host library; a CUDA tensor runs in the device kernels
+    and tensors come back (same bits, same order)."""
+    if not isinstance(volume, np.ndarray):
+        from . import hip_ops
+        data, offs, dims = _pack_luts(luts)
+        import torch
+        v, f, n, vals = hip_ops.mc_lewiner_extract(volume, level, torch.from_numpy(data).to(volume.device), offs, dims)
+        return v, f.reshape(-1), (n if raw_normals else _unit_normals(n)), vals
+    volume = np.ascontiguousarray(volume, np.float32)
+    if volume.ndim != 3:
+        raise ValueError("volume must be (nz, ny, nx)")
+    data, offs, dims = _pack_luts(luts)
+    lib = _lib()
+    nz, ny, nx = volume.shape
+    h = lib.dudf_mc_lewiner_run(volume.ctypes.data, nz, ny, nx, float(level), data.ctypes.data, offs.ctypes.data, dims.ctypes.data,
+                                len(LUT_NAMES))
+    if not h:
+        raise MeshUDFError("dudf_mc_lewiner_run failed (bad arguments or out of memory)")
+    v, f, n, vals = _read_result(lib, h)
+    return v, f, (n if raw_normals else _unit_normals(n)), vals
+
+
+def marching_cubes_lewiner(volume, level=None, spacing=(1., 1., 1.), gradient_direction='descent', step_size=1,
+                           allow_degenerate=True, use_classic=False, mask=None, luts=None):
+    """Reference `marching_cubes_lewiner` (src/marching_cubes/_marching_cubes_lewiner.py:7-76; scikit-image's function of that
+    name): same argument checks and error strings, same output conventions (vertices and normals in z-y-x order, faces flipped
+    for 'descent', spacing applied, level None -> mid-range).  numpy in -> the host library, numpy out; a CUDA tensor in -> the
+    device kernels, tensors out.  `step_size` must be 1, `mask` None, `allow_degenerate` True and `use_classic` False, as for
+    `udf_mc_lewiner`; `luts` as there."""
+    tensor = not isinstance(volume, np.ndarray)
+    if tensor:
+        import torch
+        tensor = torch.is_tensor(volume) and volume.is_cuda
+    if not (isinstance(volume, np.ndarray) or tensor) or (volume.ndim != 3):
+        raise ValueError('Input volume should be a 3D numpy array.')
+    if volume.shape[0] < 2 or volume.shape[1] < 2 or volume.shape[2] < 2:
+        raise ValueError("Input array must be at least 2x2x2.")
+    volume = volume.float().contiguous() if tensor else np.ascontiguousarray(volume, np.float32)
+    if level is None:
+        level = 0.5 * (float(volume.min()) + float(volume.max()))
+    else:
+        level = float(level)
+        if level < float(volume.min()) or level > float(volume.max()):
+            raise ValueError("Surface level must be within volume data range.")
+    if len(spacing) != 3:
+        raise ValueError("`spacing` must consist of three floats.")
+    if int(step_size) < 1:
+        raise ValueError('step_size must be at least one.')
+    if mask is not None and not mask.shape == volume.shape:
+        raise ValueError('volume and mask must have the same shape.')
+    if int(step_size) != 1 or mask is not None or not allow_degenerate or use_classic:
+        raise NotImplementedError("step_size != 1, mask, use_classic and allow_degenerate=False are not used by the reference's "
+                                  "marching-cubes paths and are not built")
+    if luts is None or isinstance(luts, (str, os.PathLike)):
+        luts = load_luts(luts)
+    vertices, faces, normals, values = marching_cubes_sdf(volume, level, luts)
+    if not len(vertices):
+        raise RuntimeError('No surface found at the given iso value.')
+    flip = (lambda a: a.flip(1)) if tensor else np.fliplr
+    vertices = flip(vertices)
+    normals = flip(normals)
+    faces = faces.reshape(-1, 3)
+    if gradient_direction == 'descent':
+        faces = flip(faces)
+    elif not gradient_direction == 'ascent':
+        raise ValueError("Incorrect input %s in `gradient_direction`, see docstring." % (gradient_direction))
+    if not np.array_equal(spacing, (1, 1, 1)):
+        if tensor:                                       # float32 vertices times float64 spacing, as numpy promotes them
+            vertices = vertices.double() * torch.tensor([float(v) for v in spacing], dtype=torch.float64, device=vertices.device)
+        else:
+            vertices = vertices * np.r_[spacing]
+    return vertices, faces, normals, values
 
 
 def udf_mc_lewiner(volume, grads, spacing=(1., 1., 1.), gradient_direction='descent', step_size=1, allow_degenerate=True,

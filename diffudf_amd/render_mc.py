@@ -2,7 +2,9 @@
 """Field extraction and CAP-UDF meshing for the marching-cubes consumers — reference src/render_mc.py:20-99
 `extract_fields` and :201-256 `extract_mesh_CAP` (BASELINE config 5: the batched field+gradient query feeding CAP-UDF
 extraction, all on the device) — and :101-199 `extract_mesh_MESHUDF`, the MeshUDF marching cubes over the same fields, on
-the host (C++ library behind `marching_cubes.udf_mc_lewiner`; serial by nature)."""
+the host (C++ library behind `marching_cubes.udf_mc_lewiner`; serial by nature) — and :259-406, the
+signed path of gt_mode 'siren': `gen_sdf_coordinate_grid`, `get_mesh_sdf` (raw network values on the grid, then Lewiner's marching
+cubes, both on the device) and `convert_sdf_samples_to_ply`."""
 import numpy as np
 import torch
 
@@ -55,14 +57,17 @@ class TriangleSoup:
     process=False)` would hold, plus OBJ / PLY export (the reference only ever calls `.export(path)` and reads
     `.vertices` / `.faces`, generate_mc.py:60-75)."""
 
-    def __init__(self, vertices, faces):
+    def __init__(self, vertices, faces, vertex_normals=None):
         self.vertices = np.asarray(vertices, dtype=np.float64)
         self.faces = np.asarray(faces, dtype=np.int64)
+        self._vertex_normals = None if vertex_normals is None else np.asarray(vertex_normals, dtype=np.float64)
 
     @property
     def vertex_normals(self):
         """(V,3) float64 area-weighted unit vertex normals (what `mesh.as_open3d.compute_vertex_normals(normalized=True)` gives the
         reference's cuantitative.py:99-100), computed on the device by `metrics.vertex_normals`."""
+        if self._vertex_normals is not None:           # given by the extraction (`get_mesh_sdf`), as trimesh keeps them
+            return self._vertex_normals
         from . import metrics
         dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         n = metrics.vertex_normals(torch.from_numpy(np.ascontiguousarray(self.vertices)).to(dev),
@@ -161,3 +166,90 @@ def extract_mesh_MESHUDF(df_values, normals, device, smooth_borders=False, luts=
                 avg = sp @ mesh.vertices / sp.sum(axis=1)
                 mesh.vertices[bv] = mesh.vertices[bv] + 0.3 * (np.asarray(avg) - mesh.vertices[bv])
     return torch.tensor(mesh.vertices).float().to(device), torch.tensor(mesh.faces).long().to(device), mesh
+
+
+def gen_sdf_coordinate_grid(N, voxel_size, device, voxel_origin=[-1, -1, -1]):
+    """Reference src/render_mc.py:259-311: the (N**3, 4) float32 tensor on `device` whose first three columns are the grid
+    coordinates (first axis slowest; column k = index_k * voxel_size + voxel_origin[2 - k]) and whose last column, zero, is
+    where the reference stores the values.  `get_mesh_sdf` here does not need it (the kernel derives coordinates from the
+    index); it is kept for callers of the reference's function."""
+    overall_index = torch.arange(0, N ** 3, 1, dtype=torch.int64)
+    samples = torch.zeros(N ** 3, 4, device=device, requires_grad=False)
+    samples[:, 2] = overall_index % N
+    samples[:, 1] = (overall_index.long() / N) % N
+    samples[:, 0] = ((overall_index.long() / N) / N) % N
+    samples[:, 0] = (samples[:, 0] * voxel_size) + voxel_origin[2]
+    samples[:, 1] = (samples[:, 1] * voxel_size) + voxel_origin[1]
+    samples[:, 2] = (samples[:, 2] * voxel_size) + voxel_origin[0]
+    return samples
+
+
+def sdf_grid_values(decoder, N, device, max_batch=64 ** 3):
+    """The (N, N, N) float32 device tensor of raw network outputs on the grid (`dudf_grid_values` in chunks of `max_batch`)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise DudfError("get_mesh_sdf: needs the GPU; there is no CPU fallback path")
+    cfg = decoder.hip_cfg
+    theta = decoder.flat_parameters()
+    total = N ** 3
+    out = torch.empty(total, dtype=torch.float32, device=dev)
+    chunk = max(1, min(int(max_batch), total))
+    ws = hip_ops.query_workspace_for(cfg, chunk, dev)
+    start = 0
+    while start < total:
+        cnt = min(chunk, total - start)
+        hip_ops.grid_values(cfg, theta, N, start, cnt, out, ws if cnt == ws.n else hip_ops.QueryWorkspace(cfg, cnt, dev))
+        start += cnt
+    return out.reshape(N, N, N)
+
+
+def convert_sdf_samples_to_ply(pytorch_3d_sdf_tensor, voxel_grid_origin, voxel_size, offset=None, scale=None, luts=None):
+    """Reference src/render_mc.py:360-406: marching cubes at level 0 of an (n, n, n) field, vertices moved to the voxel origin,
+    then `/ scale` and `- offset`.  A field without the zero level prints the reference's message and gives empty arrays.  A CUDA
+    tensor stays on the device (tensors come back); a CPU tensor or numpy array runs in the host library (numpy comes back)."""
+    from .marching_cubes import marching_cubes_lewiner
+    vol = pytorch_3d_sdf_tensor
+    on_dev = torch.is_tensor(vol) and vol.is_cuda
+    if torch.is_tensor(vol) and not on_dev:
+        vol = vol.numpy()
+    verts, faces, normals, values = np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0)
+    level = 0.0
+    if level < float(vol.min()) or level > float(vol.max()):
+        print("Surface level must be within volume data range.")
+        if on_dev:
+            verts, faces, normals, values = (torch.from_numpy(a).to(vol.device) for a in (verts, faces, normals, values))
+    else:
+        verts, faces, normals, values = marching_cubes_lewiner(vol, level, spacing=[voxel_size] * 3, luts=luts)
+    mesh_points = torch.zeros_like(verts) if on_dev else np.zeros_like(verts)
+    mesh_points[:, 0] = voxel_grid_origin[0] + verts[:, 0]
+    mesh_points[:, 1] = voxel_grid_origin[1] + verts[:, 1]
+    mesh_points[:, 2] = voxel_grid_origin[2] + verts[:, 2]
+    if on_dev:                                           # as tensors: torch divides by a Python scalar through its reciprocal
+        as_dev = lambda a: torch.as_tensor(np.atleast_1d(np.asarray(a, dtype=np.float64)), device=mesh_points.device)  # noqa: E731
+        scale, offset = (None if a is None else as_dev(a) for a in (scale, offset))
+    if scale is not None:
+        mesh_points = mesh_points / scale
+    if offset is not None:
+        mesh_points = mesh_points - offset
+    return mesh_points, faces, normals, values
+
+
+def get_mesh_sdf(decoder, N=256, device=None, max_batch=64 ** 3, offset=None, scale=None, luts=None):
+    """Reference src/render_mc.py:314-358: the zero level set of a signed network on the N^3 grid of [-1, 1]^3.  The values come
+    from `dudf_grid_values` in chunks of `max_batch`, the mesh from the device marching cubes; nothing of size N^3 leaves the
+    device (the reference copies every chunk and the whole grid to the host and calls scikit-image).  `luts`: the Lewiner tables,
+    as for `extract_mesh_MESHUDF`.  Returns (verts, faces, mesh) as numpy arrays and a `trimesh.Trimesh(vertices, faces,
+    vertex_normals=normals)` when trimesh is importable, else a `TriangleSoup` that carries those normals."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", 0)
+    if hasattr(decoder, "eval"):
+        decoder.eval()
+    voxel_origin = [-1, -1, -1]
+    voxel_size = 2.0 / (N - 1)
+    sdf_values = sdf_grid_values(decoder, N, dev, max_batch)
+    verts, faces, normals, _ = convert_sdf_samples_to_ply(sdf_values, voxel_origin, voxel_size, offset, scale, luts=luts)
+    verts, faces, normals = verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy()
+    try:
+        import trimesh
+        return verts, faces, trimesh.Trimesh(vertices=verts, faces=faces, vertex_normals=normals)
+    except ImportError:
+        return verts, faces, TriangleSoup(verts, faces, vertex_normals=normals)

@@ -10,19 +10,21 @@ src/marching_cubes as host C++), 'cap' (row 2, on the device) and 'both' (what t
 MeshUDF needs the Lewiner look-up tables, which are an input, not part of this package: `luts=` / config key "luts_path"
 (an .npz or the reference's `_marching_cubes_lewiner_luts.py`), $DUDF_MESHUDF_LUTS, or that module on sys.path (inside a
 reference checkout: `sys.path.append('src/marching_cubes')`) — `diffudf_amd.marching_cubes.load_luts`.
-'siren' (skimage's marching cubes on an SDF) is outside the build: it raises."""
+'siren' (reference generate_mc.py:56-65): `get_mesh_sdf` — the raw network values on the grid and Lewiner's marching cubes of
+that signed volume, both on the device; it needs the same tables, and without them prints a message, writes nothing and returns
+None (as 'both' skips its MeshUDF half), so that a training run is not lost over its mesh."""
 import json
 import sys
 
 import torch
 
 from src.model import SIREN
-from src.render_mc import extract_fields, extract_mesh_CAP, extract_mesh_MESHUDF
+from src.render_mc import extract_fields, extract_mesh_CAP, extract_mesh_MESHUDF, get_mesh_sdf
 from diffudf_amd.marching_cubes import MeshUDFError
 
 
 def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='meshudf', from_file=None, luts=None):
-    """`luts`: the Lewiner tables for the MeshUDF half (dict, path or None = look them up; see the module docstring)."""
+    """`luts`: the Lewiner tables for MeshUDF and 'siren' (dict, path or None = look them up; see the module docstring)."""
     if from_file is not None:
         model = SIREN(n_in_features=3, n_out_features=1, hidden_layer_config=from_file["hidden_layer_nodes"],
                       w0=from_file["w0"], ww=from_file.get("ww"), activation=from_file.get('activation', 'sine'))
@@ -52,7 +54,16 @@ def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='m
         mesh_mu.export(path_mu)
         print(f'Saved to {path_mu}, {path_cap}')
         return mesh_mu, mesh
-    raise ValueError(f"algorithm '{algorithm}' is not part of this build ('cap', 'meshudf', 'both')")
+    if algorithm == 'siren':
+        try:
+            _, _, mesh = get_mesh_sdf(model, N=N, device=dev, luts=luts)
+        except MeshUDFError as e:                              # no look-up tables: nothing is written, and the caller (a training) goes on
+            print(f'{output_path} not written (signed marching cubes skipped: {e})')
+            return None
+        mesh.export(output_path)
+        print(f'Saved to {output_path}')
+        return mesh
+    raise ValueError(f"algorithm '{algorithm}' is not part of this build ('cap', 'meshudf', 'both', 'siren')")
 
 
 if __name__ == "__main__":

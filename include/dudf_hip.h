@@ -339,6 +339,30 @@ int dudf_capudf_count(const float* ndf, const float* grad, int64_t grid_n, doubl
 int dudf_capudf_emit(const float* ndf, const float* grad, int64_t grid_n, double threshold, double* out_vertices,
                      int64_t* out_triangles, int64_t* out_cells, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The raw network output on the grid — the value loop of `get_mesh_sdf` (reference src/render_mc.py:335-348) for grid points
+ * start .. start+count-1 of the regular grid_n^3 grid on [-1,1]^3 (indexing and coordinates as dudf_grid_fields): out_f (count) = f,
+ * sign kept — no |.|, no inverse map, no gradient (the forward sweep only).  Workspace of dudf_workspace_bytes_query(cfg, count, 0). */
+int dudf_grid_values(const dudf_net_cfg* cfg, const float* theta, int64_t grid_n, int64_t start, int64_t count, float* out_f,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Lewiner marching cubes of a signed volume on the device — what `marching_cubes(volume, level)` does for `get_mesh_sdf` (reference
+ * src/render_mc.py:389, scikit-image on the host there) without the volume leaving the device.  volume [nz][ny][nx] float (device,
+ * first axis slowest), corner value (double)volume - level, inside where > 0, every cube in raster order.  The Lewiner tables are an
+ * input as they are for libdudf_meshudf.so (include/dudf_meshudf.h; order and packing of `marching_cubes._pack_luts`): lut_data int8
+ * on the DEVICE (4-byte aligned, at most 18 KiB), lut_offsets[n_luts] and lut_dims[n_luts][3] on the HOST, n_luts = 51.
+ * The output equals dudf_mc_lewiner_run of that library bit for bit and in the same order.  Two calls, the size being data dependent:
+ *   dudf_mc_lewiner_count -> out_counts (device, 2 x int64): vertices V, triangles T;
+ *   dudf_mc_lewiner_emit  -> out_vertices (V,3) float (x, y, z in grid units), out_faces (T,3) int32, out_normals (V,3) float (the
+ *                            unnormalised sums), out_values (V) float; same volume / level / tables / workspace as the count call.
+ * Dimensions 2 .. 2048 each; V must stay below 2^31 (int32 faces, as the reference). */
+size_t dudf_mc_lewiner_workspace_bytes(int64_t nz, int64_t ny, int64_t nx);
+int dudf_mc_lewiner_count(const float* volume, int64_t nz, int64_t ny, int64_t nx, double level, const signed char* lut_data,
+                          const int64_t* lut_offsets, const int32_t* lut_dims, int n_luts, int64_t* out_counts, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int dudf_mc_lewiner_emit(const float* volume, int64_t nz, int64_t ny, int64_t nx, double level, const signed char* lut_data,
+                         const int64_t* lut_offsets, const int32_t* lut_dims, int n_luts, float* out_vertices, int32_t* out_faces,
+                         float* out_normals, float* out_values, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Forward half of loss_s1 / loss_siren (reference src/loss_functions.py:123-155, :82-104):
  * SIREN forward, df/dx, the four weighted loss terms.  out_terms (device, 4 floats) receives
  * THIS RANK's share  sum_local(term_i) * weight / n_global  in the reference's dict order

@@ -1,4 +1,4 @@
-/* C ABI of libdudf_meshudf.so — MeshUDF marching cubes on the host (C++17, no GPU, no torch types).
+/* C ABI of libdudf_meshudf.so — MeshUDF and signed Lewiner marching cubes on the host (C++17, no GPU, no torch types).
  *
  * Replaces the reference's Cython extension entry point
  *   _marching_cubes_lewiner_cy.marching_cubes_udf(im, grads, luts, st=1, classic=0, avg_thresh, max_thresh, mask=None)
@@ -26,6 +26,15 @@ extern "C" {
  * Returns an opaque result handle, or NULL (bad arguments, n_luts != 51, allocation failure). */
 void* dudf_meshudf_run(const float* udf, const float* grads, int nz, int ny, int nx, const signed char* lut_data,
                        const long long* lut_offsets, const int* lut_dims, int n_luts, float avg_thresh, float max_thresh);
+/* Lewiner marching cubes of a SIGNED volume [nz][ny][nx] float32 at iso value `level` — the native half of the wrapper's
+ * `marching_cubes_lewiner` (reference src/marching_cubes/_marching_cubes_lewiner.py:7-76; the reference itself reaches it through
+ * scikit-image, src/render_mc.py:389): every cube in raster order (first axis slowest), corner value (double)volume - level, corner
+ * "inside" where that is > 0, no thin-cube filter, no pseudo-signs, no flood; triangulation, vertex slots, positions, values and
+ * normal sums are those of dudf_meshudf_run.  Same table packing, same handle: read it with dudf_meshudf_sizes / _copy / _free.
+ * Also the checker of the device kernels dudf_mc_lewiner_count / dudf_mc_lewiner_emit (include/dudf_hip.h), which give the same
+ * bits in the same order. */
+void* dudf_mc_lewiner_run(const float* volume, int nz, int ny, int nx, double level, const signed char* lut_data,
+                          const long long* lut_offsets, const int* lut_dims, int n_luts);
 /* number of vertices and of face INDICES (3 per triangle) */
 void dudf_meshudf_sizes(const void* handle, long long* n_vertices, long long* n_face_indices);
 /* vertices [n][3] float32 in (x, y, z) grid units, faces int32, normals [n][3] = the accumulated (unnormalised) gradient

@@ -20,8 +20,13 @@ After training (reference train.py:403-446): the field slice of the best model (
 reference) and, when `resolution != 0`, its meshes (`generate_mc` algorithm 'both': CAP-UDF on the device and MeshUDF's
 marching cubes in host C++; the latter needs the Lewiner tables — config key `luts_path`, $DUDF_MESHUDF_LUTS or the
 reference's table module on sys.path — and is skipped with a message when they are not there) are written to
-`reconstructions/`.  gt_mode 'siren' trains, but its post-training artefacts (skimage's SDF marching cubes) are outside
-this build: a message says so.  tensorboard is optional.
+`reconstructions/`.  gt_mode 'siren' writes the slice and the signed mesh instead (`generate_mc` algorithm 'siren': the network's
+values on the grid and Lewiner's marching cubes, both on the device, where the reference calls scikit-image; same tables, and
+likewise skipped with a message when they are not there: the run finishes, with the slice and without meshes), at the periodic
+checkpoints too (reference train.py:121-129).  tensorboard is optional.
+
+`setup_train` returns `(training_time, meshes)`: for gt_mode 'tanh' the pair `(mesh_MU or None, mesh_CAP)` of algorithm 'both', for
+gt_mode 'siren' the one signed mesh (or None without the tables), and `[]` when no mesh was asked for or no epoch improved.
 """
 import argparse
 import copy
@@ -164,14 +169,16 @@ def _train(dataset, model, device, config, schedule):
                 torch.save(snapshot_state(snap), ckpt)
                 # ... and its mesh, as reference train.py:253-268 (generate_mc, algorithm 'both', at every periodic checkpoint);
                 # from the checkpoint FILE: the live parameters are already an epoch further (bookkeeping runs one epoch late)
-                if config.get("gt_mode") == 'tanh' and config.get("resolution", 256) and config.get("network"):
+                # gt_mode 'siren': the signed mesh instead (`get_mesh_sdf`), as reference train.py:121-129
+                if config.get("gt_mode") in ('tanh', 'siren') and config.get("resolution", 256) and config.get("network"):
                     print("Generating mesh")
                     from generate_mc import generate_mc
                     net = config["network"]
                     os.makedirs(osp.join(log_path, "reconstructions"), exist_ok=True)
                     generate_mc(model=None, gt_mode=config["gt_mode"], device=int(device.index or 0), N=config.get('resolution', 256),
-                                output_path=osp.join(log_path, "reconstructions", f'mc_mesh_{epoch}.obj'), alpha=config['alpha'],
-                                algorithm='both', from_file={'w0': net["w0"], 'model_path': ckpt,
+                                output_path=osp.join(log_path, "reconstructions", f'mc_mesh_{epoch}.obj'), alpha=config.get('alpha'),
+                                algorithm='both' if config["gt_mode"] == 'tanh' else 'siren',
+                                from_file={'w0': net["w0"], 'model_path': ckpt,
                                                              'hidden_layer_nodes': net["hidden_layer_nodes"],
                                                              'activation': net.get('activation', 'sine'),
                                                              'ww': net.get('ww')},           # the hidden layers' own frequency, if the config has one (reference train.py:322)
@@ -390,6 +397,7 @@ def setup_train(parameter_dict, cuda_device):
             "optimizer": optimizer, "loss_weights": parameter_dict["loss_weights"],
             "alpha": parameter_dict.get("alpha", 100), "resolution": parameter_dict.get("resolution", 256),
             "save_every_epoch": parameter_dict.get("save_every_epoch", True),
+            "network": network_params, "luts_path": parameter_dict.get("luts_path"),
             "hip_graph": parameter_dict.get("hip_graph", True),
         }
         losses, best_weights, training_time = train_model_siren(dataset, model, device, config_dict)
@@ -405,13 +413,11 @@ def setup_train(parameter_dict, cuda_device):
     meshes = []
     if _is_main():
         # post-training artefacts as in reference train.py:403-446: the field slice of the best model (always) and, when
-        # `resolution != 0`, its meshes (algorithm 'both') — rank 0 only, the other ranks go on to tear down
+        # `resolution != 0`, its meshes (algorithm 'both', or 'siren' for gt_mode 'siren') — rank 0 only, the other ranks go on to tear down
         from generate_df import generate_df, generate_df_pc
         from generate_mc import generate_mc
         best = osp.join(full_path, "models", "model_best.pth")
-        if gt_mode != 'tanh':
-            print(f"post-training artefacts skipped: gt_mode '{gt_mode}' needs skimage's SDF marching cubes, which is outside this build")
-        elif not osp.exists(best):
+        if not osp.exists(best):
             print(f"post-training artefacts skipped: {best} was never written (no epoch improved on the initial loss)")
         else:
             print('Generating distance field slices')
@@ -429,7 +435,7 @@ def setup_train(parameter_dict, cuda_device):
                 print('Generating mesh')
                 meshes = generate_mc(model=None, gt_mode=gt_mode, device=int(device.index or 0), N=parameter_dict.get('resolution', 256),
                                      output_path=osp.join(full_path, "reconstructions", 'mc_mesh_best.obj'),
-                                     alpha=parameter_dict.get('alpha', 1), algorithm='both',
+                                     alpha=parameter_dict.get('alpha', 1), algorithm='both' if gt_mode == 'tanh' else 'siren',
                                      from_file={'w0': network_params["w0"], 'model_path': best,
                                                 'hidden_layer_nodes': network_params["hidden_layer_nodes"],
                                                 'activation': network_params.get('activation', 'sine')},
