@@ -16,18 +16,19 @@
 //   pass 1  count : 8 coalesced row reads of ndf per cell (neighbouring cells and rows hit L1/L2: ~4 B/cell from HBM),
 //                   the 8 direction vectors only for active cells (a thin shell around the surface); per-workgroup
 //                   totals (cells, vertices, triangles)
-//   pass 2  scan  : exclusive scan of the workgroup totals (one workgroup; <= 524 k entries at 512^3)
-//   pass 3  emit  : the same per-cell evaluation, an in-workgroup exclusive scan (wave shuffles + 4 LDS words), float64
+//   pass 2  scan  : exclusive scan of the workgroup totals (dudf_scan_totals_kernel<3>: one workgroup; <= 524 k entries at 512^3)
+//   pass 3  emit  : the same per-cell evaluation, an in-workgroup exclusive scan (dudf_wg_scan), float64
 //                   vertices and int64 triangle indices written at their final offsets — deterministic, no atomics.
 // The caller reads the three totals between pass 2 and pass 3 to size the outputs.
 #include "dudf_internal.h"
+#include "dudf_wgscan.h"
 
 namespace {
 
 #define DUDF_MC_QUAL __constant__ const
 #include "dudf_mc_table.h"          // kMcEdgeMask[256], kMcTri[256][1 + 3 * DUDF_MC_MAX_TRI], kMcEdgeCorner[12][2]
 
-constexpr int CB = 256;                                  // cells per workgroup
+constexpr int CB = DUDF_WG;                              // cells per workgroup
 
 struct CapArgs {
     const float* ndf; const float* grad;
@@ -100,32 +101,6 @@ __global__ __launch_bounds__(CB) void capudf_count_kernel(CapArgs a) {
     }
 }
 
-// exclusive scan of the per-workgroup totals; totals -> out_counts (3 x int64)
-__global__ __launch_bounds__(1024) void capudf_scan_kernel(const uint32_t* __restrict__ blk, int64_t* __restrict__ off,
-                                                           int64_t nblocks, int64_t* __restrict__ out_counts) {
-    __shared__ int64_t s[3][1024];
-    const int t = threadIdx.x;
-    const int64_t chunk = (nblocks + 1023) / 1024;
-    const int64_t b0 = (int64_t)t * chunk, b1 = (b0 + chunk < nblocks) ? b0 + chunk : nblocks;
-    int64_t sum[3] = {0, 0, 0};
-    for (int64_t b = b0; b < b1; ++b)
-        for (int q = 0; q < 3; ++q) sum[q] += blk[b * 3 + q];
-    for (int q = 0; q < 3; ++q) s[q][t] = sum[q];
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {                  // inclusive Hillis-Steele over the 1024 partial sums
-        int64_t add[3] = {0, 0, 0};
-        if (t >= d) for (int q = 0; q < 3; ++q) add[q] = s[q][t - d];
-        __syncthreads();
-        for (int q = 0; q < 3; ++q) s[q][t] += add[q];
-        __syncthreads();
-    }
-    int64_t run[3];
-    for (int q = 0; q < 3; ++q) run[q] = s[q][t] - sum[q];
-    for (int64_t b = b0; b < b1; ++b)
-        for (int q = 0; q < 3; ++q) { off[b * 3 + q] = run[q]; run[q] += blk[b * 3 + q]; }
-    if (t == 1023) for (int q = 0; q < 3; ++q) out_counts[q] = s[q][1023];
-}
-
 __global__ __launch_bounds__(CB) void capudf_emit_kernel(CapArgs a) {
     __shared__ unsigned part[CB / 64];
     const int64_t cell = (int64_t)blockIdx.x * CB + threadIdx.x;
@@ -133,19 +108,12 @@ __global__ __launch_bounds__(CB) void capudf_emit_kernel(CapArgs a) {
     unsigned w = 0;
     const bool live = cell < a.ncells && eval_cell(a, cell, ce);
     if (live) w = pack_counts(ce.idx);
-    // exclusive scan of the three packed counts over the workgroup (the fields cannot overflow: <= 256 / 3072 / 1280)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = w;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(inc, o);
-        if (lane >= o) inc += up;
-    }
-    if (lane == 63) part[wave] = inc;
-    __syncthreads();
-    unsigned before = 0;
-    for (int q = 0; q < wave; ++q) before += part[q];
-    const unsigned exc = before + inc - w;
+    // exclusive scan of the three packed counts over the workgroup: one word, no field can carry into the next (<= 256 / 3072 / 1280).
+    // The shared helper's total is not needed here (the compiler drops it) and its leading barrier is one more than a private scan
+    // of words nobody else uses would need: the price of ONE scan for all extraction kernels.  The extraction's time stays inside
+    // the parent's run-to-run spread (profiles/HISTORY.md).
+    unsigned total;
+    const unsigned exc = dudf_wg_scan(w, part, &total);
     if (!live) return;
     const int64_t* o3 = a.off + (int64_t)blockIdx.x * 3;
     const int64_t c0 = o3[0] + (exc & 0x1ff), v0 = o3[1] + ((exc >> 9) & 0xfff), t0 = o3[2] + (exc >> 21);
@@ -217,7 +185,7 @@ int dudf_capudf_count(const float* ndf, const float* grad, int64_t grid_n, doubl
     DudfProfScope prof(PROF_OTHER, st);
     const int64_t nb = cap_blocks(grid_n);
     hipLaunchKernelGGL(capudf_count_kernel, dim3((unsigned)nb), dim3(CB), 0, st, a);
-    hipLaunchKernelGGL(capudf_scan_kernel, dim3(1), dim3(1024), 0, st, a.blk, a.off, nb, out_counts);
+    hipLaunchKernelGGL(dudf_scan_totals_kernel<3>, dim3(1), dim3(1024), 0, st, a.blk, a.off, nb, out_counts);
     return (int)hipGetLastError();
 }
 

@@ -22,13 +22,7 @@ constexpr int kNnRows = kNnBlock * kNnPpl;       // rows of x per workgroup
 constexpr int kNnTile = 1024;                    // rows of y per LDS tile (16 KiB)
 constexpr int kNnTargetGroups = 4096;            // workgroups a launch aims for: two resident rounds of 8 per CU
 constexpr unsigned kNanBits = 0x7fc00000u;
-
-inline int grid_for(int64_t n, int block = 256, int cap = 4096) {
-    int64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
+constexpr int kGridCap = 4096;                   // workgroups of the row-wise launches; the kernels stride over the rest
 
 // ONE sequence of roundings for every pair: the fused steps are written out and contraction is off, so the unrolled body, its
 // remainder loop and any packed form the compiler picks give the same bits (a pair's distance must not depend on where in a tile it falls).
@@ -173,14 +167,14 @@ __global__ __launch_bounds__(256) void vertex_normalize_kernel(const double* __r
     }
 }
 
-inline size_t round256(size_t b) { return b < 256 ? 256 : (b + 255) / 256 * 256; }
-inline int terms_groups(int64_t n) { return grid_for(n, kTermsBlock, kTermsMaxGroups); }
+inline int terms_groups(int64_t n) { return dudf_grid_for(n, kTermsBlock, kTermsMaxGroups); }
 
 }  // namespace
 
 extern "C" {
 
-size_t dudf_nearest_workspace_bytes(int64_t n) { return round256((size_t)(n > 0 ? n : 0) * sizeof(unsigned long long)); }
+// the three byte counts of this unit are never 0: an empty input still asks for one 256-byte granule
+size_t dudf_nearest_workspace_bytes(int64_t n) { return n > 0 ? dudf_round256((size_t)n * sizeof(unsigned long long)) : 256; }
 
 int dudf_nearest_points(const float* x, int64_t n, const float* y, int64_t m, int norm, float* out_dist, int64_t* out_idx,
                         void* workspace, size_t workspace_bytes, void* stream) {
@@ -212,11 +206,12 @@ int dudf_nearest_points(const float* x, int64_t n, const float* y, int64_t m, in
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     if (out_dist || out_idx)
-        hipLaunchKernelGGL(nearest_finish_kernel, dim3(grid_for(n)), dim3(256), 0, st, keys, n, (int)m, out_dist, out_idx);
+        hipLaunchKernelGGL(nearest_finish_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), 0, st, keys, n, (int)m,
+                           out_dist, out_idx);
     return (int)hipGetLastError();
 }
 
-size_t dudf_chamfer_terms_workspace_bytes(int64_t n) { return round256((size_t)terms_groups(n) * 2 * sizeof(double)); }
+size_t dudf_chamfer_terms_workspace_bytes(int64_t n) { return dudf_round256((size_t)terms_groups(n) * 2 * sizeof(double)); }   // >= 1 group: >= 256
 
 int dudf_chamfer_terms(const float* dist, const int64_t* idx, int64_t n, const float* x_normals, const float* y_normals, int64_t m,
                        double* out_sums, void* workspace, size_t workspace_bytes, void* stream) {
@@ -238,7 +233,7 @@ int dudf_chamfer_terms(const float* dist, const int64_t* idx, int64_t n, const f
 }
 
 size_t dudf_vertex_normals_workspace_bytes(int64_t n_vertices) {
-    return round256((size_t)(n_vertices > 0 ? n_vertices : 0) * 3 * sizeof(double));
+    return n_vertices > 0 ? dudf_round256((size_t)n_vertices * 3 * sizeof(double)) : 256;
 }
 
 int dudf_vertex_normals(const double* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, float* out_normals,
@@ -253,11 +248,13 @@ int dudf_vertex_normals(const double* vertices, int64_t n_vertices, const int64_
     hipError_t e = hipMemsetAsync(acc, 0, (size_t)n_vertices * 3 * sizeof(double), st);
     if (e != hipSuccess) return (int)e;
     if (n_faces > 0) {
-        hipLaunchKernelGGL(face_normals_kernel, dim3(grid_for(n_faces)), dim3(256), 0, st, vertices, n_vertices, faces, n_faces, acc);
+        hipLaunchKernelGGL(face_normals_kernel, dim3(dudf_grid_for(n_faces, 256, kGridCap)), dim3(256), 0, st, vertices,
+                           n_vertices, faces, n_faces, acc);
         e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL(vertex_normalize_kernel, dim3(grid_for(n_vertices)), dim3(256), 0, st, acc, n_vertices, out_normals);
+    hipLaunchKernelGGL(vertex_normalize_kernel, dim3(dudf_grid_for(n_vertices, 256, kGridCap)), dim3(256), 0, st, acc, n_vertices,
+                       out_normals);
     return (int)hipGetLastError();
 }
 

@@ -108,6 +108,17 @@ inline int dudf_wgrad_max_workgroups() { return dudf_options().wgrad_max_workgro
 // carves arrays out of a buffer of floats: every array starts on a 64-float (256-byte) granule
 struct DudfCarver { int64_t o; int64_t take(int64_t cnt) { const int64_t r = o; o += (cnt + 63) / 64 * 64; return r; } };
 
+// workgroups of `block` threads for n items, at least 1 and at most `cap` (the kernels stride over the rest)
+inline int dudf_grid_for(int64_t n, int block, int cap) {
+    int64_t g = (n + block - 1) / block;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (int)g;
+}
+
+// bytes rounded up to a whole 256-byte granule; 0 stays 0
+inline size_t dudf_round256(size_t b) { return (b + 255) / 256 * 256; }
+
 static inline int dudf_make_layout(const dudf_net_cfg* cfg, int64_t n, int64_t n_h, DudfLayout* lo, int query_only = 0) {
     if (!cfg || cfg->n_in != 3 || cfg->n_hidden_layers < 1) return DUDF_E_BADCFG;
     const int H = cfg->hidden, L = cfg->n_hidden_layers;
@@ -261,11 +272,11 @@ int dudf_launch_copy_out(const DudfLayout& lo, const float* ws, float* out_f, fl
                          hipStream_t st);
 // x4 from double positions (sphere tracing, point projection; dudf_query.hip)
 int dudf_launch_rays_x4(const DudfLayout& lo, const double* t0, float* ws, hipStream_t st);
-// dudf_pointcloud.hip: ordered compaction / append behind a device row counter (scratch: 2 * dudf_pc_tiles(n) ints); dudf_render_gather
-// gathers its hits through it
+// dudf_pointcloud.hip: ordered compaction / append behind a device row counter (scratch: 2 * dudf_pc_tiles(n) ints).  rows (or
+// nullptr): rows[i] = the source row of the i-th row this call adds; dudf_render_gather gathers its hits and their image rows through it
 int64_t dudf_pc_tiles(int64_t n);
 int dudf_launch_pc_append(const unsigned char* flags, int64_t n, const double* src_a, const double* src_b, const float* src_f,
-                          double* dst_a, double* dst_b, float* out_f, int64_t capacity, int64_t quota, int64_t* counter,
+                          double* dst_a, double* dst_b, float* out_f, int* rows, int64_t capacity, int64_t quota, int64_t* counter,
                           int* scratch, hipStream_t st);
 
 // products per algorithmic multiply of the kernel a launcher is about to start in profile slot `slot`: 1 = f32-input MFMA,

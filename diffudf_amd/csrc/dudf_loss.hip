@@ -413,12 +413,7 @@ __global__ __launch_bounds__(256) void copy_in_kernel(const float* __restrict__ 
     }
 }
 
-inline int grid_for(int64_t n, int block = 256, int cap = 2048) {
-    int64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
+constexpr int kGridCap = 2048;                         // workgroups per launch; the kernels stride over the rest
 
 LossArgs make_loss_args(const DudfLayout& lo, const float* normals, const float* sdf, int64_t n_global,
                         const double* w, double alpha, float* ws) {
@@ -457,7 +452,7 @@ int dudf_launch_loss_fwd(const DudfLayout& lo, int mode, const float* normals, c
     // four addresses: at 391 blocks (100 000 points) the kernel spent 30 us queueing them; without the Hessian term a point
     // costs a few dozen flops, so 128 blocks with a grid-stride loop finish sooner.  (With it — an fp64 Jacobi eigensolve per
     // on-surface point — the work dominates: as many blocks as there are points for.)
-    int grid = dudf_deterministic() ? 1 : grid_for(lo.n);
+    int grid = dudf_deterministic() ? 1 : dudf_grid_for(lo.n, 256, kGridCap);
     if (!dudf_deterministic() && !(mode == DUDF_LOSS_S1 && w[2] != 0.0 && lo.n_h > 0) && grid > 128) grid = 128;
     if (mode == DUDF_LOSS_S1) hipLaunchKernelGGL(loss_fwd_kernel<DUDF_LOSS_S1>, dim3(grid), dim3(256), 0, st, a);
     else if (mode == DUDF_LOSS_SIREN) hipLaunchKernelGGL(loss_fwd_kernel<DUDF_LOSS_SIREN>, dim3(grid), dim3(256), 0, st, a);
@@ -474,7 +469,7 @@ int dudf_launch_loss_bwd(const DudfLayout& lo, int mode, const float* normals, c
     a.zero_f = zero_f; a.zero_fn = zero_f ? zero_fn : 0;
     // a backward may run several times per forward: the running maxima of A_l and zbar_l (rows 1, 2 of amax) start over
     a.zero_u = reinterpret_cast<unsigned*>(ws + lo.ws_amax) + lo.L; a.zero_un = (dudf_split_fp16() && 2 * lo.L <= 256) ? 2 * lo.L : 0;
-    const int grid = grid_for(lo.np);
+    const int grid = dudf_grid_for(lo.np, 256, kGridCap);
     if (mode == DUDF_LOSS_S1) hipLaunchKernelGGL(loss_bwd_kernel<DUDF_LOSS_S1>, dim3(grid), dim3(256), 0, st, a);
     else if (mode == DUDF_LOSS_SIREN) hipLaunchKernelGGL(loss_bwd_kernel<DUDF_LOSS_SIREN>, dim3(grid), dim3(256), 0, st, a);
     else if (mode == DUDF_LOSS_S2) hipLaunchKernelGGL(loss_bwd_kernel<DUDF_LOSS_S2>, dim3(grid), dim3(256), 0, st, a);
@@ -487,7 +482,8 @@ int dudf_launch_s2_stats(const DudfLayout& lo, const float* sdf, float* ws, doub
     if (e != hipSuccess) return (int)e;
     const double w0[4] = {0, 0, 0, 0};
     LossArgs a = make_loss_args(lo, nullptr, sdf, 1, w0, 0.0, ws);
-    hipLaunchKernelGGL(s2_stats_kernel, dim3(dudf_deterministic() ? 1 : grid_for(lo.n)), dim3(256), 0, st, a, stats);
+    hipLaunchKernelGGL(s2_stats_kernel, dim3(dudf_deterministic() ? 1 : dudf_grid_for(lo.n, 256, kGridCap)), dim3(256), 0, st, a,
+                       stats);
     return (int)hipGetLastError();
 }
 
@@ -501,8 +497,8 @@ int dudf_launch_adam(float* theta, const float* g, float* m, float* v, int64_t n
     DudfProfScope prof(PROF_ADAM, st);
     float step_size, bc2_sqrt;
     dudf_adam_factors(lr, b1, b2, step, &step_size, &bc2_sqrt);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, st, theta, g, m, v, n, (float)(1.0 - b1), (float)b2,
-                       (float)(1.0 - b2), (float)eps, step_size, bc2_sqrt, (float)gscale);
+    hipLaunchKernelGGL(adam_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), 0, st, theta, g, m, v, n, (float)(1.0 - b1),
+                       (float)b2, (float)(1.0 - b2), (float)eps, step_size, bc2_sqrt, (float)gscale);
     return (int)hipGetLastError();
 }
 
@@ -514,29 +510,29 @@ void dudf_adam_factors(double lr, double b1, double b2, int64_t step, float* ste
 int dudf_launch_adam_sched(float* theta, const float* g, float* m, float* v, int64_t n, double b1, double b2, double eps,
                            const float* sched, int64_t n_rows, const int64_t* row, double gscale, hipStream_t st) {
     DudfProfScope prof(PROF_ADAM, st);
-    hipLaunchKernelGGL(adam_sched_kernel, dim3(grid_for(n)), dim3(256), 0, st, theta, g, m, v, n, (float)(1.0 - b1), (float)b2,
-                       (float)(1.0 - b2), (float)eps, sched, n_rows, row, (float)gscale);
+    hipLaunchKernelGGL(adam_sched_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), 0, st, theta, g, m, v, n,
+                       (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps, sched, n_rows, row, (float)gscale);
     return (int)hipGetLastError();
 }
 
 int dudf_launch_read_stash(const DudfLayout& lo, const float* src, int layer, int channel, float* out, hipStream_t st, int per_quad, int p24,
                            const float* fx) {
-    hipLaunchKernelGGL(read_stash_kernel, dim3(grid_for(lo.n * lo.H)), dim3(256), 0, st,
-                       src + (int64_t)layer * (p24 ? lo.stash_layer / 4 * 3 : lo.stash_layer), out, lo.n, lo.n_h, lo.ncol_h, lo.np, lo.H,
-                       channel, per_quad, p24, fx ? fx + (int64_t)layer * lo.np : nullptr);
+    hipLaunchKernelGGL(read_stash_kernel, dim3(dudf_grid_for(lo.n * lo.H, 256, kGridCap)), dim3(256), 0, st,
+                       src + (int64_t)layer * (p24 ? lo.stash_layer / 4 * 3 : lo.stash_layer), out, lo.n, lo.n_h, lo.ncol_h, lo.np,
+                       lo.H, channel, per_quad, p24, fx ? fx + (int64_t)layer * lo.np : nullptr);
     return (int)hipGetLastError();
 }
 
 int dudf_launch_copy_in(const DudfLayout& lo, const float* ybar, const float* gbar, float* ws, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(copy_in_kernel, dim3(grid_for(lo.np)), dim3(256), 0, st, ybar, gbar, ws + lo.ws_ybar,
+    hipLaunchKernelGGL(copy_in_kernel, dim3(dudf_grid_for(lo.np, 256, kGridCap)), dim3(256), 0, st, ybar, gbar, ws + lo.ws_ybar,
                        ws + lo.ws_gbar, lo.n, lo.n_h, lo.ncol_h, lo.np);
     return (int)hipGetLastError();
 }
 
 int dudf_launch_make_x4(const DudfLayout& lo, const float* x, float* ws, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(make_x4_kernel, dim3(grid_for(lo.np)), dim3(256), 0, st, x, ws + lo.ws_x4, lo.n, lo.n_h,
+    hipLaunchKernelGGL(make_x4_kernel, dim3(dudf_grid_for(lo.np, 256, kGridCap)), dim3(256), 0, st, x, ws + lo.ws_x4, lo.n, lo.n_h,
                        lo.ncol_h, lo.np);
     return (int)hipGetLastError();
 }

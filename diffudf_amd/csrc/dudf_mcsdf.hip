@@ -20,18 +20,19 @@
 //                     waves; only workgroups that have any stage the other tables (17 KB) in LDS.  Per cell one 32-bit word
 //                     (tiling, configuration, in-workgroup vertex prefix; 0 = nothing) for pass 3 and for the neighbours; per
 //                     workgroup the vertex / triangle totals.
-//   pass 2 scan     : exclusive scan of the workgroup totals (one workgroup), totals -> out_counts.
+//   pass 2 scan     : exclusive scan of the workgroup totals (dudf_scan_totals_kernel<2>: one workgroup), totals -> out_counts.
 //   pass 3 emit     : active cells compacted again; faces through the owners' words, vertices / normals / values by their owners.
 // The table descriptors (offsets, dimensions) travel as kernel arguments and are staged in LDS beside the table bytes, as LDS
 // pointers: a look-up whose table is chosen per lane (the tiling) is two DS reads, none through a flat address.
 #include "dudf_internal.h"
+#include "dudf_wgscan.h"
 #include "dudf_lewiner.h"
 
 namespace {
 
 using namespace dudf_lewiner;
 
-constexpr int CB = 256;                                  // cells per workgroup
+constexpr int CB = DUDF_WG;                              // cells per workgroup
 constexpr int kLutCap = 18 * 1024;                       // bytes of LDS for the caller's tables (the standard set: 17 548)
 
 struct LutDesc { int off[N_LUTS]; short l1[N_LUTS], l2[N_LUTS]; int total; };
@@ -155,33 +156,11 @@ struct CornerView {
 
 // compaction of the workgroup's active cells: list[rank] = thread, returns the number of active cells
 __device__ __forceinline__ int compact_active(bool active, unsigned short* list, unsigned* wave_tot) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(active);
-    if (lane == 0) wave_tot[wave] = (unsigned)__popcll(b);
-    __syncthreads();
-    unsigned before = 0, total = 0;
-    for (int q = 0; q < CB / 64; ++q) { before += q < wave ? wave_tot[q] : 0; total += wave_tot[q]; }
-    if (active) list[before + (unsigned)__popcll(b & ((1ull << lane) - 1ull))] = (unsigned short)threadIdx.x;
+    unsigned total;
+    const unsigned rank = dudf_wg_rank(active, wave_tot, &total);
+    if (active) list[rank] = (unsigned short)threadIdx.x;
     __syncthreads();
     return (int)total;
-}
-
-// exclusive scan of a small count over the workgroup's threads (thread order); *total = the sum
-__device__ __forceinline__ unsigned scan_exclusive(unsigned w, unsigned* wave_tot, unsigned* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = w;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(inc, o);
-        if (lane >= o) inc += up;
-    }
-    __syncthreads();                                     // wave_tot is reused
-    if (lane == 63) wave_tot[wave] = inc;
-    __syncthreads();
-    unsigned before = 0, sum = 0;
-    for (int q = 0; q < CB / 64; ++q) { before += q < wave ? wave_tot[q] : 0; sum += wave_tot[q]; }
-    *total = sum;
-    return before + inc - w;
 }
 
 __global__ __launch_bounds__(CB) void mc_classify_kernel(McArgs a) {
@@ -235,38 +214,12 @@ __global__ __launch_bounds__(CB) void mc_classify_kernel(McArgs a) {
         }
     }
     unsigned tv, tt;
-    const unsigned prefix = scan_exclusive(nv, wave_tot, &tv);      // compacted order = raster order
-    scan_exclusive((unsigned)t.nt, wave_tot, &tt);
+    const unsigned prefix = dudf_wg_scan(nv, wave_tot, &tv);      // compacted order = raster order
+    dudf_wg_scan((unsigned)t.nt, wave_tot, &tt);
     if (tid < nact) sword[lid] = pack_word(t, config, prefix);
     __syncthreads();
     if (cell < a.ncells) a.word[cell] = sword[tid];
     if (tid == 0) { a.blk[(int64_t)blockIdx.x * 2] = tv; a.blk[(int64_t)blockIdx.x * 2 + 1] = tt; }
-}
-
-// exclusive scan of the per-workgroup totals; totals -> out_counts (vertices, triangles)
-__global__ __launch_bounds__(1024) void mc_scan_kernel(const uint32_t* __restrict__ blk, int64_t* __restrict__ off,
-                                                       int64_t nblocks, int64_t* __restrict__ out_counts) {
-    __shared__ int64_t s[2][1024];
-    const int t = threadIdx.x;
-    const int64_t chunk = (nblocks + 1023) / 1024;
-    const int64_t b0 = (int64_t)t * chunk < nblocks ? (int64_t)t * chunk : nblocks, b1 = (b0 + chunk < nblocks) ? b0 + chunk : nblocks;
-    int64_t sum[2] = {0, 0};
-    for (int64_t b = b0; b < b1; ++b)
-        for (int q = 0; q < 2; ++q) sum[q] += blk[b * 2 + q];
-    for (int q = 0; q < 2; ++q) s[q][t] = sum[q];
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {                  // inclusive Hillis-Steele over the 1024 partial sums
-        int64_t add[2] = {0, 0};
-        if (t >= d) for (int q = 0; q < 2; ++q) add[q] = s[q][t - d];
-        __syncthreads();
-        for (int q = 0; q < 2; ++q) s[q][t] += add[q];
-        __syncthreads();
-    }
-    int64_t run[2];
-    for (int q = 0; q < 2; ++q) run[q] = s[q][t] - sum[q];
-    for (int64_t b = b0; b < b1; ++b)
-        for (int q = 0; q < 2; ++q) { off[b * 2 + q] = run[q]; run[q] += blk[b * 2 + q]; }
-    if (t == 1023) for (int q = 0; q < 2; ++q) out_counts[q] = s[q][1023];
 }
 
 __device__ __forceinline__ int64_t vertex_base(const McArgs& a, int64_t cell, uint32_t w) { return a.off[(cell / CB) * 2] + (w >> 20); }
@@ -371,7 +324,7 @@ __global__ __launch_bounds__(CB) void mc_emit_kernel(McArgs a) {
     const uint32_t w = mine ? a.word[me] : 0;
     const Tiling t = word_tiling(w);
     unsigned tt;
-    const unsigned tpre = scan_exclusive(mine ? (unsigned)t.nt : 0u, wave_tot, &tt);
+    const unsigned tpre = dudf_wg_scan(mine ? (unsigned)t.nt : 0u, wave_tot, &tt);
     if (!mine) return;
     const Cell c = cell_of(a, me);
     const int config = word_config(w);
@@ -457,7 +410,7 @@ int dudf_mc_lewiner_count(const float* volume, int64_t nz, int64_t ny, int64_t n
     DudfProfScope prof(PROF_OTHER, st);
     const int64_t nb = mc_blocks(nz, ny, nx);
     hipLaunchKernelGGL(mc_classify_kernel, dim3((unsigned)nb), dim3(CB), 0, st, a);
-    hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(1024), 0, st, a.blk, a.off, nb, out_counts);
+    hipLaunchKernelGGL(dudf_scan_totals_kernel<2>, dim3(1), dim3(1024), 0, st, a.blk, a.off, nb, out_counts);
     return (int)hipGetLastError();
 }
 

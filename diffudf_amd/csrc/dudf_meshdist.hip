@@ -34,13 +34,13 @@ namespace {
 constexpr int kLeaf = 8;                         // triangles per leaf
 constexpr int kBlock = 256;                      // threads per workgroup of the query kernels
 constexpr int kHdrBytes = 256;                   // header: 3 + 3 encoded bounds, flags
+constexpr int kGridCap = 8192;                   // workgroups of the build launches; the kernels stride over the rest
 constexpr unsigned kFlagNonFinite = 1u, kFlagBadOrder = 2u;
 
 struct Layout {                                  // byte offsets inside the index
     int64_t n_leaves; int L, depth;              // L leaf slots (power of two), depth = stack entries a lane can need
     size_t ids, stri, nodes, total;
 };
-inline size_t round256(size_t b) { return (b + 255) / 256 * 256; }
 inline Layout layout_of(int64_t T) {
     Layout y;
     y.n_leaves = (T + kLeaf - 1) / kLeaf;
@@ -48,14 +48,10 @@ inline Layout layout_of(int64_t T) {
     while (((int64_t)1 << lg) < y.n_leaves) ++lg;
     y.L = 1 << lg; y.depth = lg + 1;
     y.ids = kHdrBytes;
-    y.stri = y.ids + round256((size_t)T * sizeof(int));
-    y.nodes = y.stri + round256((size_t)T * 9 * sizeof(float));
-    y.total = y.nodes + round256((size_t)(2 * (int64_t)y.L - 1) * 2 * sizeof(float4));
+    y.stri = y.ids + dudf_round256((size_t)T * sizeof(int));
+    y.nodes = y.stri + dudf_round256((size_t)T * 9 * sizeof(float));
+    y.total = y.nodes + dudf_round256((size_t)(2 * (int64_t)y.L - 1) * 2 * sizeof(float4));
     return y;
-}
-inline int grid_for(int64_t n, int block = 256, int cap = 8192) {
-    int64_t g = (n + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
 // fp32 -> uint32 whose unsigned order is the float order (for atomicMin / atomicMax of bounds)
@@ -476,7 +472,7 @@ static hipError_t launch_bounds(const float* tri, int64_t T, unsigned* hdr, hipS
     hipError_t e = hipMemsetAsync(hdr, 0, kHdrBytes, st);                     // max words 0 (below every encoded float), flags 0
     if (e == hipSuccess) e = hipMemsetAsync(hdr, 0xff, 3 * sizeof(unsigned), st);   // min words above every encoded float
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mesh_bounds_kernel, dim3(grid_for(T, 256, 256)), dim3(256), 0, st, tri, T, hdr);
+    hipLaunchKernelGGL(mesh_bounds_kernel, dim3(dudf_grid_for(T, 256, 256)), dim3(256), 0, st, tri, T, hdr);
     return hipGetLastError();
 }
 
@@ -491,7 +487,7 @@ int dudf_mesh_morton_codes(const float* tri, int64_t n_tri, void* index, size_t 
     unsigned* hdr = reinterpret_cast<unsigned*>(index);
     hipError_t e = launch_bounds(tri, n_tri, hdr, st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mesh_codes_kernel, dim3(grid_for(n_tri)), dim3(256), 0, st, tri, n_tri, hdr, codes);
+    hipLaunchKernelGGL(mesh_codes_kernel, dim3(dudf_grid_for(n_tri, 256, kGridCap)), dim3(256), 0, st, tri, n_tri, hdr, codes);
     return (int)hipGetLastError();
 }
 
@@ -509,13 +505,14 @@ int dudf_mesh_index_build(const float* tri, int64_t n_tri, const int64_t* order,
     float4* nodes = reinterpret_cast<float4*>(base + y.nodes);
     hipError_t e = launch_bounds(tri, n_tri, hdr, st);                        // the build stands alone: any permutation is a valid order
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mesh_gather_kernel, dim3(grid_for(n_tri)), dim3(256), 0, st, tri, n_tri, order, ids, stri, hdr);
+    hipLaunchKernelGGL(mesh_gather_kernel, dim3(dudf_grid_for(n_tri, 256, kGridCap)), dim3(256), 0, st, tri, n_tri, order, ids,
+                       stri, hdr);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mesh_leaves_kernel, dim3(grid_for(y.L)), dim3(256), 0, st, stri, n_tri, y.L, nodes);
+    hipLaunchKernelGGL(mesh_leaves_kernel, dim3(dudf_grid_for(y.L, 256, kGridCap)), dim3(256), 0, st, stri, n_tri, y.L, nodes);
     e = hipGetLastError();
     for (int count = y.L / 2; count >= 1 && e == hipSuccess; count /= 2) {       // level of `count` nodes starts at node count - 1
-        hipLaunchKernelGGL(mesh_level_kernel, dim3(grid_for(count)), dim3(256), 0, st, nodes, count - 1, count);
+        hipLaunchKernelGGL(mesh_level_kernel, dim3(dudf_grid_for(count, 256, kGridCap)), dim3(256), 0, st, nodes, count - 1, count);
         e = hipGetLastError();
     }
     return (int)e;

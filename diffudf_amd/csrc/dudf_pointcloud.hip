@@ -6,30 +6,16 @@
 // with `inverse` in float64 on the float32 value WITHOUT abs (:51) and moves in float64 (:53).  Same here, operation by
 // operation (no contraction: numpy rounds every product and sum).
 #include "dudf_context.h"
+#include "dudf_rng.h"
+#include "dudf_wgscan.h"
 
 namespace {
 
-inline int grid_for(int64_t n, int block = 256, int cap = 2048) {
-    int64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
+constexpr int kGridCap = 2048;                         // workgroups per launch; the kernels stride over the rest
 
-// counter-based random numbers: the splitmix64 construction of dudf_sample.hip, keyed by (seed, round, stream)
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ double uniform01(uint64_t key, uint64_t idx) {
-    uint64_t b = splitmix64(idx ^ key);
-    b = splitmix64(b + key);
-    return (double)(b >> 11) * (1.0 / 9007199254740992.0);
-}
+// counter-based random numbers (dudf_rng.h), keyed by (seed, round, stream)
 __device__ __forceinline__ double normal01(uint64_t key, uint64_t idx) {        // Box-Muller on two counters of one stream
-    const double u1 = 1.0 - uniform01(key, 2 * idx), u2 = uniform01(key, 2 * idx + 1);   // u1 in (0, 1]
+    const double u1 = 1.0 - dudf_uniform01(key, 2 * idx), u2 = dudf_uniform01(key, 2 * idx + 1);   // u1 in (0, 1]
     return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
 }
 
@@ -53,7 +39,7 @@ __global__ __launch_bounds__(256) void pc_propose_kernel(const double* __restric
             if (p >= m) {
                 q[0] = q[1] = q[2] = __builtin_nan("");
             } else if (held && p < half) {
-                int64_t idx = rand ? (int64_t)rand[p] : (int64_t)(uniform01(key, (uint64_t)p) * (double)held);
+                int64_t idx = rand ? (int64_t)rand[p] : (int64_t)(dudf_uniform01(key, (uint64_t)p) * (double)held);
                 idx = idx < 0 ? 0 : (idx >= held ? held - 1 : idx);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
@@ -64,7 +50,7 @@ __global__ __launch_bounds__(256) void pc_propose_kernel(const double* __restric
                 const int64_t r = held ? p - half : p;
 #pragma unroll
                 for (int k = 0; k < 3; ++k)
-                    q[k] = rand ? rand[(held ? 4 * half : 0) + r * 3 + k] : uniform01(key + 4 + k, (uint64_t)p) * 2.0 - 1.0;
+                    q[k] = rand ? rand[(held ? 4 * half : 0) + r * 3 + k] : dudf_uniform01(key + 4 + k, (uint64_t)p) * 2.0 - 1.0;
             }
             samples[p * 3] = q[0]; samples[p * 3 + 1] = q[1]; samples[p * 3 + 2] = q[2];
             proposals[p * 3] = q[0]; proposals[p * 3 + 1] = q[1]; proposals[p * 3 + 2] = q[2];     // kept for dudf_pointcloud_read_proposals
@@ -116,23 +102,19 @@ __global__ __launch_bounds__(256) void pc_step_kernel(PcStepArgs a) {
 }
 
 // ---- ordered compaction + append (reference :58-65: samples[mask] / vstack) ----------------------------------------------------
-// Tiles of 256 rows (one workgroup pass = 4 waves of 64).  count: accepted rows per tile (wave ballot + popcount, summed over
-// the waves);  scan: one workgroup turns the counts into exclusive offsets and moves the row counter;  scatter: row -> base +
-// tile offset + waves before it + lanes before it.  Order of the rows is kept: later rounds index the buffer.
-constexpr int kTile = 256;
+// Tiles of 256 rows (one workgroup pass = 4 waves of 64).  count: accepted rows per tile (dudf_wg_rank's total);  scan: one
+// workgroup turns the counts into exclusive offsets and moves the row counter;  scatter: row -> base + tile offset + accepted
+// rows before it in the tile (dudf_wg_rank).  Order of the rows is kept: later rounds index the buffer.
+constexpr int kTile = DUDF_WG;
 
 __global__ __launch_bounds__(256) void pc_count_kernel(const unsigned char* __restrict__ flags, int64_t n, int64_t ntiles,
                                                        int* __restrict__ tile_cnt) {
-    __shared__ int wcnt[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ unsigned wave_tot[kTile / 64];
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const int64_t row = t * kTile + threadIdx.x;
-        const bool f = row < n && flags[row] != 0;
-        const unsigned long long b = __ballot(f);
-        if (lane == 0) wcnt[wave] = __popcll(b);
-        __syncthreads();
-        if (threadIdx.x == 0) tile_cnt[t] = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
+        unsigned total;
+        dudf_wg_rank(row < n && flags[row] != 0, wave_tot, &total);
+        if (threadIdx.x == 0) tile_cnt[t] = (int)total;
     }
 }
 
@@ -162,19 +144,16 @@ __global__ __launch_bounds__(256) void pc_scatter_kernel(const unsigned char* __
                                                          const int* __restrict__ tile_off, const int64_t* __restrict__ counter,
                                                          const double* __restrict__ src_a, const double* __restrict__ src_b,
                                                          const float* __restrict__ src_f, double* __restrict__ dst_a,
-                                                         double* __restrict__ dst_b, float* __restrict__ out_f) {
-    __shared__ int wcnt[4];
+                                                         double* __restrict__ dst_b, float* __restrict__ out_f,
+                                                         int* __restrict__ rows) {
+    __shared__ unsigned wave_tot[kTile / 64];
     if (counter[1] == 0) return;                   // nothing accepted, quota reached or no room: nothing is written
     const int64_t base = counter[2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const int64_t row = t * kTile + threadIdx.x;
         const bool f = row < n && flags[row] != 0;
-        const unsigned long long b = __ballot(f);
-        if (lane == 0) wcnt[wave] = __popcll(b);
-        __syncthreads();
-        int before = __popcll(b & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; ++w) before += wcnt[w];
+        unsigned total;
+        const unsigned before = dudf_wg_rank(f, wave_tot, &total);
         if (f) {
             const int64_t local = (int64_t)tile_off[t] + before, d = base + local;
 #pragma unroll
@@ -183,8 +162,8 @@ __global__ __launch_bounds__(256) void pc_scatter_kernel(const unsigned char* __
                 if (dst_b) dst_b[d * 3 + k] = src_b[row * 3 + k];
                 if (out_f) out_f[local * 3 + k] = src_f[row * 3 + k];
             }
+            if (rows) rows[local] = (int)row;      // local < counter[1] <= n
         }
-        __syncthreads();
     }
 }
 
@@ -198,9 +177,9 @@ __global__ __launch_bounds__(256) void pc_normals_kernel(const float* __restrict
 int dudf_launch_pc_propose(const DudfLayout& lo, const double* rand, int64_t rand_count, uint64_t seed, int64_t round, const double* surface,
                            const int64_t* counter, int64_t quota, double* samples, double* proposals, float* ws, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    const uint64_t key = splitmix64(splitmix64(seed) ^ (uint64_t)round * 0x100000001B3ull) & ~0xFull;   // streams key + 0 .. 6
-    hipLaunchKernelGGL(pc_propose_kernel, dim3(grid_for(lo.np)), dim3(256), 0, st, rand, rand_count, key, lo.n, lo.np, surface, counter,
-                       quota, samples, proposals, ws + lo.ws_x4);
+    const uint64_t key = dudf_splitmix64(dudf_splitmix64(seed) ^ (uint64_t)round * 0x100000001B3ull) & ~0xFull;   // streams key + 0 .. 6
+    hipLaunchKernelGGL(pc_propose_kernel, dim3(dudf_grid_for(lo.np, 256, kGridCap)), dim3(256), 0, st, rand, rand_count, key, lo.n,
+                       lo.np, surface, counter, quota, samples, proposals, ws + lo.ws_x4);
     return (int)hipGetLastError();
 }
 
@@ -213,13 +192,13 @@ int dudf_launch_pc_step(const DudfLayout& lo, float* ws, double* samples, int in
     a.inverse_mode = inverse_mode; a.alpha = alpha; a.inv_alpha = 1.0 / alpha; a.sqrt_alpha = sqrt(alpha); a.thresh = thresh;
     a.last = last; a.out_step = out_step; a.out_unit = out_unit; a.out_pre = out_pre; a.out_accept = out_accept;
     a.counter = counter; a.quota = quota;
-    hipLaunchKernelGGL(pc_step_kernel, dim3(grid_for(lo.n)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pc_step_kernel, dim3(dudf_grid_for(lo.n, 256, kGridCap)), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 
 int dudf_launch_pc_normals(const float* V, int64_t m, double* normals, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(pc_normals_kernel, dim3(grid_for(m)), dim3(256), 0, st, V, m, normals);
+    hipLaunchKernelGGL(pc_normals_kernel, dim3(dudf_grid_for(m, 256, kGridCap)), dim3(256), 0, st, V, m, normals);
     return (int)hipGetLastError();
 }
 
@@ -270,19 +249,19 @@ int make_pc_layout(const dudf_net_cfg* cfg, int64_t n, PcLayout* pl) {
 
 int64_t dudf_pc_tiles(int64_t n) { return (n + kTile - 1) / kTile; }
 
-// scratch: [tile counts | tile offsets], dudf_pc_tiles(n) ints each
+// scratch: [tile counts | tile offsets], dudf_pc_tiles(n) ints each;  rows (or nullptr): the source row of every row this call adds
 int dudf_launch_pc_append(const unsigned char* flags, int64_t n, const double* src_a, const double* src_b, const float* src_f,
-                          double* dst_a, double* dst_b, float* out_f, int64_t capacity, int64_t quota, int64_t* counter,
+                          double* dst_a, double* dst_b, float* out_f, int* rows, int64_t capacity, int64_t quota, int64_t* counter,
                           int* scratch, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
     const int64_t ntiles = dudf_pc_tiles(n);
     int* tile_cnt = scratch; int* tile_off = scratch + ntiles;
     if (!src_b) dst_b = nullptr;
     if (!src_f) out_f = nullptr;
-    hipLaunchKernelGGL(pc_count_kernel, dim3(grid_for(n)), dim3(256), 0, st, flags, n, ntiles, tile_cnt);
+    hipLaunchKernelGGL(pc_count_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), 0, st, flags, n, ntiles, tile_cnt);
     hipLaunchKernelGGL(pc_scan_kernel, dim3(1), dim3(256), 0, st, tile_cnt, tile_off, ntiles, capacity, quota, counter);
-    hipLaunchKernelGGL(pc_scatter_kernel, dim3(grid_for(n)), dim3(256), 0, st, flags, n, ntiles, tile_off, counter, src_a, src_b,
-                       src_f, dst_a, dst_b, out_f);
+    hipLaunchKernelGGL(pc_scatter_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), 0, st, flags, n, ntiles, tile_off,
+                       counter, src_a, src_b, src_f, dst_a, dst_b, out_f, rows);
     return (int)hipGetLastError();
 }
 
@@ -303,7 +282,7 @@ int dudf_project_points(const dudf_net_cfg* cfg, const float* theta, double* poi
 
 size_t dudf_pointcloud_append_workspace_bytes(int64_t n) {
     if (n < 0) return 0;
-    return (size_t)((2 * dudf_pc_tiles(n) * (int64_t)sizeof(int) + 255) / 256 * 256 + 256);
+    return dudf_round256((size_t)(2 * dudf_pc_tiles(n)) * sizeof(int)) + 256;
 }
 
 int dudf_pointcloud_append(const unsigned char* flags, int64_t n, const double* src_a, const double* src_b, const float* src_f,
@@ -313,7 +292,7 @@ int dudf_pointcloud_append(const unsigned char* flags, int64_t n, const double* 
     if (int rc = dudf_check_buffer(workspace, workspace_bytes, dudf_pointcloud_append_workspace_bytes(n))) return rc;
     if (n == 0) return 0;
     if (!flags || !src_a || !dst_a) return DUDF_E_BADCFG;
-    return dudf_launch_pc_append(flags, n, src_a, src_b, src_f, dst_a, dst_b, out_f, capacity, quota, counter,
+    return dudf_launch_pc_append(flags, n, src_a, src_b, src_f, dst_a, dst_b, out_f, nullptr, capacity, quota, counter,
                                  reinterpret_cast<int*>(workspace), reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -361,7 +340,7 @@ int dudf_pointcloud_round(const dudf_net_cfg* cfg, const float* theta, int64_t n
         // accepted rows in their order behind the counter; 'siren': the unit gradients with them, otherwise the float32 pre-move
         // positions compacted as the input of the frame query
         if ((rc = dudf_launch_pc_append(accept, n, samples, siren ? unit : nullptr, siren ? nullptr : pre, surface_points,
-                                        siren ? normals : nullptr, siren ? nullptr : prec, capacity, n, counter,
+                                        siren ? normals : nullptr, siren ? nullptr : prec, nullptr, capacity, n, counter,
                                         reinterpret_cast<int*>(c.ws + pl.o_tiles), c.st))) return rc;
         if (!siren) {
             int64_t hc[4];

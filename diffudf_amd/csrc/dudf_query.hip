@@ -209,24 +209,19 @@ __global__ __launch_bounds__(256) void rays_descend_kernel(const float* __restri
     }
 }
 
-inline int grid_for(int64_t n, int block = 256, int cap = 2048) {
-    int64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
+constexpr int kGridCap = 2048;                         // workgroups per launch; the kernels stride over the rest
 
 int dudf_launch_make_x4_jet(const float* x, const float* V, int64_t n, int64_t npj, float* x4j, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(make_x4_jet_kernel, dim3(grid_for(npj)), dim3(256), 0, st, x, V, n, npj, x4j);
+    hipLaunchKernelGGL(make_x4_jet_kernel, dim3(dudf_grid_for(npj, 256, kGridCap)), dim3(256), 0, st, x, V, n, npj, x4j);
     return (int)hipGetLastError();
 }
 
 int dudf_launch_curvature(const float* yj, const float* lam, const float* V, int64_t n, float* out_mean,
                           float* out_gauss, float* out_shape, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(curvature_kernel, dim3(grid_for(n)), dim3(256), 0, st, yj, lam, V, n, out_mean, out_gauss,
-                       out_shape);
+    hipLaunchKernelGGL(curvature_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), 0, st, yj, lam, V, n, out_mean,
+                       out_gauss, out_shape);
     return (int)hipGetLastError();
 }
 
@@ -236,23 +231,23 @@ int dudf_launch_rays_step(const DudfLayout& lo, const float* ws, const double* r
     DudfProfScope prof(PROF_OTHER, st);
     hipError_t e = hipMemsetAsync(active, 0, sizeof(int), st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(rays_step_kernel, dim3(grid_for(lo.n)), dim3(256), 0, st, ws + lo.ws_y, rays, t0, mask, hits, lo.n,
-                       inverse_mode, (float)alpha, (float)min_step, (float)threshold, active);
+    hipLaunchKernelGGL(rays_step_kernel, dim3(dudf_grid_for(lo.n, 256, kGridCap)), dim3(256), 0, st, ws + lo.ws_y, rays, t0, mask,
+                       hits, lo.n, inverse_mode, (float)alpha, (float)min_step, (float)threshold, active);
     return (int)hipGetLastError();
 }
 
 int dudf_launch_rays_descend(const DudfLayout& lo, const float* ws, double* t0, const unsigned char* hits,
                              int inverse_mode, double alpha, double min_step, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(rays_descend_kernel, dim3(grid_for(lo.n)), dim3(256), 0, st, ws + lo.ws_y, ws + lo.ws_g, t0, hits,
-                       lo.n, inverse_mode, (float)alpha, (float)min_step);
+    hipLaunchKernelGGL(rays_descend_kernel, dim3(dudf_grid_for(lo.n, 256, kGridCap)), dim3(256), 0, st, ws + lo.ws_y, ws + lo.ws_g,
+                       t0, hits, lo.n, inverse_mode, (float)alpha, (float)min_step);
     return (int)hipGetLastError();
 }
 
 int dudf_launch_make_x4_grid(const DudfLayout& lo, int64_t grid_n, int64_t start, float* ws, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(make_x4_grid_kernel, dim3(grid_for(lo.np)), dim3(256), 0, st, ws + lo.ws_x4, lo.n, lo.np, grid_n,
-                       start);
+    hipLaunchKernelGGL(make_x4_grid_kernel, dim3(dudf_grid_for(lo.np, 256, kGridCap)), dim3(256), 0, st, ws + lo.ws_x4, lo.n,
+                       lo.np, grid_n, start);
     return (int)hipGetLastError();
 }
 
@@ -277,14 +272,14 @@ int make_curv_layout(const dudf_net_cfg* cfg, int64_t n, CurvLayout* cl) {
 
 int dudf_launch_copy_out(const DudfLayout& lo, const float* ws, float* out_f, float* out_g, float* out_h,
                          hipStream_t st) {
-    hipLaunchKernelGGL(copy_out_kernel, dim3(grid_for(lo.n)), dim3(256), 0, st, ws + lo.ws_y, ws + lo.ws_g, out_f,
-                       out_g, out_h, lo.n, lo.n_h, lo.ncol_h);
+    hipLaunchKernelGGL(copy_out_kernel, dim3(dudf_grid_for(lo.n, 256, kGridCap)), dim3(256), 0, st, ws + lo.ws_y, ws + lo.ws_g,
+                       out_f, out_g, out_h, lo.n, lo.n_h, lo.ncol_h);
     return (int)hipGetLastError();
 }
 
 int dudf_launch_rays_x4(const DudfLayout& lo, const double* t0, float* ws, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(rays_x4_kernel, dim3(grid_for(lo.np)), dim3(256), 0, st, t0, lo.n, lo.np, ws + lo.ws_x4);
+    hipLaunchKernelGGL(rays_x4_kernel, dim3(dudf_grid_for(lo.np, 256, kGridCap)), dim3(256), 0, st, t0, lo.n, lo.np, ws + lo.ws_x4);
     return (int)hipGetLastError();
 }
 
@@ -295,8 +290,9 @@ int dudf_launch_field_features(const DudfLayout& lo, const float* ws, int invers
         hipError_t e = hipMemsetAsync(out_flag_count, 0, sizeof(int), st);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL(field_features_kernel, dim3(grid_for(lo.n)), dim3(256), 0, st, ws + lo.ws_y, ws + lo.ws_g, lo.n,
-                       lo.n_h, lo.ncol_h, inverse_mode, (float)alpha, out_df, out_vec, out_flag_count, out_lam, out_V);
+    hipLaunchKernelGGL(field_features_kernel, dim3(dudf_grid_for(lo.n, 256, kGridCap)), dim3(256), 0, st, ws + lo.ws_y,
+                       ws + lo.ws_g, lo.n, lo.n_h, lo.ncol_h, inverse_mode, (float)alpha, out_df, out_vec, out_flag_count, out_lam,
+                       out_V);
     return (int)hipGetLastError();
 }
 

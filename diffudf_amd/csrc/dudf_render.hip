@@ -1,6 +1,6 @@
 // Sphere-traced images on the device — the kernels around the marching loop (dudf_trace_rays / dudf_descend_rays) and the frame /
 // curvature queries that replace the numpy glue of reference generate_st.py:41-101, :139 and src/render_st.py:104-114, :174-245:
-// camera rays against the six box planes, the row index of the gathered hits, orientation of the normals, the curvature colour
+// camera rays against the six box planes, the gather of the hits, orientation of the normals, the curvature colour
 // map, the two reflection models with the scatter into the image, and the final 8-bit image; with the dudf_render_* entry points.
 //
 // The reference does all of this in float64 numpy (normals, principal directions and curvatures arrive as float32 from torch and
@@ -12,12 +12,7 @@
 
 namespace {
 
-inline int grid_for(int64_t n, int block = 256, int cap = 4096) {
-    int64_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (int)g;
-}
+constexpr int kGridCap = 4096;                         // workgroups per launch; the kernels stride over the rest
 
 __device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 // reference src/util.py:34-39: arr / ||arr||, the norm as numpy's add.reduce sums it
@@ -79,28 +74,6 @@ __global__ __launch_bounds__(256) void render_setup_kernel(SetupArgs a) {
             a.t0[p * 3 + i] = valid ? d[i] * dmin + a.cam[i] : 0.0;
         }
         a.mask[p] = valid ? 1 : 0;
-    }
-}
-
-// ---- image row of every gathered hit: the inverse map of dudf_pointcloud_append's compaction, from its tile offsets ----------
-constexpr int kTile = 256;          // dudf_pointcloud.hip
-
-__global__ __launch_bounds__(256) void render_rows_kernel(const unsigned char* __restrict__ flags, int64_t n, int64_t ntiles,
-                                                          const int* __restrict__ tile_off, const int64_t* __restrict__ counter,
-                                                          int* __restrict__ rows) {
-    __shared__ int wcnt[4];
-    if (counter[1] == 0) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const int64_t row = t * kTile + threadIdx.x;
-        const bool f = row < n && flags[row] != 0;
-        const unsigned long long b = __ballot(f);
-        if (lane == 0) wcnt[wave] = __popcll(b);
-        __syncthreads();
-        int before = __popcll(b & ((1ull << lane) - 1ull));
-        for (int w = 0; w < wave; ++w) before += wcnt[w];
-        if (f) rows[(int64_t)tile_off[t] + before] = (int)row;        // tile_off[t] + before < counter[1] <= n
-        __syncthreads();
     }
 }
 
@@ -240,28 +213,21 @@ int dudf_launch_render_setup(int64_t width, int64_t height, double fov, double n
     for (int i = 0; i < 3; ++i) a.cam[i] = cam[i];
     for (int i = 0; i < 6; ++i) a.planes[i] = planes[i];
     a.rays = rays; a.t0 = t0; a.mask = mask;
-    hipLaunchKernelGGL(render_setup_kernel, dim3(grid_for(width * height)), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
-}
-
-// scratch: what dudf_launch_pc_append left there, [tile counts | tile offsets]
-int dudf_launch_render_rows(const unsigned char* flags, int64_t n, const int64_t* counter, const int* scratch, int* rows, hipStream_t st) {
-    DudfProfScope prof(PROF_OTHER, st);
-    const int64_t ntiles = dudf_pc_tiles(n);
-    hipLaunchKernelGGL(render_rows_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, st, flags, n, ntiles, scratch + ntiles, counter, rows);
+    hipLaunchKernelGGL(render_setup_kernel, dim3(dudf_grid_for(width * height, 256, kGridCap)), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 
 int dudf_launch_render_orient(const float* frame, const float* grad, const double* rays, int64_t k, double* normals, double* pc1,
                               double* pc2, float* mean, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(render_orient_kernel, dim3(grid_for(k)), dim3(256), 0, st, frame, grad, rays, k, normals, pc1, pc2, mean);
+    hipLaunchKernelGGL(render_orient_kernel, dim3(dudf_grid_for(k, 256, kGridCap)), dim3(256), 0, st, frame, grad, rays, k,
+                       normals, pc1, pc2, mean);
     return (int)hipGetLastError();
 }
 
 int dudf_launch_render_colormap(const float* curv, int64_t k, const float* bounds, const double* lut, double* out, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(render_colormap_kernel, dim3(grid_for(k)), dim3(256), 0, st, curv, k, bounds, lut, out);
+    hipLaunchKernelGGL(render_colormap_kernel, dim3(dudf_grid_for(k, 256, kGridCap)), dim3(256), 0, st, curv, k, bounds, lut, out);
     return (int)hipGetLastError();
 }
 
@@ -269,7 +235,7 @@ int dudf_launch_render_shade(int model, const unsigned char* hits, int64_t m, co
                              const double* normals, const double* pc1, const double* pc2, const double* cmap, const double* light,
                              const double* camera, double shininess, double alpha1, double alpha2, double* acc, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(render_background_kernel, dim3(grid_for(m)), dim3(256), 0, st, hits, m, acc);
+    hipLaunchKernelGGL(render_background_kernel, dim3(dudf_grid_for(m, 256, kGridCap)), dim3(256), 0, st, hits, m, acc);
     if (k > 0) {
         ShadeArgs a;
         a.model = model; a.k = k; a.rows = rows; a.pos = pos; a.normals = normals; a.pc1 = pc1; a.pc2 = pc2; a.cmap = cmap;
@@ -277,14 +243,15 @@ int dudf_launch_render_shade(int model, const unsigned char* hits, int64_t m, co
         a.shininess = shininess; a.alpha1 = alpha1; a.alpha2 = alpha2;
         a.ward_norm = 4 * 3.141592653589793 * alpha1 * alpha2;
         a.acc = acc;
-        hipLaunchKernelGGL(render_shade_kernel, dim3(grid_for(k)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(render_shade_kernel, dim3(dudf_grid_for(k, 256, kGridCap)), dim3(256), 0, st, a);
     }
     return (int)hipGetLastError();
 }
 
 int dudf_launch_render_finish(const double* acc, int64_t count, double sample_rate, unsigned char* out, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(render_finish_kernel, dim3(grid_for(count)), dim3(256), 0, st, acc, count, sample_rate, out);
+    hipLaunchKernelGGL(render_finish_kernel, dim3(dudf_grid_for(count, 256, kGridCap)), dim3(256), 0, st, acc, count, sample_rate,
+                       out);
     return (int)hipGetLastError();
 }
 
@@ -310,10 +277,9 @@ int dudf_render_gather(const unsigned char* hits, int64_t m, const double* t0, c
     if (e != hipSuccess) return (int)e;
     if (m == 0) return 0;
     if (!hits || !t0 || !out_pos || !out_rows || (rays && !out_rays)) return DUDF_E_BADCFG;
-    int rc = dudf_launch_pc_append(hits, m, t0, rays, nullptr, out_pos, rays ? out_rays : nullptr, nullptr, m, (int64_t)1 << 62, counter,
-                                   reinterpret_cast<int*>(workspace), st);
-    if (rc) return rc;
-    return dudf_launch_render_rows(hits, m, counter, reinterpret_cast<const int*>(workspace), out_rows, st);
+    // the compaction's scatter leaves the image row of every gathered hit (the index behind `colors[hits] = ...`) in out_rows
+    return dudf_launch_pc_append(hits, m, t0, rays, nullptr, out_pos, rays ? out_rays : nullptr, nullptr, out_rows, m, (int64_t)1 << 62,
+                                 counter, reinterpret_cast<int*>(workspace), st);
 }
 
 int dudf_render_orient(const float* frame_v, const float* grad, const double* hit_rays, int64_t k, double* out_normals,

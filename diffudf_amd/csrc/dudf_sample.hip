@@ -19,23 +19,13 @@
 // and the numpy restatement in oracle/sampler_oracle.py reproduces every sample.
 #include "dudf_internal.h"
 
+#include "dudf_rng.h"              // dudf_splitmix64, dudf_uniform01
 #include "dudf_tridist.h"          // tri_dist2, DUDF_SAMPLE_DBG
 
 namespace {
 
-__host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 __host__ __device__ __forceinline__ uint64_t stream_key(uint64_t seed, uint64_t stream) {
-    return splitmix64(seed * 0x100000001B3ull + stream);
-}
-__device__ __forceinline__ double uniform01(uint64_t key, uint64_t idx) {
-    uint64_t b = splitmix64(idx ^ key);
-    b = splitmix64(b + key);
-    return (double)(b >> 11) * (1.0 / 9007199254740992.0);
+    return dudf_splitmix64(seed * 0x100000001B3ull + stream);
 }
 
 struct SampleArgs {
@@ -144,20 +134,20 @@ __global__ __launch_bounds__(256) void sample_batch_kernel(SampleArgs a) {
     if (live) {
         if (i < n_on_l) {
             const int64_t g = a.on0 + i;
-            const int64_t c = (int64_t)(uniform01(a.k_on, (uint64_t)g) * (double)a.n_pc);
+            const int64_t c = (int64_t)(dudf_uniform01(a.k_on, (uint64_t)g) * (double)a.n_pc);
             px = a.pc_pos[c * 3]; py = a.pc_pos[c * 3 + 1]; pz = a.pc_pos[c * 3 + 2];
             nx = a.pc_nrm[c * 3]; ny = a.pc_nrm[c * 3 + 1]; nz = a.pc_nrm[c * 3 + 2];
         } else if (i < n_on_l + n_far_l) {
             const uint64_t g = (uint64_t)(a.far0 + (i - n_on_l));
-            px = (float)(uniform01(a.k_fx, g) * 2.0 - 1.0);
-            py = (float)(uniform01(a.k_fy, g) * 2.0 - 1.0);
-            pz = (float)(uniform01(a.k_fz, g) * 2.0 - 1.0);
+            px = (float)(dudf_uniform01(a.k_fx, g) * 2.0 - 1.0);
+            py = (float)(dudf_uniform01(a.k_fy, g) * 2.0 - 1.0);
+            pz = (float)(dudf_uniform01(a.k_fz, g) * 2.0 - 1.0);
             query = true;
         } else {
             const uint64_t g = (uint64_t)(a.near0 + (i - n_on_l - n_far_l));
-            const int64_t k = (int64_t)(uniform01(a.k_pick, g) * (double)a.n_on);       // which on-surface sample
-            const int64_t c = (int64_t)(uniform01(a.k_on, (uint64_t)k) * (double)a.n_pc);
-            const double u1 = uniform01(a.k_n1, g), u2 = uniform01(a.k_n2, g);
+            const int64_t k = (int64_t)(dudf_uniform01(a.k_pick, g) * (double)a.n_on);       // which on-surface sample
+            const int64_t c = (int64_t)(dudf_uniform01(a.k_on, (uint64_t)k) * (double)a.n_pc);
+            const double u1 = dudf_uniform01(a.k_n1, g), u2 = dudf_uniform01(a.k_n2, g);
             const float off = (float)(0.01 * sqrt(-2.0 * log1p(-u1)) * cos(6.283185307179586476925 * u2));
             px = __fadd_rn(a.pc_pos[c * 3], __fmul_rn(a.pc_nrm[c * 3], off));
             py = __fadd_rn(a.pc_pos[c * 3 + 1], __fmul_rn(a.pc_nrm[c * 3 + 1], off));

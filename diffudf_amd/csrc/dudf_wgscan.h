@@ -1,0 +1,74 @@
+// Index and compaction toolkit of the extraction units (point cloud and render gather, CAP-UDF cells, Lewiner marching cubes): device
+// code only.  Internal: not installed, nothing here is part of the C ABI.
+//   dudf_wg_rank, dudf_wg_scan: ballot rank and exclusive scan over a workgroup of DUDF_WG = 256 threads (four waves);
+//   dudf_scan_totals_kernel<K>: exclusive scan of per-workgroup totals, one 1024-thread workgroup
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+constexpr int DUDF_WG = 256;                             // threads of the workgroups below: four waves of 64
+
+// Flagged threads before this one, in thread order; *total = flagged threads of the workgroup.  wave_tot: DUDF_WG / 64 words of
+// LDS.  Both barriers are the helper's own: it can be called again at once (a grid-stride loop over tiles) with the same words.
+__device__ __forceinline__ unsigned dudf_wg_rank(bool flag, unsigned* wave_tot, unsigned* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(flag);
+    if (lane == 0) wave_tot[wave] = (unsigned)__popcll(b);
+    __syncthreads();
+    unsigned before = (unsigned)__popcll(b & ((1ull << lane) - 1ull)), sum = 0;
+    for (int q = 0; q < wave; ++q) before += wave_tot[q];            // a wave-uniform trip count: no per-lane selects
+    for (int q = 0; q < DUDF_WG / 64; ++q) sum += wave_tot[q];
+    __syncthreads();
+    *total = sum;
+    return before;
+}
+
+// Exclusive scan of a small count over the workgroup's threads (thread order); *total = the sum.  wave_tot as above; the leading
+// barrier lets the words be reused straight after any other use of them.
+__device__ __forceinline__ unsigned dudf_wg_scan(unsigned w, unsigned* wave_tot, unsigned* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned inc = w;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned up = __shfl_up(inc, o);
+        if (lane >= o) inc += up;
+    }
+    __syncthreads();
+    if (lane == 63) wave_tot[wave] = inc;
+    __syncthreads();
+    unsigned before = 0, sum = 0;
+    for (int q = 0; q < wave; ++q) before += wave_tot[q];            // a wave-uniform trip count: no per-lane selects
+    for (int q = 0; q < DUDF_WG / 64; ++q) sum += wave_tot[q];
+    *total = sum;
+    return before + inc - w;
+}
+
+// Exclusive scan of per-workgroup totals: blk [nblocks][K] uint32 -> off [nblocks][K] int64, the K grand totals -> out_counts.
+// One workgroup of 1024 threads (static LDS K * 8 KiB); thread t sums blocks [t * chunk, (t + 1) * chunk) clamped to nblocks —
+// an empty range for the upper threads of a short array —, the partial sums are scanned, and the thread writes its blocks' offsets.
+// static: an instantiation stays inside the unit that launches it, like the kernels beside it.
+template <int K>
+static __global__ __launch_bounds__(1024) void dudf_scan_totals_kernel(const uint32_t* __restrict__ blk, int64_t* __restrict__ off,
+                                                                       int64_t nblocks, int64_t* __restrict__ out_counts) {
+    __shared__ int64_t s[K][1024];
+    const int t = threadIdx.x;
+    const int64_t chunk = (nblocks + 1023) / 1024;
+    const int64_t b0 = (int64_t)t * chunk < nblocks ? (int64_t)t * chunk : nblocks, b1 = (b0 + chunk < nblocks) ? b0 + chunk : nblocks;
+    int64_t sum[K] = {};
+    for (int64_t b = b0; b < b1; ++b)
+        for (int q = 0; q < K; ++q) sum[q] += blk[b * K + q];
+    for (int q = 0; q < K; ++q) s[q][t] = sum[q];
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {                  // inclusive Hillis-Steele over the 1024 partial sums
+        int64_t add[K] = {};
+        if (t >= d) for (int q = 0; q < K; ++q) add[q] = s[q][t - d];
+        __syncthreads();
+        for (int q = 0; q < K; ++q) s[q][t] += add[q];
+        __syncthreads();
+    }
+    int64_t run[K];
+    for (int q = 0; q < K; ++q) run[q] = s[q][t] - sum[q];
+    for (int64_t b = b0; b < b1; ++b)
+        for (int q = 0; q < K; ++q) { off[b * K + q] = run[q]; run[q] += blk[b * K + q]; }
+    if (t == 1023) for (int q = 0; q < K; ++q) out_counts[q] = s[q][1023];
+}
