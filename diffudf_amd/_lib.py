@@ -118,6 +118,15 @@ SYMBOLS = {
                                              ctypes.c_int, _P, _P, ctypes.c_size_t, _P]),
     "dudf_mc_lewiner_emit": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _P, _P, _P,
                                             ctypes.c_int, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_mesh_clean_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "dudf_mesh_clean_count": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_mesh_clean_emit": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P, _P, _P,
+                                            ctypes.c_size_t, _P]),
+    "dudf_mesh_border_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "dudf_mesh_border_count": (ctypes.c_int, [ctypes.c_int64, _P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_mesh_border_edges": (ctypes.c_int, [ctypes.c_int64, _P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_mesh_smooth_borders": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _P,
+                                                ctypes.c_size_t, _P]),
     "dudf_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "dudf_split_mode": (ctypes.c_int, []),
     "dudf_profile_dump": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t]),

@@ -463,6 +463,70 @@ def capudf_extract(ndf, grad, threshold=0.008, want_cells=False):
     return (verts, tris, cells) if want_cells else (verts, tris)
 
 
+MESH_CLEAN_COUNTS = ("vertices", "faces", "welded", "unreferenced", "duplicate_faces", "degenerate_faces", "holes3", "holes4",
+                     "invalid_faces")
+
+
+def _mesh(vertices, faces):
+    vertices = _tensor(vertices, "vertices", torch.float64, (3,), convert=True)
+    faces = _tensor(faces, "faces", torch.int64, (3,), convert=True)
+    if faces.device != vertices.device:
+        raise _lib.DudfError("vertices and faces must be on one device")
+    return vertices, faces
+
+
+def mesh_clean_round(vertices, faces, digits=8, fill_holes=False):
+    """One clean-up round of a device mesh (`dudf_mesh_clean_count` / `_emit`; the rules: DESIGN.md §3 "Mesh clean-up"): invalid faces
+    dropped, vertices welded on rint(v * 10^digits), faces remapped and pruned (degenerate, duplicate), unused vertices dropped, and
+    with fill_holes the 3- and 4-edge holes of that result closed.  (vertices (V',3) float64, faces (F',3) int64, counts: a dict over
+    MESH_CLEAN_COUNTS).  One host sync for the counts; nothing is emitted for an empty result, and a round that changes nothing
+    returns its inputs."""
+    vertices, faces = _mesh(vertices, faces)
+    dev = vertices.device
+    V, F = vertices.shape[0], faces.shape[0]
+    nbytes = _bytes("dudf_mesh_clean_workspace_bytes", V, F, err=-4)
+    ws = _scratch(nbytes, dev)
+    counts = torch.zeros(len(MESH_CLEAN_COUNTS), dtype=torch.int64, device=dev)
+    head = (_ptr(vertices), V, _ptr(faces), F, int(digits), int(bool(fill_holes)))
+    _call("dudf_mesh_clean_count", *head, _ptr(counts), _ptr(ws), nbytes, dev=dev)
+    c = dict(zip(MESH_CLEAN_COUNTS, (int(v) for v in counts.tolist())))
+    nv, nf = c["vertices"], c["faces"]
+    if (nv, nf) == (V, F) and not c["holes3"] and not c["holes4"]:        # nothing dropped, nothing added: the identity
+        return vertices, faces, c
+    out_v = torch.empty(nv, 3, dtype=torch.float64, device=dev); out_f = torch.empty(nf, 3, dtype=torch.int64, device=dev)
+    if nv and nf:
+        _call("dudf_mesh_clean_emit", *head, _ptr(out_v), _ptr(out_f), _ptr(ws), nbytes, dev=dev)
+    return out_v, out_f, c
+
+
+def mesh_border_edges(faces, n_vertices):
+    """(E,2) int64 device tensor: the undirected edges (u < w) that exactly one face uses, ascending (`dudf_mesh_border_count` /
+    `_edges`).  One host sync for E."""
+    faces = _tensor(faces, "faces", torch.int64, (3,), convert=True)
+    dev = faces.device
+    V, F = int(n_vertices), faces.shape[0]
+    nbytes = _bytes("dudf_mesh_border_workspace_bytes", V, F, err=-4)
+    ws = _scratch(nbytes, dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    _call("dudf_mesh_border_count", V, _ptr(faces), F, _ptr(count), _ptr(ws), nbytes, dev=dev)
+    edges = torch.empty(int(count.item()), 2, dtype=torch.int64, device=dev)
+    if edges.shape[0]:
+        _call("dudf_mesh_border_edges", V, _ptr(faces), F, _ptr(edges), _ptr(ws), nbytes, dev=dev)
+    return edges
+
+
+def mesh_smooth_borders(vertices, faces, iterations=5, lam=0.3):
+    """A new (V,3) float64 device tensor: `iterations` Jacobi steps v += lam * (mean(border neighbours) - v) on the border vertices
+    of the mesh (`dudf_mesh_smooth_borders`; reference src/render_mc.py:169-197).  No host sync."""
+    vertices, faces = _mesh(vertices, faces)
+    out = vertices.clone()
+    V, F = out.shape[0], faces.shape[0]
+    nbytes = _bytes("dudf_mesh_border_workspace_bytes", V, F, err=-4)
+    ws = _scratch(nbytes, out.device)
+    _call("dudf_mesh_smooth_borders", _ptr(out), V, _ptr(faces), F, int(iterations), float(lam), _ptr(ws), nbytes, dev=out.device)
+    return out
+
+
 def _w4(weights):
     w = list(weights) + [0.0] * (4 - len(weights))
     return (ctypes.c_double * 4)(*[float(v) for v in w])

@@ -110,7 +110,7 @@ def extract_mesh_CAP(ndf, grad, resolution, threshold=0.008, device=None):
         return TriangleSoup(v, f)
 
 
-def extract_mesh_MESHUDF(df_values, normals, device, smooth_borders=False, luts=None, **kwargs):
+def extract_mesh_MESHUDF(df_values, normals, device, smooth_borders=False, luts=None, clean=None, **kwargs):
     """Reference src/render_mc.py:101-199 (`extract_mesh_MESHUDF`): the MeshUDF marching cubes over the (N, N, N) field and
     its (N, N, N, 3) direction field (outputs of `extract_fields`; tensors or numpy arrays), vertices shifted to
     [-1, 1]^3.  The extraction itself — the reference's Cython extension — is `diffudf_amd.marching_cubes.udf_mc_lewiner`
@@ -119,8 +119,17 @@ def extract_mesh_MESHUDF(df_values, normals, device, smooth_borders=False, luts=
     `_marching_cubes_lewiner_luts.py` on `sys.path`); none found: MeshUDFError.  Tensors come back on `device`, as in
     the reference.
     Returns (vertices, faces, mesh).  The reference then cleans the mesh with trimesh (`process`, duplicate / degenerate
-    faces, `fill_holes`, optional Laplacian smoothing of the border): done the same way when trimesh is importable;
-    without it the raw extraction is returned in a `TriangleSoup` (and `smooth_borders` is ignored)."""
+    faces, `fill_holes`, optional Laplacian smoothing of the border).  `clean`:
+      None      trimesh exactly as the reference when it is importable; otherwise the device clean-up (`meshclean.clean_mesh`,
+                then `meshclean.smooth_borders` when `smooth_borders`) when `device` is a CUDA device; otherwise (a CPU device
+                without trimesh) the raw extraction, `smooth_borders` ignored;
+      "device"  the device clean-up whether or not trimesh is there; a CPU device: DudfError;
+      False     the raw extraction.
+    Without trimesh the mesh is a `TriangleSoup` of what is returned."""
+    if clean not in (None, False, "device"):
+        raise ValueError(f"clean must be None, False or 'device'; got {clean!r}")
+    if clean == "device" and torch.device(device).type != "cuda":
+        raise DudfError("extract_mesh_MESHUDF(clean='device'): needs the GPU; there is no CPU fallback path")
     from .marching_cubes import udf_mc_lewiner
     d = df_values.detach().cpu().numpy() if torch.is_tensor(df_values) else np.asarray(df_values)
     g = normals.detach().cpu().numpy() if torch.is_tensor(normals) else np.asarray(normals)
@@ -131,9 +140,19 @@ def extract_mesh_MESHUDF(df_values, normals, device, smooth_borders=False, luts=
     verts = verts - 1                                   # voxel origin (-1, -1, -1)
     if len(faces) == 0:
         raise ValueError("Could not find surface in volume")
-    try:
-        import trimesh
-    except ImportError:
+    trimesh = None
+    if clean is None:
+        try:
+            import trimesh
+        except ImportError:
+            pass
+    if trimesh is None:
+        if clean == "device" or (clean is None and torch.device(device).type == "cuda"):
+            from . import meshclean
+            dv, dfc, _ = meshclean.clean_mesh(verts, faces, device=device)
+            if smooth_borders:
+                dv = meshclean.smooth_borders(dv, dfc)
+            return dv.float(), dfc, TriangleSoup(dv.cpu().numpy(), dfc.cpu().numpy())
         mesh = TriangleSoup(verts, faces)
         return (torch.from_numpy(np.ascontiguousarray(verts)).float().to(device),
                 torch.from_numpy(np.ascontiguousarray(faces)).long().to(device), mesh)

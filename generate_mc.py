@@ -10,6 +10,8 @@ src/marching_cubes as host C++), 'cap' (row 2, on the device) and 'both' (what t
 MeshUDF needs the Lewiner look-up tables, which are an input, not part of this package: `luts=` / config key "luts_path"
 (an .npz or the reference's `_marching_cubes_lewiner_luts.py`), $DUDF_MESHUDF_LUTS, or that module on sys.path (inside a
 reference checkout: `sys.path.append('src/marching_cubes')`) — `diffudf_amd.marching_cubes.load_luts`.
+The MeshUDF mesh is cleaned as the reference cleans it (weld, duplicate / degenerate faces, small holes, smoothed border): with trimesh
+where it is installed, otherwise on the device (`diffudf_amd.meshclean`).
 'siren' (reference generate_mc.py:56-65): `get_mesh_sdf` — the raw network values on the grid and Lewiner's marching cubes of
 that signed volume, both on the device; it needs the same tables, and without them prints a message, writes nothing and returns
 None (as 'both' skips its MeshUDF half), so that a training run is not lost over its mesh."""

@@ -363,6 +363,43 @@ int dudf_mc_lewiner_emit(const float* volume, int64_t nz, int64_t ny, int64_t nx
                          const int64_t* lut_offsets, const int32_t* lut_dims, int n_luts, float* out_vertices, int32_t* out_faces,
                          float* out_normals, float* out_values, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Mesh clean-up on the device — what `extract_mesh_MESHUDF` asks of trimesh (reference src/render_mc.py:136-197: process, duplicate and
+ * degenerate faces, fill_holes, border smoothing).  vertices (V,3) double, faces (F,3) int64, both on the device; V, F < 2^31
+ * (DUDF_E_UNSUPPORTED beyond); workspaces 256-byte aligned.  The rules are DESIGN.md §3 "Mesh clean-up" (tests/meshclean_oracle.py restates
+ * them; the device result equals it bit for bit and is the same from run to run).  One ROUND:
+ *   1. a face with an index outside [0, V) or a non-finite vertex coordinate is dropped (counted, never dereferenced);
+ *   2. vertices used by the remaining faces weld on the key rint(v * 10^digits) per coordinate (int64, 0 <= digits <= 15) into the
+ *      smallest original index of the key, which keeps its own coordinates;
+ *   3. faces are remapped, then pruned: degenerate (longest edge L <= 1e-8 or |(v1-v0) x (v2-v0)| / L <= 1e-8, compared squared), then
+ *      all but the smallest face index of every vertex set;
+ *   4. unused vertices go; survivors keep their relative order.
+ * fill_holes = 1 adds, behind the surviving faces and in ascending smallest vertex, the faces that close the border cycles of 3 or 4
+ * vertices which lie on exactly two border edges each (one face / two faces, wound against the existing face on the cycle's edge).
+ *   dudf_mesh_clean_count -> out_counts (device, 9 x int64): V', F', welded vertices, unreferenced vertices, duplicate faces, degenerate
+ *                            faces, 3-edge holes, 4-edge holes, invalid faces; maps and flags stay in the workspace;
+ *   dudf_mesh_clean_emit  -> out_vertices (V',3) double, out_faces (F',3) int64; same arguments and workspace as the count call (a
+ *                            workspace that does not hold that call's result is left alone: nothing is written). */
+size_t dudf_mesh_clean_workspace_bytes(int64_t V, int64_t F);
+int dudf_mesh_clean_count(const double* vertices, int64_t V, const int64_t* faces, int64_t F, int digits, int fill_holes,
+                          int64_t* out_counts, void* workspace, size_t workspace_bytes, void* stream);
+int dudf_mesh_clean_emit(const double* vertices, int64_t V, const int64_t* faces, int64_t F, int digits, int fill_holes,
+                         double* out_vertices, int64_t* out_faces, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Border edges — undirected edges (u < w, u != w) that exactly one face uses; faces with an index outside [0, V) are skipped — and the
+ * reference's border smoothing (src/render_mc.py:169-197).  F < 2^32 / 6.
+ *   dudf_mesh_border_count -> out_count (device, 1 x int64): E;    dudf_mesh_border_edges -> out_edges (E,2) int64, ascending; same
+ *                             faces and workspace as the count call;
+ *   dudf_mesh_smooth_borders: `iterations` Jacobi steps v += lambda * (mean(border neighbours) - v) on the endpoints of the border
+ *                             edges, in double, the sum starting at 0.0 and taking the neighbours in ascending index order, every
+ *                             average formed from the positions before the step. */
+size_t dudf_mesh_border_workspace_bytes(int64_t V, int64_t F);
+int dudf_mesh_border_count(int64_t V, const int64_t* faces, int64_t F, int64_t* out_count, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int dudf_mesh_border_edges(int64_t V, const int64_t* faces, int64_t F, int64_t* out_edges, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int dudf_mesh_smooth_borders(double* vertices_inout, int64_t V, const int64_t* faces, int64_t F, int iterations, double lambda,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* Forward half of loss_s1 / loss_siren (reference src/loss_functions.py:123-155, :82-104):
  * SIREN forward, df/dx, the four weighted loss terms.  out_terms (device, 4 floats) receives
  * THIS RANK's share  sum_local(term_i) * weight / n_global  in the reference's dict order
