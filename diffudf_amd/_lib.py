@@ -74,6 +74,13 @@ SYMBOLS = {
     "dudf_chamfer_terms": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
     "dudf_vertex_normals_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "dudf_vertex_normals": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_knn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "dudf_knn_grid_build": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_size_t, _P]),
+    "dudf_knn_points": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P,
+                                       ctypes.c_size_t, _P]),
+    "dudf_orient_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "dudf_orient_normals": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int64), _P,
+                                           ctypes.c_size_t, _P]),
     "dudf_mesh_index_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "dudf_mesh_morton_codes": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_size_t, _P, _P]),
     "dudf_mesh_index_build": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),

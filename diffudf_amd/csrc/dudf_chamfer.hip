@@ -13,6 +13,7 @@
 //   - a finishing kernel unpacks the keys.
 // Every pair is evaluated by the same expression, so the result is a pure function of the inputs: repeated calls are bit-identical.
 #include "dudf_context.h"
+#include "dudf_pairdist.h"
 
 namespace {
 
@@ -24,15 +25,7 @@ constexpr int kNnTargetGroups = 4096;            // workgroups a launch aims for
 constexpr unsigned kNanBits = 0x7fc00000u;
 constexpr int kGridCap = 4096;                   // workgroups of the row-wise launches; the kernels stride over the rest
 
-// ONE sequence of roundings for every pair: the fused steps are written out and contraction is off, so the unrolled body, its
-// remainder loop and any packed form the compiler picks give the same bits (a pair's distance must not depend on where in a tile it falls).
-template <int NORM>
-__device__ __forceinline__ float pair_distance(float ax, float ay, float az, const float4& q) {
-#pragma clang fp contract(off)
-    const float dx = ax - q.x, dy = ay - q.y, dz = az - q.z;
-    if (NORM == 2) return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-    return (fabsf(dx) + fabsf(dy)) + fabsf(dz);
-}
+// pair_distance<NORM>: dudf_pairdist.h (shared with the K-nearest search of dudf_orient.hip, which must return the same bits)
 
 // grid (ceil(n / kNnRows), splits); workgroup (bx, by) scans y rows [by * ychunk, min(m, (by + 1) * ychunk)) — never empty — for x
 // rows bx * kNnRows + k * kNnBlock + lane.  Rows past n repeat row n - 1 and are not written.

@@ -1,0 +1,14 @@
+// The distance of one (x row, y row) pair as every nearest-neighbour kernel forms it (dudf_chamfer.hip, dudf_orient.hip): device code
+// only.  Internal: not installed, nothing here is part of the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+// ONE sequence of roundings for every pair: the fused steps are written out and contraction is off, so the unrolled body, its
+// remainder loop and any packed form the compiler picks give the same bits (a pair's distance must not depend on where in a tile it falls).
+template <int NORM>
+__device__ __forceinline__ float pair_distance(float ax, float ay, float az, const float4& q) {
+#pragma clang fp contract(off)
+    const float dx = ax - q.x, dy = ay - q.y, dz = az - q.z;
+    if (NORM == 2) return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+    return (fabsf(dx) + fabsf(dy)) + fabsf(dz);
+}

@@ -905,6 +905,66 @@ def vertex_normals(vertices, faces):
     return out
 
 
+# ---- K nearest neighbours and normal orientation (reference generate_pc.py:40; csrc/dudf_orient.hip) ----------------------------
+KNN_MAX_K = 16
+
+
+def knn_points(x, y, K=1, exclude_self=False, brute=False, want_dist=True, want_idx=True):
+    """For every row of x (n,3) its K nearest rows of y (m,3) by squared Euclidean distance — `knn_points(x, y, K=K)` of pytorch3d:
+    (dist (n,K) float32, idx (n,K) int64), each row ascending by (distance, index); a row with fewer than K candidates is padded with
+    +inf / -1.  exclude_self (for x is y): row i never returns i.  brute=True scans all of y instead of walking the cell list built
+    over it (the same bits).  Bit-reproducible; K = 1 equals `nearest_points`."""
+    x = _tensor(x, "knn_points: x", torch.float32, (3,), convert=True); y = _tensor(y, "knn_points: y", torch.float32, (3,), convert=True)
+    if y.device != x.device:
+        raise _lib.DudfError("knn_points: x and y live on different devices")
+    K, mode = int(K), 1 if brute else 0
+    n, m, dev = x.shape[0], y.shape[0], x.device
+    dist = torch.empty(n, K, dtype=torch.float32, device=dev) if want_dist and K > 0 else None
+    idx = torch.empty(n, K, dtype=torch.int64, device=dev) if want_idx and K > 0 else None
+    nbytes = _bytes("dudf_knn_workspace_bytes", n, m, K, mode, err=-4)
+    ws = _scratch(nbytes, dev)
+    _call("dudf_knn_points", _ptr(x), n, _ptr(y), m, K, int(bool(exclude_self)), mode, _ptr(dist), _ptr(idx), _ptr(ws), nbytes, dev=dev)
+    return dist, idx
+
+
+def knn_grid_build(y):
+    """The cell list `knn_points` builds over y (m,3) before it searches, alone (for timing); returns the workspace that holds it."""
+    y = _tensor(y, "knn_grid_build: y", torch.float32, (3,), convert=True)
+    nbytes = _bytes("dudf_knn_workspace_bytes", 0, y.shape[0], 1, 0, err=-4)
+    ws = _scratch(nbytes, y.device)
+    _call("dudf_knn_grid_build", _ptr(y), y.shape[0], _ptr(ws), nbytes, dev=y.device)
+    return ws
+
+
+def orient_normals(points, normals, knn_idx, out=None):
+    """Consistent signs for the normals (n,3) of the cloud points (n,3) over the graph knn_idx (n,K) int64 (`knn_points(points, points,
+    K, exclude_self=True)`; entries outside [0, n) or equal to their row are no edges) — DESIGN.md §3.7.  Returns (normals (n,3)
+    float32: the input or its negation, written to `out` if given — which may be `normals` itself —, flip (n,) uint8, component (n,)
+    int64, counts (2,) int64 on the device: components and forest edges, stats: {"rounds", "launches"}).  Synchronises the stream
+    once per round.  Byte-reproducible."""
+    points = _tensor(points, "orient_normals: points", torch.float32, (3,), convert=True)
+    normals = _tensor(normals, "orient_normals: normals", torch.float32, (3,), convert=True)
+    if not torch.is_tensor(knn_idx) or knn_idx.dim() != 2:
+        raise _lib.DudfError("orient_normals: knn_idx must be an (n, K) tensor")
+    knn_idx = _tensor(knn_idx, "orient_normals: knn_idx", torch.int64, (knn_idx.shape[1],), convert=True)
+    n, K, dev = points.shape[0], knn_idx.shape[1], points.device
+    if normals.shape[0] != n or knn_idx.shape[0] != n or normals.device != dev or knn_idx.device != dev:
+        raise _lib.DudfError("orient_normals: points, normals and knn_idx must have one row per point and live on one device")
+    if out is None:
+        out = torch.empty_like(normals)
+    elif _tensor(out, "orient_normals: out", torch.float32, (3,)).shape != normals.shape or out.device != dev:
+        raise _lib.DudfError("orient_normals: out must have the shape and device of normals")
+    flip = torch.empty(n, dtype=torch.uint8, device=dev)
+    comp = torch.empty(n, dtype=torch.int64, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    stats = (ctypes.c_int64 * 2)()
+    nbytes = _bytes("dudf_orient_workspace_bytes", n, K, err=-4)
+    ws = _scratch(nbytes, dev)
+    _call("dudf_orient_normals", _ptr(points), _ptr(normals), _ptr(knn_idx), n, K, _ptr(out), _ptr(flip), _ptr(comp), _ptr(counts), stats,
+          _ptr(ws), nbytes, dev=dev)
+    return out, flip, comp, counts, {"rounds": int(stats[0]), "launches": int(stats[1])}
+
+
 # ---- distance to a triangle mesh (reference generate_df.py:108-110, open3d RaycastingScene; csrc/dudf_meshdist.hip) -------------
 MESH_INDEX_FLAGS_OFFSET, MESH_FLAG_NONFINITE, MESH_FLAG_BAD_ORDER = 24, 1, 2       # include/dudf_hip.h
 

@@ -5,6 +5,9 @@ cuantitative.py:10-19 uses (pytorch3d is a CUDA extension), and the vertex norma
 The nearest-neighbour search, the sums behind the means and the vertex normals are HIP kernels (csrc/dudf_chamfer.hip);
 there is no CPU path: CPU tensors raise DudfError.
 
+`knn_points` is the K > 1 half of pytorch3d's `knn_points` and `orient_normals` stands in for open3d's
+`orient_normals_consistent_tangent_plane` (reference generate_pc.py:40); both are HIP kernels too (csrc/dudf_orient.hip).
+
 `MeshIndex` / `mesh_distance` stand in for `o3d.t.geometry.RaycastingScene().add_triangles(...)` / `.compute_distance(...)`
 (reference generate_df.py:108-110): the exact unsigned distance from points to a triangle mesh through a bounding-volume
 hierarchy built and walked on the device (csrc/dudf_meshdist.hip).  `MeshIndex.occupancy` / `.signed_distance` are its
@@ -21,6 +24,35 @@ def nearest_points(x, y, norm=2):
     """(dist (n,) float32, idx (n,) int64): for every row of x (n,3) its nearest row of y (m,3) — the `dists[..., 0]` and
     `idx[..., 0]` of pytorch3d's `knn_points(x[None], y[None], norm=norm, K=1)`.  norm 2: squared Euclidean; norm 1: L1."""
     return hip_ops.nearest_points(x, y, norm)
+
+
+def knn_points(x, y, K=1, exclude_self=False, brute=False):
+    """(dists (n,K) float32, idx (n,K) int64): for every row of x (n,3) its K nearest rows of y (m,3) by squared Euclidean distance,
+    nearest first (equal distances by index) — the `dists[0]` / `idx[0]` of pytorch3d's `knn_points(x[None], y[None], K=K)`.
+    1 <= K <= 16.  exclude_self (for x is y): a point is not its own neighbour.  A row with fewer than K candidates is padded with
+    +inf / -1.  The search walks a cell list built over y on the device; brute=True scans all of y (the same bits)."""
+    return hip_ops.knn_points(x, y, K, exclude_self, brute)
+
+
+def orient_normals(points, normals, k=10, return_info=False):
+    """Normals (n,3) float32 with consistent signs — open3d's `orient_normals_consistent_tangent_plane(k)`: the k nearest
+    neighbours of every point of the cloud, a minimum spanning forest of that graph under the weight 1 - |n_i . n_j|, signs
+    propagated along it from the highest point of every connected component, which ends with n_z >= 0 (open3d joins
+    the components with a Delaunay graph first, here each is seeded on its own).  With return_info also a dict: flip (n,) uint8,
+    component (n,) int64, components, forest_edges, rounds, launches."""
+    if not torch.is_tensor(points) or points.dim() != 2:
+        raise DudfError("orient_normals: points must be an (n, 3) tensor")
+    n = points.shape[0]
+    if n == 0:
+        out = hip_ops._tensor(normals, "orient_normals: normals", torch.float32, (3,), convert=True).clone()
+        return (out, {"flip": torch.empty(0, dtype=torch.uint8, device=out.device), "component": torch.empty(0, dtype=torch.int64, device=out.device),
+                      "components": 0, "forest_edges": 0, "rounds": 0, "launches": 0}) if return_info else out
+    _, idx = hip_ops.knn_points(points, points, int(k), exclude_self=True, want_dist=False)
+    out, flip, comp, counts, stats = hip_ops.orient_normals(points, normals, idx)
+    if not return_info:
+        return out
+    c = counts.tolist()
+    return out, {"flip": flip, "component": comp, "components": int(c[0]), "forest_edges": int(c[1]), **stats}
 
 
 def _batched(t, what):

@@ -256,6 +256,43 @@ size_t dudf_vertex_normals_workspace_bytes(int64_t n_vertices);
 int dudf_vertex_normals(const double* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, float* out_normals,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* K nearest neighbours and consistent normal orientation — the device side of pytorch3d's `knn_points(x, y, K=K)` and of open3d's
+ * `orient_normals_consistent_tangent_plane(k)` (reference generate_pc.py:40).  csrc/dudf_orient.hip; the rules are DESIGN.md §3.7
+ * (tests/orient_oracle.py restates them in numpy).  These entry points arrived after ABI 8 without changing any existing signature.
+ *
+ * dudf_knn_points — for every row of x (n,3) the K rows of y (m,3) at the smallest SQUARED Euclidean distance, both fp32: out_dist
+ *   (n,K) fp32 and out_idx (n,K) int64, either may be NULL, each row ascending by (distance bits, index).  A pair's distance is the
+ *   expression of dudf_nearest_points (norm 2), so K = 1 repeats that call bit for bit on finite inputs.  exclude_self != 0 (meant for
+ *   x == y): row i never returns index i.  A row with fewer than K candidates is padded with +inf / -1.  Rows of y with a NaN or an
+ *   infinity, and pairs whose distance overflows, are never returned; such a row of x gets NaN distances and -1 indices.
+ *   mode 0: a uniform cell list over y, built on the device by this call inside the workspace, walked in growing shells (the default
+ *   of the Python side); mode 1: the tiled scan over all of y.  Both return the same bits on every input, ties included.  The result
+ *   is a function of the inputs alone: not of launch geometry, not of the order in which atomics arrive; two calls are bit-identical.
+ *   mode not in {0, 1}: DUDF_E_BADMODE; n < 0: DUDF_E_BADCFG; n or m >= 2^31, K < 1 or K > 16: DUDF_E_UNSUPPORTED; n == 0: nothing is
+ *   launched, 0; m <= 0 or a NULL x / y with n > 0: DUDF_E_BADCFG; workspace: dudf_knn_workspace_bytes(n, m, K, mode) (0 for arguments
+ *   the call refuses), 256-byte aligned, else DUDF_E_WORKSPACE.  Every check is made before the first device call.
+ * dudf_knn_grid_build — the cell list of mode 0 alone, into a workspace of dudf_knn_workspace_bytes(0, m, 1, 0) or more (what
+ *   dudf_knn_points does first; here for timing).  m >= 2^31: DUDF_E_UNSUPPORTED; m <= 0 or y NULL: DUDF_E_BADCFG. */
+size_t dudf_knn_workspace_bytes(int64_t n, int64_t m, int K, int mode);
+int dudf_knn_grid_build(const float* y, int64_t m, void* workspace, size_t workspace_bytes, void* stream);
+int dudf_knn_points(const float* x, int64_t n, const float* y, int64_t m, int K, int exclude_self, int mode, float* out_dist,
+                    int64_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dudf_orient_normals — signs for the normals (n,3) fp32 of the cloud points (n,3) fp32 such that neighbours agree: the minimum
+ *   spanning forest of the graph with one edge per slot of knn_idx (n,K) int64 (as dudf_knn_points wrote it; a slot outside [0, n) or
+ *   equal to its own row is no edge and is not dereferenced), weight 1 - |n_i . n_j| in fp32, ties broken by the slot number; an edge
+ *   with n_i . n_j < 0 flips.  Per connected component the vertex with the largest z (smallest index among equal z) ends with n_z >= 0.
+ *   out_normals (n,3) fp32 = the input or its exact negation (may be `normals` itself); out_flip (n) uint8; out_component (n) int64 =
+ *   the smallest vertex index of the component; out_counts (device, 2 int64) = components, forest edges.  Any output may be NULL.
+ *   host_stats (HOST memory, 2 int64, may be NULL) = Borůvka rounds and kernel launches of this call.  Integer atomics only: two calls
+ *   are byte-identical.  The call synchronises the stream once per round (at most ceil(log2 n) + 1 rounds).
+ *   n < 0: DUDF_E_BADCFG; n >= 2^31, K < 1, K > 16 or n * K >= 2^32: DUDF_E_UNSUPPORTED; n == 0: nothing is launched, 0; a NULL input
+ *   with n > 0: DUDF_E_BADCFG; workspace: dudf_orient_workspace_bytes(n, K) (0 for arguments the call refuses), else DUDF_E_WORKSPACE. */
+size_t dudf_orient_workspace_bytes(int64_t n, int K);
+int dudf_orient_normals(const float* points, const float* normals, const int64_t* knn_idx, int64_t n, int K, float* out_normals,
+                        unsigned char* out_flip, int64_t* out_component, int64_t* out_counts, int64_t* host_stats, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* Exact unsigned distance from points to a triangle mesh with a bounding-volume hierarchy — the device side of open3d's
  * `RaycastingScene.add_triangles / compute_distance` (reference generate_df.py:108-110).  csrc/dudf_meshdist.hip.  Like the Chamfer
  * entry points these arrived after ABI 8 without changing any existing signature.  tri (n_tri,9) fp32 is the triangle soup
