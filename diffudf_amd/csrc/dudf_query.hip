@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void make_x4_grid_kernel(float* __restrict__ x
 //             reference src/render_st.py:57-62 `compute_normals_and_cd` (normal = V[:,2])
 __global__ __launch_bounds__(256) void field_features_kernel(const float* __restrict__ y, const float* __restrict__ g,
                                                              int64_t n, int64_t n_h, int64_t ncol_h, int inverse_mode,
-                                                             float alpha, float* __restrict__ out_df,
+                                                             float alpha, double sqrt_alpha, float* __restrict__ out_df,
                                                              float* __restrict__ out_vec, int* __restrict__ flag_count,
                                                              float* __restrict__ out_lam, float* __restrict__ out_V) {
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void field_features_kernel(const float* __rest
             float d;
             if (inverse_mode == 0) d = (f < 1.0f / alpha) ? sqrtf(f / alpha) : f;          // 'tanh'
             else if (inverse_mode == 1) d = (f > 0.f) ? f : 0.01f;                        // 'siren' (min_step 0.01)
-            else d = ((f > 0.f) ? sqrtf(f) : 0.01f) / sqrtf(alpha);                       // 'squared'
+            else d = (float)((double)((f > 0.f) ? sqrtf(f) : 0.01f) / sqrt_alpha);        // 'squared': the division in double
             out_df[p] = d;
         }
         if (out_vec) {
@@ -151,10 +151,11 @@ __global__ __launch_bounds__(256) void curvature_kernel(const float* __restrict_
 // ---- sphere tracing on the device (reference src/render_st.py:136-172 `propagate_rays`, `grad_descent`) ----------------
 // The reference keeps ray positions in float64 numpy, feeds float32 copies to the network, takes the step in float32
 // (`inverse`, src/inverses.py:3-21) and adds it in float64.  Same here: t0 is double, x4 = (float)t0, the step float.
-__device__ __forceinline__ float inverse_step(float f, int inverse_mode, float alpha, float min_step) {
+// 'squared' divides by the float64 sqrt(alpha) and rounds once, as the reference's in-place `/=` does (sqrt_alpha: host side).
+__device__ __forceinline__ float inverse_step(float f, int inverse_mode, float alpha, double sqrt_alpha, float min_step) {
     if (inverse_mode == 0) return (f < 1.0f / alpha) ? sqrtf(f / alpha) : f;               // 'tanh'
     if (inverse_mode == 1) return (f > 0.f) ? f : min_step;                               // 'siren'
-    return ((f > 0.f) ? sqrtf(f) : min_step) / sqrtf(alpha);                              // 'squared'
+    return (float)((double)((f > 0.f) ? sqrtf(f) : min_step) / sqrt_alpha);               // 'squared'
 }
 
 __global__ __launch_bounds__(256) void rays_x4_kernel(const double* __restrict__ t0, int64_t m, int64_t np,
@@ -170,13 +171,13 @@ __global__ __launch_bounds__(256) void rays_x4_kernel(const double* __restrict__
 __global__ __launch_bounds__(256) void rays_step_kernel(const float* __restrict__ y, const double* __restrict__ rays,
                                                         double* __restrict__ t0, unsigned char* __restrict__ mask,
                                                         unsigned char* __restrict__ hits, int64_t m, int inverse_mode,
-                                                        float alpha, float min_step, float threshold,
+                                                        float alpha, double sqrt_alpha, float min_step, float threshold,
                                                         int* __restrict__ active) {
     int mine = 0;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += (int64_t)gridDim.x * blockDim.x) {
         if (!mask[p]) continue;
         const float udf = y[p];
-        const float step = inverse_step(fabsf(udf), inverse_mode, alpha, min_step);
+        const float step = inverse_step(fabsf(udf), inverse_mode, alpha, sqrt_alpha, min_step);
         double q[3];
         bool inside = true;
 #pragma unroll
@@ -197,12 +198,13 @@ __global__ __launch_bounds__(256) void rays_step_kernel(const float* __restrict_
 // one descent step for the hit rays: t0 -= normalize(grad f) * inverse(|f|)  (:163-172; src/util.py:35-40 `normalize`)
 __global__ __launch_bounds__(256) void rays_descend_kernel(const float* __restrict__ y, const float* __restrict__ g,
                                                            double* __restrict__ t0, const unsigned char* __restrict__ hits,
-                                                           int64_t m, int inverse_mode, float alpha, float min_step) {
+                                                           int64_t m, int inverse_mode, float alpha, double sqrt_alpha,
+                                                           float min_step) {
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < m; p += (int64_t)gridDim.x * blockDim.x) {
         if (!hits[p]) continue;
         const float gx = g[p * 4], gy = g[p * 4 + 1], gz = g[p * 4 + 2];
         const float nrm = sqrtf(gx * gx + gy * gy + gz * gz);
-        const float step = inverse_step(fabsf(y[p]), inverse_mode, alpha, min_step);
+        const float step = inverse_step(fabsf(y[p]), inverse_mode, alpha, sqrt_alpha, min_step);
         t0[p * 3] -= (double)((gx / nrm) * step);
         t0[p * 3 + 1] -= (double)((gy / nrm) * step);
         t0[p * 3 + 2] -= (double)((gz / nrm) * step);
@@ -232,7 +234,7 @@ int dudf_launch_rays_step(const DudfLayout& lo, const float* ws, const double* r
     hipError_t e = hipMemsetAsync(active, 0, sizeof(int), st);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(rays_step_kernel, dim3(dudf_grid_for(lo.n, 256, kGridCap)), dim3(256), 0, st, ws + lo.ws_y, rays, t0, mask,
-                       hits, lo.n, inverse_mode, (float)alpha, (float)min_step, (float)threshold, active);
+                       hits, lo.n, inverse_mode, (float)alpha, sqrt(alpha), (float)min_step, (float)threshold, active);
     return (int)hipGetLastError();
 }
 
@@ -240,7 +242,7 @@ int dudf_launch_rays_descend(const DudfLayout& lo, const float* ws, double* t0, 
                              int inverse_mode, double alpha, double min_step, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
     hipLaunchKernelGGL(rays_descend_kernel, dim3(dudf_grid_for(lo.n, 256, kGridCap)), dim3(256), 0, st, ws + lo.ws_y, ws + lo.ws_g,
-                       t0, hits, lo.n, inverse_mode, (float)alpha, (float)min_step);
+                       t0, hits, lo.n, inverse_mode, (float)alpha, sqrt(alpha), (float)min_step);
     return (int)hipGetLastError();
 }
 
@@ -291,7 +293,8 @@ int dudf_launch_field_features(const DudfLayout& lo, const float* ws, int invers
         if (e != hipSuccess) return (int)e;
     }
     hipLaunchKernelGGL(field_features_kernel, dim3(dudf_grid_for(lo.n, 256, kGridCap)), dim3(256), 0, st, ws + lo.ws_y,
-                       ws + lo.ws_g, lo.n, lo.n_h, lo.ncol_h, inverse_mode, (float)alpha, out_df, out_vec, out_flag_count, out_lam,
+                       ws + lo.ws_g, lo.n, lo.n_h, lo.ncol_h, inverse_mode, (float)alpha, sqrt(alpha), out_df, out_vec, out_flag_count,
+                       out_lam,
                        out_V);
     return (int)hipGetLastError();
 }
