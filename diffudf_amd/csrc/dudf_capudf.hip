@@ -20,7 +20,7 @@
 //   pass 3  emit  : the same per-cell evaluation, an in-workgroup exclusive scan (dudf_wg_scan), float64
 //                   vertices and int64 triangle indices written at their final offsets — deterministic, no atomics.
 // The caller reads the three totals between pass 2 and pass 3 to size the outputs.
-#include "dudf_internal.h"
+#include "dudf_context.h"
 #include "dudf_wgscan.h"
 
 namespace {
@@ -154,13 +154,18 @@ __global__ __launch_bounds__(CB) void capudf_emit_kernel(CapArgs a) {
 
 int64_t cap_blocks(int64_t grid_n) { const int64_t m = grid_n - 1; return (m * m * m + CB - 1) / CB; }
 
+// the one statement of the workspace's layout: sizes with a null base, places on the caller's
+size_t carve_cap(void* ws, int64_t grid_n, CapArgs* a) {
+    DudfByteCarver cv = dudf_carve(ws);
+    const int64_t nb = cap_blocks(grid_n);
+    a->off = cv.take<int64_t>(nb * 3); a->blk = cv.take<uint32_t>(nb * 3);
+    return cv.o;
+}
+
 int fill_args(const float* ndf, const float* grad, int64_t grid_n, double threshold, void* ws, size_t bytes, CapArgs* a) {
     if (grid_n < 2 || grid_n > 2048 || !ndf || !grad) return DUDF_E_BADCFG;
-    const int64_t nb = cap_blocks(grid_n);
-    if (!ws || bytes < dudf_capudf_workspace_bytes(grid_n) || (reinterpret_cast<uintptr_t>(ws) & 15)) return DUDF_E_WORKSPACE;
+    if (int rc = dudf_check_buffer(ws, bytes, carve_cap(ws, grid_n, a))) return rc;
     a->ndf = ndf; a->grad = grad; a->n = grid_n; a->m = grid_n - 1; a->ncells = a->m * a->m * a->m; a->threshold = threshold;
-    a->off = reinterpret_cast<int64_t*>(ws);
-    a->blk = reinterpret_cast<uint32_t*>(a->off + nb * 3);
     a->verts = nullptr; a->tris = nullptr; a->cells = nullptr;
     return 0;
 }
@@ -171,8 +176,8 @@ extern "C" {
 
 size_t dudf_capudf_workspace_bytes(int64_t grid_n) {
     if (grid_n < 2 || grid_n > 2048) return 0;
-    const int64_t nb = cap_blocks(grid_n);
-    return (size_t)(nb * 3 * (sizeof(int64_t) + sizeof(uint32_t)) + 64);
+    CapArgs a;
+    return carve_cap(nullptr, grid_n, &a);
 }
 
 int dudf_capudf_count(const float* ndf, const float* grad, int64_t grid_n, double threshold, int64_t* out_counts,

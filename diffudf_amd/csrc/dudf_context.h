@@ -8,6 +8,19 @@
 inline int dudf_check_buffer(const void* ptr, size_t have, size_t need) {
     return (!ptr || have < need || (reinterpret_cast<uintptr_t>(ptr) & 255)) ? DUDF_E_WORKSPACE : 0;
 }
+// Carves typed arrays out of such a buffer, each on a 256-byte granule and at least one element long; base == nullptr: sizes only
+// (null pointers, `o` the byte count).  A stage's carve_* function is *_workspace_bytes() on a null base and the kernels' pointers
+// on the caller's: one statement of the layout.  Host glue, so it stands beside the check of the buffer it carves; DudfCarver
+// (dudf_internal.h) hands out the float OFFSETS of the network layout, which kernel arguments carry.
+struct DudfByteCarver {
+    char* base; size_t o;
+    template <class T> T* take(int64_t count) {
+        T* p = base ? reinterpret_cast<T*>(base + o) : nullptr;
+        o += dudf_round256((size_t)(count > 0 ? count : 1) * sizeof(T));
+        return p;
+    }
+};
+inline DudfByteCarver dudf_carve(const void* base) { return DudfByteCarver{static_cast<char*>(const_cast<void*>(base)), 0}; }
 // 0 'tanh', 1 'siren', 2 'squared' (reference src/inverses.py)
 inline bool dudf_valid_inverse_mode(int inverse_mode) { return !(inverse_mode < 0 || inverse_mode > 2); }
 

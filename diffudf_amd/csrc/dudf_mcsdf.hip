@@ -24,7 +24,7 @@
 //   pass 3 emit     : active cells compacted again; faces through the owners' words, vertices / normals / values by their owners.
 // The table descriptors (offsets, dimensions) travel as kernel arguments and are staged in LDS beside the table bytes, as LDS
 // pointers: a look-up whose table is chosen per lane (the tiling) is two DS reads, none through a flat address.
-#include "dudf_internal.h"
+#include "dudf_context.h"
 #include "dudf_wgscan.h"
 #include "dudf_lewiner.h"
 
@@ -361,6 +361,14 @@ __global__ __launch_bounds__(CB) void mc_emit_kernel(McArgs a) {
 int64_t mc_blocks(int64_t nz, int64_t ny, int64_t nx) { return ((nz - 1) * (ny - 1) * (nx - 1) + CB - 1) / CB; }
 bool mc_dims_ok(int64_t nz, int64_t ny, int64_t nx) { return nz >= 2 && ny >= 2 && nx >= 2 && nz <= 2048 && ny <= 2048 && nx <= 2048; }
 
+// the one statement of the workspace's layout: sizes with a null base, places on the caller's
+size_t carve_mc(void* ws, int64_t nz, int64_t ny, int64_t nx, McArgs* a) {
+    DudfByteCarver cv = dudf_carve(ws);
+    const int64_t nb = mc_blocks(nz, ny, nx);
+    a->off = cv.take<int64_t>(nb * 2); a->blk = cv.take<uint32_t>(nb * 2); a->word = cv.take<uint32_t>((nz - 1) * (ny - 1) * (nx - 1));
+    return cv.o;
+}
+
 int fill_args(const float* volume, int64_t nz, int64_t ny, int64_t nx, double level, const signed char* luts, const int64_t* offs,
               const int32_t* dims, int n_luts, void* ws, size_t bytes, McArgs* a) {
     if (!mc_dims_ok(nz, ny, nx) || !volume || !luts || !offs || !dims || n_luts != N_LUTS) return DUDF_E_BADCFG;
@@ -377,14 +385,10 @@ int fill_args(const float* volume, int64_t nz, int64_t ny, int64_t nx, double le
     if (dims[3 * CASES] * dims[3 * CASES + 1] < 512 || dims[3 * EDGESRELX] * dims[3 * EDGESRELX + 1] < 24 ||
         dims[3 * EDGESRELY] * dims[3 * EDGESRELY + 1] < 24 || dims[3 * EDGESRELZ] * dims[3 * EDGESRELZ + 1] < 24) return DUDF_E_BADCFG;
     a->d.total = (int)total;
-    if (!ws || bytes < dudf_mc_lewiner_workspace_bytes(nz, ny, nx) || (reinterpret_cast<uintptr_t>(ws) & 15)) return DUDF_E_WORKSPACE;
-    const int64_t nb = mc_blocks(nz, ny, nx);
+    if (int rc = dudf_check_buffer(ws, bytes, carve_mc(ws, nz, ny, nx, a))) return rc;
     a->im = volume; a->luts = reinterpret_cast<const int8_t*>(luts);
     a->ny = ny; a->nx = nx; a->cz = (int)(nz - 1); a->cy = ny - 1; a->cx = nx - 1; a->ncells = (nz - 1) * (ny - 1) * (nx - 1);
     a->level = level;
-    a->off = reinterpret_cast<int64_t*>(ws);
-    a->blk = reinterpret_cast<uint32_t*>(a->off + nb * 2);
-    a->word = a->blk + nb * 2;
     a->verts = nullptr; a->faces = nullptr; a->normals = nullptr; a->values = nullptr;
     return 0;
 }
@@ -395,8 +399,8 @@ extern "C" {
 
 size_t dudf_mc_lewiner_workspace_bytes(int64_t nz, int64_t ny, int64_t nx) {
     if (!mc_dims_ok(nz, ny, nx)) return 0;
-    const int64_t nb = mc_blocks(nz, ny, nx);
-    return (size_t)(nb * 2 * (sizeof(int64_t) + sizeof(uint32_t)) + (nz - 1) * (ny - 1) * (nx - 1) * sizeof(uint32_t) + 64);
+    McArgs a;
+    return carve_mc(nullptr, nz, ny, nx, &a);
 }
 
 int dudf_mc_lewiner_count(const float* volume, int64_t nz, int64_t ny, int64_t nx, double level, const signed char* luts,

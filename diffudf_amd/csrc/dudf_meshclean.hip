@@ -11,7 +11,7 @@
 //   edges     a slot holds the key itself, (min << 32 | max), claimed with a 64-bit atomicCAS; `einfo` beside it counts the uses
 //             (bits 0..30) and notes whether min -> max occurs as a directed edge (bit 31).
 // Every probe loop is bounded by the capacity.
-#include "dudf_internal.h"
+#include "dudf_context.h"
 #include "dudf_wgscan.h"
 
 namespace {
@@ -374,20 +374,10 @@ int64_t pow2_at_least(int64_t n) { int64_t c = 2; while (c < n) c <<= 1; return 
 int64_t blocks_of(int64_t n) { return (n + WG - 1) / WG; }
 bool sizes_ok(int64_t V, int64_t F) { return V >= 0 && F >= 0 && V < (1ll << 31) && F < (1ll << 31); }
 
-// carves 256-byte-aligned arrays out of a byte buffer (base == nullptr: sizes only)
-struct ByteCarver {
-    char* base; size_t o;
-    template <class T> T* take(int64_t cnt) {
-        T* p = base ? reinterpret_cast<T*>(base + o) : nullptr;
-        o += dudf_round256((size_t)(cnt > 0 ? cnt : 1) * sizeof(T));
-        return p;
-    }
-};
-
 // zero-initialised arrays first, 0xff-initialised tables second, the rest behind: two memsets per call
 struct CleanSpans { size_t zero_end, ff_begin, ff_end, total; };
 CleanSpans carve_clean(void* ws, int64_t V, int64_t F, CleanArgs* a) {
-    ByteCarver cv = {static_cast<char*>(ws), 0};
+    DudfByteCarver cv = dudf_carve(ws);
     a->V = V; a->F = F;
     a->capV = pow2_at_least(2 * V); a->capF = pow2_at_least(2 * F); a->capE = pow2_at_least(6 * F);
     a->nbV = blocks_of(V); a->nbF = blocks_of(F);
@@ -413,8 +403,8 @@ int fill_clean(const double* vertices, int64_t V, const int64_t* faces, int64_t 
     if (V < 0 || F < 0 || digits < 0 || digits > 15 || (fill != 0 && fill != 1)) return DUDF_E_BADCFG;
     if (!sizes_ok(V, F)) return DUDF_E_UNSUPPORTED;
     if ((V > 0 && !vertices) || (F > 0 && !faces)) return DUDF_E_BADCFG;
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255) || bytes < dudf_mesh_clean_workspace_bytes(V, F)) return DUDF_E_WORKSPACE;
     *sp = carve_clean(ws, V, F, a);
+    if (int rc = dudf_check_buffer(ws, bytes, sp->total)) return rc;
     a->vert = vertices; a->face = faces; a->scale = kPow10[digits]; a->fill = fill;
     a->out_v = nullptr; a->out_f = nullptr;
     return 0;
@@ -523,7 +513,7 @@ __global__ __launch_bounds__(WG) void border_smooth_kernel(BorderArgs a, const d
 
 struct BorderSpans { size_t zero_end, ff_end, total; };
 BorderSpans carve_border(void* ws, int64_t V, int64_t F, BorderArgs* a) {
-    ByteCarver cv = {static_cast<char*>(ws), 0};
+    DudfByteCarver cv = dudf_carve(ws);
     a->V = V; a->F = F; a->capE = pow2_at_least(6 * F); a->nbV = blocks_of(V);
     a->head = cv.take<int64_t>(3); a->tot = cv.take<int64_t>(2);
     a->deg = cv.take<int32_t>(V); a->up = cv.take<int32_t>(V); a->cur = cv.take<int32_t>(V); a->einfo = cv.take<uint32_t>(a->capE);
@@ -544,8 +534,8 @@ int fill_border(int64_t V, const int64_t* faces, int64_t F, void* ws, size_t byt
     if (V < 0 || F < 0) return DUDF_E_BADCFG;
     if (!border_sizes_ok(V, F)) return DUDF_E_UNSUPPORTED;
     if (F > 0 && !faces) return DUDF_E_BADCFG;
-    if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255) || bytes < dudf_mesh_border_workspace_bytes(V, F)) return DUDF_E_WORKSPACE;
     *sp = carve_border(ws, V, F, a);
+    if (int rc = dudf_check_buffer(ws, bytes, sp->total)) return rc;
     a->face = faces;
     return 0;
 }

@@ -37,20 +37,21 @@ constexpr int kHdrBytes = 256;                   // header: 3 + 3 encoded bounds
 constexpr int kGridCap = 8192;                   // workgroups of the build launches; the kernels stride over the rest
 constexpr unsigned kFlagNonFinite = 1u, kFlagBadOrder = 2u;
 
-struct Layout {                                  // byte offsets inside the index
+struct Layout {                                  // the sections of the index (null for a null index) and its size
     int64_t n_leaves; int L, depth;              // L leaf slots (power of two), depth = stack entries a lane can need
-    size_t ids, stri, nodes, total;
+    unsigned* hdr; int* ids; float* stri; float4* nodes; size_t total;
 };
-inline Layout layout_of(int64_t T) {
+// the published layout (include/dudf_hip.h): header, ids [T], sorted triangles [T][9], nodes [2L - 1][2], each on a 256-byte granule
+inline Layout carve_index(const void* index, int64_t T) {
     Layout y;
     y.n_leaves = (T + kLeaf - 1) / kLeaf;
     int lg = 0;
     while (((int64_t)1 << lg) < y.n_leaves) ++lg;
     y.L = 1 << lg; y.depth = lg + 1;
-    y.ids = kHdrBytes;
-    y.stri = y.ids + dudf_round256((size_t)T * sizeof(int));
-    y.nodes = y.stri + dudf_round256((size_t)T * 9 * sizeof(float));
-    y.total = y.nodes + dudf_round256((size_t)(2 * (int64_t)y.L - 1) * 2 * sizeof(float4));
+    DudfByteCarver cv = dudf_carve(index);
+    y.hdr = cv.take<unsigned>(kHdrBytes / sizeof(unsigned));
+    y.ids = cv.take<int>(T); y.stri = cv.take<float>(T * 9); y.nodes = cv.take<float4>((2 * (int64_t)y.L - 1) * 2);
+    y.total = cv.o;
     return y;
 }
 
@@ -464,7 +465,7 @@ extern "C" {
 
 size_t dudf_mesh_index_bytes(int64_t n_tri) {
     if (n_tri <= 0 || n_tri >= ((int64_t)1 << 31)) return 0;
-    return layout_of(n_tri).total;
+    return carve_index(nullptr, n_tri).total;
 }
 
 // header: bounds of all vertices and the non-finite flag; clears the other flags
@@ -476,7 +477,7 @@ static hipError_t launch_bounds(const float* tri, int64_t T, unsigned* hdr, hipS
     return hipGetLastError();
 }
 
-static int check_index(const void* index, size_t index_bytes, int64_t T) { return dudf_check_buffer(index, index_bytes, layout_of(T).total); }
+static int check_index(const void* index, size_t index_bytes, int64_t T) { return dudf_check_buffer(index, index_bytes, carve_index(nullptr, T).total); }
 
 int dudf_mesh_morton_codes(const float* tri, int64_t n_tri, void* index, size_t index_bytes, int64_t* codes, void* stream) {
     if (n_tri <= 0 || !tri || !codes) return DUDF_E_BADCFG;
@@ -484,7 +485,7 @@ int dudf_mesh_morton_codes(const float* tri, int64_t n_tri, void* index, size_t 
     if (int rc = check_index(index, index_bytes, n_tri)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    unsigned* hdr = reinterpret_cast<unsigned*>(index);
+    unsigned* hdr = carve_index(index, n_tri).hdr;
     hipError_t e = launch_bounds(tri, n_tri, hdr, st);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(mesh_codes_kernel, dim3(dudf_grid_for(n_tri, 256, kGridCap)), dim3(256), 0, st, tri, n_tri, hdr, codes);
@@ -497,22 +498,17 @@ int dudf_mesh_index_build(const float* tri, int64_t n_tri, const int64_t* order,
     if (int rc = check_index(index, index_bytes, n_tri)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    const Layout y = layout_of(n_tri);
-    char* base = reinterpret_cast<char*>(index);
-    unsigned* hdr = reinterpret_cast<unsigned*>(base);
-    int* ids = reinterpret_cast<int*>(base + y.ids);
-    float* stri = reinterpret_cast<float*>(base + y.stri);
-    float4* nodes = reinterpret_cast<float4*>(base + y.nodes);
-    hipError_t e = launch_bounds(tri, n_tri, hdr, st);                        // the build stands alone: any permutation is a valid order
+    const Layout y = carve_index(index, n_tri);
+    hipError_t e = launch_bounds(tri, n_tri, y.hdr, st);                      // the build stands alone: any permutation is a valid order
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mesh_gather_kernel, dim3(dudf_grid_for(n_tri, 256, kGridCap)), dim3(256), 0, st, tri, n_tri, order, ids,
-                       stri, hdr);
+    hipLaunchKernelGGL(mesh_gather_kernel, dim3(dudf_grid_for(n_tri, 256, kGridCap)), dim3(256), 0, st, tri, n_tri, order, y.ids,
+                       y.stri, y.hdr);
     e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mesh_leaves_kernel, dim3(dudf_grid_for(y.L, 256, kGridCap)), dim3(256), 0, st, stri, n_tri, y.L, nodes);
+    hipLaunchKernelGGL(mesh_leaves_kernel, dim3(dudf_grid_for(y.L, 256, kGridCap)), dim3(256), 0, st, y.stri, n_tri, y.L, y.nodes);
     e = hipGetLastError();
     for (int count = y.L / 2; count >= 1 && e == hipSuccess; count /= 2) {       // level of `count` nodes starts at node count - 1
-        hipLaunchKernelGGL(mesh_level_kernel, dim3(dudf_grid_for(count, 256, kGridCap)), dim3(256), 0, st, nodes, count - 1, count);
+        hipLaunchKernelGGL(mesh_level_kernel, dim3(dudf_grid_for(count, 256, kGridCap)), dim3(256), 0, st, y.nodes, count - 1, count);
         e = hipGetLastError();
     }
     return (int)e;
@@ -523,12 +519,8 @@ static MeshView view_of(const float* tri, int64_t n_tri, const void* index) {
     MeshView m;
     m.tri = tri; m.T = n_tri; m.ids = nullptr; m.stri = nullptr; m.nodes = nullptr; m.L = 0; m.depth = 0;
     if (index) {
-        const Layout y = layout_of(n_tri);
-        const char* base = reinterpret_cast<const char*>(index);
-        m.ids = reinterpret_cast<const int*>(base + y.ids);
-        m.stri = reinterpret_cast<const float*>(base + y.stri);
-        m.nodes = reinterpret_cast<const float4*>(base + y.nodes);
-        m.L = y.L; m.depth = y.depth;
+        const Layout y = carve_index(index, n_tri);
+        m.ids = y.ids; m.stri = y.stri; m.nodes = y.nodes; m.L = y.L; m.depth = y.depth;
     }
     return m;
 }

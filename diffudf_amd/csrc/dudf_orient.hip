@@ -585,112 +585,104 @@ inline int grid_cells_per_axis(int64_t m) {
     return g < 1 ? 1 : g > kMaxG ? kMaxG : g;
 }
 
-struct GridLayout {                                            // byte offsets into the workspace, each a multiple of 256
+// The cell grid's arrays.  Those that depend on n come last, so the layout of (0, m) is a prefix of the layout of (n, m): the grid
+// dudf_knn_grid_build leaves in a workspace sized for (0, m) is the one dudf_knn_points(n, m) builds in front of its query arrays.
+struct GridLayout {
     int G; int64_t ncells, nblocks;
-    size_t o_prm, o_below, o_above, o_total, o_blk, o_off, o_pcell, o_pts, o_cstart, o_tmp, o_qcell, o_qorder, bytes;
+    GridParams* prm; float *below, *above;                     // [3][G + 1] each
+    int64_t* total; uint32_t* blk; int64_t* off;               // the scan's [nblocks] block sums and their offsets
+    int* pcell; float4* pts;                                   // [m]
+    unsigned *cstart, *tmp;                                    // [ncells + 1], [ncells]
+    int* qcell; unsigned* qorder;                              // [n]
+    size_t bytes;
 };
-inline GridLayout grid_layout(int64_t n, int64_t m) {
+inline GridLayout carve_grid(void* ws, int64_t n, int64_t m) {
     GridLayout g;
     g.G = grid_cells_per_axis(m);
     g.ncells = (int64_t)g.G * g.G * g.G;
     g.nblocks = (g.ncells + DUDF_WG * kScanItems - 1) / (DUDF_WG * kScanItems);
-    size_t o = 0;
-    auto take = [&o](size_t b) { const size_t at = o; o += dudf_round256(b); return at; };
-    g.o_prm = take(sizeof(GridParams));
-    g.o_below = take((size_t)3 * (g.G + 1) * sizeof(float));
-    g.o_above = take((size_t)3 * (g.G + 1) * sizeof(float));
-    g.o_total = take(sizeof(int64_t));
-    g.o_blk = take((size_t)g.nblocks * sizeof(uint32_t));
-    g.o_off = take((size_t)g.nblocks * sizeof(int64_t));
-    g.o_pcell = take((size_t)(m > 0 ? m : 1) * sizeof(int));
-    g.o_pts = take((size_t)(m > 0 ? m : 1) * sizeof(float4));
-    g.o_cstart = take((size_t)(g.ncells + 1) * sizeof(unsigned));
-    g.o_tmp = take((size_t)g.ncells * sizeof(unsigned));
-    g.o_qcell = take((size_t)(n > 0 ? n : 1) * sizeof(int));
-    g.o_qorder = take((size_t)(n > 0 ? n : 1) * sizeof(unsigned));
-    g.bytes = o;
+    DudfByteCarver cv = dudf_carve(ws);
+    g.prm = cv.take<GridParams>(1); g.below = cv.take<float>(3 * (g.G + 1)); g.above = cv.take<float>(3 * (g.G + 1));
+    g.total = cv.take<int64_t>(1); g.blk = cv.take<uint32_t>(g.nblocks); g.off = cv.take<int64_t>(g.nblocks);
+    g.pcell = cv.take<int>(m); g.pts = cv.take<float4>(m);
+    g.cstart = cv.take<unsigned>(g.ncells + 1); g.tmp = cv.take<unsigned>(g.ncells);
+    g.qcell = cv.take<int>(n); g.qorder = cv.take<unsigned>(n);
+    g.bytes = cv.o;
     return g;
 }
 
 #define KNN_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 // counts in `tmp` -> exclusive starts in `out` (may be tmp itself)
-int scan_cells_host(const GridLayout& g, char* ws, unsigned* out, int write_end, hipStream_t st) {
-    unsigned* tmp = reinterpret_cast<unsigned*>(ws + g.o_tmp);
-    uint32_t* blk = reinterpret_cast<uint32_t*>(ws + g.o_blk);
-    int64_t* off = reinterpret_cast<int64_t*>(ws + g.o_off);
-    int64_t* total = reinterpret_cast<int64_t*>(ws + g.o_total);
-    hipLaunchKernelGGL(cell_scan_local_kernel, dim3((unsigned)g.nblocks), dim3(DUDF_WG), 0, st, tmp, g.ncells, out, blk);
+int scan_cells_host(const GridLayout& g, unsigned* out, int write_end, hipStream_t st) {
+    hipLaunchKernelGGL(cell_scan_local_kernel, dim3((unsigned)g.nblocks), dim3(DUDF_WG), 0, st, g.tmp, g.ncells, out, g.blk);
     KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dudf_scan_totals_kernel<1>, dim3(1), dim3(1024), 0, st, blk, off, g.nblocks, total);
+    hipLaunchKernelGGL(dudf_scan_totals_kernel<1>, dim3(1), dim3(1024), 0, st, g.blk, g.off, g.nblocks, g.total);
     KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(cell_scan_add_kernel, dim3((unsigned)g.nblocks), dim3(DUDF_WG), 0, st, out, g.ncells, off, total, write_end);
+    hipLaunchKernelGGL(cell_scan_add_kernel, dim3((unsigned)g.nblocks), dim3(DUDF_WG), 0, st, out, g.ncells, g.off, g.total, write_end);
     KNN_CHECK_LAUNCH();
     return 0;
 }
 
-int grid_build(const GridLayout& g, const float* y, int64_t m, char* ws, hipStream_t st) {
-    GridParams* prm = reinterpret_cast<GridParams*>(ws + g.o_prm);
-    float* below = reinterpret_cast<float*>(ws + g.o_below);
-    float* above = reinterpret_cast<float*>(ws + g.o_above);
-    int* pcell = reinterpret_cast<int*>(ws + g.o_pcell);
-    float4* pts = reinterpret_cast<float4*>(ws + g.o_pts);
-    unsigned* cstart = reinterpret_cast<unsigned*>(ws + g.o_cstart);
-    unsigned* tmp = reinterpret_cast<unsigned*>(ws + g.o_tmp);
+int grid_build(const GridLayout& g, const float* y, int64_t m, hipStream_t st) {
     const dim3 rows(dudf_grid_for(m, kBlock, kGridCap));
-    hipLaunchKernelGGL(grid_init_kernel, dim3(1), dim3(64), 0, st, prm);
+    hipLaunchKernelGGL(grid_init_kernel, dim3(1), dim3(64), 0, st, g.prm);
     KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(grid_bbox_kernel, rows, dim3(kBlock), 0, st, y, (int)m, prm);
+    hipLaunchKernelGGL(grid_bbox_kernel, rows, dim3(kBlock), 0, st, y, (int)m, g.prm);
     KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(grid_params_kernel, dim3(1), dim3(kBlock), 0, st, prm, g.G, below, above);
+    hipLaunchKernelGGL(grid_params_kernel, dim3(1), dim3(kBlock), 0, st, g.prm, g.G, g.below, g.above);
     KNN_CHECK_LAUNCH();
-    hipError_t e = hipMemsetAsync(tmp, 0, (size_t)g.ncells * sizeof(unsigned), st);
+    hipError_t e = hipMemsetAsync(g.tmp, 0, (size_t)g.ncells * sizeof(unsigned), st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cell_count_kernel, rows, dim3(kBlock), 0, st, y, m, prm, 1, pcell, tmp);
+    hipLaunchKernelGGL(cell_count_kernel, rows, dim3(kBlock), 0, st, y, m, g.prm, 1, g.pcell, g.tmp);
     KNN_CHECK_LAUNCH();
-    if (int rc = scan_cells_host(g, ws, cstart, 1, st)) return rc;
-    e = hipMemcpyAsync(tmp, cstart, (size_t)g.ncells * sizeof(unsigned), hipMemcpyDeviceToDevice, st);
+    if (int rc = scan_cells_host(g, g.cstart, 1, st)) return rc;
+    e = hipMemcpyAsync(g.tmp, g.cstart, (size_t)g.ncells * sizeof(unsigned), hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cell_scatter_points_kernel, rows, dim3(kBlock), 0, st, y, (int)m, pcell, tmp, pts);
+    hipLaunchKernelGGL(cell_scatter_points_kernel, rows, dim3(kBlock), 0, st, y, (int)m, g.pcell, g.tmp, g.pts);
     KNN_CHECK_LAUNCH();
     return 0;
 }
 
 template <int KC>
 int knn_grid_run(const GridLayout& g, const float* x, int64_t n, int64_t m, int K, int exclude_self, float* out_dist, int64_t* out_idx,
-                 char* ws, hipStream_t st) {
-    GridParams* prm = reinterpret_cast<GridParams*>(ws + g.o_prm);
-    unsigned* tmp = reinterpret_cast<unsigned*>(ws + g.o_tmp);
-    int* qcell = reinterpret_cast<int*>(ws + g.o_qcell);
-    unsigned* qorder = reinterpret_cast<unsigned*>(ws + g.o_qorder);
+                 hipStream_t st) {
     const dim3 rows(dudf_grid_for(n, kBlock, kGridCap));
     // the queries in cell order: a wave's lanes then walk the same rows of cells and share their cache lines
-    hipError_t e = hipMemsetAsync(tmp, 0, (size_t)g.ncells * sizeof(unsigned), st);
+    hipError_t e = hipMemsetAsync(g.tmp, 0, (size_t)g.ncells * sizeof(unsigned), st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cell_count_kernel, rows, dim3(kBlock), 0, st, x, n, prm, 0, qcell, tmp);
+    hipLaunchKernelGGL(cell_count_kernel, rows, dim3(kBlock), 0, st, x, n, g.prm, 0, g.qcell, g.tmp);
     KNN_CHECK_LAUNCH();
-    if (int rc = scan_cells_host(g, ws, tmp, 0, st)) return rc;
-    hipLaunchKernelGGL(cell_scatter_queries_kernel, rows, dim3(kBlock), 0, st, n, qcell, tmp, qorder);
+    if (int rc = scan_cells_host(g, g.tmp, 0, st)) return rc;
+    hipLaunchKernelGGL(cell_scatter_queries_kernel, rows, dim3(kBlock), 0, st, n, g.qcell, g.tmp, g.qorder);
     KNN_CHECK_LAUNCH();
     hipLaunchKernelGGL(knn_grid_kernel<KC>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, x, n, (int)m, K, exclude_self,
-                       prm, reinterpret_cast<const float*>(ws + g.o_below), reinterpret_cast<const float*>(ws + g.o_above), g.G,
-                       reinterpret_cast<const float4*>(ws + g.o_pts), reinterpret_cast<const unsigned*>(ws + g.o_cstart), qorder,
-                       out_dist, out_idx);
+                       g.prm, g.below, g.above, g.G, g.pts, g.cstart, g.qorder, out_dist, out_idx);
     KNN_CHECK_LAUNCH();
     return 0;
 }
 
+// the brute mode's one array: [splits][n][K] partial lists
+struct BruteLayout { BruteSplit b; unsigned long long* part; size_t bytes; };
+inline BruteLayout carve_brute(void* ws, int64_t n, int64_t m, int K) {
+    BruteLayout l;
+    l.b = brute_split(n > 0 ? n : 1, m > 0 ? m : 1, K);
+    DudfByteCarver cv = dudf_carve(ws);
+    l.part = cv.take<unsigned long long>((n > 0 ? n : 1) * K * l.b.splits);
+    l.bytes = cv.o;
+    return l;
+}
+
 template <int KC, int PPL>
-int knn_brute_run(const float* x, int64_t n, const float* y, int64_t m, int K, int exclude_self, float* out_dist, int64_t* out_idx,
-                  char* ws, hipStream_t st) {
-    const BruteSplit b = brute_split(n, m, K);
-    unsigned long long* part = reinterpret_cast<unsigned long long*>(ws);
+int knn_brute_run(const BruteLayout& l, const float* x, int64_t n, const float* y, int64_t m, int K, int exclude_self, float* out_dist,
+                  int64_t* out_idx, hipStream_t st) {
+    const BruteSplit& b = l.b;
     hipLaunchKernelGGL((knn_brute_kernel<KC, PPL>), dim3((unsigned)b.xgroups, (unsigned)b.splits), dim3(kBlock), 0, st, x, n, y, (int)m,
-                       (int)b.ychunk, K, exclude_self, part);
+                       (int)b.ychunk, K, exclude_self, l.part);
     KNN_CHECK_LAUNCH();
     if (out_dist || out_idx) {
         hipLaunchKernelGGL(knn_merge_kernel<KC>, dim3(dudf_grid_for(n, kBlock, kGridCap)), dim3(kBlock), 0, st, x, n, (int)m, K,
-                           (int)b.splits, part, out_dist, out_idx);
+                           (int)b.splits, l.part, out_dist, out_idx);
         KNN_CHECK_LAUNCH();
     }
     return 0;
@@ -706,21 +698,23 @@ inline int ceil_log2(int64_t n) {
     return b;
 }
 
-struct OrientLayout { size_t o_cnt, o_flags, o_pp0, o_pp1, o_best, o_minidx, o_rootflip, o_wbits, bytes; };
-inline OrientLayout orient_layout(int64_t n, int K) {
+struct OrientLayout {
+    unsigned long long* cnt;                                   // [4] hooks in all, components, hooks of this round
+    unsigned* flags;                                           // [64]
+    unsigned* pp[2];                                           // [n] each: the union-find words, ping-pong
+    unsigned long long* best;                                  // [n] the best edge of a round, later the seed key
+    unsigned* minidx; unsigned char* rootflip;                 // [n]
+    unsigned* wbits;                                           // [n][K]
+    size_t bytes;
+};
+inline OrientLayout carve_orient(void* ws, int64_t n, int K) {
     OrientLayout l;
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    size_t o = 0;
-    auto take = [&o](size_t b) { const size_t at = o; o += dudf_round256(b); return at; };
-    l.o_cnt = take(4 * sizeof(unsigned long long));            // hooks in all, components, hooks of this round
-    l.o_flags = take(64 * sizeof(unsigned));
-    l.o_pp0 = take(nn * sizeof(unsigned));
-    l.o_pp1 = take(nn * sizeof(unsigned));
-    l.o_best = take(nn * sizeof(unsigned long long));          // the best edge of a round, later the seed key
-    l.o_minidx = take(nn * sizeof(unsigned));
-    l.o_rootflip = take(nn);
-    l.o_wbits = take(nn * (size_t)K * sizeof(unsigned));
-    l.bytes = o;
+    DudfByteCarver cv = dudf_carve(ws);
+    l.cnt = cv.take<unsigned long long>(4); l.flags = cv.take<unsigned>(64);
+    l.pp[0] = cv.take<unsigned>(n); l.pp[1] = cv.take<unsigned>(n);
+    l.best = cv.take<unsigned long long>(n); l.minidx = cv.take<unsigned>(n); l.rootflip = cv.take<unsigned char>(n);
+    l.wbits = cv.take<unsigned>(n * K);
+    l.bytes = cv.o;
     return l;
 }
 
@@ -730,21 +724,17 @@ extern "C" {
 
 size_t dudf_knn_workspace_bytes(int64_t n, int64_t m, int K, int mode) {
     if (n < 0 || m < 0 || (mode != 0 && mode != 1) || !knn_sizes_supported(n, m, K)) return 0;
-    if (mode == 1) {
-        const BruteSplit b = brute_split(n > 0 ? n : 1, m > 0 ? m : 1, K);
-        return dudf_round256((size_t)(n > 0 ? n : 1) * (size_t)K * (size_t)b.splits * sizeof(unsigned long long));
-    }
-    return grid_layout(n, m).bytes;
+    return mode == 1 ? carve_brute(nullptr, n, m, K).bytes : carve_grid(nullptr, n, m).bytes;
 }
 
 int dudf_knn_grid_build(const float* y, int64_t m, void* workspace, size_t workspace_bytes, void* stream) {
     if (m >= ((int64_t)1 << 31)) return DUDF_E_UNSUPPORTED;
     if (m <= 0 || !y) return DUDF_E_BADCFG;
-    const GridLayout g = grid_layout(0, m);
+    const GridLayout g = carve_grid(workspace, 0, m);
     if (int rc = dudf_check_buffer(workspace, workspace_bytes, g.bytes)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    return grid_build(g, y, m, reinterpret_cast<char*>(workspace), st);
+    return grid_build(g, y, m, st);
 }
 
 int dudf_knn_points(const float* x, int64_t n, const float* y, int64_t m, int K, int exclude_self, int mode, float* out_dist,
@@ -754,35 +744,35 @@ int dudf_knn_points(const float* x, int64_t n, const float* y, int64_t m, int K,
     if (!knn_sizes_supported(n, m, K)) return DUDF_E_UNSUPPORTED;
     if (n == 0) return 0;
     if (m <= 0 || !x || !y) return DUDF_E_BADCFG;
-    if (int rc = dudf_check_buffer(workspace, workspace_bytes, dudf_knn_workspace_bytes(n, m, K, mode))) return rc;
+    const BruteLayout l = carve_brute(workspace, n, m, K);
+    const GridLayout g = carve_grid(workspace, n, m);
+    if (int rc = dudf_check_buffer(workspace, workspace_bytes, mode == 1 ? l.bytes : g.bytes)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    char* ws = reinterpret_cast<char*>(workspace);
     exclude_self = exclude_self ? 1 : 0;
     if (mode == 1) {
         switch (knn_cap(K)) {
-            case 1: return knn_brute_run<1, 4>(x, n, y, m, K, exclude_self, out_dist, out_idx, ws, st);
-            case 4: return knn_brute_run<4, 4>(x, n, y, m, K, exclude_self, out_dist, out_idx, ws, st);
-            case 8: return knn_brute_run<8, 2>(x, n, y, m, K, exclude_self, out_dist, out_idx, ws, st);
-            case 10: return knn_brute_run<10, 2>(x, n, y, m, K, exclude_self, out_dist, out_idx, ws, st);
-            default: return knn_brute_run<16, 2>(x, n, y, m, K, exclude_self, out_dist, out_idx, ws, st);
+            case 1: return knn_brute_run<1, 4>(l, x, n, y, m, K, exclude_self, out_dist, out_idx, st);
+            case 4: return knn_brute_run<4, 4>(l, x, n, y, m, K, exclude_self, out_dist, out_idx, st);
+            case 8: return knn_brute_run<8, 2>(l, x, n, y, m, K, exclude_self, out_dist, out_idx, st);
+            case 10: return knn_brute_run<10, 2>(l, x, n, y, m, K, exclude_self, out_dist, out_idx, st);
+            default: return knn_brute_run<16, 2>(l, x, n, y, m, K, exclude_self, out_dist, out_idx, st);
         }
     }
-    const GridLayout g = grid_layout(n, m);
-    if (int rc = grid_build(g, y, m, ws, st)) return rc;
+    if (int rc = grid_build(g, y, m, st)) return rc;
     if (!out_dist && !out_idx) return 0;
     switch (knn_cap(K)) {
-        case 1: return knn_grid_run<1>(g, x, n, m, K, exclude_self, out_dist, out_idx, ws, st);
-        case 4: return knn_grid_run<4>(g, x, n, m, K, exclude_self, out_dist, out_idx, ws, st);
-        case 8: return knn_grid_run<8>(g, x, n, m, K, exclude_self, out_dist, out_idx, ws, st);
-        case 10: return knn_grid_run<10>(g, x, n, m, K, exclude_self, out_dist, out_idx, ws, st);
-        default: return knn_grid_run<16>(g, x, n, m, K, exclude_self, out_dist, out_idx, ws, st);
+        case 1: return knn_grid_run<1>(g, x, n, m, K, exclude_self, out_dist, out_idx, st);
+        case 4: return knn_grid_run<4>(g, x, n, m, K, exclude_self, out_dist, out_idx, st);
+        case 8: return knn_grid_run<8>(g, x, n, m, K, exclude_self, out_dist, out_idx, st);
+        case 10: return knn_grid_run<10>(g, x, n, m, K, exclude_self, out_dist, out_idx, st);
+        default: return knn_grid_run<16>(g, x, n, m, K, exclude_self, out_dist, out_idx, st);
     }
 }
 
 size_t dudf_orient_workspace_bytes(int64_t n, int K) {
     if (n < 0 || n >= ((int64_t)1 << 31) || K < 1 || K > kMaxK || n * K >= ((int64_t)1 << 32)) return 0;
-    return orient_layout(n, K).bytes;
+    return carve_orient(nullptr, n, K).bytes;
 }
 
 int dudf_orient_normals(const float* points, const float* normals, const int64_t* knn_idx, int64_t n, int K, float* out_normals,
@@ -793,56 +783,48 @@ int dudf_orient_normals(const float* points, const float* normals, const int64_t
     if (host_stats) host_stats[0] = host_stats[1] = 0;
     if (n == 0) return 0;
     if (!points || !normals || !knn_idx) return DUDF_E_BADCFG;
-    const OrientLayout l = orient_layout(n, K);
+    const OrientLayout l = carve_orient(workspace, n, K);
     if (int rc = dudf_check_buffer(workspace, workspace_bytes, l.bytes)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    char* ws = reinterpret_cast<char*>(workspace);
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(ws + l.o_cnt);
-    unsigned* flags = reinterpret_cast<unsigned*>(ws + l.o_flags);
-    unsigned* pp[2] = {reinterpret_cast<unsigned*>(ws + l.o_pp0), reinterpret_cast<unsigned*>(ws + l.o_pp1)};
-    unsigned long long* best = reinterpret_cast<unsigned long long*>(ws + l.o_best);
-    unsigned* minidx = reinterpret_cast<unsigned*>(ws + l.o_minidx);
-    unsigned char* rootflip = reinterpret_cast<unsigned char*>(ws + l.o_rootflip);
-    unsigned* wbits = reinterpret_cast<unsigned*>(ws + l.o_wbits);
     const dim3 vgrid(dudf_grid_for(n, kBlock, kGridCap)), sgrid(dudf_grid_for(n * K, kBlock, kGridCap)), blk(kBlock);
     int64_t launches = 0, rounds = 0;
-    hipError_t e = hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), st);
+    hipError_t e = hipMemsetAsync(l.cnt, 0, 4 * sizeof(unsigned long long), st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(orient_init_kernel, sgrid, blk, 0, st, normals, knn_idx, n, K, pp[0], wbits);
+    hipLaunchKernelGGL(orient_init_kernel, sgrid, blk, 0, st, normals, knn_idx, n, K, l.pp[0], l.wbits);
     KNN_CHECK_LAUNCH(); ++launches;
     // Borůvka: the components at least halve per round that hooks anything, and a round that hooks nothing is the last
     const int jumps = ceil_log2(n) > 0 ? ceil_log2(n) : 1, max_rounds = ceil_log2(n) + 1;
     int c = 0;                                                   // pp[c] is current and flat
     unsigned long long total_hooks = 0;
     for (int r = 0; r < max_rounds; ++r) {
-        if ((e = hipMemsetAsync(best, 0xff, (size_t)n * sizeof(unsigned long long), st)) != hipSuccess) return (int)e;
-        if ((e = hipMemsetAsync(flags, 0, 64 * sizeof(unsigned), st)) != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(orient_best_kernel, sgrid, blk, 0, st, knn_idx, n, K, pp[c], wbits, best);
+        if ((e = hipMemsetAsync(l.best, 0xff, (size_t)n * sizeof(unsigned long long), st)) != hipSuccess) return (int)e;
+        if ((e = hipMemsetAsync(l.flags, 0, 64 * sizeof(unsigned), st)) != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(orient_best_kernel, sgrid, blk, 0, st, knn_idx, n, K, l.pp[c], l.wbits, l.best);
         KNN_CHECK_LAUNCH();
-        hipLaunchKernelGGL(orient_hook_kernel, vgrid, blk, 0, st, normals, knn_idx, n, K, pp[c], pp[1 - c], best, cnt);
+        hipLaunchKernelGGL(orient_hook_kernel, vgrid, blk, 0, st, normals, knn_idx, n, K, l.pp[c], l.pp[1 - c], l.best, l.cnt);
         KNN_CHECK_LAUNCH();
         c = 1 - c;
         for (int s = 0; s < jumps; ++s) {
-            hipLaunchKernelGGL(orient_jump_kernel, vgrid, blk, 0, st, n, pp[c], pp[1 - c], flags, s);
+            hipLaunchKernelGGL(orient_jump_kernel, vgrid, blk, 0, st, n, l.pp[c], l.pp[1 - c], l.flags, s);
             KNN_CHECK_LAUNCH();
             c = 1 - c;
         }
         launches += 2 + jumps; ++rounds;
         unsigned long long hooks = 0;                            // the one read-back of the round
-        if ((e = hipMemcpyAsync(&hooks, cnt, sizeof(hooks), hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
+        if ((e = hipMemcpyAsync(&hooks, l.cnt, sizeof(hooks), hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e;
         if (hooks == total_hooks) break;
         total_hooks = hooks;
     }
-    if ((e = hipMemsetAsync(best, 0, (size_t)n * sizeof(unsigned long long), st)) != hipSuccess) return (int)e;
-    if ((e = hipMemsetAsync(minidx, 0xff, (size_t)n * sizeof(unsigned), st)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(orient_seed_kernel, vgrid, blk, 0, st, points, n, pp[c], best, minidx);
+    if ((e = hipMemsetAsync(l.best, 0, (size_t)n * sizeof(unsigned long long), st)) != hipSuccess) return (int)e;
+    if ((e = hipMemsetAsync(l.minidx, 0xff, (size_t)n * sizeof(unsigned), st)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(orient_seed_kernel, vgrid, blk, 0, st, points, n, l.pp[c], l.best, l.minidx);
     KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(orient_root_kernel, vgrid, blk, 0, st, normals, n, pp[c], best, rootflip, cnt + 1);
+    hipLaunchKernelGGL(orient_root_kernel, vgrid, blk, 0, st, normals, n, l.pp[c], l.best, l.rootflip, l.cnt + 1);
     KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(orient_write_kernel, vgrid, blk, 0, st, normals, n, pp[c], rootflip, minidx, cnt, out_normals, out_flip, out_component,
-                       out_counts);
+    hipLaunchKernelGGL(orient_write_kernel, vgrid, blk, 0, st, normals, n, l.pp[c], l.rootflip, l.minidx, l.cnt, out_normals, out_flip,
+                       out_component, out_counts);
     KNN_CHECK_LAUNCH();
     launches += 3;
     if (host_stats) { host_stats[0] = rounds; host_stats[1] = launches; }

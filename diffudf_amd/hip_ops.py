@@ -133,6 +133,12 @@ def _scratch(nbytes, device):
     return buf
 
 
+def _workspace(device, name, *args, err=-1):
+    """(scratch, its byte count) for the stage whose size `name(*args)` publishes."""
+    nbytes = _bytes(name, *args, err=err)
+    return _scratch(nbytes, device), nbytes
+
+
 def _tensor(t, what, dtype, shape=None, convert=False):
     """`t` as the C ABI reads it: a contiguous CUDA tensor of `dtype` whose dimensions behind the first are `shape` (None: any
     shape).  convert: another dtype or stride is converted, otherwise it is refused."""
@@ -176,8 +182,7 @@ class Workspace:
 
     def __init__(self, cfg, n, device, n_hess=0):
         self.cfg, self.n, self.n_hess = cfg, int(n), int(n_hess)
-        self.nbytes = _bytes(self._bytes_symbol, ctypes.byref(cfg), self.n, self.n_hess)
-        self.buf = _scratch(self.nbytes, device)
+        self.buf, self.nbytes = _workspace(device, self._bytes_symbol, ctypes.byref(cfg), self.n, self.n_hess)
 
 
 class QueryWorkspace(Workspace):
@@ -261,8 +266,7 @@ def query_curvature(cfg, theta, x, want_shape=False, chunk=65536):
     gauss = torch.empty(n, dtype=torch.float32, device=dev) if want_shape else None
     shape = torch.empty(n, 3, 3, dtype=torch.float32, device=dev) if want_shape else None
     m = min(max(n, 1), int(chunk))
-    nbytes = _bytes("dudf_workspace_bytes_curvature", ctypes.byref(cfg), m)
-    buf = _scratch(nbytes, dev)
+    buf, nbytes = _workspace(dev, "dudf_workspace_bytes_curvature", ctypes.byref(cfg), m)
     for s in range(0, n, m):
         e = min(s + m, n)
         _call("dudf_query_curvature", ctypes.byref(cfg), _ptr(theta), _ptr(x[s:e]), e - s, _ptr(lam[s:e]), _ptr(v[s:e]),
@@ -338,8 +342,7 @@ def pointcloud_append(flags, src_a, dst_a, counter, src_b=None, dst_b=None, src_
     if src_a.shape[0] != n or (src_b is not None and (src_b.shape[0] != n or dst_b.shape[0] != dst_a.shape[0])) or \
             (src_f is not None and src_f.shape[0] != n):
         raise _lib.DudfError("pointcloud_append: row counts of flags and sources differ")
-    nbytes = _bytes("dudf_pointcloud_append_workspace_bytes", n)
-    ws = _scratch(nbytes, dev)
+    ws, nbytes = _workspace(dev, "dudf_pointcloud_append_workspace_bytes", n)
     _call("dudf_pointcloud_append", _ptr(flags), n, _ptr(src_a), _ptr(src_b), _ptr(src_f), _ptr(dst_a), _ptr(dst_b), _ptr(out_f),
           dst_a.shape[0], (1 << 62) if quota is None else int(quota), _ptr(counter), _ptr(ws), nbytes, dev=dev)
 
@@ -354,8 +357,7 @@ class PointCloudState:
         self.points = torch.zeros(self.capacity, 3, dtype=torch.float64, device=device)
         self.normals = torch.zeros(self.capacity, 3, dtype=torch.float64, device=device)
         self.counter = torch.zeros(4, dtype=torch.int64, device=device)
-        self.nbytes = _bytes("dudf_pointcloud_workspace_bytes", ctypes.byref(cfg), self.num_points)
-        self.buf = _scratch(self.nbytes, device)
+        self.buf, self.nbytes = _workspace(device, "dudf_pointcloud_workspace_bytes", ctypes.byref(cfg), self.num_points)
         self.rounds = 0
 
     def count(self):
@@ -423,8 +425,7 @@ def mc_lewiner_extract(volume, level, lut_data, lut_offsets, lut_dims):
         raise _lib.DudfError(f"mc_lewiner_extract: a (nz, ny, nx) volume and tables on its device expected, got {tuple(volume.shape)}")
     nz, ny, nx = volume.shape
     dev = volume.device
-    nbytes = _bytes("dudf_mc_lewiner_workspace_bytes", nz, ny, nx)
-    ws = _scratch(nbytes, dev)
+    ws, nbytes = _workspace(dev, "dudf_mc_lewiner_workspace_bytes", nz, ny, nx)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
     head = (_ptr(volume), nz, ny, nx, float(level), _ptr(lut_data), ctypes.c_void_p(lut_offsets.ctypes.data),
             ctypes.c_void_p(lut_dims.ctypes.data), len(lut_offsets))
@@ -448,8 +449,7 @@ def capudf_extract(ndf, grad, threshold=0.008, want_cells=False):
     if ndf.shape != (n, n, n) or grad.shape != (n, n, n, 3):
         raise _lib.DudfError(f"capudf_extract: ndf (N,N,N) and grad (N,N,N,3) expected, got {tuple(ndf.shape)}, {tuple(grad.shape)}")
     dev = ndf.device
-    nbytes = _bytes("dudf_capudf_workspace_bytes", n)
-    ws = _scratch(nbytes, dev)
+    ws, nbytes = _workspace(dev, "dudf_capudf_workspace_bytes", n)
     counts = torch.zeros(3, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         _call("dudf_capudf_count", _ptr(ndf), _ptr(grad), n, float(threshold), _ptr(counts), _ptr(ws), nbytes)
@@ -484,8 +484,7 @@ def mesh_clean_round(vertices, faces, digits=8, fill_holes=False):
     vertices, faces = _mesh(vertices, faces)
     dev = vertices.device
     V, F = vertices.shape[0], faces.shape[0]
-    nbytes = _bytes("dudf_mesh_clean_workspace_bytes", V, F, err=-4)
-    ws = _scratch(nbytes, dev)
+    ws, nbytes = _workspace(dev, "dudf_mesh_clean_workspace_bytes", V, F, err=-4)
     counts = torch.zeros(len(MESH_CLEAN_COUNTS), dtype=torch.int64, device=dev)
     head = (_ptr(vertices), V, _ptr(faces), F, int(digits), int(bool(fill_holes)))
     _call("dudf_mesh_clean_count", *head, _ptr(counts), _ptr(ws), nbytes, dev=dev)
@@ -505,8 +504,7 @@ def mesh_border_edges(faces, n_vertices):
     faces = _tensor(faces, "faces", torch.int64, (3,), convert=True)
     dev = faces.device
     V, F = int(n_vertices), faces.shape[0]
-    nbytes = _bytes("dudf_mesh_border_workspace_bytes", V, F, err=-4)
-    ws = _scratch(nbytes, dev)
+    ws, nbytes = _workspace(dev, "dudf_mesh_border_workspace_bytes", V, F, err=-4)
     count = torch.zeros(1, dtype=torch.int64, device=dev)
     _call("dudf_mesh_border_count", V, _ptr(faces), F, _ptr(count), _ptr(ws), nbytes, dev=dev)
     edges = torch.empty(int(count.item()), 2, dtype=torch.int64, device=dev)
@@ -521,8 +519,7 @@ def mesh_smooth_borders(vertices, faces, iterations=5, lam=0.3):
     vertices, faces = _mesh(vertices, faces)
     out = vertices.clone()
     V, F = out.shape[0], faces.shape[0]
-    nbytes = _bytes("dudf_mesh_border_workspace_bytes", V, F, err=-4)
-    ws = _scratch(nbytes, out.device)
+    ws, nbytes = _workspace(out.device, "dudf_mesh_border_workspace_bytes", V, F, err=-4)
     _call("dudf_mesh_smooth_borders", _ptr(out), V, _ptr(faces), F, int(iterations), float(lam), _ptr(ws), nbytes, dev=out.device)
     return out
 
@@ -688,8 +685,7 @@ def render_gather(hits, t0, rays=None):
     hr = torch.empty(m, 3, dtype=torch.float64, device=dev) if rays is not None else None
     rows = torch.empty(m, dtype=torch.int32, device=dev)
     counter = torch.empty(4, dtype=torch.int64, device=dev)
-    nbytes = _bytes("dudf_pointcloud_append_workspace_bytes", m)
-    ws = _scratch(nbytes, dev)
+    ws, nbytes = _workspace(dev, "dudf_pointcloud_append_workspace_bytes", m)
     _call("dudf_render_gather", _ptr(hits), m, _ptr(t0), _ptr(rays), _ptr(pos), _ptr(hr), _ptr(rows), _ptr(counter), _ptr(ws),
           nbytes, dev=dev)
     k = int(counter[1].item())
@@ -856,8 +852,7 @@ def nearest_points(x, y, norm=2, want_dist=True, want_idx=True):
     n, m, dev = x.shape[0], y.shape[0], x.device
     dist = torch.empty(n, dtype=torch.float32, device=dev) if want_dist else None
     idx = torch.empty(n, dtype=torch.int64, device=dev) if want_idx else None
-    nbytes = _bytes("dudf_nearest_workspace_bytes", n)
-    ws = _scratch(nbytes, dev)
+    ws, nbytes = _workspace(dev, "dudf_nearest_workspace_bytes", n)
     _call("dudf_nearest_points", _ptr(x), n, _ptr(y), m, int(norm), _ptr(dist), _ptr(idx), _ptr(ws), nbytes, dev=dev)
     return dist, idx
 
@@ -881,8 +876,7 @@ def chamfer_terms(dist, idx, x_normals=None, y_normals=None, out=None):
         out = torch.zeros(2, dtype=torch.float64, device=dev)
     elif _tensor(out, "chamfer_terms: out", torch.float64).numel() != 2:
         raise _lib.DudfError("chamfer_terms: out must be a float64 tensor of 2")
-    nbytes = _bytes("dudf_chamfer_terms_workspace_bytes", n)
-    ws = _scratch(nbytes, dev)
+    ws, nbytes = _workspace(dev, "dudf_chamfer_terms_workspace_bytes", n)
     _call("dudf_chamfer_terms", _ptr(dist), _ptr(idx) if x_normals is not None else _ptr(None), n, _ptr(x_normals),
           _ptr(y_normals), m, _ptr(out), _ptr(ws), nbytes, dev=dev)
     return out
@@ -899,8 +893,7 @@ def vertex_normals(vertices, faces):
         raise _lib.DudfError("vertex_normals: vertices and faces live on different devices")
     nv, nf, dev = vertices.shape[0], faces.shape[0], vertices.device
     out = torch.empty(nv, 3, dtype=torch.float32, device=dev)
-    nbytes = _bytes("dudf_vertex_normals_workspace_bytes", nv)
-    ws = _scratch(nbytes, dev)
+    ws, nbytes = _workspace(dev, "dudf_vertex_normals_workspace_bytes", nv)
     _call("dudf_vertex_normals", _ptr(vertices), nv, _ptr(faces), nf, _ptr(out), _ptr(ws), nbytes, dev=dev)
     return out
 
@@ -921,8 +914,7 @@ def knn_points(x, y, K=1, exclude_self=False, brute=False, want_dist=True, want_
     n, m, dev = x.shape[0], y.shape[0], x.device
     dist = torch.empty(n, K, dtype=torch.float32, device=dev) if want_dist and K > 0 else None
     idx = torch.empty(n, K, dtype=torch.int64, device=dev) if want_idx and K > 0 else None
-    nbytes = _bytes("dudf_knn_workspace_bytes", n, m, K, mode, err=-4)
-    ws = _scratch(nbytes, dev)
+    ws, nbytes = _workspace(dev, "dudf_knn_workspace_bytes", n, m, K, mode, err=-4)
     _call("dudf_knn_points", _ptr(x), n, _ptr(y), m, K, int(bool(exclude_self)), mode, _ptr(dist), _ptr(idx), _ptr(ws), nbytes, dev=dev)
     return dist, idx
 
@@ -930,8 +922,7 @@ def knn_points(x, y, K=1, exclude_self=False, brute=False, want_dist=True, want_
 def knn_grid_build(y):
     """The cell list `knn_points` builds over y (m,3) before it searches, alone (for timing); returns the workspace that holds it."""
     y = _tensor(y, "knn_grid_build: y", torch.float32, (3,), convert=True)
-    nbytes = _bytes("dudf_knn_workspace_bytes", 0, y.shape[0], 1, 0, err=-4)
-    ws = _scratch(nbytes, y.device)
+    ws, nbytes = _workspace(y.device, "dudf_knn_workspace_bytes", 0, y.shape[0], 1, 0, err=-4)
     _call("dudf_knn_grid_build", _ptr(y), y.shape[0], _ptr(ws), nbytes, dev=y.device)
     return ws
 
@@ -958,8 +949,7 @@ def orient_normals(points, normals, knn_idx, out=None):
     comp = torch.empty(n, dtype=torch.int64, device=dev)
     counts = torch.zeros(2, dtype=torch.int64, device=dev)
     stats = (ctypes.c_int64 * 2)()
-    nbytes = _bytes("dudf_orient_workspace_bytes", n, K, err=-4)
-    ws = _scratch(nbytes, dev)
+    ws, nbytes = _workspace(dev, "dudf_orient_workspace_bytes", n, K, err=-4)
     _call("dudf_orient_normals", _ptr(points), _ptr(normals), _ptr(knn_idx), n, K, _ptr(out), _ptr(flip), _ptr(comp), _ptr(counts), stats,
           _ptr(ws), nbytes, dev=dev)
     return out, flip, comp, counts, {"rounds": int(stats[0]), "launches": int(stats[1])}

@@ -369,7 +369,8 @@ int dudf_grid_fields(const dudf_net_cfg* cfg, const float* theta, int64_t grid_n
  * Two calls because the output size is data dependent:
  *   dudf_capudf_count -> out_counts (device, 3 x int64): emitted cells, vertices, triangles;
  *   dudf_capudf_emit  -> out_vertices (V,3) double, out_triangles (T,3) int64 (indices into out_vertices),
- *                        out_cells (C,3) int64 or NULL; same ndf / grad / threshold / workspace as the count call. */
+ *                        out_cells (C,3) int64 or NULL; same ndf / grad / threshold / workspace as the count call.
+ * workspace: dudf_capudf_workspace_bytes(grid_n), 256-byte aligned, else DUDF_E_WORKSPACE. */
 size_t dudf_capudf_workspace_bytes(int64_t grid_n);
 int dudf_capudf_count(const float* ndf, const float* grad, int64_t grid_n, double threshold, int64_t* out_counts,
                       void* workspace, size_t workspace_bytes, void* stream);
@@ -391,7 +392,8 @@ int dudf_grid_values(const dudf_net_cfg* cfg, const float* theta, int64_t grid_n
  *   dudf_mc_lewiner_count -> out_counts (device, 2 x int64): vertices V, triangles T;
  *   dudf_mc_lewiner_emit  -> out_vertices (V,3) float (x, y, z in grid units), out_faces (T,3) int32, out_normals (V,3) float (the
  *                            unnormalised sums), out_values (V) float; same volume / level / tables / workspace as the count call.
- * Dimensions 2 .. 2048 each; V must stay below 2^31 (int32 faces, as the reference). */
+ * Dimensions 2 .. 2048 each; V must stay below 2^31 (int32 faces, as the reference).  workspace: dudf_mc_lewiner_workspace_bytes(nz, ny,
+ * nx), 256-byte aligned, else DUDF_E_WORKSPACE. */
 size_t dudf_mc_lewiner_workspace_bytes(int64_t nz, int64_t ny, int64_t nx);
 int dudf_mc_lewiner_count(const float* volume, int64_t nz, int64_t ny, int64_t nx, double level, const signed char* lut_data,
                           const int64_t* lut_offsets, const int32_t* lut_dims, int n_luts, int64_t* out_counts, void* workspace,

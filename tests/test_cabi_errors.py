@@ -6,10 +6,13 @@ dereferenced, the workspace a 256-byte-aligned host buffer.  The expected values
 before the host glue was reorganised (entry points moved beside their kernels, shared checks written once); they pin the
 precedence of the checks, which nothing else does."""
 import ctypes
+import os
 
+import numpy as np
 import pytest
 
 from diffudf_amd import _lib
+from diffudf_amd import marching_cubes as M
 
 OK, E_CFG, E_WS, E_MODE, E_UNSUP = 0, -1, -2, -3, -4
 N = 8                                                   # points / rays / rows of every call
@@ -19,6 +22,11 @@ BASE = (ctypes.addressof(_arena) + 255) // 256 * 256    # 256-byte aligned; 4 Mi
 P = ctypes.c_void_p(BASE)                               # stands in for any device pointer (never read)
 W4 = (ctypes.c_double * 4)(1.0, 1.0, 0.0, 1.0)
 W4H = (ctypes.c_double * 4)(1.0, 1.0, 1.0, 1.0)         # with a Hessian weight
+
+# the Lewiner tables' descriptors (read on the host by dudf_mc_lewiner_*; the table bytes themselves are a "device" pointer)
+_z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g10_meshudf.npz"))
+_, _LUT_OFFS, _LUT_DIMS = M._pack_luts({k[4:]: _z[k] for k in _z.files if k.startswith("lut_")})
+LUTS = (P, ctypes.c_void_p(_LUT_OFFS.ctypes.data), ctypes.c_void_p(_LUT_DIMS.ctypes.data), len(_LUT_OFFS))
 
 
 def good_cfg():
@@ -86,6 +94,29 @@ CALLS = {
                           lambda L, c, n: L.dudf_capudf_workspace_bytes(n), False, False),
     "dudf_capudf_emit": (lambda L, c, n, ws, nb: L.dudf_capudf_emit(P, P, n, 0.008, P, P, None, ws, nb, None),
                          lambda L, c, n: L.dudf_capudf_workspace_bytes(n), False, False),
+    # the stages that arrived later: recorded from the library as it stood before they shared one workspace carver
+    "dudf_mc_lewiner_count": (lambda L, c, n, ws, nb: L.dudf_mc_lewiner_count(P, n, n, n, 0.0, *LUTS, P, ws, nb, None),
+                              lambda L, c, n: L.dudf_mc_lewiner_workspace_bytes(n, n, n), False, False),
+    "dudf_mc_lewiner_emit": (lambda L, c, n, ws, nb: L.dudf_mc_lewiner_emit(P, n, n, n, 0.0, *LUTS, P, P, P, P, ws, nb, None),
+                             lambda L, c, n: L.dudf_mc_lewiner_workspace_bytes(n, n, n), False, False),
+    "dudf_mesh_clean_count": (lambda L, c, n, ws, nb: L.dudf_mesh_clean_count(P, n, P, n, 8, 0, P, ws, nb, None),
+                              lambda L, c, n: L.dudf_mesh_clean_workspace_bytes(n, n), False, False),
+    "dudf_mesh_clean_emit": (lambda L, c, n, ws, nb: L.dudf_mesh_clean_emit(P, n, P, n, 8, 0, P, P, ws, nb, None),
+                             lambda L, c, n: L.dudf_mesh_clean_workspace_bytes(n, n), False, True),
+    "dudf_mesh_border_count": (lambda L, c, n, ws, nb: L.dudf_mesh_border_count(n, P, n, P, ws, nb, None),
+                               lambda L, c, n: L.dudf_mesh_border_workspace_bytes(n, n), False, False),
+    "dudf_mesh_border_edges": (lambda L, c, n, ws, nb: L.dudf_mesh_border_edges(n, P, n, P, ws, nb, None),
+                               lambda L, c, n: L.dudf_mesh_border_workspace_bytes(n, n), False, True),
+    "dudf_mesh_smooth_borders": (lambda L, c, n, ws, nb: L.dudf_mesh_smooth_borders(P, n, P, n, 5, 0.3, ws, nb, None),
+                                 lambda L, c, n: L.dudf_mesh_border_workspace_bytes(n, n), False, True),
+    "dudf_knn_points[grid]": (lambda L, c, n, ws, nb: L.dudf_knn_points(P, n, P, 4, 1, 0, 0, P, P, ws, nb, None),
+                              lambda L, c, n: L.dudf_knn_workspace_bytes(n, 4, 1, 0), False, True),
+    "dudf_knn_points[brute]": (lambda L, c, n, ws, nb: L.dudf_knn_points(P, n, P, 4, 1, 0, 1, P, P, ws, nb, None),
+                               lambda L, c, n: L.dudf_knn_workspace_bytes(n, 4, 1, 1), False, True),
+    "dudf_knn_grid_build": (lambda L, c, n, ws, nb: L.dudf_knn_grid_build(P, n, ws, nb, None),
+                            lambda L, c, n: L.dudf_knn_workspace_bytes(0, n, 1, 0), False, False),
+    "dudf_orient_normals": (lambda L, c, n, ws, nb: L.dudf_orient_normals(P, P, P, n, 10, P, P, P, P, None, ws, nb, None),
+                            lambda L, c, n: L.dudf_orient_workspace_bytes(n, 10), False, True),
 }
 WITH_CFG = sorted(k for k, v in CALLS.items() if v[2])
 ZERO_OK = sorted(k for k, v in CALLS.items() if v[3])
@@ -105,6 +136,39 @@ def test_workspace_null_misaligned_short(name):
     assert call(lib, cfg, N, None, nb) == E_WS
     assert call(lib, cfg, N, ctypes.c_void_p(BASE + 8), nb) == E_WS
     assert call(lib, cfg, N, P, nb - 1) == E_WS
+
+
+# a check BEHIND the workspace check that a call can trip without a GPU (a null output): with exactly `need` bytes the call gets
+# that far, so `need` is enough for the entry point's own layout, not merely one more than what it refuses
+BEHIND = {
+    "dudf_capudf_count": lambda L, ws, nb: L.dudf_capudf_count(P, P, N, 0.008, None, ws, nb, None),
+    "dudf_capudf_emit": lambda L, ws, nb: L.dudf_capudf_emit(P, P, N, 0.008, None, P, None, ws, nb, None),
+    "dudf_mc_lewiner_count": lambda L, ws, nb: L.dudf_mc_lewiner_count(P, N, N, N, 0.0, *LUTS, None, ws, nb, None),
+    "dudf_mc_lewiner_emit": lambda L, ws, nb: L.dudf_mc_lewiner_emit(P, N, N, N, 0.0, *LUTS, P, P, P, None, ws, nb, None),
+    "dudf_mesh_clean_count": lambda L, ws, nb: L.dudf_mesh_clean_count(P, N, P, N, 8, 0, None, ws, nb, None),
+    "dudf_mesh_clean_emit": lambda L, ws, nb: L.dudf_mesh_clean_emit(P, N, P, N, 8, 0, P, None, ws, nb, None),
+    "dudf_mesh_border_count": lambda L, ws, nb: L.dudf_mesh_border_count(N, P, N, None, ws, nb, None),
+    "dudf_mesh_border_edges": lambda L, ws, nb: L.dudf_mesh_border_edges(N, P, N, None, ws, nb, None),
+    "dudf_mesh_smooth_borders": lambda L, ws, nb: L.dudf_mesh_smooth_borders(None, N, P, N, 5, 0.3, ws, nb, None),
+}
+
+
+@pytest.mark.parametrize("name", sorted(BEHIND))
+def test_exactly_the_published_bytes_pass_the_workspace_check(name):
+    lib = _lib.load()
+    nb = need_of(lib, name, None, N)
+    assert BEHIND[name](lib, P, nb) == E_CFG
+    assert BEHIND[name](lib, P, nb - 1) == E_WS                 # ... and the workspace is looked at first
+    assert BEHIND[name](lib, None, nb) == E_WS
+
+
+@pytest.mark.parametrize("name", ["dudf_capudf_count", "dudf_capudf_emit", "dudf_mc_lewiner_count", "dudf_mc_lewiner_emit"])
+def test_extraction_workspaces_are_256_byte_aligned_like_every_other(name):
+    """These two stages once took any 16-byte-aligned base; include/dudf_hip.h has always asked for 256."""
+    lib = _lib.load()
+    nb = need_of(lib, name, None, N)
+    assert CALLS[name][0](lib, None, N, ctypes.c_void_p(BASE + 16), nb) == E_WS
+    assert CALLS[name][0](lib, None, N, ctypes.c_void_p(BASE + 128), nb) == E_WS
 
 
 def test_mesh_distance_index_is_optional_but_checked():
