@@ -21,6 +21,15 @@ __device__ __forceinline__ unsigned cvt_pk(f32x2 v) {              // one v_cvt_
 __device__ __forceinline__ f32x2 unpack(unsigned p) {              // the two bf16 back as exact floats
     return f32x2{__builtin_bit_cast(float, p << 16), __builtin_bit_cast(float, p & 0xffff0000u)};
 }
+// The three dwords of a 24-bit fixed-point granule (dudf_sweep_common.h c24_pack / fx24_pack: values 0-2 in the low three
+// bytes of a dword each, value 3 spread over the three top bytes) -> the four bit patterns t = 0x40000000 | 24 bits, floats in [2, 4]
+__device__ __forceinline__ u32x4 fx24_patterns(unsigned d0, unsigned d1, unsigned d2) {
+    const unsigned m = 0x00ffffffu, two = 0x40000000u;                                     // (the pattern of 2.0f: an inline constant)
+    const unsigned t0 = (d0 & m) | two, t1 = (d1 & m) | two, t2 = (d2 & m) | two;          // v_and_or_b32
+    const unsigned y = __builtin_amdgcn_perm(d1, d0, 0x0c0c0703u);                        // [d0.b3, d1.b3, 0, 0]
+    const unsigned t3 = __builtin_amdgcn_perm(d2, y, 0x0c070100u) | two;                   // [.., .., d2.b3, 0] | 0x40 on top
+    return u32x4{t0, t1, t2, t3};
+}
 
 #define DUDF_TILE_PTS 64           // columns per workgroup pass of the f32 sweep kernel (4 waves x 16)
 #define DUDF_COL_PAD 128           // column ranges are padded to this: the bf16 sweep kernel's pass (8 waves x 16)

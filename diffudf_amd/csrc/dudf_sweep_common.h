@@ -155,11 +155,8 @@ __device__ __forceinline__ dudf_u3 c24_pack(const f32x4 c) {
     return d;
 }
 __device__ __forceinline__ f32x4 c24_unpack(const dudf_u3 d) {
-    const unsigned m = 0x00ffffffu, two = 0x40000000u;          // (the pattern of 2.0f: an inline constant)
-    const unsigned t0 = (d.x & m) | two, t1 = (d.y & m) | two, t2 = (d.z & m) | two;     // v_and_or_b32
-    const unsigned y = __builtin_amdgcn_perm(d.y, d.x, 0x0c0c0703u);                    // [d0.b3, d1.b3, 0, 0]
-    const unsigned t3 = __builtin_amdgcn_perm(d.z, y, 0x0c070100u) | two;               // [.., .., d2.b3, 0] | 0x40 on top
-    return f32x4{__uint_as_float(t0) - 3.0f, __uint_as_float(t1) - 3.0f, __uint_as_float(t2) - 3.0f, __uint_as_float(t3) - 3.0f};
+    const u32x4 t = fx24_patterns(d.x, d.y, d.z);
+    return f32x4{__uint_as_float(t[0]) - 3.0f, __uint_as_float(t[1]) - 3.0f, __uint_as_float(t[2]) - 3.0f, __uint_as_float(t[3]) - 3.0f};
 }
 // ---- S, Q, A, Z as 24-bit FIXED POINT relative to the column's bound (DudfLayout::p24 bit 0; same granules as C) --------------------
 // The fp16x3 sweeps fix, per layer and column, a power of two 2^E above everything the tail of that column can produce (set_scale:

@@ -43,15 +43,71 @@ struct WgradArgs {
     int j0, nj;                         // hidden matrices [j0, j0 + nj) of this launch (matrix j = layer l = j + 2); grid.x = nj
     int Hs;                             // real layer width; the kernels' template H is the output TILE (<= 256):
                                         // blockIdx.z walks the (Hs/H)^2 tiles of a wider layer
-    int remap_nsplit;                   // > 0: 1-D grid, the output tiles of one (layer, column split) share an XCD (see the body)
+    int remap_nsplit;                   // > 0: 1-D grid, the output tiles of one (layer, column split) share an XCD (see wgrad_pipeline)
     unsigned long long* clk;            // profiling: (shader clock, 100 MHz reference) ticks of workgroup (0,0,0), or nullptr
     const unsigned* amax;               // [4][L] bit patterns of max |q_l|, |A_l|, |zbar_l| over all columns (fp16x3 kernel)
-    int p24;                            // the operands are 24-bit tile-major arrays (DudfLayout::p24 bit 0: fixed point relative to a column scale)
-    const float *fxS, *fxQ, *fxA, *fxZ; // p24: [L][np] — per layer and column the power of two 2^E of that array's values (dudf_sweep_common.h fx24_pack)
+    const float *fxS, *fxQ, *fxA, *fxZ; // 24-bit tile-major operands (DudfLayout::p24 bit 0): [L][np] — per layer and column the power of two 2^E of that array's values (dudf_sweep_common.h fx24_pack)
 };
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+// What the three GEMM bodies share.  A workgroup (bx, by, bz) owns output tile bz of hidden matrix j = bx + j0 for the
+// stages [s0, s1) of `steps` (column split by of nsplit) and walks them as nit (stage, pair) iterations:
+// pair 0: X = q_l (layer index j+1), Y = A_{l-1} (index j);  pair 1: X = zbar_l, Y = s_{l-1}
+struct WgTile {
+    int j, s0, s1, o_off, i_off, have_g, nit;
+    const float *X0, *X1, *Y0, *Y1;
+    // (Idx: blockIdx's unsigned as it is, or the int of a remapped grid — the divisions below are those of that type)
+    template <class Idx>
+    __device__ __forceinline__ WgTile(const WgradArgs& a, int H, Idx bx, Idx by, Idx bz, int nsplit, int steps, int64_t lstride) {
+        j = bx + a.j0;                                  // hidden matrix index: layer l = j + 2
+        s0 = (int)((int64_t)steps * by / nsplit);
+        s1 = (int)((int64_t)steps * (by + 1) / nsplit);
+        const int tz = a.Hs / H;                        // output tiles per side
+        o_off = (bz / tz) * H; i_off = (bz % tz) * H;
+        const int64_t xrow = (int64_t)(o_off / 4) * a.np * 4, yrow = (int64_t)(i_off / 4) * a.np * 4;
+        X0 = a.Q + (int64_t)(j + 1) * lstride + xrow;
+        X1 = a.Z + (int64_t)(j + 1) * lstride + xrow;
+        Y0 = a.A + (int64_t)j * lstride + yrow;
+        Y1 = a.S + (int64_t)j * lstride + yrow;
+        have_g = a.have_g;
+        nit = (have_g ? 2 : 1) * (s1 - s0);
+    }
+    __device__ __forceinline__ int pair_of(int it) const { return have_g ? (it & 1) : 1; }
+    __device__ __forceinline__ int step_of(int it) const { return s0 + (have_g ? (it >> 1) : it); }
+    // this tile's corner of the weight gradient and its slice of the bias gradient
+    __device__ __forceinline__ float* dW(const WgradArgs& a) const { return a.dtheta + a.off_hid + (int64_t)j * a.hid_stride + (int64_t)o_off * a.Hs + i_off; }
+    __device__ __forceinline__ float* dB(const WgradArgs& a) const { return a.dtheta + a.off_hid + (int64_t)j * a.hid_stride + (int64_t)a.Hs * a.Hs + o_off; }
+};
+template <int M, int N>
+__device__ __forceinline__ void wg_zero(f32x16 (&acc)[M][N]) {
+#pragma unroll
+    for (int m = 0; m < M; ++m)
+#pragma unroll
+        for (int n = 0; n < N; ++n)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.f;
+}
+// wave (wo, wi) adds its accumulators (times `scale`: a literal 1 folds away) into the tile of dtheta
+// D layout 32x32: col = lane&31 (input index i), row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) (output index o)
+template <int H>
+__device__ __forceinline__ void wg_add_tile(const WgradArgs& a, float* dW, int wo, int wi,
+                                            const f32x16 (&acc)[WG<H>::MT][WG<H>::NTL], float scale = 1.f) {
+    using W = WG<H>;
+    const int l32 = threadIdx.x & 31, hh = (threadIdx.x & 63) >> 5;
+#pragma unroll
+    for (int m = 0; m < W::MT; ++m)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int o = (wo * W::MT + m) * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+#pragma unroll
+            for (int n = 0; n < W::NTL; ++n) {
+                const int i = (wi * W::NTL + n) * 32 + l32;
+                atomicAdd(dW + (int64_t)o * a.Hs + i, acc[m][n][e] * scale);
+            }
+        }
 }
 
 template <int H>
@@ -67,31 +123,11 @@ __device__ __forceinline__ void wgrad_hidden_body(const WgradArgs& a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wo = wave / W::WI, wi = wave % W::WI;
     const int l32 = lane & 31, hh = lane >> 5;
-    const int j = blockIdx.x + a.j0;                // hidden matrix index: layer l = j + 2
-    const int nsplit = gridDim.y;
-    const int s0 = (int)((int64_t)a.steps_total * blockIdx.y / nsplit);
-    const int s1 = (int)((int64_t)a.steps_total * (blockIdx.y + 1) / nsplit);
-    const int tz = a.Hs / H;                        // output tiles per side
-    const int o_off = (blockIdx.z / tz) * H, i_off = (blockIdx.z % tz) * H;
-    const int64_t xrow = (int64_t)(o_off / 4) * a.np * 4, yrow = (int64_t)(i_off / 4) * a.np * 4;
+    const WgTile t(a, H, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, a.steps_total, a.stash_layer);
 
     f32x16 acc[W::MT][W::NTL];
-    float bsum[W::MT];                              // bias gradient: running row sums of zbar (VALU, beside the MFMAs)
-#pragma unroll
-    for (int m = 0; m < W::MT; ++m) {
-#pragma unroll
-        for (int n = 0; n < W::NTL; ++n)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.f;
-        bsum[m] = 0.f;
-    }
-
-    // pair 0: X = q_l (layer index j+1), Y = A_{l-1} (index j);  pair 1: X = zbar_l, Y = s_{l-1}
-    const int64_t lstride = a.stash_layer;
-    const float* X0 = a.Q + (int64_t)(j + 1) * lstride + xrow;
-    const float* X1 = a.Z + (int64_t)(j + 1) * lstride + xrow;
-    const float* Y0 = a.A + (int64_t)j * lstride + yrow;
-    const float* Y1 = a.S + (int64_t)j * lstride + yrow;
+    float bsum[W::MT] = {};                         // bias gradient: running row sums of zbar (VALU, beside the MFMAs)
+    wg_zero(acc);
 
     f32x4 rx[NLD], ry[NLD];
     auto issue = [&](int pair, int step) {
@@ -101,8 +137,8 @@ __device__ __forceinline__ void wgrad_hidden_body(const WgradArgs& a) {
             if (F4 % NTHR == 0 || f < F4) {
                 const int fq = f / KT, pt = f % KT;
                 const int64_t off = ((int64_t)fq * a.np + (int64_t)step * KT + pt) * 4;
-                rx[u] = *reinterpret_cast<const f32x4*>((pair ? X1 : X0) + off);
-                ry[u] = *reinterpret_cast<const f32x4*>((pair ? Y1 : Y0) + off);
+                rx[u] = *reinterpret_cast<const f32x4*>((pair ? t.X1 : t.X0) + off);
+                ry[u] = *reinterpret_cast<const f32x4*>((pair ? t.Y1 : t.Y0) + off);
             }
         }
     };
@@ -118,22 +154,18 @@ __device__ __forceinline__ void wgrad_hidden_body(const WgradArgs& a) {
         }
     };
 
-    const int npair = a.have_g ? 2 : 1;
-    const int nit = npair * (s1 - s0);              // (step, pair) iterations
-    auto pair_of = [&](int it) { return a.have_g ? (it & 1) : 1; };
-    auto step_of = [&](int it) { return s0 + (a.have_g ? (it >> 1) : it); };
-    if (nit > 0) {
-        issue(pair_of(0), step_of(0));
+    if (t.nit > 0) {
+        issue(t.pair_of(0), t.step_of(0));
         commit(lds);
     }
     __syncthreads();
-    for (int it = 0; it < nit; ++it) {
+    for (int it = 0; it < t.nit; ++it) {
         const float* buf = lds + (it & 1) * 2 * TILE;
-        if (it + 1 < nit) issue(pair_of(it + 1), step_of(it + 1));      // next stage: global -> registers
+        if (it + 1 < t.nit) issue(t.pair_of(it + 1), t.step_of(it + 1));      // next stage: global -> registers
         // bias mask of this stage's columns: k index 2*kk+hh is a value column always (plain range) or when
         // (2*kk+hh) % 4 == 0 (Hessian range: stages never straddle the two ranges)
-        const float bflag = (pair_of(it) == 1 && wi == 0 && i_off == 0) ? 1.f : 0.f;
-        const bool hstage = (int64_t)step_of(it) * KT < a.ncol_h;
+        const float bflag = (t.pair_of(it) == 1 && wi == 0 && t.i_off == 0) ? 1.f : 0.f;
+        const bool hstage = (int64_t)t.step_of(it) * KT < a.ncol_h;
         const float f_even = hstage ? (hh == 0 ? bflag : 0.f) : bflag;
         const float f_odd = hstage ? 0.f : bflag;
         const float* xa[W::MT];
@@ -164,28 +196,19 @@ __device__ __forceinline__ void wgrad_hidden_body(const WgradArgs& a) {
             }
         }
         // the other buffer was last read in iteration it-1 and every wave is past that iteration's barrier
-        if (it + 1 < nit) commit(lds + ((it + 1) & 1) * 2 * TILE);
+        if (it + 1 < t.nit) commit(lds + ((it + 1) & 1) * 2 * TILE);
         __syncthreads();
     }
 
-    // D layout 32x32: col = lane&31 (input index i), row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) (output index o)
-    float* dW = a.dtheta + a.off_hid + (int64_t)j * a.hid_stride + (int64_t)o_off * a.Hs + i_off;
-    float* dB = a.dtheta + a.off_hid + (int64_t)j * a.hid_stride + (int64_t)a.Hs * a.Hs + o_off;
-    if (nit > 0) {
+    float* dW = t.dW(a);
+    float* dB = t.dB(a);
+    if (t.nit > 0) {
+        wg_add_tile<H>(a, dW, wo, wi, acc);
 #pragma unroll
         for (int m = 0; m < W::MT; ++m) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int o = (wo * W::MT + m) * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-#pragma unroll
-                for (int n = 0; n < W::NTL; ++n) {
-                    const int i = (wi * W::NTL + n) * 32 + l32;
-                    atomicAdd(dW + (int64_t)o * a.Hs + i, acc[m][n][e]);
-                }
-            }
             // lane (l32, hh) summed zbar[feature l32] over the points of parity hh
             const float tot = bsum[m] + __shfl_xor(bsum[m], 32);
-            if (wi == 0 && hh == 0 && i_off == 0) atomicAdd(dB + (wo * W::MT + m) * 32 + l32, tot);
+            if (wi == 0 && hh == 0 && t.i_off == 0) atomicAdd(dB + (wo * W::MT + m) * 32 + l32, tot);
         }
     }
 }
@@ -252,43 +275,19 @@ __device__ __forceinline__ void wgrad_hidden_bf16_body(const WgradArgs& a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wo = wave / W::WI, wi = wave % W::WI;
     const int l32 = lane & 31, hh = lane >> 5;
-    const int j = blockIdx.x + a.j0;
-    const int nsplit = gridDim.y;
-    const int steps16 = a.steps_total * (KT / KB);
-    const int s0 = (int)((int64_t)steps16 * blockIdx.y / nsplit);
-    const int s1 = (int)((int64_t)steps16 * (blockIdx.y + 1) / nsplit);
-    const int tz = a.Hs / H;
-    const int o_off = (blockIdx.z / tz) * H, i_off = (blockIdx.z % tz) * H;
-    const int64_t xrow = (int64_t)(o_off / 4) * a.np * 4, yrow = (int64_t)(i_off / 4) * a.np * 4;
+    const WgTile t(a, H, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y, a.steps_total * (KT / KB), a.stash_layer);
 
     f32x16 acc[W::MT][W::NTL];
-    float bsum[W::MT];
-#pragma unroll
-    for (int m = 0; m < W::MT; ++m) {
-#pragma unroll
-        for (int n = 0; n < W::NTL; ++n)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.f;
-        bsum[m] = 0.f;
-    }
-    const int64_t lstride = a.stash_layer;
-    const float* X0 = a.Q + (int64_t)(j + 1) * lstride + xrow;
-    const float* X1 = a.Z + (int64_t)(j + 1) * lstride + xrow;
-    const float* Y0 = a.A + (int64_t)j * lstride + yrow;
-    const float* Y1 = a.S + (int64_t)j * lstride + yrow;
-
-    const int npair = a.have_g ? 2 : 1;
-    const int nit = npair * (s1 - s0);
-    auto pair_of = [&](int it) { return a.have_g ? (it & 1) : 1; };
-    auto step_of = [&](int it) { return s0 + (a.have_g ? (it >> 1) : it); };
+    float bsum[W::MT] = {};
+    wg_zero(acc);
 
     // lane part of the DMA source: granule (fq_in_piece = lane/16, slot = lane%16) holds column slot ^ (fq & 7)
     auto issue = [&](int it) {
-        const int pair = pair_of(it);
-        const int64_t col0 = (int64_t)step_of(it) * KB;
+        const int pair = t.pair_of(it);
+        const int64_t col0 = (int64_t)t.step_of(it) * KB;
         float* ring = lds + (it % NRING) * STAGE;
-        const float* xs = pair ? X1 : X0;
-        const float* ys = pair ? Y1 : Y0;
+        const float* xs = pair ? t.X1 : t.X0;
+        const float* ys = pair ? t.Y1 : t.Y0;
 #pragma unroll
         for (int oper = 0; oper < 2; ++oper) {
 #pragma unroll
@@ -307,18 +306,18 @@ __device__ __forceinline__ void wgrad_hidden_bf16_body(const WgradArgs& a) {
         }
     };
     // prologue: three stages in flight
-    for (int it = 0; it < NRING - 1 && it < nit; ++it) issue(it);
-    if (nit > 0) {
-        if (nit >= 3) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * PER_WAVE) : "memory");
+    for (int it = 0; it < NRING - 1 && it < t.nit; ++it) issue(it);
+    if (t.nit > 0) {
+        if (t.nit >= 3) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * PER_WAVE) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
-    for (int it = 0; it < nit; ++it) {
+    for (int it = 0; it < t.nit; ++it) {
         // the ring slot of stage it+3 was read in iteration it-1; every wave is past that iteration's barrier
-        if (it + NRING - 1 < nit) issue(it + NRING - 1);
+        if (it + NRING - 1 < t.nit) issue(it + NRING - 1);
         const float* buf = lds + (it % NRING) * STAGE;
-        const float bflag = (pair_of(it) == 1 && wi == 0 && i_off == 0) ? 1.f : 0.f;
-        const bool hstage = (int64_t)step_of(it) * KB < a.ncol_h;
+        const float bflag = (t.pair_of(it) == 1 && wi == 0 && t.i_off == 0) ? 1.f : 0.f;
+        const bool hstage = (int64_t)t.step_of(it) * KB < a.ncol_h;
         const float f_other = hstage ? 0.f : 1.f;
         const int c0 = 8 * hh;                                    // MFMA k = 8*(lane>>5) + jj -> column c0 + jj
         Split3 af[W::MT];
@@ -348,49 +347,42 @@ __device__ __forceinline__ void wgrad_hidden_bf16_body(const WgradArgs& a) {
             }
         }
         // stage it+1 has landed: all but the DMA pieces of the (up to) two younger stages are retired
-        if (it + 1 < nit) {
-            if (it + 3 < nit) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * PER_WAVE) : "memory");
-            else if (it + 2 < nit) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER_WAVE) : "memory");
+        if (it + 1 < t.nit) {
+            if (it + 3 < t.nit) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * PER_WAVE) : "memory");
+            else if (it + 2 < t.nit) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER_WAVE) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         __syncthreads();
     }
 
-    float* dW = a.dtheta + a.off_hid + (int64_t)j * a.hid_stride + (int64_t)o_off * a.Hs + i_off;
-    float* dB = a.dtheta + a.off_hid + (int64_t)j * a.hid_stride + (int64_t)a.Hs * a.Hs + o_off;
-    if (nit > 0) {
+    float* dW = t.dW(a);
+    float* dB = t.dB(a);
+    if (t.nit > 0) {
+        wg_add_tile<H>(a, dW, wo, wi, acc);
 #pragma unroll
         for (int m = 0; m < W::MT; ++m) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int o = (wo * W::MT + m) * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-#pragma unroll
-                for (int n = 0; n < W::NTL; ++n) {
-                    const int i = (wi * W::NTL + n) * 32 + l32;
-                    atomicAdd(dW + (int64_t)o * a.Hs + i, acc[m][n][e]);
-                }
-            }
             const float tot = bsum[m] + __shfl_xor(bsum[m], 32);
-            if (wi == 0 && hh == 0 && i_off == 0) atomicAdd(dB + (wo * W::MT + m) * 32 + l32, tot);
+            if (wi == 0 && hh == 0 && t.i_off == 0) atomicAdd(dB + (wo * W::MT + m) * 32 + l32, tot);
         }
     }
 }
 template <int H>
 __global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_bf16_kernel(WgradArgs a) { wgrad_hidden_bf16_body<H>(a); }   // no packed fp32: see dudf_internal.h
 
-// ---- bf16x6 with a COOPERATIVE split (256 x 256 tiles) ----------------------------------------------------------------
+// ---- bf16x6 / fp16x3 with a COOPERATIVE split (256 x 256 tiles) -------------------------------------------------------
 // The kernel above is bound by vector-ALU issue, not by the matrix cores: every wave splits the fragments it consumes, so
 // an X element is split by 2 waves and a Y element by 4 (7.5 VALU instructions per MFMA, PMC).  Here every element is
-// split ONCE: a stage (16 columns x 256 features x 2 operands = 2048 16-byte granules) is dealt out 4 granules per lane
-// — four consecutive columns of one feature quad, 64 contiguous bytes of the stash — loaded straight into registers
-// (no raw copy in LDS), split, and written as bf16 pieces into an LDS image laid out in MFMA-FRAGMENT
-// order ([operand][piece][32-feature block][column half][feature][8 columns]: a fragment is two lane-linear 512-byte
-// halves, conflict-free for ds_read_b128; the halves are 528 bytes apart so that the 8-byte writes do not collide).
-// Producer lanes are dealt out so that each ds_write_b64 wave-instruction is bank-conflict free (a 16-lane service group
-// spans offsets 16 a + 2 b + 4 c + 8 d dwords: fq bit 0 | column-group bit 0 | column half | fq bit 3); the plain (tid >> 2)
-// order put feature quads 0/2 and 1/3 of a group on the same banks (PMC r01: 29 % of LDS cycles).
+// split ONCE: a stage (16 columns x 256 features x 2 operands = 2048 16-byte granules) is dealt out 4 granules per lane,
+// loaded straight into registers (no raw copy in LDS), split, and written as 16-bit pieces into an LDS image that the
+// MFMA fragments are read back from.  Two things make up a build:
+//   * the PIPELINE (wgrad_pipeline), the same for all builds: progress flags in LDS instead of barriers, three register
+//     sets in flight across the back edge behind hand-counted vmcnt, the hot loop of three stages, the drains, the MFMA
+//     groups and the hand-over flag;
+//   * the STAGER, the format a stage travels in — which granules a lane loads, how they are split, where the pieces go in
+//     the image and how a fragment comes back out: RowStager (row granules, fragment-ordered image, ds_read_b128) or
+//     TileStager (tile granules, [column][feature] image, ds_read_b64_tr_b16).
 // There is no workgroup barrier per stage: NB = 3 or 4 images live in LDS beside per-wave progress counters (the flags, see
-// `poll` below).  A wave starts stage `it` when all eight waves have written image `it`, multiplies FIRST, and behind its
+// wg_poll below).  A wave starts stage `it` when all eight waves have written image `it`, multiplies FIRST, and behind its
 // MFMAs splits image it + 2 — two images ahead — whose register set is then refilled with the stage three further on.
 // (Predecessors — two images and a barrier per stage, split slices between the MFMA groups, static wave priorities: DESIGN.md
 // Appendix A has their numbers, `git log -- diffudf_amd/csrc/dudf_wgrad.hip` their code.)
@@ -399,20 +391,6 @@ __global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_h
 // dudf_make_layout), the hinted loads fetched 4.17 GB per launch against 2.87 GB of operands and 3.04 GB without the hint
 // (profiles/r03_wgrad_nt.txt); on the aligned layout both forms fetch 2.87 GB and take the same time.
 constexpr int kHandOver = 2;       // a wave hands the matrix pipe over this many MFMA groups before the end of a stage
-#ifndef DUDF_WGRAD_DBG
-#define DUDF_WGRAD_DBG 0           // timing experiments only (wrong results): 1 no loads, 2 no barrier, 4 no MFMA, 8 no split,
-#endif                             // 16 no LDS fragment reads, 32 stage stamps, 64 no output atomics
-#if DUDF_WGRAD_DBG & 32
-// phase stamps of the LAST steady-state stage of one workgroup (timing experiments): [wave][stamp], shader-clock cycles
-__device__ unsigned long long g_wstamp[8][12];
-extern "C" int dudf_dbg_wstamps(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wstamp), sizeof(g_wstamp)); }
-#define DUDF_WSTAMP(i) do { if constexpr (HOT) { __builtin_amdgcn_sched_barrier(0); if (it == DUDF_WSTAMP_IT) wst[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } } while (0)
-#ifndef DUDF_WSTAMP_IT
-#define DUDF_WSTAMP_IT 60
-#endif
-#else
-#define DUDF_WSTAMP(i) do { } while (0)
-#endif
 // SP = 1: the fp16 hi/lo split ("fp16x3": products hi*hi + hi*lo + lo*hi, see dudf_sweep_bf16.hip) — half the MFMAs, two
 // pieces instead of three to convert, write and read back.  fp16's range is bought with per-layer powers of two: the
 // sweeps leave max |q_l|, |A_l|, |zbar_l| over all columns in `amax` (|s_l| <= 1); each operand is scaled so that its
@@ -429,39 +407,399 @@ __device__ __forceinline__ int dudf_exp_above(unsigned bits) {     // e with |v|
 }
 __device__ __forceinline__ float dudf_pow2(int k) { return __uint_as_float((unsigned)(127 + k) << 23); }
 
-// P24 = 2: the fp32 row layout read the way the sweeps read it — a wave-instruction takes 256-byte pieces of FOUR feature-quad rows
-// (lane = (q, li): row 16 pw + 4 t + q, column li) instead of 64-byte pieces of sixteen — into the same [column][feature] image
-// and transposed fragment reads as P24 = 1, without the 24-bit decode ("row-major staging").
-// P24 = 1: the operands arrive as 24-bit tile-major stash arrays (dudf_internal.h "p24": [layer][feature tile][16-column group]
-// [64 lanes][3 dwords]) of FIXED-POINT values relative to a per-layer, per-column power of two 2^E (round 5; round 4 read 24-bit
-// floats here): value = (t - 3) 2^E with t = 0x40000000 | the 24 bits.  The lane's column is fixed for a stage (lane = (q, li)), so
-// ONE extra dword per lane and stage brings 2^E, and one FMA per value — t * g - 3 g with g = 2^E x the operand's layer scale —
-// yields the number the fp16 split starts from.  A 16-column stage of an operand is then 16 contiguous 768-byte blocks, one per feature tile: a wave
-// loads a block with ONE dwordx3 instruction (six full lines), lane (q, li) holding features 16 T + 4 q .. + 3 of column li.
+// The fp16 hi/lo pieces of four values as packed dwords.  hi = fp16(v scl) comes from the caller (the stagers round it with
+// different instructions); lo = fp16(v scl - hi): the residual as ONE v_fma_mix_f32 per value (exact; reads the fp16 half in
+// place and issues beside the SIMD partner's MFMAs like v_fma_f32 — tools/micro/coissue.hip).  `scl` is wave-uniform (an SGPR
+// operand); the overload without it multiplies by the literal 1.0.
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+struct F16HiLo { u32x2 hi, lo; };
+__device__ __forceinline__ F16HiLo f16_pack(f16x2 h0, f16x2 h1, f32x2 r0, f32x2 r1) {
+    const f16x2 l0 = __builtin_convertvector(r0, f16x2), l1 = __builtin_convertvector(r1, f16x2);
+    return F16HiLo{u32x2{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)},
+                   u32x2{__builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1)}};
+}
+__device__ __forceinline__ F16HiLo f16_hi_lo(f32x2 v0, f32x2 v1, f16x2 h0, f16x2 h1, float scl) {
+    f32x2 r0, r1;
+    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r0.x) : "v"(v0.x), "s"(scl), "v"(h0));
+    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r0.y) : "v"(v0.y), "s"(scl), "v"(h0));
+    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r1.x) : "v"(v1.x), "s"(scl), "v"(h1));
+    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1.y) : "v"(v1.y), "s"(scl), "v"(h1));
+    return f16_pack(h0, h1, r0, r1);
+}
+__device__ __forceinline__ F16HiLo f16_hi_lo(f32x2 v0, f32x2 v1, f16x2 h0, f16x2 h1) {
+    f32x2 r0, r1;
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r0.x) : "v"(v0.x), "v"(h0));
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r0.y) : "v"(v0.y), "v"(h0));
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r1.x) : "v"(v1.x), "v"(h1));
+    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1.y) : "v"(v1.y), "v"(h1));
+    return f16_pack(h0, h1, r0, r1);
+}
+template <int pieceb>
+__device__ __forceinline__ void put_hi_lo(char* dst, const F16HiLo& p) {       // the hi piece's image, then the lo piece's
+    *reinterpret_cast<u32x2*>(dst) = p.hi;
+    *reinterpret_cast<u32x2*>(dst + pieceb) = p.lo;
+}
+// a wave-uniform address as a scalar register pair: the base of the asm staging loads (scalar base + the lane's fixed 32-bit
+// byte offset: no per-stage 64-bit address arithmetic in vector registers)
+__device__ __forceinline__ uint64_t wg_uniform64(const void* p) {
+    const uint64_t g0 = (uint64_t)(size_t)p;
+    const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)g0), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(g0 >> 32));
+    return ((uint64_t)hi32 << 32) | lo32;
+}
+
+// What the two stagers share: the wave's producer operand (waves 0..3 stage X, 4..7 stage Y), its fp16x3 layer scales and
+// which of the lane's values count towards the bias gradient.  A stager's interface to the pipeline:
+//   NPC, PIECEB / OPERB / BUFB   pieces per operand and the bytes of a piece, an operand, an image buffer
+//   RawSet, kSetLoads, drain     the registers a stage travels in, its loads, and the wait for all three sets
+//   layer_stride(a)              floats per layer of the operand arrays
+//   load / load_plain            stage `it` -> a register set: inline asm for the hand-counted loop, ordinary loads outside it
+//   wait<N>(r)                   set r has landed; the N loads issued after it stay in flight
+//   split_store(it, r, buf)      registers -> the pieces of image buffer `buf` (+ the bias sums)
+//   fragA / fragB(buf, block, piece)   this lane's part of an MFMA fragment
+//   flush_bias(dB)               the bias sums -> dtheta
+struct StagerBase {
+    using W = WG<256>;
+    static constexpr int NW_ = W::WO * W::WI;
+    const WgradArgs& a;
+    const WgTile& t;
+    char* ldsb;
+    int p_oper, wo, wi;
+    const float *P0, *P1;                   // this wave's operand for the (q, A) / (zbar, s) pair
+    float sc0 = 1.f, sc1 = 1.f;             // fp16x3: its power of two for each pair, set by the pipeline
+    float bm_plain, bm_quad;
+    __device__ __forceinline__ StagerBase(const WgradArgs& a_, const WgTile& t_, char* ldsb_, int tid, int wave)
+        : a(a_), t(t_), ldsb(ldsb_), p_oper(wave / (NW_ / 2)), wo(wave / W::WI), wi(wave % W::WI),
+          P0(p_oper ? t_.Y0 : t_.X0), P1(p_oper ? t_.Y1 : t_.X1) {
+        bm_plain = (p_oper == 0 && t.i_off == 0) ? 1.f : 0.f;           // this lane's granules count towards the bias gradient ...
+        bm_quad = ((tid & 3) == 0) ? bm_plain : 0.f;            // ... on a Hessian-quad stage (the value channel: column % 4 == 0)
+    }
+    // once per stage: the zbar pair only, and on a Hessian-quad stage only the value channel
+    // (branch-free: scalar selects times per-lane constants — a branch here would cut the hand-counted loop body into
+    //  several basic blocks)
+    __device__ __forceinline__ float bias_mask(int it) const {
+        const float hs = ((int64_t)t.step_of(it) * KB < a.ncol_h) ? 1.f : 0.f;
+        const float pf = t.pair_of(it) == 1 ? 1.f : 0.f;
+        return pf * (bm_plain + hs * (bm_quad - bm_plain));
+    }
+    __device__ __forceinline__ float layer_scale(int it) const {
+        return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(t.pair_of(it) ? sc1 : sc0)));
+    }
+    __device__ __forceinline__ const float* operand(int it) const { return t.pair_of(it) ? P1 : P0; }
+};
+
+// Row granules: a lane takes four columns of one feature quad of the fp32 stash rows (its four lanes read 64 contiguous bytes
+// per instruction) and writes its pieces into an image laid out in MFMA-FRAGMENT order ([operand][piece][32-feature block][column half][feature]
+// [8 columns]: a fragment is two lane-linear 512-byte halves, conflict-free for ds_read_b128; the halves are 528 bytes apart so
+// that the 8-byte writes do not collide).  Producer lanes are dealt out so that each ds_write_b64 wave-instruction is bank-conflict
+// free (a 16-lane service group spans offsets 16 a + 2 b + 4 c + 8 d dwords: fq bit 0 | column-group bit 0 | column half | fq
+// bit 3); the plain (tid >> 2) order put feature quads 0/2 and 1/3 of a group on the same banks (PMC r01: 29 % of LDS cycles).
+// SP = 0: three bf16 pieces; SP = 1: fp16 hi / lo.
+template <int SP>
+struct RowStager : StagerBase {
+    static constexpr int NPC = SP ? 2 : 3;
+    static constexpr int HALFB = 32 * 16 + 16;              // 32 features x 8 columns of a block, +16: the second column half
+    static constexpr int BLKB = 2 * HALFB;                  //   must not sit 512 B = 0 banks after the first (ds_write_b64)
+    static constexpr int PIECEB = (256 / 32) * BLKB;        // 8.25 KiB
+    static constexpr int OPERB = NPC * PIECEB;              // 24 KiB (SP: 16.5)
+    static constexpr int BUFB = 2 * OPERB;                  // 48 KiB (33)
+    static constexpr int kSetLoads = 4;
+    struct RawSet { f32x4 g0, g1, g2, g3; };                // granule j: 4 features of column 4 * cg + j
+    __device__ static __forceinline__ int64_t layer_stride(const WgradArgs& a) { return a.stash_layer; }
+    __device__ static __forceinline__ void drain(RawSet& r0, RawSet& r1, RawSet& r2) {      // everything in flight has landed
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(r0.g0), "+v"(r0.g1), "+v"(r0.g2), "+v"(r0.g3), "+v"(r1.g0), "+v"(r1.g1),
+                     "+v"(r1.g2), "+v"(r1.g3), "+v"(r2.g0), "+v"(r2.g1), "+v"(r2.g2), "+v"(r2.g3));
+    }
+
+    int p_cg, p_fq, p_loff, c_lane;         // producer role of this lane: group of four columns, feature quad, image offset; its fragment offset
+    int64_t p_goff;
+    unsigned p_voff;
+    f32x4 bacc = {0.f, 0.f, 0.f, 0.f};                      // bias gradient partial sums (X operand, zbar pair)
+    __device__ __forceinline__ RowStager(const WgradArgs& a_, const WgTile& t_, char* ldsb_, int tid, int wave)
+        : StagerBase(a_, t_, ldsb_, tid, wave) {
+        const int lane = tid & 63;
+        p_cg = tid & 3;
+        p_fq = ((tid >> 2) & 1) | (((tid >> 4) & 3) << 1) | (((tid >> 3) & 1) << 3) | (((tid >> 6) & 3) << 4);   // conflict-free writes: see above
+        // granule j of this lane = stage column p_cg + 4 j: one load instruction then reads 64 contiguous bytes per feature
+        // quad (4 lanes x 16 B) and touches each 128-byte line twice instead of four times (PMC r01: 2x the ideal L2
+        // requests; the loads alone held the kernel at 0.8 ms).  The image slot 4 p_cg + j therefore holds column p_cg + 4 j:
+        // a permutation of the contraction index, the same for both operands, hence free.
+        p_goff = ((int64_t)p_fq * a.np + p_cg) * 4;             // floats, + col0 * 4 per stage
+        p_loff = p_oper * OPERB + (p_fq >> 3) * BLKB + (p_cg >> 1) * HALFB + ((p_fq & 7) * 4) * 16 + (p_cg & 1) * 8;   // + f * 16 + piece * PIECEB
+        p_voff = (unsigned)(p_goff * 4);                        // (the launcher keeps FQ * np * 16 below 2^32)
+        c_lane = (lane >> 5) * HALFB + (lane & 31) * 16;        // consumer role: fragment (32-feature block b, piece p) of an operand = 1 KiB, lane-linear
+    }
+    // Inline asm + hand-counted vmcnt (as in the sweeps): with compiler-visible loads hipcc drains ALL stages in flight
+    // (vmcnt(0)) at the loop head.  A set's loads are the only vector-memory operations of the loop.
+    __device__ __forceinline__ void load(int it, RawSet& r) const {
+        const uint64_t sbase = wg_uniform64(operand(it) + (int64_t)t.step_of(it) * KB * 4);
+        asm volatile("global_load_dwordx4 %0, %4, %5\n\tglobal_load_dwordx4 %1, %4, %5 offset:64\n\t"
+                     "global_load_dwordx4 %2, %4, %5 offset:128\n\tglobal_load_dwordx4 %3, %4, %5 offset:192"
+                     : "=&v"(r.g0), "=&v"(r.g1), "=&v"(r.g2), "=&v"(r.g3) : "v"(p_voff), "s"(sbase) : "memory");
+    }
+    // outside the steady-state loop (prologue, last stages: conditional loads) the loads are ordinary ones: a conditional
+    // asm load makes hipcc merge "loaded" and "not loaded" values with register copies — of registers still in flight
+    __device__ __forceinline__ void load_plain(int it, RawSet& r) const {
+        const float* src = operand(it) + p_goff + (int64_t)t.step_of(it) * KB * 4;
+        r.g0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src));
+        r.g1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src) + 4);
+        r.g2 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src) + 8);
+        r.g3 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src) + 12);
+    }
+    template <int N>
+    __device__ static __forceinline__ void wait(RawSet& r) {
+        asm volatile("s_waitcnt vmcnt(%4)" : "+v"(r.g0), "+v"(r.g1), "+v"(r.g2), "+v"(r.g3) : "n"(N));
+    }
+    __device__ __forceinline__ void split_slice(int it, const RawSet& r, int f, int bsel) {    // feature f of the lane's quad -> piece image buffer bsel
+        char* dst = ldsb + bsel * BUFB + p_loff + 16 * f;
+        // Hessian quads: only columns % 4 == 0 (the value channel) carry the bias — all four granules of the lanes
+        // with p_cg == 0, none of the others
+        if (f == 0) bacc += bias_mask(it) * (r.g0 + r.g1 + r.g2 + r.g3);
+        const f32x2 v0 = {r.g0[f], r.g1[f]}, v1 = {r.g2[f], r.g3[f]};     // four columns of one feature -> NPC x 8 bytes
+        if constexpr (SP != 0) {
+            const float scl = layer_scale(it);                            // t = v 2^k -> hi = fp16(t), lo = fp16(t - hi)
+            const f16x2 h0 = __builtin_convertvector(v0 * scl, f16x2), h1 = __builtin_convertvector(v1 * scl, f16x2);
+            put_hi_lo<PIECEB>(dst, f16_hi_lo(v0, v1, h0, h1, scl));
+        } else {
+            const unsigned h0 = cvt_pk(v0), h1 = cvt_pk(v1);
+            const f32x2 r0 = v0 - unpack(h0), r1 = v1 - unpack(h1);
+            const unsigned m0 = cvt_pk(r0), m1 = cvt_pk(r1);
+            const f32x2 q0 = r0 - unpack(m0), q1 = r1 - unpack(m1);
+            const unsigned l0 = cvt_pk(q0), l1 = cvt_pk(q1);
+            *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
+            *reinterpret_cast<u32x2*>(dst + PIECEB) = u32x2{m0, m1};
+            *reinterpret_cast<u32x2*>(dst + 2 * PIECEB) = u32x2{l0, l1};
+        }
+    }
+    __device__ __forceinline__ void split_store(int it, const RawSet& r, int bsel) {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) split_slice(it, r, f, bsel);
+    }
+    __device__ __forceinline__ u32x4 fragA(const char* buf, int m, int pc) const {
+        return *reinterpret_cast<const u32x4*>(buf + pc * PIECEB + (wo * W::MT + m) * BLKB + c_lane);
+    }
+    __device__ __forceinline__ u32x4 fragB(const char* buf, int n, int pc) const {
+        return *reinterpret_cast<const u32x4*>(buf + OPERB + pc * PIECEB + (wi * W::NTL + n) * BLKB + c_lane);
+    }
+    __device__ __forceinline__ void flush_bias(float* dB) const {     // sum the four column groups of a quad first
+        if (p_oper != 0 || t.i_off != 0) return;
+        auto red = [&](float v, int f) {
+            v += __shfl_xor(v, 1);
+            v += __shfl_xor(v, 2);
+            if (p_cg == 0) atomicAdd(dB + 4 * p_fq + f, v);
+        };
+        red(bacc.x, 0); red(bacc.y, 1); red(bacc.z, 2); red(bacc.w, 3);
+    }
+};
+
+// Tile granules: the operands are read the way the sweeps write them — wave pw (0..3 of its operand) stages feature tiles
+// 4 pw .. 4 pw + 3, lane = (q, li) holding features 16 T + 4 q .. + 3 of column li.
+// FX = true: the operands arrive as 24-bit tile-major stash arrays (dudf_internal.h "p24": [layer][feature tile][16-column group]
+// [64 lanes][3 dwords]) of FIXED-POINT values relative to a per-layer, per-column power of two 2^E: value = (t - 3) 2^E with
+// t = 0x40000000 | the 24 bits.  The lane's column is fixed for a stage, so ONE extra dword per lane and stage (`sc`) brings 2^E,
+// and one FMA per value — t * g - 3 g with g = 2^E x the operand's layer scale — yields the number the fp16 split starts from.
+// A 16-column stage of an operand is 16 contiguous 768-byte blocks, one per feature tile: a wave loads a block with ONE dwordx3
+// instruction (six full lines).
+// FX = false: the fp32 row layout — a wave-instruction takes 256-byte pieces of FOUR feature-quad rows (row 16 pw + 4 t + q,
+// column li) instead of 64-byte pieces of sixteen — without the 24-bit decode ("row-major staging").
 // A lane therefore has many features of ONE column — the transpose of what the MFMA wants (one feature, 8 columns) — so the
 // LDS image is [column k][feature] (rows of 576 bytes: 256 fp16 + 64, four consecutive rows start 16 banks apart; the
 // 8-byte unit index of a row XORed in its low three bits with (k >> 1) & 7: a 16-lane ds_write_b64 service group covers
 // the 32 write banks once) and the fragments come out of it through ds_read_b64_tr_b16, gfx950's transposing LDS read: a
 // 16-lane group reads 4 rows (columns k) x 16 features and every lane receives its feature's four k — two of them per
 // fragment (tools/micro/tr_image.hip checks image, swizzle and fragment maps against a host GEMM).
-// NB: image buffers in LDS, 3 or 4 (see the flags below)
-template <int H, int NB, int SP = 0, int P24 = 0>
-__device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
+template <bool FX>
+struct TileStager : StagerBase {
+    static constexpr int NPC = 2;                           // an fp16x3 stager: hi / lo
+    static constexpr int ROWB = 576;                        // one column's 256 fp16 + 64 bytes
+    static constexpr int PIECEB = 16 * ROWB;                // 9 KiB
+    static constexpr int OPERB = NPC * PIECEB;              // 18 KiB
+    static constexpr int BUFB = 2 * OPERB;                  // 36 KiB
+    static constexpr int kSetLoads = FX ? 5 : 4;            // FX: + the column scale
+    typedef unsigned u3_t __attribute__((ext_vector_type(3)));
+    typedef typename std::conditional<FX, u3_t, f32x4>::type raw_t;      // FX: a granule is 3 dwords (four 24-bit values)
+    struct RawSet { raw_t g0, g1, g2, g3; float sc; };      // granule j: tile 4 pw + j, column li; sc (FX): the column's 2^E
+    // (FX: a layer of a 24-bit array is 3/4 of stash_layer floats; H == Hs, so the tile's row offsets are 0)
+    __device__ static __forceinline__ int64_t layer_stride(const WgradArgs& a) { return FX ? a.stash_layer / 4 * 3 : a.stash_layer; }
+    __device__ static __forceinline__ void drain(RawSet& r0, RawSet& r1, RawSet& r2) {      // everything in flight has landed
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(r0.g0), "+v"(r0.g1), "+v"(r0.g2), "+v"(r0.g3), "+v"(r1.g0), "+v"(r1.g1),
+                     "+v"(r1.g2), "+v"(r1.g3), "+v"(r2.g0), "+v"(r2.g1), "+v"(r2.g2), "+v"(r2.g3));
+        if constexpr (FX) asm volatile("" : "+v"(r0.sc), "+v"(r1.sc), "+v"(r2.sc));
+    }
+
+    int pw, p_q, p_li;
+    unsigned t_voff0, t_vstep, p_li4;
+    int t_w0, t_w1;                 // image write offsets of this lane: tiles with even / odd t
+    int c_t0, c_t1;                 // ... and its two transposed reads of a fragment
+    const float *F0, *F1;           // FX: the column scales of the wave's operands (layer j + 1 for q / zbar, layer j for A / s)
+    f32x4 bacc[4] = {};             // bias gradient partial sums: one quad of features per tile
+    __device__ __forceinline__ TileStager(const WgradArgs& a_, const WgTile& t_, char* ldsb_, int tid, int wave)
+        : StagerBase(a_, t_, ldsb_, tid, wave) {
+        const int lane = tid & 63, j = t.j;
+        F0 = FX ? (p_oper ? a.fxA + (int64_t)j * a.np : a.fxQ + (int64_t)(j + 1) * a.np) : nullptr;
+        F1 = FX ? (p_oper ? a.fxS + (int64_t)j * a.np : a.fxZ + (int64_t)(j + 1) * a.np) : nullptr;
+        pw = wave & (NW_ / 2 - 1); p_q = lane >> 4; p_li = lane & 15;
+        const int64_t ngrp = a.np >> 4;                                       // 16-column groups per row of tiles
+        // FX: tile 4 pw (+ t) of the tile-major array; else row 16 pw + q (+ 4 t) of the fp32 row layout, column li
+        t_voff0 = FX ? (unsigned)(lane * 12 + (int64_t)(4 * pw) * ngrp * 768)   // (the launcher keeps a layer below 2^32 bytes)
+                     : (unsigned)((((int64_t)(16 * pw + p_q)) * a.np + p_li) * 16);
+        t_vstep = FX ? (unsigned)(ngrp * 768) : (unsigned)(4 * a.np * 16);
+        p_li4 = (unsigned)p_li * 4u;                                           // FX: this lane's column scale inside a stage's 16
+        // row li, unit 16 pw + 4 t + q with its low three bits swizzled
+        const int p_sw = (p_li >> 1) & 7;
+        t_w0 = p_oper * OPERB + p_li * ROWB + 128 * pw + 8 * (p_q ^ p_sw);
+        t_w1 = p_oper * OPERB + p_li * ROWB + 128 * pw + 8 * ((4 + p_q) ^ p_sw);
+        // rows k = 8 (lane >> 5) + ((lane & 15) >> 2) and k + 4, unit 8 b + 4 ((lane >> 4) & 1) + (lane & 3) of block b, low
+        // three bits swizzled with the row's (k >> 1) & 7
+        // (FX: the same two numbers written through (q, li) — with the lane form hipcc folds the row index of that build
+        //  differently and its three-buffer hot loop gains a v_add_u32; the fp32-row build is the other way round)
+        const int c_k = FX ? 8 * (p_q >> 1) + (p_li >> 2) : 8 * (lane >> 5) + ((lane & 15) >> 2);
+        const int c_u = FX ? 4 * (p_q & 1) + (p_li & 3) : 4 * ((lane >> 4) & 1) + (lane & 3);
+        c_t0 = c_k * ROWB + 8 * (c_u ^ ((c_k >> 1) & 7));
+        c_t1 = (c_k + 4) * ROWB + 8 * (c_u ^ (((c_k + 4) >> 1) & 7));
+    }
+    __device__ __forceinline__ const char* stage_src(int it) const {          // wave-uniform: this stage's 16 columns of the operand
+        return reinterpret_cast<const char*>(operand(it)) + (int64_t)t.step_of(it) * (FX ? 768 : KB * 16);
+    }
+    __device__ __forceinline__ void load(int it, RawSet& r) const {
+        const uint64_t sbase = wg_uniform64(stage_src(it));
+        if constexpr (FX) {
+            const uint64_t fbase = wg_uniform64((t.pair_of(it) ? F1 : F0) + (int64_t)t.step_of(it) * KB);
+            asm volatile("global_load_dwordx3 %0, %5, %9\n\tglobal_load_dwordx3 %1, %6, %9\n\t"
+                         "global_load_dwordx3 %2, %7, %9\n\tglobal_load_dwordx3 %3, %8, %9\n\t"
+                         "global_load_dword %4, %10, %11"
+                         : "=&v"(r.g0), "=&v"(r.g1), "=&v"(r.g2), "=&v"(r.g3), "=&v"(r.sc)
+                         : "v"(t_voff0), "v"(t_voff0 + t_vstep), "v"(t_voff0 + 2 * t_vstep), "v"(t_voff0 + 3 * t_vstep), "s"(sbase),
+                           "v"(p_li4), "s"(fbase) : "memory");
+        } else {
+            asm volatile("global_load_dwordx4 %0, %4, %8\n\tglobal_load_dwordx4 %1, %5, %8\n\t"
+                         "global_load_dwordx4 %2, %6, %8\n\tglobal_load_dwordx4 %3, %7, %8"
+                         : "=&v"(r.g0), "=&v"(r.g1), "=&v"(r.g2), "=&v"(r.g3)
+                         : "v"(t_voff0), "v"(t_voff0 + t_vstep), "v"(t_voff0 + 2 * t_vstep), "v"(t_voff0 + 3 * t_vstep), "s"(sbase) : "memory");
+        }
+    }
+    __device__ __forceinline__ void load_plain(int it, RawSet& r) const {     // (ordinary loads: see RowStager)
+        const char* src = stage_src(it) + t_voff0;
+        r.g0 = __builtin_nontemporal_load(reinterpret_cast<const raw_t*>(src));
+        r.g1 = __builtin_nontemporal_load(reinterpret_cast<const raw_t*>(src + t_vstep));
+        r.g2 = __builtin_nontemporal_load(reinterpret_cast<const raw_t*>(src + 2 * (size_t)t_vstep));
+        r.g3 = __builtin_nontemporal_load(reinterpret_cast<const raw_t*>(src + 3 * (size_t)t_vstep));
+        if constexpr (FX) r.sc = (t.pair_of(it) ? F1 : F0)[(int64_t)t.step_of(it) * KB + p_li];
+    }
+    template <int N>
+    __device__ static __forceinline__ void wait(RawSet& r) {
+        if constexpr (FX) asm volatile("s_waitcnt vmcnt(%5)" : "+v"(r.g0), "+v"(r.g1), "+v"(r.g2), "+v"(r.g3), "+v"(r.sc) : "n"(N));
+        else asm volatile("s_waitcnt vmcnt(%4)" : "+v"(r.g0), "+v"(r.g1), "+v"(r.g2), "+v"(r.g3) : "n"(N));
+    }
+    // tile tt of this lane's four (features 16 (4 pw + tt) + 4 q .. + 3 of column li): unpack, bias sums, fp16 hi / lo, two
+    // 8-byte writes into row li of the image
+    // (FX: `scl` = 2^E of this lane's column x the operand's layer scale, `m3` = -3 scl: v = (t - 3) scl is the value in the GEMM's
+    //  scale, the bias sums run in that scale too and are divided by the layer scale at the end)
+    __device__ __forceinline__ void split_tile(const raw_t& g, int tt, int bsel, const float bmask, const float scl, const float m3) {
+        f32x4 v;
+        f16x2 h0, h1;
+        if constexpr (FX) {
+            const u32x4 p = fx24_patterns(g[0], g[1], g[2]);
+            v = f32x4{__builtin_fmaf(__uint_as_float(p[0]), scl, m3), __builtin_fmaf(__uint_as_float(p[1]), scl, m3),
+                      __builtin_fmaf(__uint_as_float(p[2]), scl, m3), __builtin_fmaf(__uint_as_float(p[3]), scl, m3)};
+            h0 = __builtin_convertvector(f32x2{v[0], v[1]}, f16x2); h1 = __builtin_convertvector(f32x2{v[2], v[3]}, f16x2);
+        } else {
+            v = g;
+        }
+        bacc[tt] += bmask * v;
+        const f32x2 v0 = {v[0], v[1]}, v1 = {v[2], v[3]};
+        char* dst = ldsb + bsel * BUFB + ((tt & 1) ? t_w1 : t_w0) + 64 * (tt >> 1);
+        if constexpr (FX) {
+            put_hi_lo<PIECEB>(dst, f16_hi_lo(v0, v1, h0, h1));
+        } else {
+            // hi = fp16(v 2^k) in ONE instruction per value (v_fma_mixlo_f16 / v_fma_mixhi_f16: fp32 sources, fp16 result into one
+            // half of the destination; the product with a power of two is exact, so this is the rounding of multiply + convert)
+            asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h0) : "v"(v0.x), "s"(scl));
+            asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h0) : "v"(v0.y), "s"(scl));
+            asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h1) : "v"(v1.x), "s"(scl));
+            asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h1) : "v"(v1.y), "s"(scl));
+            put_hi_lo<PIECEB>(dst, f16_hi_lo(v0, v1, h0, h1, scl));
+        }
+    }
+    __device__ __forceinline__ void split_store(int it, const RawSet& r, int bsel) {
+        const float bmask = bias_mask(it);
+        const float scl0 = layer_scale(it);
+        const float scl = FX ? r.sc * scl0 : scl0;          // FX: per lane — the column's 2^E times the layer scale (both powers of two)
+        const float m3 = -3.0f * scl;
+        split_tile(r.g0, 0, bsel, bmask, scl, m3); split_tile(r.g1, 1, bsel, bmask, scl, m3);
+        split_tile(r.g2, 2, bsel, bmask, scl, m3); split_tile(r.g3, 3, bsel, bmask, scl, m3);
+    }
+    __device__ __forceinline__ u32x4 frag_tr(const char* base) const {
+        typedef short s16x4 __attribute__((ext_vector_type(4)));
+        const u32x2 lo = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + c_t0)));
+        const u32x2 hi = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + c_t1)));
+        return u32x4{lo.x, lo.y, hi.x, hi.y};
+    }
+    __device__ __forceinline__ u32x4 fragA(const char* buf, int m, int pc) const { return frag_tr(buf + pc * PIECEB + (wo * W::MT + m) * 64); }
+    __device__ __forceinline__ u32x4 fragB(const char* buf, int n, int pc) const { return frag_tr(buf + (OPERB + pc * PIECEB + n * 64) + wi * (W::NTL * 64)); }
+    __device__ __forceinline__ void flush_bias(float* dB) const {     // the 16 columns (lanes li) of features 16 (4 pw + tt) + 4 q + e
+        if (p_oper != 0 || t.i_off != 0) return;
+        const float bun = FX ? 1.0f / sc1 : 1.0f;           // FX: the sums ran in zbar's layer scale (a power of two)
+        auto red = [&](float v, int f) {
+            v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
+            if (p_li == 0) atomicAdd(dB + f, v * bun);
+        };
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) red(bacc[tt][e], 16 * (4 * pw + tt) + 4 * p_q + e);
+    }
+};
+
+// The flags: per-buffer stage counters in LDS instead of a workgroup barrier per stage.  A wave starts stage `it` when all
+// eight waves have written their part of image `it` (counter W) and have finished reading the buffer its own split is about
+// to overwrite (counter R): waves may drift up to a stage apart, so the SIMD partner that the issue arbitration serves first
+// (the older wave) no longer idles a third of every stage at the barrier while the younger one finishes.
+// NB = 3: a wave must ask — a second poll per stage — whether every wave has finished READING image it - 1 before it splits
+// image it + 2 into that buffer.  NB = 4: the buffer of image it + 2 is the one image it - 2 lived in, and the poll at the top
+// of stage `it` (every wave has WRITTEN image it, which it does behind its reads of image it - 2: LDS executes a wave's
+// operations in order) already says so: one poll and one flag less per stage.
+// Per-wave progress words in LDS (no atomics, no address registers).  A wave publishes with ds_write_addtid_b32 from lane 0
+// (address M0) and polls the whole block with one ds_read_addtid_b32 (lane i reads word i).  Inline asm: the poll is a
+// loop, and a compiler-visible loop inside the hand-counted stage loop makes hipcc spill registers that still have loads
+// in flight.
+__device__ __forceinline__ void wg_publish(unsigned lds_addr, unsigned value) {
+    unsigned keep, vt; uint64_t ex;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_mov_b64 %2, exec\n\ts_mov_b64 exec, 1\n\t"
+                 "v_mov_b32 %1, %4\n\tds_write_addtid_b32 %1\n\ts_mov_b64 exec, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep), "=&v"(vt), "=&s"(ex) : "s"(lds_addr), "s"(value) : "memory");
+}
+// one block of 24 words at flag0: lanes 0-7 = images written by waves 0..7, 8-15 = stages whose fragment reads are finished,
+// 16-23 = stages whose MFMAs are nearly all issued.  All three are plain stage counters.
+__device__ __forceinline__ void wg_poll(unsigned flag0, unsigned need_w, unsigned need_r, unsigned need_h03, unsigned need_h47) {
+    unsigned keep, vt, t0, t1;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n"
+                 ".Ldudf_poll%=:\n\t"
+                 "ds_read_addtid_b32 %1\n\ts_waitcnt lgkmcnt(0)\n\t"
+                 "v_cmp_le_u32 vcc, %5, %1\n\ts_and_b32 %2, vcc_lo, 0xff\n\t"
+                 "v_cmp_le_u32 vcc, %6, %1\n\ts_and_b32 %3, vcc_lo, 0xff00\n\ts_or_b32 %2, %2, %3\n\t"
+                 "v_cmp_le_u32 vcc, %7, %1\n\ts_and_b32 %3, vcc_lo, 0xf0000\n\ts_or_b32 %2, %2, %3\n\t"
+                 "v_cmp_le_u32 vcc, %8, %1\n\ts_and_b32 %3, vcc_lo, 0xf00000\n\ts_or_b32 %2, %2, %3\n\t"
+                 "s_cmp_eq_u32 %2, 0xffffff\n\t"
+                 "s_cbranch_scc1 .Ldudf_done%=\n\ts_sleep 1\n\ts_branch .Ldudf_poll%=\n"
+                 ".Ldudf_done%=:\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(keep), "=&v"(vt), "=&s"(t0), "=&s"(t1)
+                 : "s"(flag0), "s"(need_w), "s"(need_r), "s"(need_h03), "s"(need_h47) : "memory", "vcc", "scc");
+}
+
+// NB: image buffers in LDS, 3 or 4 (see the flags above); SP: 0 = bf16x6, 1 = fp16x3 MFMA groups
+template <int H, int NB, int SP, class Stager>
+__device__ __forceinline__ void wgrad_pipeline(const WgradArgs& a) {
     using W = WG<H>;
     static_assert(H == 256 && (NB == 3 || NB == 4), "256 x 256 output tiles, three or four images");
-    static_assert(P24 == 0 || SP != 0, "24-bit operands: the fp16x3 build");
-    constexpr int NPC = SP ? 2 : 3;                         // pieces per operand
+    static_assert(Stager::NPC == (SP ? 2 : 3), "the stager writes the pieces the MFMA groups read: TileStager is an fp16x3 stager");
+    using RawSet = typename Stager::RawSet;
+    constexpr int NPC = Stager::NPC;                        // pieces per operand
     constexpr int NW_ = W::WO * W::WI;
-    constexpr int FQ = H / 4;
-    constexpr int HALFB = 32 * 16 + 16;                     // 32 features x 8 columns of a block, +16: the second column half
-    constexpr int BLKB = 2 * HALFB;                         //   must not sit 512 B = 0 banks after the first (ds_write_b64)
-    constexpr int ROWB = 576;                               // P24: one column's 256 fp16 + 64 bytes
-    constexpr int PIECEB = P24 ? 16 * ROWB : (H / 32) * BLKB;   // 8.25 KiB (P24: 9)
-    constexpr int OPERB = NPC * PIECEB;                     // 24 KiB (16.5; P24: 18)
-    constexpr int BUFB = 2 * OPERB;                         // 48 KiB (33; P24: 36)
-    extern __shared__ __attribute__((aligned(16))) char ldsb[];     // [NB buffers][X | Y][h | m | l][feature][16 columns], then the flags
+    constexpr int BUFB = Stager::BUFB;
+    extern __shared__ __attribute__((aligned(16))) char ldsb[];     // [NB image buffers: X | Y, each NPC pieces], then the flags
 
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wo = wave / W::WI, wi = wave % W::WI;
     // Layers wider than the tile (512: 2 x 2 tiles): the four tiles of one (layer, column split) read the same X rows twice
@@ -474,61 +812,19 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
         if (grp >= a.nj * a.remap_nsplit) return;               // the grid is padded to whole XCD rounds
         bz = slot & 3; bx = grp % a.nj; by = grp / a.nj; nsplit = a.remap_nsplit;
     }
-    const int j = bx + a.j0;
-    const int steps16 = a.steps_total * (KT / KB);
-    const int s0 = (int)((int64_t)steps16 * by / nsplit);
-    const int s1 = (int)((int64_t)steps16 * (by + 1) / nsplit);
-    const int tz = a.Hs / H;
-    const int o_off = (bz / tz) * H, i_off = (bz % tz) * H;
-    const int64_t xrow = (int64_t)(o_off / 4) * a.np * 4, yrow = (int64_t)(i_off / 4) * a.np * 4;
+    const WgTile t(a, H, bx, by, bz, nsplit, a.steps_total * (KT / KB), Stager::layer_stride(a));
+    const int j = t.j, nit = t.nit;
     // (fp16x3 build only: the bf16x6 build sits at 256 registers and four more live scalars make it spill)
     const bool clk_on = SP != 0 && a.clk != nullptr && bx == 0 && by == 0 && bz == 0;
     const unsigned long long clk_t0 = clk_on ? __builtin_amdgcn_s_memtime() : 0ull, clk_r0 = clk_on ? __builtin_amdgcn_s_memrealtime() : 0ull;
 
     f32x16 acc[W::MT][W::NTL];
-#pragma unroll
-    for (int m = 0; m < W::MT; ++m)
-#pragma unroll
-        for (int n = 0; n < W::NTL; ++n)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][n][e] = 0.f;
-    // (P24: a layer of a 24-bit array is 3/4 of stash_layer floats; H == Hs, so xrow == yrow == 0)
-    const int64_t lstride = P24 == 1 ? a.stash_layer / 4 * 3 : a.stash_layer;
-    const float* X0 = a.Q + (int64_t)(j + 1) * lstride + xrow;
-    const float* X1 = a.Z + (int64_t)(j + 1) * lstride + xrow;
-    const float* Y0 = a.A + (int64_t)j * lstride + yrow;
-    const float* Y1 = a.S + (int64_t)j * lstride + yrow;
-
-    const int npair = a.have_g ? 2 : 1;
-    const int nit = npair * (s1 - s0);
-    auto pair_of = [&](int it) { return a.have_g ? (it & 1) : 1; };
-    auto step_of = [&](int it) { return s0 + (a.have_g ? (it >> 1) : it); };
-
-    // producer role of this lane: operand, feature quad, group of four columns
-    const int p_oper = wave / (NW_ / 2);                                  // wave-uniform: waves 0..3 stage X, 4..7 stage Y
-    const int p_cg = tid & 3;
-    const int p_fq = ((tid >> 2) & 1) | (((tid >> 4) & 3) << 1) | (((tid >> 3) & 1) << 3) | (((tid >> 6) & 3) << 4);   // conflict-free writes: see above
-    // granule j of this lane = stage column p_cg + 4 j: one load instruction then reads 64 contiguous bytes per feature
-    // quad (4 lanes x 16 B) and touches each 128-byte line twice instead of four times (PMC r01: 2x the ideal L2
-    // requests; the loads alone held the kernel at 0.8 ms).  The image slot 4 p_cg + j therefore holds column p_cg + 4 j:
-    // a permutation of the contraction index, the same for both operands, hence free.
-    const int64_t p_goff = ((int64_t)p_fq * a.np + p_cg) * 4;             // floats, + col0 * 4 per stage
-    // image of one piece: [32-feature block][column half][feature in block][8 columns] = the fragment order of the MFMA
-    const int p_loff = p_oper * OPERB + (p_fq >> 3) * BLKB + (p_cg >> 1) * HALFB + ((p_fq & 7) * 4) * 16 + (p_cg & 1) * 8;   // + f * 16 + piece * PIECEB
-    typedef unsigned u3_t __attribute__((ext_vector_type(3)));
-    typedef typename std::conditional<P24 == 1, u3_t, f32x4>::type raw_t;      // P24 = 1: a granule is 3 dwords (four 24-bit values)
-    struct RawSet { raw_t g0, g1, g2, g3; float sc; };                    // granule j: 4 features of column 4*cg + j (P24: of tile 4 pw + j, column li); sc (P24 = 1): the column's 2^E
-    RawSet R0, R1, R2;                                                    // stage s travels in set s % 3, three stages ahead
-    f32x4 bacc = {0.f, 0.f, 0.f, 0.f};                                    // bias gradient partial sums (X operand, zbar pair)
-    f32x4 bacc1 = bacc, bacc2 = bacc, bacc3 = bacc;                       // P24: one quad of features per tile
-    const float* P0 = p_oper ? Y0 : X0;                                   // this wave's operand for the (q, A) / (zbar, s) pair
-    const float* P1 = p_oper ? Y1 : X1;
-    // P24 = 1: the column scales of those operands (layer j + 1 for q / zbar, layer j for A / s)
-    const float* F0 = P24 == 1 ? (p_oper ? a.fxA + (int64_t)j * a.np : a.fxQ + (int64_t)(j + 1) * a.np) : nullptr;
-    const float* F1 = P24 == 1 ? (p_oper ? a.fxS + (int64_t)j * a.np : a.fxZ + (int64_t)(j + 1) * a.np) : nullptr;
-    // fp16x3: this wave's operand scale for each pair, and the common product scale 2^P of the layer
-    float sc0 = 1.f, sc1 = 1.f, inv_p = 1.f;
+    wg_zero(acc);
+    // fp16x3: this wave's operand scale for each pair (waves 0..3 stage X, 4..7 stage Y), and the common product scale 2^P of the layer
+    Stager st(a, t, ldsb, tid, wave);
+    float inv_p = 1.f;
     if constexpr (SP != 0) {
+        const int oper = st.p_oper;
         const int eq = dudf_exp_above(a.amax[0 * a.L + j + 1]), eA = dudf_exp_above(a.amax[1 * a.L + j]);
         const int ez = dudf_exp_above(a.amax[2 * a.L + j + 1]);
         const int esh = dudf_exp_above(a.amax[3 * a.L + j]);             // h | hdot^k of the Hessian quads; plain columns: |h| <= 1 (+ an ulp)
@@ -536,280 +832,36 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
         const int P1l = 30 - eq - eA, P2l = 30 - ez - es;
         const int P = (a.have_g && P1l < P2l) ? P1l : P2l;
         // the pair with the larger admissible product gives the surplus back through its X operand
-        sc0 = p_oper ? dudf_pow2(15 - eA) : dudf_pow2(15 - eq - (P1l - P));
-        sc1 = p_oper ? dudf_pow2(15 - es) : dudf_pow2(15 - ez - (P2l - P));
-        if (!a.have_g) sc0 = sc1;
+        st.sc0 = oper ? dudf_pow2(15 - eA) : dudf_pow2(15 - eq - (P1l - P));
+        st.sc1 = oper ? dudf_pow2(15 - es) : dudf_pow2(15 - ez - (P2l - P));
+        if (!a.have_g) st.sc0 = st.sc1;
         inv_p = dudf_pow2(-P);
     }
-    // Inline asm + hand-counted vmcnt (as in the sweeps): with compiler-visible loads hipcc drains ALL stages in flight
-    // (vmcnt(0)) at the loop head.  These twelve loads are the only vector-memory operations of the loop.
-    // scalar base (operand, pair, stage: wave-uniform) + this lane's fixed 32-bit byte offset: no per-stage 64-bit address
-    // arithmetic in vector registers (the launcher keeps FQ * np * 16 below 2^32)
-    const unsigned p_voff = (unsigned)(p_goff * 4);
-    const float bm_plain = (p_oper == 0 && i_off == 0) ? 1.f : 0.f;     // this lane's granules count towards the bias gradient ...
-    const float bm_quad = ((P24 ? (lane & 3) : p_cg) == 0) ? bm_plain : 0.f;   // ... on a Hessian-quad stage (the value channel: column % 4 == 0)
-    // P24 producer role: wave pw (0..3 of its operand) stages feature tiles 4 pw .. 4 pw + 3; lane = (q, li) as in the sweeps
-    const int pw = wave & (NW_ / 2 - 1), p_q = lane >> 4, p_li = lane & 15;
-    const int64_t ngrp = a.np >> 4;                                       // 16-column groups per row of tiles
-    // P24 = 1: tile 4 pw (+ t) of the tile-major array; P24 = 2: row 16 pw + q (+ 4 t) of the fp32 row layout, column li
-    const unsigned t_voff0 = P24 == 2 ? (unsigned)((((int64_t)(16 * pw + p_q)) * a.np + p_li) * 16)
-                                      : (unsigned)(lane * 12 + (int64_t)(4 * pw) * ngrp * 768);   // (the launcher keeps a layer below 2^32 bytes)
-    const unsigned t_vstep = P24 == 2 ? (unsigned)(4 * a.np * 16) : (unsigned)(ngrp * 768);
-    const unsigned p_li4 = (unsigned)p_li * 4u;                            // P24 = 1: this lane's column scale inside a stage's 16
-    // image write offsets of this lane (row li, unit 16 pw + 4 t + q with its low three bits swizzled): tiles with even / odd t
-    const int p_sw = (p_li >> 1) & 7;
-    const int t_w0 = p_oper * OPERB + p_li * ROWB + 128 * pw + 8 * (p_q ^ p_sw), t_w1 = p_oper * OPERB + p_li * ROWB + 128 * pw + 8 * ((4 + p_q) ^ p_sw);
-    auto load_raw = [&](int it, RawSet& r) {
-        if constexpr (P24 == 2) {
-            const uint64_t g0 = (uint64_t)(size_t)(reinterpret_cast<const char*>(pair_of(it) ? P1 : P0) + (int64_t)step_of(it) * (KB * 16));
-            const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)g0), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(g0 >> 32));
-            const uint64_t sbase = ((uint64_t)hi32 << 32) | lo32;
-            asm volatile("global_load_dwordx4 %0, %4, %8\n\tglobal_load_dwordx4 %1, %5, %8\n\t"
-                         "global_load_dwordx4 %2, %6, %8\n\tglobal_load_dwordx4 %3, %7, %8"
-                         : "=&v"(r.g0), "=&v"(r.g1), "=&v"(r.g2), "=&v"(r.g3)
-                         : "v"(t_voff0), "v"(t_voff0 + t_vstep), "v"(t_voff0 + 2 * t_vstep), "v"(t_voff0 + 3 * t_vstep), "s"(sbase) : "memory");
-        } else if constexpr (P24 != 0) {
-            const uint64_t g0 = (uint64_t)(size_t)(reinterpret_cast<const char*>(pair_of(it) ? P1 : P0) + (int64_t)step_of(it) * 768);
-            const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)g0), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(g0 >> 32));
-            const uint64_t sbase = ((uint64_t)hi32 << 32) | lo32;
-            const uint64_t f0 = (uint64_t)(size_t)((pair_of(it) ? F1 : F0) + (int64_t)step_of(it) * KB);
-            const unsigned flo = __builtin_amdgcn_readfirstlane((unsigned)f0), fhi = __builtin_amdgcn_readfirstlane((unsigned)(f0 >> 32));
-            const uint64_t fbase = ((uint64_t)fhi << 32) | flo;
-            asm volatile("global_load_dwordx3 %0, %5, %9\n\tglobal_load_dwordx3 %1, %6, %9\n\t"
-                         "global_load_dwordx3 %2, %7, %9\n\tglobal_load_dwordx3 %3, %8, %9\n\t"
-                         "global_load_dword %4, %10, %11"
-                         : "=&v"(r.g0), "=&v"(r.g1), "=&v"(r.g2), "=&v"(r.g3), "=&v"(r.sc)
-                         : "v"(t_voff0), "v"(t_voff0 + t_vstep), "v"(t_voff0 + 2 * t_vstep), "v"(t_voff0 + 3 * t_vstep), "s"(sbase),
-                           "v"(p_li4), "s"(fbase) : "memory");
-        } else {
-        const uint64_t g0 = (uint64_t)(size_t)((pair_of(it) ? P1 : P0) + (int64_t)step_of(it) * KB * 4);
-        const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)g0), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(g0 >> 32));
-        const uint64_t sbase = ((uint64_t)hi32 << 32) | lo32;
-        asm volatile("global_load_dwordx4 %0, %4, %5\n\tglobal_load_dwordx4 %1, %4, %5 offset:64\n\t"
-                     "global_load_dwordx4 %2, %4, %5 offset:128\n\tglobal_load_dwordx4 %3, %4, %5 offset:192"
-                     : "=&v"(r.g0), "=&v"(r.g1), "=&v"(r.g2), "=&v"(r.g3) : "v"(p_voff), "s"(sbase) : "memory");
-        }
-    };
-    // outside the steady-state loop (prologue, last stages: conditional loads) the loads are ordinary ones: a conditional
-    // asm load makes hipcc merge "loaded" and "not loaded" values with register copies — of registers still in flight
-    auto load_raw_plain = [&](int it, RawSet& r) {
-        if constexpr (P24 == 2) {
-            const char* src = reinterpret_cast<const char*>(pair_of(it) ? P1 : P0) + (int64_t)step_of(it) * (KB * 16) + t_voff0;
-            r.g0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src));
-            r.g1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + t_vstep));
-            r.g2 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + 2 * (size_t)t_vstep));
-            r.g3 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + 3 * (size_t)t_vstep));
-        } else if constexpr (P24 != 0) {
-            const char* src = reinterpret_cast<const char*>(pair_of(it) ? P1 : P0) + (int64_t)step_of(it) * 768 + t_voff0;
-            r.g0 = __builtin_nontemporal_load(reinterpret_cast<const u3_t*>(src));
-            r.g1 = __builtin_nontemporal_load(reinterpret_cast<const u3_t*>(src + t_vstep));
-            r.g2 = __builtin_nontemporal_load(reinterpret_cast<const u3_t*>(src + 2 * (size_t)t_vstep));
-            r.g3 = __builtin_nontemporal_load(reinterpret_cast<const u3_t*>(src + 3 * (size_t)t_vstep));
-            r.sc = (pair_of(it) ? F1 : F0)[(int64_t)step_of(it) * KB + p_li];
-        } else {
-        const float* src = (pair_of(it) ? P1 : P0) + p_goff + (int64_t)step_of(it) * KB * 4;
-        r.g0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src));
-        r.g1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src) + 4);
-        r.g2 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src) + 8);
-        r.g3 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src) + 12);
-        }
-    };
-    constexpr int kSetLoads = P24 == 1 ? 5 : 4;          // loads per register set (P24 = 1: + the column scale)
-    auto wait_raw = [&](RawSet& r, auto younger) {       // this set has landed; `younger` loads issued after it stay in flight
-        if constexpr (P24 == 1) asm volatile("s_waitcnt vmcnt(%5)" : "+v"(r.g0), "+v"(r.g1), "+v"(r.g2), "+v"(r.g3), "+v"(r.sc) : "n"(decltype(younger)::value));
-        else asm volatile("s_waitcnt vmcnt(%4)" : "+v"(r.g0), "+v"(r.g1), "+v"(r.g2), "+v"(r.g3) : "n"(decltype(younger)::value));
-    };
-    // The flags: per-buffer stage counters in LDS instead of a workgroup barrier per stage.  A wave starts stage `it` when all
-    // eight waves have written their part of image `it` (counter W) and have finished reading the buffer its own split is about
-    // to overwrite (counter R): waves may drift up to a stage apart, so the SIMD partner that the issue arbitration serves first
-    // (the older wave) no longer idles a third of every stage at the barrier while the younger one finishes.
-    // NB = 3: a wave must ask — a second poll per stage — whether every wave has finished READING image it - 1 before it splits
-    // image it + 2 into that buffer.  NB = 4: the buffer of image it + 2 is the one image it - 2 lived in, and the poll at the top
-    // of stage `it` (every wave has WRITTEN image it, which it does behind its reads of image it - 2: LDS executes a wave's
-    // operations in order) already says so: one poll and one flag less per stage.
-    // Per-wave progress words in LDS (no atomics, no address registers).  A wave publishes with ds_write_addtid_b32 from lane 0
-    // (address M0) and polls the whole block with one ds_read_addtid_b32 (lane i reads word i).  Inline asm: the poll is a
-    // loop, and a compiler-visible loop inside the hand-counted stage loop makes hipcc spill registers that still have loads
-    // in flight.
+    RawSet R0, R1, R2;                                                    // stage s travels in set s % 3, three stages ahead
     const unsigned flag0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)(ldsb + NB * BUFB);
-    auto publish = [&](unsigned lds_addr, unsigned value) {
-        unsigned keep, vt; uint64_t ex;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_mov_b64 %2, exec\n\ts_mov_b64 exec, 1\n\t"
-                     "v_mov_b32 %1, %4\n\tds_write_addtid_b32 %1\n\ts_mov_b64 exec, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep), "=&v"(vt), "=&s"(ex) : "s"(lds_addr), "s"(value) : "memory");
-    };
-    // one block of 24 words: lanes 0-7 = images written by waves 0..7, 8-15 = stages whose fragment reads are finished,
-    // 16-23 = stages whose MFMAs are nearly all issued.  All three are plain stage counters.
-    auto poll = [&](unsigned need_w, unsigned need_r, unsigned need_h03, unsigned need_h47) {
-        unsigned keep, vt, t0, t1;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n"
-                     ".Ldudf_poll%=:\n\t"
-                     "ds_read_addtid_b32 %1\n\ts_waitcnt lgkmcnt(0)\n\t"
-                     "v_cmp_le_u32 vcc, %5, %1\n\ts_and_b32 %2, vcc_lo, 0xff\n\t"
-                     "v_cmp_le_u32 vcc, %6, %1\n\ts_and_b32 %3, vcc_lo, 0xff00\n\ts_or_b32 %2, %2, %3\n\t"
-                     "v_cmp_le_u32 vcc, %7, %1\n\ts_and_b32 %3, vcc_lo, 0xf0000\n\ts_or_b32 %2, %2, %3\n\t"
-                     "v_cmp_le_u32 vcc, %8, %1\n\ts_and_b32 %3, vcc_lo, 0xf00000\n\ts_or_b32 %2, %2, %3\n\t"
-                     "s_cmp_eq_u32 %2, 0xffffff\n\t"
-                     "s_cbranch_scc1 .Ldudf_done%=\n\ts_sleep 1\n\ts_branch .Ldudf_poll%=\n"
-                     ".Ldudf_done%=:\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep), "=&v"(vt), "=&s"(t0), "=&s"(t1)
-                     : "s"(flag0), "s"(need_w), "s"(need_r), "s"(need_h03), "s"(need_h47) : "memory", "vcc", "scc");
-    };
-    auto split_slice = [&](int it, const RawSet& r, int f, int bsel) {    // feature f of the lane's quad -> piece image buffer bsel
-      if constexpr (P24 == 0) {
-        char* dst = ldsb + bsel * BUFB + p_loff + 16 * f;
-        if (f == 0) {
-            // Hessian quads: only columns % 4 == 0 (the value channel) carry the bias — all four granules of the lanes
-            // with p_cg == 0, none of the others
-            // (branch-free: scalar selects times per-lane constants — a branch here would cut the hand-counted loop body
-            // into several basic blocks)
-            const float hs = ((int64_t)step_of(it) * KB < a.ncol_h) ? 1.f : 0.f;
-            const float pf = pair_of(it) == 1 ? 1.f : 0.f;
-            const float bm = pf * (bm_plain + hs * (bm_quad - bm_plain));
-            bacc += bm * (r.g0 + r.g1 + r.g2 + r.g3);
-        }
-        const f32x2 v0 = {r.g0[f], r.g1[f]}, v1 = {r.g2[f], r.g3[f]};     // four columns of one feature -> 3 x 8 bytes
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        if constexpr (SP != 0) {
-            // t = v 2^k -> hi = fp16(t), lo = fp16(t - hi): the residual as ONE v_fma_mix_f32 (v * 2^k - hi, exact; reads the
-            // fp16 half in place and issues beside the SIMD partner's MFMAs like v_fma_f32 — tools/micro/coissue.hip)
-            const float scl = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(pair_of(it) ? sc1 : sc0)));
-            const f16x2 h0 = __builtin_convertvector(v0 * scl, f16x2), h1 = __builtin_convertvector(v1 * scl, f16x2);
-            f32x2 r0, r1;
-            asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r0.x) : "v"(v0.x), "s"(scl), "v"(h0));
-            asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r0.y) : "v"(v0.y), "s"(scl), "v"(h0));
-            asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r1.x) : "v"(v1.x), "s"(scl), "v"(h1));
-            asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1.y) : "v"(v1.y), "s"(scl), "v"(h1));
-            const f16x2 l0 = __builtin_convertvector(r0, f16x2), l1 = __builtin_convertvector(r1, f16x2);
-            *reinterpret_cast<u32x2*>(dst) = u32x2{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)};
-            *reinterpret_cast<u32x2*>(dst + PIECEB) = u32x2{__builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1)};
-            return;
-        }
-        const unsigned h0 = cvt_pk(v0), h1 = cvt_pk(v1);
-        const f32x2 r0 = v0 - unpack(h0), r1 = v1 - unpack(h1);
-        const unsigned m0 = cvt_pk(r0), m1 = cvt_pk(r1);
-        const f32x2 q0 = r0 - unpack(m0), q1 = r1 - unpack(m1);
-        const unsigned l0 = cvt_pk(q0), l1 = cvt_pk(q1);
-        *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
-        *reinterpret_cast<u32x2*>(dst + PIECEB) = u32x2{m0, m1};
-        *reinterpret_cast<u32x2*>(dst + 2 * PIECEB) = u32x2{l0, l1};
-      }
-    };
-    // P24: tile t of this lane's four (features 16 (4 pw + t) + 4 q .. + 3 of column li): unpack, bias sums, fp16 hi / lo, two
-    // 8-byte writes into row li of the [column][feature] image
-    // (P24 = 1: `scl` = 2^E of this lane's column x the operand's layer scale, `m3` = -3 scl: v = (t - 3) scl is the value in the GEMM's
-    //  scale, the bias sums run in that scale too and are divided by the layer scale at the end)
-    auto split_tile = [&](int it, const raw_t& g, f32x4& bsum, int t, int bsel, const float bmask, const float scl, const float m3) {
-        if constexpr (P24 != 0) {
-            f32x4 v;
-            f16x2 h0, h1;
-            if constexpr (P24 == 1) {
-                const unsigned d0 = g[0], d1 = g[1], d2 = g[2];
-                const unsigned m = 0x00ffffffu, two = 0x40000000u;
-                const unsigned t0 = (d0 & m) | two, t1 = (d1 & m) | two, t2 = (d2 & m) | two;          // v_and_or_b32
-                const unsigned y = __builtin_amdgcn_perm(d1, d0, 0x0c0c0703u);                        // [d0.b3, d1.b3, 0, 0]
-                const unsigned t3 = __builtin_amdgcn_perm(d2, y, 0x0c070100u) | two;                   // [.., .., d2.b3, 0] | 0x40 on top
-                v = f32x4{__builtin_fmaf(__uint_as_float(t0), scl, m3), __builtin_fmaf(__uint_as_float(t1), scl, m3),
-                          __builtin_fmaf(__uint_as_float(t2), scl, m3), __builtin_fmaf(__uint_as_float(t3), scl, m3)};
-                h0 = __builtin_convertvector(f32x2{v[0], v[1]}, f16x2); h1 = __builtin_convertvector(f32x2{v[2], v[3]}, f16x2);
-            } else {
-                v = g;
-            }
-            bsum += bmask * v;
-            const f32x2 v0 = {v[0], v[1]}, v1 = {v[2], v[3]};
-            f32x2 r0, r1;
-            if constexpr (P24 == 1) {
-                asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r0.x) : "v"(v0.x), "v"(h0));
-                asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r0.y) : "v"(v0.y), "v"(h0));
-                asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(r1.x) : "v"(v1.x), "v"(h1));
-                asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1.y) : "v"(v1.y), "v"(h1));
-            } else {
-            // hi = fp16(v 2^k) in ONE instruction per value (v_fma_mixlo_f16 / v_fma_mixhi_f16: fp32 sources, fp16 result into one
-            // half of the destination; the product with a power of two is exact, so this is the rounding of multiply + convert)
-            asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h0) : "v"(v0.x), "s"(scl));
-            asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h0) : "v"(v0.y), "s"(scl));
-            asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h1) : "v"(v1.x), "s"(scl));
-            asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h1) : "v"(v1.y), "s"(scl));
-            asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r0.x) : "v"(v0.x), "s"(scl), "v"(h0));
-            asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r0.y) : "v"(v0.y), "s"(scl), "v"(h0));
-            asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(r1.x) : "v"(v1.x), "s"(scl), "v"(h1));
-            asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1.y) : "v"(v1.y), "s"(scl), "v"(h1));
-            }
-            const f16x2 l0 = __builtin_convertvector(r0, f16x2), l1 = __builtin_convertvector(r1, f16x2);
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-            char* dst = ldsb + bsel * BUFB + ((t & 1) ? t_w1 : t_w0) + 64 * (t >> 1);
-            *reinterpret_cast<u32x2*>(dst) = u32x2{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)};
-            *reinterpret_cast<u32x2*>(dst + PIECEB) = u32x2{__builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1)};
-        }
-    };
-    auto split_store = [&](int it, const RawSet& r, int bsel) {           // raw (stage it) -> piece image buffer bsel
-        if constexpr (P24 != 0) {
-            // once per stage: which of this lane's values count towards the bias gradient (zbar pair; on a Hessian-quad stage
-            // only the value channel, column % 4 == 0), and this operand's power of two
-            const float hs = ((int64_t)step_of(it) * KB < a.ncol_h) ? 1.f : 0.f;
-            const float pf = pair_of(it) == 1 ? 1.f : 0.f;
-            const float bmask = pf * (bm_plain + hs * (bm_quad - bm_plain));
-            const float scl0 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(pair_of(it) ? sc1 : sc0)));
-            const float scl = P24 == 1 ? r.sc * scl0 : scl0;              // P24 = 1: per lane — the column's 2^E times the layer scale (both powers of two)
-            const float m3 = -3.0f * scl;
-            split_tile(it, r.g0, bacc, 0, bsel, bmask, scl, m3); split_tile(it, r.g1, bacc1, 1, bsel, bmask, scl, m3);
-            split_tile(it, r.g2, bacc2, 2, bsel, bmask, scl, m3); split_tile(it, r.g3, bacc3, 3, bsel, bmask, scl, m3);
-        } else {
-#pragma unroll
-            for (int f = 0; f < 4; ++f) split_slice(it, r, f, bsel);
-        }
-    };
-    // consumer role: fragment (32-feature block b, piece p) of an operand = 1 KiB, lane-linear
-    const int c_lane = (lane >> 5) * HALFB + (lane & 31) * 16;
-    // P24: this lane's two transposed reads of a fragment — rows k = 8 (lane >> 5) + ((lane & 15) >> 2) and k + 4, unit
-    // 8 b + 4 ((lane >> 4) & 1) + (lane & 3) of block b, low three bits swizzled with the row's (k >> 1) & 7
-    const int c_k = 8 * (lane >> 5) + ((lane & 15) >> 2), c_u = 4 * ((lane >> 4) & 1) + (lane & 3);
-    const int c_t0 = c_k * ROWB + 8 * (c_u ^ ((c_k >> 1) & 7)), c_t1 = (c_k + 4) * ROWB + 8 * (c_u ^ (((c_k + 4) >> 1) & 7));
-    auto frag_tr = [&](const char* base) -> u32x4 {
-        typedef short s16x4 __attribute__((ext_vector_type(4)));
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        const u32x2 lo = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + c_t0)));
-        const u32x2 hi = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + c_t1)));
-        return u32x4{lo.x, lo.y, hi.x, hi.y};
-    };
-    auto fragA = [&](const char* buf, int m, int pc) -> u32x4 {
-        if constexpr ((DUDF_WGRAD_DBG & 16) != 0) { u32x4 z; asm volatile("" : "=v"(z)); return z; }     // timing only: no LDS read
-        if constexpr (P24 != 0) return frag_tr(buf + pc * PIECEB + (wo * W::MT + m) * 64);
-        else return *reinterpret_cast<const u32x4*>(buf + pc * PIECEB + (wo * W::MT + m) * BLKB + c_lane);
-    };
-    auto fragB = [&](const char* buf, int n, int pc) -> u32x4 {
-        if constexpr ((DUDF_WGRAD_DBG & 16) != 0) { u32x4 z; asm volatile("" : "=v"(z)); return z; }
-        if constexpr (P24 != 0) return frag_tr(buf + OPERB + pc * PIECEB + (wi * W::NTL + n) * 64);
-        else return *reinterpret_cast<const u32x4*>(buf + OPERB + pc * PIECEB + (wi * W::NTL + n) * BLKB + c_lane);
-    };
 
     if (tid < 128) reinterpret_cast<unsigned*>(ldsb + NB * BUFB)[tid] = 0;
     __syncthreads();
     if (nit > 0) {                                       // images 0 and 1 written, images 2, 3, 4 in flight (image k: set k % 3)
-        load_raw_plain(0, R0);
-        if (nit > 1) load_raw_plain(1, R1);
-        if (nit > 2) load_raw_plain(2, R2);
-        split_store(0, R0, 0);
-        publish(flag0 + 4u * (unsigned)wave, 1u);                              // one image written
-        if (nit > 3) load_raw_plain(3, R0);
+        st.load_plain(0, R0);
+        if (nit > 1) st.load_plain(1, R1);
+        if (nit > 2) st.load_plain(2, R2);
+        st.split_store(0, R0, 0);
+        wg_publish(flag0 + 4u * (unsigned)wave, 1u);                           // one image written
+        if (nit > 3) st.load_plain(3, R0);
         if (nit > 1) {
-            split_store(1, R1, 1);
-            publish(flag0 + 4u * (unsigned)wave, 2u);                          // two
+            st.split_store(1, R1, 1);
+            wg_publish(flag0 + 4u * (unsigned)wave, 2u);                       // two
         }
-        if (nit > 4) load_raw_plain(4, R1);
+        if (nit > 4) st.load_plain(4, R1);
     }
     __syncthreads();
     // one stage: 48 MFMAs, then the registers of the stage two further on -> pieces (that set is then refilled with the stage
     // three further on, so three stages = 96 KiB per CU stay in flight: with one, the kernel measured latency-bound at 2 TB/s)
-#if DUDF_WGRAD_DBG & 32
-    unsigned long long wst[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     auto stage = [&](int it, RawSet& r, auto hot, auto bidx) {
         constexpr int BI = decltype(bidx)::value;             // it % 3 (the loops advance by three stages)
         const char* buf = ldsb + (NB == 4 ? (it & 3) : BI) * BUFB;
         constexpr bool HOT = decltype(hot)::value;
-        DUDF_WSTAMP(0);
         {
             // every wave has written its part of image `it` (generation g + 1 of W[BI]) and has finished reading image
             // it - 1, whose buffer this wave's split of image it + 2 is going to overwrite (R[(BI + 2) % 3])
@@ -820,17 +872,15 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
             //   raised one MFMA group before the end, so that the hand-over latency is covered)
             const unsigned uit = (unsigned)it;
             const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(wave >= NW_ / 2));
-            poll(uit + 1u, 0u, hi ? uit + 1u : 0u, hi ? 0u : uit);
+            wg_poll(flag0, uit + 1u, 0u, hi ? uit + 1u : 0u, hi ? 0u : uit);
         }
-        constexpr int DBG = HOT ? DUDF_WGRAD_DBG : 0;
         u32x4 af[W::MT][NPC], bn[NPC];
 #pragma unroll
         for (int m = 0; m < W::MT; ++m)
 #pragma unroll
-            for (int pc = 0; pc < NPC; ++pc) af[m][pc] = fragA(buf, m, pc);
-        DUDF_WSTAMP(1);
+            for (int pc = 0; pc < NPC; ++pc) af[m][pc] = st.fragA(buf, m, pc);
 #pragma unroll
-        for (int pc = 0; pc < NPC; ++pc) bn[pc] = fragB(buf, 0, pc);
+        for (int pc = 0; pc < NPC; ++pc) bn[pc] = st.fragB(buf, 0, pc);
 #pragma unroll
         for (int n = 0; n < W::NTL; ++n) {
             u32x4 bc[NPC];
@@ -838,12 +888,11 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
             for (int pc = 0; pc < NPC; ++pc) bc[pc] = bn[pc];
             if (n + 1 < W::NTL) {
 #pragma unroll
-                for (int pc = 0; pc < NPC; ++pc) bn[pc] = fragB(buf, n + 1, pc);
+                for (int pc = 0; pc < NPC; ++pc) bn[pc] = st.fragB(buf, n + 1, pc);
                 __builtin_amdgcn_sched_barrier(0x76);        // LDS reads and MFMAs keep their order: fragments one block ahead
             }
 #pragma unroll
             for (int m = 0; m < W::MT; ++m) {
-                if constexpr ((DBG & 4) != 0) { asm volatile("" :: "v"(af[m][0]), "v"(af[m][1]), "v"(bc[0]), "v"(bc[1])); continue; }
                 f32x16 c = acc[m][n];
                 if constexpr (SP != 0) {                          // smallest terms first: lo*hi, hi*lo, hi*hi
                     auto H8 = [](u32x4 v) { return __builtin_bit_cast(f16x8, v); };
@@ -864,47 +913,35 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
             }
             if (n == W::NTL - kHandOver) {
                 __builtin_amdgcn_sched_barrier(0);
-                publish(flag0 + 64u + 4u * (unsigned)wave, (unsigned)it + 1u);                     // nearly done with the matrix pipe
+                wg_publish(flag0 + 64u + 4u * (unsigned)wave, (unsigned)it + 1u);                  // nearly done with the matrix pipe
                 __builtin_amdgcn_sched_barrier(0);
             }
-            DUDF_WSTAMP(3 + 2 * n);
         }
         // behind this stage's last fragment reads (LDS executes a wave's operations in order): image `it` read; then
         // the split of image it + 2 into the buffer image it - 1 (NB = 4: it - 2) lived in, and its flag
         __builtin_amdgcn_sched_barrier(0);
         const int BW = NB == 4 ? ((it + 2) & 3) : (BI + 2) % 3;
         if constexpr (NB == 3) {
-            publish(flag0 + 32u + 4u * (unsigned)wave, (unsigned)it + 1u);                       // fragment reads of stage `it` done
-            DUDF_WSTAMP(2);
-            if (HOT || it + 2 < nit) poll(0u, (unsigned)it, 0u, 0u);                             // image it - 1 read by everybody: its buffer is free
+            wg_publish(flag0 + 32u + 4u * (unsigned)wave, (unsigned)it + 1u);                    // fragment reads of stage `it` done
+            if (HOT || it + 2 < nit) wg_poll(flag0, 0u, (unsigned)it, 0u, 0u);                   // image it - 1 read by everybody: its buffer is free
         }
-        DUDF_WSTAMP(4);
         if constexpr (HOT) {
-            if constexpr (!(DBG & 1)) wait_raw(r, std::integral_constant<int, 2 * kSetLoads>{});             // (DBG: timing experiments, wrong results)
-            DUDF_WSTAMP(6);
-            if constexpr (!(DBG & 8)) split_store(it + 2, r, BW);
-            DUDF_WSTAMP(8);
-            if constexpr (!(DBG & 1)) load_raw(it + 5, r);
-            publish(flag0 + 4u * (unsigned)wave, (unsigned)it + 3u);                             // images 0 .. it + 2 written
+            Stager::template wait<2 * Stager::kSetLoads>(r);                                     // the two younger sets stay in flight
+            st.split_store(it + 2, r, BW);
+            st.load(it + 5, r);
+            wg_publish(flag0 + 4u * (unsigned)wave, (unsigned)it + 3u);                          // images 0 .. it + 2 written
         } else if (it + 2 < nit) {
-            split_store(it + 2, r, BW);
-            if (it + 5 < nit) load_raw_plain(it + 5, r);
-            publish(flag0 + 4u * (unsigned)wave, (unsigned)it + 3u);
+            st.split_store(it + 2, r, BW);
+            if (it + 5 < nit) st.load_plain(it + 5, r);
+            wg_publish(flag0 + 4u * (unsigned)wave, (unsigned)it + 3u);
         }
-        DUDF_WSTAMP(10);
-        DUDF_WSTAMP(11);
     };
     int it = 0;
     const int nhot = nit >= 8 ? ((nit - 5) / 3) * 3 : 0;
     // hipcc does not know the sets are in flight: enter (and leave) the hand-counted loop with everything landed, so that
     // the register copies it places on the loop's edges are harmless; inside, the sets stay put (tests/isa_contract.py
     // replays the loop body twice and fails on any instruction that touches a register with a load in flight)
-    auto drain = [&]() {
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(R0.g0), "+v"(R0.g1), "+v"(R0.g2), "+v"(R0.g3), "+v"(R1.g0), "+v"(R1.g1),
-                     "+v"(R1.g2), "+v"(R1.g3), "+v"(R2.g0), "+v"(R2.g1), "+v"(R2.g2), "+v"(R2.g3));
-        if constexpr (P24 == 1) asm volatile("" : "+v"(R0.sc), "+v"(R1.sc), "+v"(R2.sc));
-    };
-    drain();
+    Stager::drain(R0, R1, R2);
     using B0 = std::integral_constant<int, 0>; using B1 = std::integral_constant<int, 1>; using B2 = std::integral_constant<int, 2>;
     // register set of a stage: that of the image it splits, it + 2 (set (it + 2) % 3)
     for (; it < nhot; it += 3) {
@@ -912,57 +949,18 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
         stage(it + 1, R0, std::true_type{}, B1{});
         stage(it + 2, R1, std::true_type{}, B2{});
     }
-    drain();
+    Stager::drain(R0, R1, R2);
     for (; it < nit; it += 3) {
         stage(it, R2, std::false_type{}, B0{});
         if (it + 1 < nit) stage(it + 1, R0, std::false_type{}, B1{});
         if (it + 2 < nit) stage(it + 2, R1, std::false_type{}, B2{});
     }
-#if DUDF_WGRAD_DBG & 32
-    if (bx == 3 && by == 10 && lane == 0)
-        for (int i = 0; i < 12; ++i) g_wstamp[wave][i] = wst[i];
-#endif
 
-    float* dW = a.dtheta + a.off_hid + (int64_t)j * a.hid_stride + (int64_t)o_off * a.Hs + i_off;
-    float* dB = a.dtheta + a.off_hid + (int64_t)j * a.hid_stride + (int64_t)a.Hs * a.Hs + o_off;
+    float* dW = t.dW(a);
+    float* dB = t.dB(a);
     if (nit > 0) {
-        const int l32 = lane & 31, hh = lane >> 5;
-#pragma unroll
-        for (int m = 0; m < W::MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int o = (wo * W::MT + m) * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-#pragma unroll
-                for (int n = 0; n < W::NTL; ++n) {
-                    const int i = (wi * W::NTL + n) * 32 + l32;
-#if DUDF_WGRAD_DBG & 64
-                    asm volatile("" :: "v"(acc[m][n][e]));               // timing experiment: no output atomics
-#else
-                    atomicAdd(dW + (int64_t)o * a.Hs + i, SP != 0 ? acc[m][n][e] * inv_p : acc[m][n][e]);
-#endif
-                }
-            }
-        if (p_oper == 0 && i_off == 0) {                          // bias gradient: sum the four column groups of a quad first
-            if constexpr (P24 != 0) {                             // ... P24: the 16 columns (lanes li) of features 16 (4 pw + t) + 4 q + e
-                const float bun = P24 == 1 ? 1.0f / sc1 : 1.0f;          // P24 = 1: the sums ran in zbar's layer scale (a power of two)
-                auto red = [&](float v, int f) {
-                    v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
-                    if (p_li == 0) atomicAdd(dB + f, v * bun);
-                };
-                const f32x4 bs[4] = {bacc, bacc1, bacc2, bacc3};
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) red(bs[t][e], 16 * (4 * pw + t) + 4 * p_q + e);
-            } else {
-            auto red = [&](float v, int f) {
-                v += __shfl_xor(v, 1);
-                v += __shfl_xor(v, 2);
-                if (p_cg == 0) atomicAdd(dB + 4 * p_fq + f, v);
-            };
-            red(bacc.x, 0); red(bacc.y, 1); red(bacc.z, 2); red(bacc.w, 3);
-            }
-        }
+        wg_add_tile<H>(a, dW, wo, wi, acc, inv_p);           // (bf16x6: inv_p is the literal 1)
+        st.flush_bias(dB);
     }
     if (clk_on && tid == 0) {
         a.clk[0] = __builtin_amdgcn_s_memtime() - clk_t0;
@@ -970,28 +968,20 @@ __device__ __forceinline__ void wgrad_hidden_bf16p_body(const WgradArgs& a) {
     }
 }
 // built without packed fp32 instructions (dudf_internal.h, DUDF_NO_PK): the split slices of one wave then execute beside its
-// SIMD partner's MFMAs (-5 % on this kernel).  The body is a forced-inline function: lambdas defined inside a function
-// that carries the target attribute do not inherit it and would not be inlined.
+// SIMD partner's MFMAs (-5 % on this kernel).  The pipeline and the stagers' members are forced-inline functions: lambdas
+// defined inside a function that carries the target attribute do not inherit it and would not be inlined.
 // VAR in the kernels' names (profiles, DESIGN.md and the tests know them by it): 9 = three image buffers, 25 = four.
 template <int VAR> constexpr int wg_buffers() { static_assert(VAR == 9 || VAR == 25, "VAR 9: three image buffers, 25: four"); return VAR == 25 ? 4 : 3; }
 template <int H, int VAR>
-__global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_bf16p_kernel(WgradArgs a) {
-    wgrad_hidden_bf16p_body<H, wg_buffers<VAR>()>(a);
-}
+__global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_bf16p_kernel(WgradArgs a) { wgrad_pipeline<H, wg_buffers<VAR>(), 0, RowStager<0>>(a); }
 template <int H, int VAR>
-__global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_f16p_kernel(WgradArgs a) {
-    wgrad_hidden_bf16p_body<H, wg_buffers<VAR>(), 1>(a);
-}
-// ... the fp32 rows staged 4 rows x 256 bytes per wave-instruction, [column][feature] image, transposed fragment reads
+__global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_f16p_kernel(WgradArgs a) { wgrad_pipeline<H, wg_buffers<VAR>(), 1, RowStager<1>>(a); }
+// ... the fp32 rows staged 4 rows x 256 bytes per wave-instruction
 template <int H, int VAR>
-__global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_f16tr_kernel(WgradArgs a) {
-    wgrad_hidden_bf16p_body<H, wg_buffers<VAR>(), 1, 2>(a);
-}
+__global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_f16tr_kernel(WgradArgs a) { wgrad_pipeline<H, wg_buffers<VAR>(), 1, TileStager<false>>(a); }
 // ... reading 24-bit tile-major operands (dudf_internal.h "p24")
 template <int H, int VAR>
-__global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_f16p24_kernel(WgradArgs a) {
-    wgrad_hidden_bf16p_body<H, wg_buffers<VAR>(), 1, 1>(a);
-}
+__global__ __launch_bounds__(64 * WG<H>::WO * WG<H>::WI) DUDF_NO_PK void wgrad_hidden_f16p24_kernel(WgradArgs a) { wgrad_pipeline<H, wg_buffers<VAR>(), 1, TileStager<true>>(a); }
 
 // ---- first and last layer: thin reductions over columns (bandwidth-bound, VALU) -------------------------
 //   dW_1[o][d] | db_1[o] = sum_c  q_1[o][c] * gbar[c][d]  +  zbar_1[o][c] * x4[c][d]      (d = 3 is the bias: x4[c][3])
@@ -1082,6 +1072,8 @@ __global__ __launch_bounds__(256) DUDF_NO_PK void wgrad_small_kernel(WgradSmallA
 __device__ __forceinline__ f32x4 small_unpack24(const unsigned* g, const float sc) {
     typedef unsigned u3_t __attribute__((ext_vector_type(3)));
     const u3_t d = __builtin_nontemporal_load(reinterpret_cast<const u3_t*>(g));
+    // (the decode of fx24_patterns, dudf_internal.h, written out: through the shared helper this kernel — 223 registers and a
+    //  64-byte spill slot — comes out with another instruction order and measured 0.5 us slower)
     const unsigned d0 = d.x, d1 = d.y, d2 = d.z;
     const unsigned m = 0x00ffffffu, two = 0x40000000u;
     const unsigned y = __builtin_amdgcn_perm(d1, d0, 0x0c0c0703u);
@@ -1210,14 +1202,13 @@ int dudf_launch_wgrad(const DudfLayout& lo, float* ws, float* dtheta, int have_g
     a.amax = reinterpret_cast<const unsigned*>(ws + lo.ws_amax);
     a.clk = dudf_prof_clk(PROF_WGRAD_HIDDEN);
     a.remap_nsplit = 0;
-    a.p24 = lo.p24 & 1;
     a.fxS = ws + lo.ws_fx[0]; a.fxQ = ws + lo.ws_fx[1]; a.fxA = ws + lo.ws_fx[2]; a.fxZ = ws + lo.ws_fx[3];
     const int hb = layer_begin < 1 ? 1 : layer_begin, he = layer_end > lo.L ? lo.L : layer_end;   // hidden matrices asked for
     a.j0 = hb - 1; a.nj = he > hb ? he - hb : 0;
     int rc = 0;
     if (a.nj > 0) {
         DudfProfScope prof(PROF_WGRAD_HIDDEN, st);
-        const SweepChoice c = dudf_choose_wgrad(WgradRequest{lo.H, lo.L, a.p24, lo.np}, dudf_options());
+        const SweepChoice c = dudf_choose_wgrad(WgradRequest{lo.H, lo.L, lo.p24 & 1, lo.np}, dudf_options());
         if (c.status) return c.status;
         dudf_note_products(PROF_WGRAD_HIDDEN, c.products);
         switch (c.H) {

@@ -119,6 +119,8 @@ def analyse_wgrad_presplit(asm_path, var=0, kernel="p"):
         m = re.search(r"^(_ZN\w*wgrad_hidden_f16p_kernelILi256ELi%dE\w*):" % var, txt, re.M)
     elif kernel == "f16p24":   # ... reading 24-bit tile-major operands: dwordx3 staging loads
         m = re.search(r"^(_ZN\w*wgrad_hidden_f16p24_kernelILi256ELi%dE\w*):" % var, txt, re.M)
+    elif kernel == "f16tr":    # ... reading the fp32 rows through the [column][feature] image: dwordx4 staging loads, transposed fragment reads
+        m = re.search(r"^(_ZN\w*wgrad_hidden_f16tr_kernelILi256ELi%dE\w*):" % var, txt, re.M)
     elif kernel == "q":        # the fragment-prefetching kernel: two register sets (8 loads) per pass of its two-stage loop
         m = re.search(r"^(_ZN\w*wgrad_hidden_bf16q_kernelILi256E\w*):", txt, re.M)
     else:

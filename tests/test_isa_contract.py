@@ -164,6 +164,9 @@ def test_wgrad_register_staging_contract(tmp_path):
     for var in (25, 9):                                   # 25 = the default (four image buffers), 9 = option wgrad_buffers = 3
         res = analyse_wgrad_presplit(asm, var, "f16p24")
         assert res["loads"] == 15 and res["carried"] == 15 and not res["bad"] and res["scratch"] == 0, (var, res)
+    # ... and of the build that stages the fp32 rows through the same [column][feature] image (option wgrad_tr): 4 loads per set
+    res = analyse_wgrad_presplit(asm, 9, "f16tr")
+    assert res["loads"] == 12 and res["carried"] == 12 and not res["bad"] and res["scratch"] == 0, res
     txt = open(asm).read()
     import re
     m = re.search(r"^(_ZN\w*wgrad_hidden_f16p24_kernelILi256ELi25E\w*):", txt, re.M)

@@ -1,4 +1,4 @@
-// Check of the LDS image the 24-bit weight-gradient GEMM stages its operands in (dudf_wgrad.hip, P24 build), before the kernel
+// Check of the LDS image the 24-bit weight-gradient GEMM stages its operands in (dudf_wgrad.hip, TileStager), before the kernel
 // itself is built around it:
 //   * producer lane (q = lane >> 4, li = lane & 15) of wave pw holds, for tiles T = 4 pw + t, the 4 features 16 T + 4 q + e of
 //     column li of a 16-column stage and writes them as 4 fp16 = 8 bytes (ds_write_b64) into  image[k = li][feature]  with

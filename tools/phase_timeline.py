@@ -40,28 +40,3 @@ for s in range(4 if have_sweeps else 0):
             print("  kb %d wave %d: top %6d feed %6d | tail %6d..%6d | mfma issued %6d | wait done %6d | mid feed %6d..%6d" % (kb, w, *st))
     step = (int(buf[s, 0, 7, 0]) - t0) * 10 / 7.0
     print("  mean step %.0f cycles" % (step / 10))
-
-# weight-gradient kernel (library built with -DDUDF_WGRAD_DBG=32): last steady-state stage of one workgroup
-if hasattr(lib, "dudf_dbg_wstamps") or True:
-    try:
-        fnw = lib.dudf_dbg_wstamps
-        fnw.argtypes = [ctypes.c_void_p]
-        wb = np.zeros((8, 12), dtype=np.uint64)
-        assert fnw(wb.ctypes.data_as(ctypes.c_void_p)) == 0
-        t0 = int(wb[:, 0].min())
-        print("== wgrad_hidden, one stage (cycles): 0 start | 1 A frags issued (past the first poll) | 3 5 7 9 MFMA groups issued | 2 reads published | 4 buffer free | 6 loads landed | 8 split written | 10 loads issued, image published")
-        for w in range(8):
-            print("  wave %d: " % w + " ".join("%d:%6d" % (i, int(wb[w][i]) - t0) for i in (0, 1, 3, 5, 7, 9, 2, 4, 6, 8, 10)))
-    except AttributeError:
-        pass
-
-# sixteen-wave experiment (DUDF_WGRAD_W16=1, -DDUDF_WGRAD_DBG=32): stage 40 of one workgroup, six stamps per wave
-if os.environ.get("DUDF_WGRAD_W16") == "1":
-    fnw = lib.dudf_dbg_wstamps
-    fnw.argtypes = [ctypes.c_void_p]
-    wb = np.zeros(96, dtype=np.uint64)
-    assert fnw(wb.ctypes.data_as(ctypes.c_void_p)) == 0
-    wb = wb.reshape(16, 6); t0 = int(wb[:, 0].min())
-    print("== W16 stage: start | fetch (+ MFMAs if first) | raw landed | split + DMA issued | MFMAs (if second) | barrier passed")
-    for w in range(16):
-        print("  wave %2d (simd %d, %s): " % (w, w % 4, "M first" if (w >> 2) & 1 else "S first") + " ".join("%6d" % (int(v) - t0) for v in wb[w]))
