@@ -81,6 +81,10 @@ SYMBOLS = {
     "dudf_orient_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
     "dudf_orient_normals": (ctypes.c_int, [_P, _P, _P, ctypes.c_int64, ctypes.c_int, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_int64), _P,
                                            ctypes.c_size_t, _P]),
+    "dudf_estimate_normals_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "dudf_estimate_normals": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_cloud_outliers_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "dudf_cloud_outliers": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "dudf_mesh_index_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "dudf_mesh_morton_codes": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_size_t, _P, _P]),
     "dudf_mesh_index_build": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),

@@ -67,7 +67,8 @@ class PointCloud:
     produced on the GPU by `dudf_sample_batch` and yielded as DEVICE tensors (the loop's `.to(device)` is then a
     no-op), ordered [on | far | near] exactly like the reference.  `rank`/`world` shard each stratum.
     `onlyPCloud=True` (point-cloud input, reference :80-131): only `<prefix>_pc.ply` (or the in-memory cloud) is used;
-    far distances go to the nearest cloud point and near distances are |offset|."""
+    far distances go to the nearest cloud point and near distances are |offset|.  A `_pc.ply` without normals (a raw scan) gets
+    them estimated and oriented once at load (`metrics.estimate_normals`)."""
 
     def __init__(self, meshPath, batchSize, samplingPercentiles, batchesPerEpoch, device=None, onlyPCloud=False,
                  seed=123, rank=0, world=1, surfacePoints=100000):
@@ -77,7 +78,7 @@ class PointCloud:
         self.device = torch.device("cuda", 0) if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise _lib.DudfError("PointCloud: the sampler runs on the GPU; there is no CPU fallback path")
-        tri, pos, nrm = mesh.prepare(meshPath, surfacePoints, seed, cloud_only=self.onlyPCloud)
+        tri, pos, nrm = mesh.prepare(meshPath, surfacePoints, seed, cloud_only=self.onlyPCloud, device=self.device)
         self.tri = None if self.onlyPCloud else torch.from_numpy(tri).to(self.device)
         self.pc_pos = torch.from_numpy(pos).to(self.device)
         self.pc_nrm = torch.from_numpy(nrm).to(self.device)

@@ -955,6 +955,50 @@ def orient_normals(points, normals, knn_idx, out=None):
     return out, flip, comp, counts, {"rounds": int(stats[0]), "launches": int(stats[1])}
 
 
+# ---- raw scans: estimated normals and the statistical outlier test (open3d's stand-ins; csrc/dudf_cloudprep.hip) --------------------
+def estimate_normals(points, knn_idx, include_self=True, want_info=False):
+    """Unoriented normals (n,3) float32 of the cloud points (n,3) from the graph knn_idx (n,K) int64 (`knn_points(points, points, K,
+    exclude_self=True)`): the eigenvector of the smallest eigenvalue of the fp64 covariance of every neighbourhood — the point itself
+    with include_self, then its row's slots; fewer than 3 points, coincident points or a non-finite coordinate give (0, 0, 1)
+    (DESIGN.md §3.8).  Returns (normals, eigenvalues (n,3) float64 ascending, counts (n,) int32); the last two are None without
+    want_info.  Byte-reproducible."""
+    points = _tensor(points, "estimate_normals: points", torch.float32, (3,), convert=True)
+    if not torch.is_tensor(knn_idx) or knn_idx.dim() != 2:
+        raise _lib.DudfError("estimate_normals: knn_idx must be an (n, K) tensor")
+    knn_idx = _tensor(knn_idx, "estimate_normals: knn_idx", torch.int64, (knn_idx.shape[1],), convert=True)
+    n, K, dev = points.shape[0], knn_idx.shape[1], points.device
+    if knn_idx.shape[0] != n or knn_idx.device != dev:
+        raise _lib.DudfError("estimate_normals: points and knn_idx must have one row per point and live on one device")
+    out = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    eig = torch.empty(n, 3, dtype=torch.float64, device=dev) if want_info else None
+    cnt = torch.empty(n, dtype=torch.int32, device=dev) if want_info else None
+    ws, nbytes = _workspace(dev, "dudf_estimate_normals_workspace_bytes", n, K, err=-4)
+    _call("dudf_estimate_normals", _ptr(points), _ptr(knn_idx), n, K, int(bool(include_self)), _ptr(out), _ptr(eig), _ptr(cnt), _ptr(ws),
+          nbytes, dev=dev)
+    return out, eig, cnt
+
+
+def cloud_outliers(knn_dist, std_ratio=2.0):
+    """The statistical outlier test on knn_dist (n,K) float32, the squared distances of `knn_points(points, points, K,
+    exclude_self=True)`: (mean_dist (n,) float64 = the mean distance of every row to its finite neighbours, keep (n,) uint8 =
+    mean_dist <= mu + std_ratio * sigma, stats (3,) float64 on the device = mu, sigma, threshold over the finite rows, kept_idx (n,)
+    int64 whose head holds the kept rows in ascending order, counts (1,) int64 on the device = how many) — DESIGN.md §3.8.  Nothing is
+    read back.  Byte-reproducible."""
+    if not torch.is_tensor(knn_dist) or knn_dist.dim() != 2:
+        raise _lib.DudfError("cloud_outliers: knn_dist must be an (n, K) tensor")
+    knn_dist = _tensor(knn_dist, "cloud_outliers: knn_dist", torch.float32, (knn_dist.shape[1],), convert=True)
+    n, K, dev = knn_dist.shape[0], knn_dist.shape[1], knn_dist.device
+    mean = torch.empty(n, dtype=torch.float64, device=dev)
+    keep = torch.empty(n, dtype=torch.uint8, device=dev)
+    stats = torch.full((3,), float("nan"), dtype=torch.float64, device=dev)
+    kept = torch.empty(n, dtype=torch.int64, device=dev)
+    counts = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws, nbytes = _workspace(dev, "dudf_cloud_outliers_workspace_bytes", n, K, err=-4)
+    _call("dudf_cloud_outliers", _ptr(knn_dist), n, K, float(std_ratio), _ptr(mean), _ptr(keep), _ptr(stats), _ptr(kept), _ptr(counts),
+          _ptr(ws), nbytes, dev=dev)
+    return mean, keep, stats, kept, counts
+
+
 # ---- distance to a triangle mesh (reference generate_df.py:108-110, open3d RaycastingScene; csrc/dudf_meshdist.hip) -------------
 MESH_INDEX_FLAGS_OFFSET, MESH_FLAG_NONFINITE, MESH_FLAG_BAD_ORDER = 24, 1, 2       # include/dudf_hip.h
 

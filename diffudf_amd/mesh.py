@@ -85,8 +85,9 @@ def write_ply_points(path, pos, nrm):
         f.write(np.concatenate([pos, nrm], axis=1).astype("<f4").tobytes())
 
 
-def read_ply_points(path):
-    """positions (P,3), normals (P,3) float32 from an ascii or binary_little_endian PLY (float/double props)."""
+def read_ply_points(path, require_normals=True):
+    """positions (P,3), normals (P,3) float32 from an ascii or binary_little_endian PLY (float/double props).  A file without
+    `nx, ny, nz` (a raw scan): DudfError, or (positions, None) with require_normals=False."""
     with open(path, "rb") as f:
         header = []
         while True:
@@ -117,6 +118,11 @@ def read_ply_points(path):
             raw = np.frombuffer(f.read(n * dt.itemsize), dtype=dt, count=n)
             cols = {nm: raw[nm] for nm in names}
     pos = np.stack([cols["x"], cols["y"], cols["z"]], 1).astype(np.float32)
+    if not all(c in cols for c in ("nx", "ny", "nz")):
+        if require_normals:
+            from ._lib import DudfError
+            raise DudfError(f"{path} has no normals: run preprocess.py -pc, which estimates them")
+        return pos, None
     nrm = np.stack([cols["nx"], cols["ny"], cols["nz"]], 1).astype(np.float32)
     return pos, nrm
 
@@ -131,15 +137,19 @@ def write_obj(path, verts, tris, fmt="%.9g"):
             f.write("f %d %d %d\n" % (t[0] + 1, t[1] + 1, t[2] + 1))
 
 
-def prepare(mesh_prefix, surface_points=100000, seed=123, cloud_only=False):
+def prepare(mesh_prefix, surface_points=100000, seed=123, cloud_only=False, device="cuda:0"):
     """What the sampler needs for `<mesh_prefix>`: (triangle soup (T,9), cloud positions (P,3), cloud normals (P,3)).
 
     Like the reference's PointCloud (src/dataset.py:149-155) it reads `<prefix>_t.obj` and `<prefix>_pc.ply` when
     they exist (files written by the reference's preprocess.py work); otherwise it does that preprocessing
     itself, in memory, from `<prefix>.obj`.  cloud_only (reference :157-159): a `<prefix>_pc.ply` alone is enough and
-    no triangles are returned."""
+    no triangles are returned; one without normals (a raw scan) gets them estimated once, on `device`."""
     if cloud_only and os.path.exists(mesh_prefix + "_pc.ply"):
-        pos, nrm = read_ply_points(mesh_prefix + "_pc.ply")
+        pos, nrm = read_ply_points(mesh_prefix + "_pc.ply", require_normals=False)
+        if nrm is None:                              # imported here: the rest of this module is host numpy and imports without a GPU
+            import torch
+            from . import metrics
+            nrm = metrics.estimate_normals(torch.from_numpy(pos).to(device)).cpu().numpy()
         return None, pos, nrm
     t_obj, pc_ply, raw = mesh_prefix + "_t.obj", mesh_prefix + "_pc.ply", mesh_prefix + ".obj"
     if os.path.exists(t_obj):

@@ -7,6 +7,8 @@ there is no CPU path: CPU tensors raise DudfError.
 
 `knn_points` is the K > 1 half of pytorch3d's `knn_points` and `orient_normals` stands in for open3d's
 `orient_normals_consistent_tangent_plane` (reference generate_pc.py:40); both are HIP kernels too (csrc/dudf_orient.hip).
+`estimate_normals` and `remove_statistical_outliers` stand in for open3d's `estimate_normals` and `remove_statistical_outlier`, what
+a raw scan needs before any of the above (csrc/dudf_cloudprep.hip).
 
 `MeshIndex` / `mesh_distance` stand in for `o3d.t.geometry.RaycastingScene().add_triangles(...)` / `.compute_distance(...)`
 (reference generate_df.py:108-110): the exact unsigned distance from points to a triangle mesh through a bounding-volume
@@ -53,6 +55,48 @@ def orient_normals(points, normals, k=10, return_info=False):
         return out
     c = counts.tolist()
     return out, {"flip": flip, "component": comp, "components": int(c[0]), "forest_edges": int(c[1]), **stats}
+
+
+def estimate_normals(points, k=15, orient=True, orient_k=10, return_info=False):
+    """Normals (n,3) float32 for a cloud that has none — open3d's `estimate_normals(KDTreeSearchParamKNN(k))` followed (orient=True)
+    by `orient_normals_consistent_tangent_plane(orient_k)`: per point the direction of least variance of itself and its k nearest
+    neighbours (fp64 covariance), then consistent signs.  ONE k-nearest search serves both steps when orient_k <= k:
+    rows come nearest first, so the first orient_k columns are the orient_k-NN graph.  With return_info also a dict: eigenvalues
+    (n,3) float64 ascending, counts (n,) int32 (neighbourhood sizes), and under "orient" the info dict of `orient_normals`."""
+    points = hip_ops._tensor(points, "estimate_normals: points", torch.float32, (3,), convert=True)
+    k, orient_k = int(k), int(orient_k)
+    _, idx = hip_ops.knn_points(points, points, k, exclude_self=True, want_dist=False)
+    normals, eig, cnt = hip_ops.estimate_normals(points, idx, include_self=True, want_info=return_info)
+    info = {"eigenvalues": eig, "counts": cnt, "orient": None}
+    if orient and points.shape[0] > 0:
+        if orient_k <= k:
+            oidx = idx[:, :orient_k].contiguous()
+        else:
+            _, oidx = hip_ops.knn_points(points, points, orient_k, exclude_self=True, want_dist=False)
+        normals, flip, comp, counts, stats = hip_ops.orient_normals(points, normals, oidx, out=normals)
+        if return_info:
+            c = counts.tolist()
+            info["orient"] = {"flip": flip, "component": comp, "components": int(c[0]), "forest_edges": int(c[1]), **stats}
+    return (normals, info) if return_info else normals
+
+
+def remove_statistical_outliers(points, nb_neighbors=16, std_ratio=2.0):
+    """(kept_points (m,3), kept_index (m,) int64, info) — open3d's `remove_statistical_outlier(nb_neighbors, std_ratio)`: a point goes
+    when its mean distance to its nb_neighbors nearest neighbours exceeds the cloud's mean of that quantity by more than std_ratio
+    standard deviations.  info: mean, std, threshold (floats), removed (int), mean_dist (n,) float64, keep (n,)
+    uint8.  The search, the statistics and the compaction run on the device; the count and the three statistics are read once."""
+    points = hip_ops._tensor(points, "remove_statistical_outliers: points", torch.float32, (3,), convert=True)
+    n = points.shape[0]
+    if n == 0:
+        return points, torch.empty(0, dtype=torch.int64, device=points.device), {
+            "mean": float("nan"), "std": float("nan"), "threshold": float("nan"), "removed": 0,
+            "mean_dist": torch.empty(0, dtype=torch.float64, device=points.device), "keep": torch.empty(0, dtype=torch.uint8, device=points.device)}
+    dist, _ = hip_ops.knn_points(points, points, int(nb_neighbors), exclude_self=True, want_idx=False)
+    mean_dist, keep, stats, kept, counts = hip_ops.cloud_outliers(dist, std_ratio)
+    m = int(counts.item())
+    s = stats.tolist()
+    kept = kept[:m]
+    return points[kept], kept, {"mean": s[0], "std": s[1], "threshold": s[2], "removed": n - m, "mean_dist": mean_dist, "keep": keep}
 
 
 def _batched(t, what):

@@ -4,7 +4,8 @@
     preprocessMesh(outputPath, meshFile)          -> <name>_t.obj (normalised mesh)  + <name>_pc.ply (area-uniform surface cloud)
     preprocessPointCloud(outputPath, pcFile)      -> <name>_t.ply (normalised cloud) + <name>_pc.ply (subset without replacement)
 
-Host numpy through `diffudf_amd.mesh`; nothing here needs the GPU.  open3d's RNG stream is not reproduced, its distributions
+Host numpy through `diffudf_amd.mesh`; only a raw scan needs the GPU (`preprocessPointCloud` estimates its normals and removes its
+outliers there).  open3d's RNG stream is not reproduced, its distributions
 are: the surface cloud comes from `mesh.sample_surface` (counter-based `synth.uniform01`), the subset from a counter-based
 permutation; both are pure functions of (input, sample count, seed)."""
 import os
@@ -13,6 +14,7 @@ import numpy as np
 
 from . import mesh as dmesh
 from . import synth
+from ._lib import DudfError
 
 
 class TriangleMesh:
@@ -83,15 +85,42 @@ def preprocessMesh(outputPath, meshFile, surfacePoints=1e5, seed=123):
     return M
 
 
-def preprocessPointCloud(outputPath, pcFile, surfacePoints=1e5, seed=123):
+def preprocessPointCloud(outputPath, pcFile, surfacePoints=1e5, seed=123, estimate_normals=None, normals_k=15, remove_outliers=False,
+                         nb_neighbors=16, std_ratio=2.0, device="cuda:0"):
     """Writes <outputPath>/<name>_t.ply (all points) and <name>_pc.ply (`surfacePoints` of them, no repeats; reference :42-66);
-    returns the normalising matrix."""
-    pos, nrm = dmesh.read_ply_points(pcFile)
-    pointcloud = PointCloud(pos, nrm)
-    pointcloud.normalize_normals()
+    returns the normalising matrix.
+
+    A raw scan has no normals and may carry stray points; both steps run on `device` (diffudf_amd.metrics, imported only when asked
+    for: a cloud with normals still needs no GPU).  remove_outliers: the statistical outlier test (nb_neighbors, std_ratio) on the
+    cloud as read.  estimate_normals: None = when the file has none, True = always; normals_k neighbours, on the normalised cloud,
+    oriented consistently.  Order: read, outlier removal, normalise, estimate and orient, subset, write."""
+    pos, nrm = dmesh.read_ply_points(pcFile, require_normals=False)
+    estimate = (nrm is None) if estimate_normals is None else bool(estimate_normals)
+    if nrm is None and not estimate:
+        raise DudfError(f"{pcFile} has no normals and estimate_normals=False: nothing to train on")
+    removed = 0
+    if remove_outliers:
+        import torch
+        from . import metrics
+        _, kept, info = metrics.remove_statistical_outliers(torch.from_numpy(pos).to(device), nb_neighbors, std_ratio)
+        kept, removed = kept.cpu().numpy(), info["removed"]
+        pos, nrm = pos[kept], (None if nrm is None else nrm[kept])
+    pointcloud = PointCloud(pos, np.zeros_like(pos) if estimate else nrm)
+    if not estimate:
+        pointcloud.normalize_normals()
     M = normalizePointCloud(pointcloud)
     pointcloud_name = _name(pcFile)
     print(pointcloud_name)
+    components = None
+    if estimate:                                  # on the float32 positions the files will hold
+        import torch
+        from . import metrics
+        est, info = metrics.estimate_normals(torch.from_numpy(pointcloud.points.astype(np.float32)).to(device), k=normals_k, return_info=True)
+        pointcloud.normals = est.cpu().numpy().astype(np.float64)
+        components = info["orient"]["components"] if info["orient"] else 0
+    if remove_outliers or estimate:
+        print(f"{pointcloud_name}: {removed} outlier(s) removed, " +
+              (f"normals estimated (k={int(normals_k)}), {components} orientation component(s)" if estimate else "normals kept from the file"))
     points, normals = pointcloud.points, pointcloud.normals
     if surfacePoints > len(points):
         raise ValueError(f'Cannot sample more points ({surfacePoints}) than present on the input pointcloud ({len(points)}).')

@@ -82,7 +82,7 @@ def cloud_distances(pc_path, samples, device):
     """Distance of the samples, as fp32, to the nearest point of a PLY cloud: `metrics.nearest_points` in place of the KD-tree of
     reference :205-206.  (S,1) float32."""
     from diffudf_amd import mesh as dmesh, metrics
-    pos, _ = dmesh.read_ply_points(pc_path)
+    pos, _ = dmesh.read_ply_points(pc_path, require_normals=False)
     pts = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.float32)).to(device)
     d2, _ = metrics.nearest_points(pts, torch.from_numpy(pos).to(device), norm=2)
     return torch.sqrt(d2.double()).float().cpu().numpy().reshape(-1, 1)

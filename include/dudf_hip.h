@@ -293,6 +293,41 @@ int dudf_orient_normals(const float* points, const float* normals, const int64_t
                         unsigned char* out_flip, int64_t* out_component, int64_t* out_counts, int64_t* host_stats, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* Raw scans: normals estimated from the k-NN graph and the statistical outlier test — the device side of open3d's
+ * `estimate_normals(KDTreeSearchParamKNN(k))` and `remove_statistical_outlier(nb_neighbors, std_ratio)`, which a cloud without normals
+ * needs before dudf_orient_normals.  csrc/dudf_cloudprep.hip; the rules are DESIGN.md §3.8 (tests/cloudprep_oracle.py restates them in
+ * numpy).  These entry points arrived after ABI 8 without changing any existing signature.
+ *
+ * dudf_estimate_normals — per point the eigenvector of the smallest eigenvalue of its neighbourhood's covariance.  points (n,3) fp32,
+ *   knn_idx (n,K) int64 as dudf_knn_points wrote it.  The neighbourhood of row i is i itself when include_self != 0, then the slots of
+ *   row i in slot order; a slot outside [0, n) or equal to i is skipped and never dereferenced; c is the neighbourhood size.  The mean
+ *   is formed in fp64 (the sum starts at 0.0 and runs in neighbourhood order, then is divided by c), the covariance is the sum of the
+ *   outer products of (p_j - mean) in fp64 in the same order, without contraction, divided by c (lower triangle).  The cyclic Jacobi
+ *   solver of the loss kernels gives ascending eigenvalues; the normal is the first eigenvector, normalised in fp64 and rounded once
+ *   to fp32, with the sign the solver gives (orientation is dudf_orient_normals' job).  c < 3, an all-zero covariance (coincident
+ *   points) or a non-finite coordinate in the neighbourhood: normal (0, 0, 1), eigenvalues 0 (open3d's fallback).
+ *   out_normals (n,3) fp32; out_eigenvalues (n,3) fp64 and out_count (n) int32 = c may be NULL.  Two calls are byte-identical.
+ *   n < 0: DUDF_E_BADCFG; K < 1, K > 16 or n >= 2^31: DUDF_E_UNSUPPORTED; n == 0: nothing is launched, 0; points, knn_idx or
+ *   out_normals NULL with n > 0: DUDF_E_BADCFG; workspace: dudf_estimate_normals_workspace_bytes(n, K) (0 for arguments the call
+ *   refuses; the cloud as 16-byte rows), 256-byte aligned, else DUDF_E_WORKSPACE.  Every check is made before the first device call. */
+size_t dudf_estimate_normals_workspace_bytes(int64_t n, int K);
+int dudf_estimate_normals(const float* points, const int64_t* knn_idx, int64_t n, int K, int include_self, float* out_normals,
+                          double* out_eigenvalues, int* out_count, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dudf_cloud_outliers — the statistical outlier test on knn_dist (n,K) fp32, the SQUARED distances dudf_knn_points wrote.
+ *   out_mean_dist (n) fp64: d_i = the mean over the finite slots of row i of sqrt((double)dist), summed in slot order; a row with no
+ *   finite slot gets +inf, is dropped and stays out of the statistics.  out_stats (device, 3 doubles, may be NULL) = mu, sigma,
+ *   threshold: the population mean and standard deviation of the finite d_i in fp64 — per-workgroup partials added in index order by
+ *   one workgroup, sigma from the centred second pass — and mu + std_ratio * sigma.  out_keep (n) uint8 = d_i <= threshold;
+ *   out_kept_idx (n int64, may be NULL) = the kept rows in ascending order, out_counts (device, 1 int64, may be NULL) = how many: the
+ *   library reads nothing back.  No atomics: two calls are byte-identical.  No finite row: the statistics are NaN and nothing is kept.
+ *   Refusals as dudf_estimate_normals (NULL knn_dist, out_mean_dist or out_keep with n > 0: DUDF_E_BADCFG); workspace:
+ *   dudf_cloud_outliers_workspace_bytes(n, K). */
+size_t dudf_cloud_outliers_workspace_bytes(int64_t n, int K);
+int dudf_cloud_outliers(const float* knn_dist, int64_t n, int K, double std_ratio, double* out_mean_dist, unsigned char* out_keep,
+                        double* out_stats, int64_t* out_kept_idx, int64_t* out_counts, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
 /* Exact unsigned distance from points to a triangle mesh with a bounding-volume hierarchy — the device side of open3d's
  * `RaycastingScene.add_triangles / compute_distance` (reference generate_df.py:108-110).  csrc/dudf_meshdist.hip.  Like the Chamfer
  * entry points these arrived after ABI 8 without changing any existing signature.  tri (n_tri,9) fp32 is the triangle soup
