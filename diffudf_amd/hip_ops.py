@@ -6,6 +6,7 @@ hand-written HIP kernels in diffudf_amd/csrc.  No function in this module has a 
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -719,20 +720,27 @@ def render_orient(hit_rays, frame_v=None, grad=None, mean=None, want_pc=False):
 
 
 def render_percentile_bounds(curvatures, q_low, q_high):
-    """(2,) float32 on the device: `np.percentile(curvatures, q)` for the two q of reference src/render_st.py:111, numpy's default
-    linear interpolation between the two order statistics (its _lerp: float32 difference, float64 weight, rounded to float32 once).
-    torch.sort is the plumbing; nothing goes to the host."""
+    """(2,) float32 on the device: `np.percentile(curvatures, q)` for the two q of reference src/render_st.py:111, bit for bit what
+    numpy 2.x returns for a float32 array and python numbers q (default 'linear' method).  That numpy keeps the array's dtype
+    throughout: q is rounded to float32 and divided by float32(100); the virtual index is float32(k - 1) times that; the weight
+    is the index minus its floor; and its _lerp is a + (b - a) t for t < 0.5, b - (b - a) (1 - t) otherwise, every product,
+    sum and 1 - t rounded to float32.  An index at or past k - 1 takes the largest value, a NaN anywhere gives NaN.  The index
+    and the weight depend on k and q alone and are formed on the host; torch.sort is the plumbing; nothing is read back."""
+    f32 = np.float32
     k = curvatures.numel()
-    s = torch.sort(curvatures.reshape(-1)).values
+    s = torch.sort(curvatures.reshape(-1).float()).values            # NaN sorts last, as in numpy
     out = []
     for q in (q_low, q_high):
-        virtual = (k - 1) * (float(q) / 100.0)
-        lo = min(max(int(virtual // 1), 0), k - 1)
-        hi = min(lo + 1, k - 1)
-        t = virtual - lo
-        a, b = s[lo], s[hi]
-        diff = (b - a).double()
-        out.append((a.double() + diff * t if t < 0.5 else b.double() - diff * (1 - t)).float())
+        virtual = f32(k - 1) * (f32(q) / f32(100))
+        if virtual >= f32(k - 1):
+            r = s[k - 1]
+        else:
+            lo = int(np.floor(virtual))
+            t = virtual - f32(lo)
+            a, b = s[lo], s[lo + 1]
+            diff = b - a
+            r = a + diff * float(t) if t < f32(0.5) else b - diff * float(f32(1) - t)
+        out.append(torch.where(torch.isnan(s[k - 1]), s[k - 1], r))
     return torch.stack(out)
 
 
