@@ -7,7 +7,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# DUDF_LIB: another build of the same library (timing experiments with debug knobs compiled in); default: the in-tree one
+# DUDF_LIB: another build of the same library (the DUDF_FX_CHECK build of tools/build_dbg.sh; a parent build for A/B runs); default: the in-tree one
 LIB_PATH = os.environ.get("DUDF_LIB") or os.path.join(_HERE, "libdudf_hip.so")
 
 LOSS_S1, LOSS_S2, LOSS_SIREN = 0, 1, 2

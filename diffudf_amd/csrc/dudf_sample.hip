@@ -20,7 +20,7 @@
 #include "dudf_internal.h"
 
 #include "dudf_rng.h"              // dudf_splitmix64, dudf_uniform01
-#include "dudf_tridist.h"          // tri_dist2, DUDF_SAMPLE_DBG
+#include "dudf_tridist.h"          // tri_dist2
 
 namespace {
 
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void sample_batch_kernel(SampleArgs a) {
         for (int64_t c0 = 0; c0 < a.n_tri; c0 += SPH_CAP) {
             const int cnt = (int)((a.n_tri - c0 < SPH_CAP) ? a.n_tri - c0 : SPH_CAP);
             __syncthreads();
-            for (int e = threadIdx.x; e < cnt && DUDF_SAMPLE_DBG != 3; e += blockDim.x) {
+            for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
                 const float* t = a.tri + (c0 + e) * 9;
                 float v[9];
 #pragma unroll
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256) void sample_batch_kernel(SampleArgs a) {
             __syncthreads();
             // pass 0: bound from the spheres, and who attains it
             float ub0 = 3.0e38f; int arg = 0;
-            if (query && DUDF_SAMPLE_DBG != 4)
+            if (query)
                 for (int t = part; t < cntp; t += QSPLIT * SCAN_U) screen_bound(ts + t, px, py, pz, t, ub0, arg);
 #pragma unroll
             for (int m = 1; m < QSPLIT; m <<= 1) {
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void sample_batch_kernel(SampleArgs a) {
             }
             // pass 1: who can still beat the bound
             int len = 0;
-            if (query && DUDF_SAMPLE_DBG != 2 && DUDF_SAMPLE_DBG != 4)
+            if (query)
                 for (int t0 = part; t0 < cntp; t0 += QSPLIT * SCAN_U) {
                     unsigned m = screen_near(ts + t0, px, py, pz, ub);
                     while (m) {

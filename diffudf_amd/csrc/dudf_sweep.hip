@@ -102,14 +102,19 @@ __device__ __forceinline__ void dma_wait() {
 }
 
 
-// One sweep over one 64-column tile.  `seed` replaces the per-column operand the prologue would read from HBM when
-// the caller already has it in registers (fused step kernel: gbar[q] for SWEEP_ADJ_FWD, ybar for SWEEP_ADJ_REV);
-// `res` returns what the tail produced: y in [0] (SWEEP_FWD, every lane), the a_0 rows in [0..2] (SWEEP_REV, lanes < 16).
+// Two finished accumulator tiles whose elementwise tail has not run yet.  The tail of chunk r-1 is executed in
+// the middle of chunk r's MFMA stream (same basic block), so sin/cos, stash traffic and MFMAs overlap inside
+// one wave instead of serialising at every chunk barrier.
+struct Pending {
+    f32x4 acc0, acc1, o1a, o2a, o3a, o1b, o2b, o3b;
+    int64_t ub0, ub1;
+};
+
+// One sweep over one 64-column tile.
 // `tmax`: running max |.| of what the tails store for the weight-gradient GEMM (dudf_sweep_common.h, amax_row) — here one
 // value for all layers of the sweep (an upper bound per layer is all the fp16x3 GEMM's scale needs).
-template <int H, int SW, int FL, bool SEEDED = false>
-__device__ __forceinline__ void sweep_tile(const SweepArgs& a, const int tile, float* lds, unsigned& gc, float seed,
-                                           f32x4& res, TailTrack& tmax) {
+template <int H, int SW, int FL>
+__device__ __forceinline__ void sweep_tile(const SweepArgs& a, const int tile, float* lds, unsigned& gc, TailTrack& tmax) {
     using G = Geo<H>;
     constexpr int BS = base_of(SW);
     constexpr bool HS = is_hess(SW);
@@ -117,7 +122,7 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, const int tile, f
     const int li = lane & 15, q = lane >> 4;
     const bool isv = !HS || (is_jet(SW) ? li == 0 : (lane & 3) == 0);   // value channel (always, on the plain path)
     const int nhid = a.L - 1;                          // hidden x hidden layers
-    constexpr bool kFwdDir = (BS == SWEEP_FWD || BS == SWEEP_ADJ_FWD);
+    constexpr bool kFwdDir = fwd_dir<SW>();
 
     f32x4 in[G::NT], nxt[G::NT];
     f32x4 stg[G::NSTG];
@@ -129,9 +134,7 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, const int tile, f
                            : a.wt + (int64_t)(nhid - 1 - j) * H * H;
         };
         auto out_layer = [&](int j) -> int { return kFwdDir ? j + 1 : nhid - 1 - j; };
-        auto stash_base = [&](int layer, int T) -> int64_t {                   // wave-uniform
-            return (int64_t)layer * a.stash_layer + (int64_t)(16 * T) * a.np;
-        };
+        auto stash_base = [&](int layer, int T) -> int64_t { return sweep_stash_base<false>(a, layer, T); };
         const unsigned vo = (unsigned)(((int64_t)q * a.np + p) * 16);          // this lane's granule, in bytes
         const LaneOff vl(vo, (is_hess(SW) && !is_jet(SW)) ? (unsigned)(((int64_t)q * a.np + (p >> 2)) * 16) : vo);   // C: one copy per quad
 
@@ -144,10 +147,10 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, const int tile, f
         {
             float b = 0.f, yb = 1.f;
             if constexpr (BS == SWEEP_FWD) b = a.x4[p * 4 + q];                       // (x,1) | (e_k,0): k=3 carries the bias
-            if constexpr (BS == SWEEP_ADJ_FWD) b = SEEDED ? seed : ((q < 3) ? a.gbar[p * 4 + q] : 0.f);   // A_0 = gbar | Hbar columns
-            if constexpr (BS == SWEEP_ADJ_REV) yb = SEEDED ? seed : a.ybar[p];
+            if constexpr (BS == SWEEP_ADJ_FWD) b = (q < 3) ? a.gbar[p * 4 + q] : 0.f;   // A_0 = gbar | Hbar columns
+            if constexpr (BS == SWEEP_ADJ_REV) yb = a.ybar[p];
             if constexpr (SW == SWEEP_REV_H) yb = isv ? 1.f : 0.f;                    // adot_L^k = 0
-            const int l0 = kFwdDir ? 0 : a.L - 1;
+            const int l0 = sweep_in_layer<SW>(a, 0);
 #pragma unroll
             for (int T = 0; T < G::NT; ++T) {
                 const int64_t ub = stash_base(l0, T);
@@ -279,7 +282,6 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, const int tile, f
             part += __shfl_xor(part, 32);
             if (isv) part += a.theta[a.off_bo];         // tangent / jet columns are derivatives: no constant term
             if (q == 0) a.y[p] = part;
-            res[0] = part;
         } else if constexpr (BS == SWEEP_REV) {         // a_0 = W_1^T q_1 (rows 0..2 of a 16-row tile): df/dx | Hessian column
             f32x4 accg = {0, 0, 0, 0};
 #pragma unroll
@@ -289,7 +291,6 @@ __device__ __forceinline__ void sweep_tile(const SweepArgs& a, const int tile, f
                 for (int t = 0; t < 4; ++t) accg = mfma16(w[t], in[T][t], accg);
             }
             if (q == 0) *reinterpret_cast<f32x4*>(a.g + p * 4) = f32x4{accg[0], accg[1], accg[2], 0.f};
-            res = accg;
         }
     }
 }
@@ -298,10 +299,9 @@ template <int H, int SW, int FL>
 __global__ __launch_bounds__(64 * NW, Geo<H>::WPSIMD) void sweep_kernel(SweepArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     unsigned gc = 0;                                   // running chunk counter: LDS buffer parity
-    f32x4 res;
     TailTrack tmax;
     for (int tile = a.tile0 + blockIdx.x; tile < a.tile0 + a.ntiles; tile += gridDim.x)
-        sweep_tile<H, SW, FL>(a, tile, lds, gc, 0.f, res, tmax);
+        sweep_tile<H, SW, FL>(a, tile, lds, gc, tmax);
     if constexpr (amax_row<SW, FL>() >= 0) {            // one bound for every layer of this operand (fp16x3 weight-gradient GEMM)
         __shared__ unsigned s_amax;
         if (threadIdx.x == 0) s_amax = 0u;

@@ -18,8 +18,7 @@
 // conflict-free without padding or swizzle.
 //
 // Everything below sits in the anonymous namespace: each unit gets its own copy, and the kernels keep their names.  That holds
-// for the debug state too: a unit built with DUDF_SWEEP_DBG & 128 carries its own stamps and their reader (build one unit that
-// way, tools/build_dbg.sh), and the DUDF_FX_CHECK counters of dudf_sweep_common.h exist once per unit (dudf_fx_read below).
+// for the debug state too: the DUDF_FX_CHECK counters of dudf_sweep_common.h exist once per unit (dudf_fx_read below).
 #pragma once
 #include "dudf_sweep_common.h"
 #include <type_traits>
@@ -47,7 +46,7 @@ constexpr int TILEB = NWB * 16;                        // columns per workgroup 
 // produced by v_cvt_pk_f16_f32 and honoured by the MFMA — tools/micro/f16_split.hip, profiles/r03_f16_split_facts.txt),
 // products hi*hi + hi*lo + lo*hi; the dropped lo*lo is <= 2^-22 of the product.  Half the matrix-core work, a third less
 // LDS traffic, 2 conversions instead of 3 per value; the price is fp16's range: the weights are scaled per matrix by a power
-// of two (pack kernel), the activations where their size is not known a priori (see `ColScale`).
+// of two (pack kernel), the activations where their size is not known a priori (see `col_scale`).
 template <int H, int SP = 0>
 struct GeoB {
     static constexpr int NPC = SP ? 2 : 3;             // pieces per operand
@@ -62,9 +61,6 @@ struct GeoB {
 
 
 __device__ __forceinline__ f32x4 mfma_b(bf16x8 a, bf16x8 b, f32x4 c) {
-#if DUDF_SWEEP_DBG & 4
-    asm volatile("" : "+v"(c) : "v"(a), "v"(b)); return c;
-#endif
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 // 8 fp32 values (two accumulator tiles' registers of one lane) -> the three bf16x8 pieces of a B / A operand
@@ -80,9 +76,6 @@ __device__ __forceinline__ void split8(const f32x4 e0, const f32x4 e1, u32x4& h,
     }
 }
 __device__ __forceinline__ f32x4 mfma_h(f16x8 a, f16x8 b, f32x4 c) {
-#if DUDF_SWEEP_DBG & 4
-    asm volatile("" : "+v"(c) : "v"(a), "v"(b)); return c;
-#endif
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 // 8 fp32 values -> the two fp16x8 pieces hi = fp16(v), lo = fp16(v - hi) (the caller has scaled v into fp16's range)
@@ -114,9 +107,6 @@ template <int H, int SP = 0>
 __device__ __forceinline__ void dma_issue(const char* __restrict__ chunk, unsigned lds_off, unsigned voff, int wave) {
     using G = GeoB<H, SP>;
     static_assert(G::NDMA == 6 || G::NDMA == 3 || G::NDMA == 4 || G::NDMA == 2, "asm below is written for 2, 3, 4 or 6 pieces per wave");
-#if DUDF_SWEEP_DBG & 8
-    return;
-#endif
     const uint64_t g0 = (uint64_t)(size_t)chunk + (uint64_t)wave * (G::NDMA * G::FRAG);       // wave-uniform
     const unsigned lo32 = __builtin_amdgcn_readfirstlane((unsigned)g0), hi32 = __builtin_amdgcn_readfirstlane((unsigned)(g0 >> 32));
     const uint64_t sbase = ((uint64_t)hi32 << 32) | lo32;
@@ -163,17 +153,22 @@ __device__ __forceinline__ void dma_wait_b() {
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
 }
 
-#if DUDF_SWEEP_DBG & 128
-// phase stamps (timing experiments): [sweep][wave][k-block][stamp] of one workgroup's first pass, layer 3
-__device__ unsigned long long g_stamp[4][8][8][8];
-extern "C" int dudf_dbg_stamps(unsigned long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp), sizeof(g_stamp));
+// fp16x3 column scale, plain columns: what a tail can make of accumulators bounded by amax_true — |q_l| <= w0 max_f |a_l|,
+// |A_l| <= w0 max_f |Q_l|, |zbar_l| <= w0 max_f |hbar_l| + max_f |e_l| (`extra`; the quads' and jets' bounds: set_scale, dudf_sweep_bf16.hip)
+__device__ __forceinline__ float plain_bound(float w0, float amax_true, float extra) { return w0 * amax_true + extra; }
+// One product group: cc[u] += A[u] x B for TP tiles (rows of `af`: their pieces), chains interleaved, smallest terms first —
+// fp16x3 (SP): lo*hi, hi*lo, hi*hi; bf16x6: mm, lh, hl, mh, hm, hh
+template <int SP, int TP, int NPC>
+__device__ __forceinline__ void mma_products(const u32x4 (*af)[NPC], const u32x4* bp, f32x4* cc) {
+    constexpr int kA[6] = {1, SP ? 0 : 2, 0, 1, 0, 0}, kB[6] = {SP ? 0 : 1, SP ? 1 : 0, SP ? 0 : 2, 0, 1, 0};
+#pragma unroll
+    for (int i = 0; i < (SP ? 3 : 6); ++i)
+#pragma unroll
+        for (int u = 0; u < TP; ++u) {
+            if constexpr (SP) cc[u] = mfma_h(as_h(af[u][kA[i]]), as_h(bp[kB[i]]), cc[u]);
+            else cc[u] = mfma_b(as_bf(af[u][kA[i]]), as_bf(bp[kB[i]]), cc[u]);
+        }
 }
-#define DUDF_STAMP(i) do { if (stamp_on && j == 3) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-        if (lane == 0) g_stamp[BS & 3][wave][kb][i] = t_; __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define DUDF_STAMP(i) do { } while (0)
-#endif
 struct TailOps { f32x4 o1a, o2a, o3a, o1b, o2b, o3b, ba, bb; };   // operands of one pair of tiles (+ bias, forward sweeps)
 
 // LDS offset of the per-layer running maxima: behind the three weight buffers — and behind the biases where the fp16x3 forward
@@ -183,8 +178,7 @@ __device__ __forceinline__ unsigned amax_lds_off(const SweepArgs& a) {
     return 3u * GeoB<H, SP>::CHUNKB + ((SP != 0 && base_of(SW) == SWEEP_FWD) ? (unsigned)(a.L * H * sizeof(float)) : 0u);
 }
 
-// Shared by the three tile bodies.  (Their other repeated lambdas — image, in_layer, stash_base, the LaneOff construction — and the
-// drivers' amax / clock code stay per body: as free functions they moved the generated code of 3 to 140 kernels, tools/asm_diff.py.)
+// Shared by the tile bodies, with the lane context of dudf_sweep_common.h.
 __device__ __forceinline__ bool nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
 // fp16x3 column scale from a bound < 2^(E - 126) of the column: sb = 2^(15 - (E - 126)) brings it below 2^15, inv_sb = 1 / sb
 __device__ __forceinline__ void col_scale(float bound, float& sb, float& inv_sb) {
@@ -207,6 +201,46 @@ __device__ __forceinline__ float col_absmax(const f32x4 (&t)[N]) {
     for (int T = 0; T < N; ++T) dudf_track(m, t[T]);
     m = fmaxf(m, __shfl_xor(m, 16));
     return fmaxf(m, __shfl_xor(m, 32));
+}
+
+// ---- output stage (fp32), shared by sweep_tile_b (forward sweeps) and sweep_tile_oct; sweep_tile_b's reverse sweep and sweep_tile_w
+// keep copies, with the measured reason at each ----
+// tile T's post-tail values `e` into the column's y partial sum (forward sweep) or df/dx accumulator (reverse sweep)
+template <int BS, int H>
+__device__ __forceinline__ void out_tile(const SweepArgs& a, int T, int li, int q, const f32x4 e, float& part, f32x4& accg) {
+    if constexpr (BS == SWEEP_FWD) {
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(a.theta + a.off_wo + 16 * T + 4 * q);
+        part += e[0] * wv[0] + e[1] * wv[1] + e[2] * wv[2] + e[3] * wv[3];
+    } else if constexpr (BS == SWEEP_REV) {
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(a.w1t16 + li * H + 16 * T + 4 * q);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) accg = mfma16(wv[t], e[t], accg);
+    }
+}
+__device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7fc00000u); }
+// forward sweep, fixed-point stash: column p's scale in every layer (NaN: the column's output is not finite, see store_fx)
+__device__ __forceinline__ void out_fxs(const SweepArgs& a, int64_t p, float sc) {
+    for (int l = 0; l < a.L; ++l) a.fxs[(int64_t)l * a.np + p] = sc;
+}
+// reverse sweep: df/dx of column p (a poisoned column's cos came back as a finite number: NaN instead)
+template <bool FX>
+__device__ __forceinline__ void out_grad(const SweepArgs& a, int64_t p, f32x4 g, bool poison) {
+    if constexpr (FX) { if (poison) g = f32x4{quiet_nan(), quiet_nan(), quiet_nan(), 0.f}; }
+    *reinterpret_cast<f32x4*>(a.g + p * 4) = f32x4{g[0], g[1], g[2], 0.f};
+}
+// a wave that holds all of its columns' tiles (sweep_tile_b): the lane quarters' sums, b_out, y | df/dx
+template <int BS, bool FX, bool CS>
+__device__ __forceinline__ void out_finish(const SweepArgs& a, int64_t p, int q, bool isv, float part, const f32x4 accg, bool poison) {
+    if constexpr (BS == SWEEP_FWD) {
+        part += __shfl_xor(part, 16);
+        part += __shfl_xor(part, 32);
+        if (isv) part += a.theta[a.off_bo];             // tangent / jet columns are derivatives: no constant term
+        if (q == 0) a.y[p] = part;
+        if constexpr (FX && CS) { if (q == 0 && nonfinite(part)) out_fxs(a, p, quiet_nan()); }
+        else if constexpr (FX) { if (q == 0) out_fxs(a, p, nonfinite(part) ? quiet_nan() : 1.f); }   // plain columns: |sin| <= 1, the scale is 1
+    } else if constexpr (BS == SWEEP_REV) {
+        if (q == 0) out_grad<FX>(a, p, accg, poison);
+    }
 }
 
 #if DUDF_FX_CHECK

@@ -43,8 +43,7 @@ namespace {
 // One pass: the workgroup's waves 0..nact-1 take the 16-column groups g_first.. through a whole sweep.  Waves beyond
 // nact (the last, partial pass of a workgroup's share) only keep the weight stream and the barriers going.
 template <int H, int SW, int FL, int SP = 0, int P24 = 0>
-__device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_first, const int nact, char* lds, unsigned& gc,
-                                             const bool stamp_on = false) {
+__device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_first, const int nact, char* lds, unsigned& gc) {
     using G = GeoB<H, SP>;
     constexpr int NPC = G::NPC;
     static_assert(SP == 0 || SW <= SWEEP_FWD_J, "fp16x3: plain columns, Hessian quads, jets");
@@ -57,18 +56,15 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
     const int li = lane & 15, q = lane >> 4;
     const bool isv = !HS || (is_jet(SW) ? li == 0 : (lane & 3) == 0);   // value channel (always, on the plain path)
     const int nhid = a.L - 1;                          // hidden x hidden layers (>= 1 here)
-    constexpr bool kFwdDir = (BS == SWEEP_FWD || BS == SWEEP_ADJ_FWD);
+    constexpr bool kFwdDir = fwd_dir<SW>();
 
     f32x4 acc[G::NT], prev[G::NT];                     // this layer's accumulators / the previous layer's, tails pending
     const int64_t p = (int64_t)(g_first + wave) * 16 + li;
-    auto image = [&](int j) -> const char* {
-        if constexpr (SP) return kFwdDir ? a.wimg16_f + (size_t)j * G::IMGB : a.wimg16_t + (size_t)(nhid - 1 - j) * G::IMGB;
-        return kFwdDir ? a.wimg_f + (size_t)j * G::IMGB : a.wimg_t + (size_t)(nhid - 1 - j) * G::IMGB;
-    };
+    auto image = [&](int j) -> const char* { return sweep_image<SW, G::IMGB, SP>(a, nhid, j); };
     // fp16x3: the accumulators of matrix j hold 2^k_j (W h); `unscale` = 2^-k_j of the matrix whose outputs wait in `prev`
     // (1 for the first layer, which runs on the fp32 MFMA) — folded into the bias add of the forward tail
     float unscale = 1.f;
-    auto unscale_of = [&](int j) -> float { return a.wsc[kFwdDir ? j : nhid - 1 - j]; };
+    auto unscale_of = [&](int j) -> float { return sweep_unscale<SW>(a, nhid, j); };
     // fp16x3, B operand.  The forward sweep's is h_l = sin(.): |h| <= 1 fits fp16 as it stands (small values keep an absolute
     // error of 2^-25: fp16 subnormals are honoured).  The other sweeps' operands (q_l, A_l, zbar_l) have no a-priori size, so
     // every COLUMN gets its own power of two `sb`, fixed when the previous layer's accumulators are final — before any of
@@ -91,8 +87,11 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
     //   adjoint reverse  value: |E| + w0 |hbar| + w0^2 sum_k |zdot^k| |hdotbar^k|   tangent k: |E| + w0 |hdotbar^k|
     auto set_scale = [&](float amax_true, float extra, float zb) {
         float bound;
-        if constexpr (!HS) { (void)zb; bound = a.w0 * amax_true + extra; }
+        if constexpr (!HS) { (void)zb; bound = plain_bound(a.w0, amax_true, extra); }
         else if constexpr (is_jet(SW)) {
+            // (a second copy of the polynomial of epilogue<SWEEP_FWD_J>, dudf_sweep_common.h — keep the two in step: as ONE function all
+            //  11 jet kernels of the three units changed and 6 of them spill more, up to 1920 bytes of scratch from none: outside the
+            //  per-kernel limit "scratch not larger", tools/asm_diff.py)
             // third-order jets: the tail of a monomial's column multiplies lower-order columns of the same point (epilogue,
             // SWEEP_FWD_J) — the same combination, evaluated on the columns' maxima, bounds it (|sin|, |cos| <= 1)
             const int l0 = lane & 48;
@@ -153,7 +152,7 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
             // (every lane stores — the four lane quarters of a column the same number to the same address: a store under `if (q == 0)`
             //  splits the last k-block step of every layer into several basic blocks, and the reverse sweeps, which had no such
             //  store before, lost 12-18 % to it: profiles/r05_e_ab.txt)
-            if constexpr (kColScale) a.fxs[(int64_t)layer * a.np + p] = poison ? __uint_as_float(0x7fc00000u) : inv_sb * 0x1p15f;
+            if constexpr (kColScale) a.fxs[(int64_t)layer * a.np + p] = poison ? quiet_nan() : inv_sb * 0x1p15f;
         }
     };
     unsigned* lds_amax = reinterpret_cast<unsigned*>(lds + amax_lds_off<H, SW, SP>(a));
@@ -162,16 +161,11 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
         //  weight-gradient GEMM does not read the table — no uniform branch in the layer-switch step either)
         if constexpr (kRow >= 0) { lds_max_wave(lds_amax + (layer < kMaxAmaxLayers ? layer : kMaxAmaxLayers - 1), tmax.t); tmax.t = 0.f; }
     };
-    // layer whose tail feeds matrix j (j == nhid: the last one, feeding the output stage), 0-based
-    auto in_layer = [&](int j) -> int { return kFwdDir ? j : a.L - 1 - j; };
+    auto in_layer = [&](int j) -> int { return sweep_in_layer<SW>(a, j); };
     auto bias_ptr = [&](int layer) -> const float* {   // forward sweep: b_{layer+1}
         return a.b1s + (size_t)layer * H;              // [L][H] biases as packed (row 0 = rho b_1)
     };
-    auto stash_base = [&](int layer, int T) -> int64_t {              // wave-uniform, and told so: SGPR base + lane offset
-        const int64_t v = (int64_t)layer * a.stash_layer + (int64_t)(16 * T) * a.np;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return (int64_t)(((uint64_t)hi << 32) | lo);
-    };
+    auto stash_base = [&](int layer, int T) -> int64_t { return sweep_stash_base(a, layer, T); };
     const unsigned vo = (unsigned)(((int64_t)q * a.np + p) * 16);     // this lane's granule, in bytes
     const LaneOff vl(vo, (is_hess(SW) && !is_jet(SW)) ? (unsigned)(((int64_t)q * a.np + (p >> 2)) * 16) : vo,   // C: one copy per quad
                      P24 ? (unsigned)(((p >> 4) * 64 + lane) * 12) : 0u,                                          // 24-bit tile-major arrays
@@ -354,12 +348,8 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
             const int c = j * G::NKB + kb;
             const char* bpl = lds + gc * G::CHUNKB + lane * 16;
             auto frag = [&](int T, int pc) -> u32x4 {
-#if DUDF_SWEEP_DBG & 32
-                u32x4 z; asm volatile("" : "=v"(z)); return z;
-#endif
                 return *reinterpret_cast<const u32x4*>(bpl + (T * NPC + pc) * G::FRAG);
             };
-            DUDF_STAMP(0);
             if constexpr (!kOneSet) ops_cur = ops_n1;
             pin_ops(ops_cur);
             const bool more = c + 2 < total;
@@ -377,16 +367,13 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
             // MFMAs of the other) twice, and neither tail should wait for anything
             constexpr bool kTailTop = SP != 0 && BS == SWEEP_FWD;
             if (kTailTop && !late && kb + 1 < G::NKB) {
-                DUDF_STAMP(2);
                 f32x4 e0, e1;
                 run_tail(lin, kb + 1, prev[2 * kb + 2], prev[2 * kb + 3], ops_cur, e0, e1);
                 split(e0, e1, nb);
                 if constexpr (kOneSet) load_after_next(ops_cur);
-                DUDF_STAMP(3);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if ((FA < 0 && !late) || (FB < 0 && late)) feed();
-            DUDF_STAMP(1);
             __builtin_amdgcn_sched_barrier(0);
             // A fragments travel two tiles (12 MFMAs, ~190 cycles) ahead of their use: with both waves of a SIMD and the
             // chunk DMA on the LDS, one tile of distance does not cover the read latency
@@ -420,45 +407,21 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
                 f32x4 cc[TP];
 #pragma unroll
                 for (int u = 0; u < TP; ++u) cc[u] = acc[T + u];
-                if constexpr (SP) {                                     // smallest terms first: lo*hi, hi*lo, hi*hi
-#pragma unroll
-                    for (int u = 0; u < TP; ++u) cc[u] = mfma_h(as_h(af[u][1]), as_h(bp[0]), cc[u]);
-#pragma unroll
-                    for (int u = 0; u < TP; ++u) cc[u] = mfma_h(as_h(af[u][0]), as_h(bp[1]), cc[u]);
-#pragma unroll
-                    for (int u = 0; u < TP; ++u) cc[u] = mfma_h(as_h(af[u][0]), as_h(bp[0]), cc[u]);
-                } else {
-#pragma unroll
-                    for (int u = 0; u < TP; ++u) cc[u] = mfma_b(as_bf(af[u][1]), as_bf(bp[1]), cc[u]);   // smallest terms first
-#pragma unroll
-                    for (int u = 0; u < TP; ++u) cc[u] = mfma_b(as_bf(af[u][2]), as_bf(bp[0]), cc[u]);
-#pragma unroll
-                    for (int u = 0; u < TP; ++u) cc[u] = mfma_b(as_bf(af[u][0]), as_bf(bp[2]), cc[u]);
-#pragma unroll
-                    for (int u = 0; u < TP; ++u) cc[u] = mfma_b(as_bf(af[u][1]), as_bf(bp[0]), cc[u]);
-#pragma unroll
-                    for (int u = 0; u < TP; ++u) cc[u] = mfma_b(as_bf(af[u][0]), as_bf(bp[1]), cc[u]);
-#pragma unroll
-                    for (int u = 0; u < TP; ++u) cc[u] = mfma_b(as_bf(af[u][0]), as_bf(bp[0]), cc[u]);
-                }
+                mma_products<SP, TP, NPC>(af, bp, cc);
 #pragma unroll
                 for (int u = 0; u < TP; ++u) acc[T + u] = cc[u];
                 const int Tl = T + TP - 1;                              // last tile of this trip
                 if ((FA >= T && FA <= Tl && !late) || (FB >= T && FB <= Tl && late)) {   // the late half issues its DMA pieces (60-180 cycles
                     __builtin_amdgcn_sched_barrier(0);                  // of issue each) under the other half's MFMAs
-                    DUDF_STAMP(6);
                     feed();
-                    DUDF_STAMP(7);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if (kb + 1 < G::NKB && ((TA >= T && TA <= Tl && !late && !kTailTop) || (TB >= T && TB <= Tl && late))) {   // the next step's B operand
                     if (T != 0) __builtin_amdgcn_sched_barrier(0);
-                    DUDF_STAMP(2);
                     f32x4 e0, e1;
                     run_tail(lin, kb + 1, prev[2 * kb + 2], prev[2 * kb + 3], ops_cur, e0, e1);
                     split(e0, e1, nb);
                     if constexpr (kOneSet) load_after_next(ops_cur);
-                    DUDF_STAMP(3);
                 }
             }
             if (kb + 1 == G::NKB) {                                     // layer done: first tail of the next one
@@ -485,18 +448,12 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
 #pragma unroll
             for (int pc = 0; pc < NPC; ++pc) bp[pc] = nb[pc];
             gc = (gc + 1) % 3;
-            DUDF_STAMP(4);
-#if !(DUDF_SWEEP_DBG & 8)
             // chunk c+1 landed; c+2 and two steps' stash traffic stay in flight.  Only the waves that issued DMA pieces wait
             // (0-3: the barrier behind publishes the chunk to the others)
             // (tail at the top of the step: its stores are OLDER than this step's pieces — one step of stash traffic less)
             if (more) { if (wave < NWB / 2) dma_wait_b<(kTailTop ? 1 : 2) * kYoung + 2 * G::NDMA>(); }
             else dma_wait_b<0>();
-#endif
-            DUDF_STAMP(5);
-#if !(DUDF_SWEEP_DBG & 16)
             __syncthreads();
-#endif
         }
     }
 
@@ -516,40 +473,26 @@ __device__ __forceinline__ void sweep_tile_b(const SweepArgs& a, const int g_fir
                 run_tail(lin, kb, prev[2 * kb], prev[2 * kb + 1], ops_cur, e0, e1);
                 if constexpr (kOneSet) { if (kb + 1 < G::NKB) load_ops(lin, kb + 1, ops_cur); }
             }
-            if constexpr (BS == SWEEP_FWD) {
-                const f32x4 w0v = *reinterpret_cast<const f32x4*>(a.theta + a.off_wo + 32 * kb + 4 * q);
-                const f32x4 w1v = *reinterpret_cast<const f32x4*>(a.theta + a.off_wo + 32 * kb + 16 + 4 * q);
-                part += e0[0] * w0v[0] + e0[1] * w0v[1] + e0[2] * w0v[2] + e0[3] * w0v[3];
-                part += e1[0] * w1v[0] + e1[1] * w1v[1] + e1[2] * w1v[2] + e1[3] * w1v[3];
-            } else if constexpr (BS == SWEEP_REV) {
+            if constexpr (BS == SWEEP_REV) {
+                // (own copy of out_tile / out_grad, dudf_sweep16.h: through them the default step's reverse sweep took 0.5060 ms (median of
+                //  three) against the parent's 0.5036 + 0.0006 of spread, MI355X, profiles/HISTORY.md)
                 const f32x4 w0v = *reinterpret_cast<const f32x4*>(a.w1t16 + li * H + 32 * kb + 4 * q);
                 const f32x4 w1v = *reinterpret_cast<const f32x4*>(a.w1t16 + li * H + 32 * kb + 16 + 4 * q);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) accg = mfma16(w0v[t], e0[t], accg);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) accg = mfma16(w1v[t], e1[t], accg);
+            } else {
+                out_tile<BS, H>(a, 2 * kb, li, q, e0, part, accg);
+                out_tile<BS, H>(a, 2 * kb + 1, li, q, e1, part, accg);
             }
         }
         publish(lin);
         store_ebound(lin);
-        if constexpr (BS == SWEEP_FWD) {
-            part += __shfl_xor(part, 16);
-            part += __shfl_xor(part, 32);
-            if (isv) part += a.theta[a.off_bo];         // tangent columns are derivatives: no constant term
-            if (q == 0) a.y[p] = part;
-            if constexpr (kFx) {                        // a column whose output is not finite: its h_l scales become NaN (store_fx)
-                if constexpr (kColScale) {
-                    if (q == 0 && nonfinite(part))
-                        for (int l = 0; l < a.L; ++l) a.fxs[(int64_t)l * a.np + p] = __uint_as_float(0x7fc00000u);
-                } else if (q == 0) {                    // plain columns: |sin| <= 1, the scale is 1 in every layer
-                    const float sc = nonfinite(part) ? __uint_as_float(0x7fc00000u) : 1.f;
-                    for (int l = 0; l < a.L; ++l) a.fxs[(int64_t)l * a.np + p] = sc;
-                }
-            }
-        } else if constexpr (BS == SWEEP_REV) {
-            if constexpr (kFx) { if (poison) accg = f32x4{__uint_as_float(0x7fc00000u), __uint_as_float(0x7fc00000u), __uint_as_float(0x7fc00000u), 0.f}; }   // df/dx of a poisoned column (its cos came back as a finite number)
+        if constexpr (BS == SWEEP_REV) {
+            if constexpr (kFx) { if (poison) accg = f32x4{quiet_nan(), quiet_nan(), quiet_nan(), 0.f}; }   // df/dx of a poisoned column (its cos came back as a finite number)
             if (q == 0) *reinterpret_cast<f32x4*>(a.g + p * 4) = f32x4{accg[0], accg[1], accg[2], 0.f};
-        }
+        } else out_finish<BS, kFx, kColScale>(a, p, q, isv, part, accg, poison);
     }
 }
 
@@ -575,22 +518,16 @@ __device__ __forceinline__ void sweep_tile_oct(const SweepArgs& a, const int g, 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, q = lane >> 4;
     const int nhid = a.L - 1;
-    constexpr bool kFwdDir = (BS == SWEEP_FWD || BS == SWEEP_ADJ_FWD);
+    constexpr bool kFwdDir = fwd_dir<SW>();
     constexpr bool kColScale = BS != SWEEP_FWD;
     constexpr bool kTrackE = BS == SWEEP_ADJ_FWD;
     constexpr int kRow = amax_row<SW, FL>();
     const int64_t p = (int64_t)g * 16 + li;
     const int T0 = 2 * wave;
-    auto image = [&](int j) -> const char* {
-        return kFwdDir ? a.wimg16_f + (size_t)j * G::IMGB : a.wimg16_t + (size_t)(nhid - 1 - j) * G::IMGB;
-    };
-    auto unscale_of = [&](int j) -> float { return a.wsc[kFwdDir ? j : nhid - 1 - j]; };
-    auto in_layer = [&](int j) -> int { return kFwdDir ? j : a.L - 1 - j; };
-    auto stash_base = [&](int layer, int T) -> int64_t {
-        const int64_t v = (int64_t)layer * a.stash_layer + (int64_t)(16 * T) * a.np;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return (int64_t)(((uint64_t)hi << 32) | lo);
-    };
+    auto image = [&](int j) -> const char* { return sweep_image<SW, G::IMGB, 1>(a, nhid, j); };
+    auto unscale_of = [&](int j) -> float { return sweep_unscale<SW>(a, nhid, j); };
+    auto in_layer = [&](int j) -> int { return sweep_in_layer<SW>(a, j); };
+    auto stash_base = [&](int layer, int T) -> int64_t { return sweep_stash_base(a, layer, T); };
     const LaneOff vo((unsigned)(((int64_t)q * a.np + p) * 16), (unsigned)(((int64_t)q * a.np + p) * 16),
                      P24 ? (unsigned)(((p >> 4) * 64 + lane) * 12) : 0u);
     char* ox = lds + oct_off;
@@ -655,11 +592,11 @@ __device__ __forceinline__ void sweep_tile_oct(const SweepArgs& a, const int g, 
             float mm = 0.f;
 #pragma unroll
             for (int w = 0; w < NWB; ++w) mm = fmaxf(mm, cmx[w * 16 + li]);
-            col_scale((a.w0 * (mm * unscale) + eb) * DUDF_FX_HEADROOM, sb, inv_sb);   // (2^-10 of head room: see set_scale)
+            col_scale(plain_bound(a.w0, mm * unscale, eb) * DUDF_FX_HEADROOM, sb, inv_sb);   // (2^-10 of head room: see set_scale)
         }
         if constexpr (kFx) {                            // fixed-point stash: this layer's column scale for the readers
             if constexpr (kColScale) tk.fs = sb * 0x1p-15f;
-            if (wave == 0 && q == 0) a.fxs[(int64_t)lin * a.np + p] = poison ? __uint_as_float(0x7fc00000u) : (kColScale ? inv_sb * 0x1p15f : 1.f);
+            if (wave == 0 && q == 0) a.fxs[(int64_t)lin * a.np + p] = poison ? quiet_nan() : (kColScale ? inv_sb * 0x1p15f : 1.f);
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {                   // ONE tail pair per wave and layer
@@ -707,28 +644,20 @@ __device__ __forceinline__ void sweep_tile_oct(const SweepArgs& a, const int g, 
         acc[0] = f32x4{0, 0, 0, 0}; acc[1] = acc[0];
 #pragma unroll
         for (int kb = 0; kb < G::NKB; ++kb) {
-            const u32x4 b0 = Bx[(kb * NPC + 0) * 64 + lane], b1 = Bx[(kb * NPC + 1) * 64 + lane];
+            const u32x4 bx[NPC] = {Bx[(kb * NPC + 0) * 64 + lane], Bx[(kb * NPC + 1) * 64 + lane]};
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                f32x4 cc = acc[u];
-                cc = mfma_h(as_h(fr[kb][u][1]), as_h(b0), cc);    // smallest terms first: lo*hi, hi*lo, hi*hi
-                cc = mfma_h(as_h(fr[kb][u][0]), as_h(b1), cc);
-                cc = mfma_h(as_h(fr[kb][u][0]), as_h(b0), cc);
-                acc[u] = cc;
-            }
+            for (int u = 0; u < 2; ++u) mma_products<1, 1, NPC>(&fr[kb][u], bx, &acc[u]);
         }
         __syncthreads();                                // every wave has read B: the next layer may overwrite it
         prev[0] = acc[0]; prev[1] = acc[1];
         unscale = kColScale ? unscale_of(j) * inv_sb : unscale_of(j);
     }
     // output stage: the eight waves' partial results through LDS
-    if constexpr (BS == SWEEP_FWD) {
-        float part = 0.f;
+    float part = 0.f;
+    f32x4 accg = {0, 0, 0, 0};
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const f32x4 wv = *reinterpret_cast<const f32x4*>(a.theta + a.off_wo + 16 * (T0 + u) + 4 * q);
-            part += e[u][0] * wv[0] + e[u][1] * wv[1] + e[u][2] * wv[2] + e[u][3] * wv[3];
-        }
+    for (int u = 0; u < 2; ++u) out_tile<BS, H>(a, T0 + u, li, q, e[u], part, accg);
+    if constexpr (BS == SWEEP_FWD) {
         part += __shfl_xor(part, 16);
         part += __shfl_xor(part, 32);
         if (q == 0) cmx[wave * 16 + li] = part;
@@ -738,27 +667,16 @@ __device__ __forceinline__ void sweep_tile_oct(const SweepArgs& a, const int g, 
 #pragma unroll
             for (int w = 0; w < NWB; ++w) y += cmx[w * 16 + li];
             a.y[p] = y;
-            if constexpr (kFx) {
-                if (nonfinite(y))
-                    for (int l = 0; l < a.L; ++l) a.fxs[(int64_t)l * a.np + p] = __uint_as_float(0x7fc00000u);
-            }
+            if constexpr (kFx) { if (nonfinite(y)) out_fxs(a, p, quiet_nan()); }
         }
     } else if constexpr (BS == SWEEP_REV) {
-        f32x4 accg = {0, 0, 0, 0};
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const f32x4 wv = *reinterpret_cast<const f32x4*>(a.w1t16 + li * H + 16 * (T0 + u) + 4 * q);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) accg = mfma16(wv[t], e[u][t], accg);
-        }
         red[wave * 64 + lane] = accg;
         __syncthreads();
         if (wave == 0 && q == 0) {
             f32x4 sum = {0, 0, 0, 0};
 #pragma unroll
             for (int w = 0; w < NWB; ++w) sum += red[w * 64 + lane];
-            if constexpr (kFx) { if (poison) sum = f32x4{__uint_as_float(0x7fc00000u), __uint_as_float(0x7fc00000u), __uint_as_float(0x7fc00000u), 0.f}; }
-            *reinterpret_cast<f32x4*>(a.g + p * 4) = f32x4{sum[0], sum[1], sum[2], 0.f};
+            out_grad<kFx>(a, p, sum, poison);
         }
     } else if constexpr (kTrackE) {                     // the last layer's max |e_l|
         __syncthreads();
@@ -773,6 +691,8 @@ __device__ __forceinline__ void sweep_tile_oct(const SweepArgs& a, const int g, 
 
 // (bid, nblk): this workgroup's index among the `nblk` that share the columns of `a` — the whole grid, or one of the two
 // parts of a pair launch (sweep_pair_kernel)
+// (sweep_w_body, dudf_sweep_wide.hip, is the same driver — clock, amax init and flush, shares.  As one function that takes the pass as
+//  a lambda it changed 35 of 35 and 74 of 94 kernels, with more scratch in 11 of them — outside the per-kernel limit: tools/asm_diff.py.)
 template <int H, int SW, int FL, int SP = 0, int P24 = 0>
 __device__ __forceinline__ void sweep_body_b(const SweepArgs& a, const int bid, const int nblk) {
     extern __shared__ __attribute__((aligned(16))) char lds_b[];
@@ -799,7 +719,7 @@ __device__ __forceinline__ void sweep_body_b(const SweepArgs& a, const int bid, 
                 continue;
             }
         }
-        sweep_tile_b<H, SW, FL, SP, P24>(a, gbase + g, (g1 - g < NWB) ? g1 - g : NWB, lds_b, gc, (DUDF_SWEEP_DBG & 128) && bid == 100 && g == g0);
+        sweep_tile_b<H, SW, FL, SP, P24>(a, gbase + g, (g1 - g < NWB) ? g1 - g : NWB, lds_b, gc);
     }
     if constexpr (kRow >= 0) {
         __syncthreads();

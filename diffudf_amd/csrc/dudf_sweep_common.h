@@ -21,9 +21,6 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
 typedef float dudf_f2 __attribute__((ext_vector_type(2)));
 typedef int dudf_i2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void dudf_sincos2(dudf_f2 x, dudf_f2& s_out, dudf_f2& c_out) {
-#if DUDF_SWEEP_DBG & 64
-    s_out = x; c_out = x * 0.5f; return;
-#endif
     const dudf_f2 k = {rintf(x.x * 0.636619772367581343f), rintf(x.y * 0.636619772367581343f)};
     dudf_f2 r = __builtin_elementwise_fma(-k, (dudf_f2)(1.57079637050628662109375f), x);
     r = __builtin_elementwise_fma(-k, (dudf_f2)(-4.37113900018624283e-8f), r);
@@ -51,20 +48,8 @@ __device__ __forceinline__ void dudf_sincos2(dudf_f2 x, dudf_f2& s_out, dudf_f2&
 #define DUDF_AT(arr, ub, vo) reinterpret_cast<f32x4*>(reinterpret_cast<char*>((arr) + (ub)) + (vo))
 #define DUDF_CAT(arr, ub, vo) reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>((arr) + (ub)) + (vo))
 // the stash is a stream (written once, read once or twice, 14 GB per step): non-temporal accesses
-#ifndef DUDF_SWEEP_DBG
-#define DUDF_SWEEP_DBG 0    // timing experiments only (wrong results): 1 no stash stores, 2 no stash loads, 4 no MFMA (bf16 kernel),
-#endif                      // 8 no weight DMA, 16 no k-block barrier, 32 no LDS fragment reads, 64 no sin/cos
-#if DUDF_SWEEP_DBG & 1
-#define DUDF_ST(arr, ub, vo, val) asm volatile("" :: "v"((f32x4)(val)))
-#else
 #define DUDF_ST(arr, ub, vo, val) __builtin_nontemporal_store((f32x4)(val), DUDF_AT(arr, ub, vo))
-#endif
-#if DUDF_SWEEP_DBG & 2
-__device__ __forceinline__ f32x4 dudf_dbg_any() { f32x4 z; asm volatile("" : "=v"(z)); return z; }
-#define DUDF_LD(arr, ub, vo) dudf_dbg_any()
-#else
 #define DUDF_LD(arr, ub, vo) __builtin_nontemporal_load(DUDF_CAT(arr, ub, vo))
-#endif
 
 // ---- 24-bit tile-major stash arrays (dudf_internal.h, "p24") -----------------------------------------------------------------
 // four fp32 values -> three dwords: round to nearest at bit 8 (an integer add on the bit pattern: a carry out of the mantissa
@@ -89,35 +74,18 @@ __device__ __forceinline__ f32x4 p24_unpack(const dudf_u3 d) {
 // (layer, T) is exactly 3 * ub; `vt` = the lane's ((p / 16) * 64 + lane) * 12
 #define DUDF_AT24(arr, ub, vt) reinterpret_cast<dudf_u3*>(reinterpret_cast<char*>(arr) + 3 * (ub) + (vt))
 #define DUDF_CAT24(arr, ub, vt) reinterpret_cast<const dudf_u3*>(reinterpret_cast<const char*>(arr) + 3 * (ub) + (vt))
-#if DUDF_SWEEP_DBG & 1
-#define DUDF_ST24(arr, ub, vt, val) asm volatile("" :: "v"(p24_pack((f32x4)(val))))
-#else
 #define DUDF_ST24(arr, ub, vt, val) __builtin_nontemporal_store(p24_pack((f32x4)(val)), DUDF_AT24(arr, ub, vt))
-#endif
-#if DUDF_SWEEP_DBG & 2
-__device__ __forceinline__ dudf_u3 dudf_dbg_any3() { dudf_u3 z; asm volatile("" : "=v"(z)); return z; }
-#define DUDF_LD24(arr, ub, vt) p24_unpack(dudf_dbg_any3())
-#else
 #define DUDF_LD24(arr, ub, vt) p24_unpack(__builtin_nontemporal_load(DUDF_CAT24(arr, ub, vt)))
-#endif
 // default cache policy (no `nt`): the 512-wide kernel reads an array it has just written back as the next layer's operand
 // (sweep_tile_w: the "relay"); with the hint the line has left L2 by then (config 3: -2.3 % step time without it on the relay)
-#if DUDF_SWEEP_DBG & 1
-#define DUDF_ST_CACHED(arr, ub, vo, val) asm volatile("" :: "v"((f32x4)(val)))
-#else
 #define DUDF_ST_CACHED(arr, ub, vo, val) (*DUDF_AT(arr, ub, vo) = (f32x4)(val))
-#endif
 // The three dwords of a 24-bit granule as they come from memory (in .xyz of an f32x4): epilogue_loads must not unpack — the
 // operands are requested two steps ahead between scheduling fences, and an unpack next to the load makes the wave wait for the
 // data right there (measured: the adjoint reverse sweep got 9 % SLOWER reading 25 % fewer bytes); epilogue() unpacks at use.
-#if DUDF_SWEEP_DBG & 2
-#define DUDF_LD24RAW(arr, ub, vt) dudf_dbg_any()
-#else
 // (the constant fourth lane costs nothing: it folds; an UNDEFINED lane made hipcc spill three values inside the adjoint forward
 //  sweep's k-block step instead of one)
 __device__ __forceinline__ f32x4 dudf_raw3(const dudf_u3 d) { return f32x4{__uint_as_float(d.x), __uint_as_float(d.y), __uint_as_float(d.z), 0.f}; }
 #define DUDF_LD24RAW(arr, ub, vt) dudf_raw3(__builtin_nontemporal_load(DUDF_CAT24(arr, ub, vt)))
-#endif
 __device__ __forceinline__ f32x4 p24_unpack_raw(const f32x4 r) { return p24_unpack(dudf_u3{__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2])}); }
 // ---- C = cos(w0 z_l) as 24-bit FIXED POINT (DudfLayout::p24 bit 2; same tile-major granules) ------------------------------------
 // |c| <= 1 needs no exponent: t = c + 3 lies in [2, 4], one binade, so the float add itself rounds c to nearest on a 2^-22 grid
@@ -176,17 +144,9 @@ __device__ __forceinline__ dudf_u3 fx24_pack(const f32x4 v, const float fs) {
     d.z = __builtin_amdgcn_perm(u3, u2, 0x06020100u);
     return d;
 }
-#if DUDF_SWEEP_DBG & 1
-#define DUDF_STF24(arr, ub, vt, val, fs) asm volatile("" :: "v"(fx24_pack((f32x4)(val), fs)))
-#else
 #define DUDF_STF24(arr, ub, vt, val, fs) __builtin_nontemporal_store(fx24_pack((f32x4)(val), fs), DUDF_AT24(arr, ub, vt))
-#endif
 __device__ __forceinline__ f32x4 c24_unpack_raw(const f32x4 r) { return c24_unpack(dudf_u3{__float_as_uint(r[0]), __float_as_uint(r[1]), __float_as_uint(r[2])}); }
-#if DUDF_SWEEP_DBG & 1
-#define DUDF_STC24(arr, ub, vt, val) asm volatile("" :: "v"(c24_pack((f32x4)(val))))
-#else
 #define DUDF_STC24(arr, ub, vt, val) __builtin_nontemporal_store(c24_pack((f32x4)(val)), DUDF_AT24(arr, ub, vt))
-#endif
 // a backward-only array in the format of this build: P (compile-time) = 24-bit tile-major, else fp32 rows
 #define DUDF_STB(P, arr, ub, lo, val) do { if constexpr (P) DUDF_ST24(arr, ub, (lo).t, val); else DUDF_ST(arr, ub, (lo).v, val); } while (0)
 // ... or, RL (compile-time): this array is the caller's relay — default cache policy
@@ -268,9 +228,6 @@ __constant__ unsigned kJetLane[16] = {
 // maximum of what they store (2 v_max3_f32 per tile), published per layer through LDS and once per workgroup to HBM.
 template <int SW, int FL>
 constexpr int amax_row() {
-#ifdef DUDF_DBG_NOTRACK_H                        // timing experiment only (wrong weight-gradient scales): no running maxima in the quad sweeps
-    if (SW >= 4) return -1;
-#endif
     return SW == SWEEP_FWD_H ? ((FL & 1) ? 3 : -1)      // h | hdot^k: the tangent channels are not bounded by 1 (plain columns: |h| <= 1)
          : (base_of(SW) == SWEEP_REV && SW != SWEEP_FWD_J) ? ((FL & 1) ? 0 : -1)
          : base_of(SW) == SWEEP_ADJ_FWD ? 1
@@ -303,6 +260,38 @@ struct LaneOff {
     __device__ __forceinline__ LaneOff(unsigned x, unsigned y, unsigned z) : v(x), c(y), t(z), ct(z) {}
     __device__ __forceinline__ LaneOff(unsigned x, unsigned y, unsigned z, unsigned w) : v(x), c(y), t(z), ct(w) {}
 };
+
+// ---- what a tile body derives from its sweep's direction: sweep_tile_b, sweep_tile_oct and sweep_tile_w take all of it from here,
+// the f32 sweep_tile the direction, the first layer's index and the stash base (its matrices are not images, and it names the layer a
+// matrix writes).  The bodies forward through one-line lambdas, which leaves every kernel's code as it was (tools/asm_diff.py).
+// Per body still, each built as one shared function, compared and, inside the per-kernel limits, timed parent against new on one
+// MI355X (kernels changed f32 | 128/256 | 512 unit; profiles/HISTORY.md):
+//   LaneOff construction  21 of 60 | 22 of 94 | 0 of 35: the pair launch's forward sweep took 0.9897 ms against the parent's 0.9762 + 0.0115
+//     (sweep_tile_b / sweep_tile_oct; the f32 and 512-wide kernels stayed inside the spread or unchanged)
+//   first-layer seed (x4 / gbar / ybar, poison test, N tiles)  - | 54 of 94 | 33 of 35, 14 descriptors: sweep_pair_kernel<256,6,0,2,0,1,6>
+//     goes from 52 to 56 bytes of scratch — outside the per-kernel limit "scratch not larger"
+//   lane geometry as one struct  0 of 60 | 34 of 94, more scratch in 9 — outside the same limit | 7 of 35 ----
+template <int SW> constexpr bool fwd_dir() { return base_of(SW) == SWEEP_FWD || base_of(SW) == SWEEP_ADJ_FWD; }
+// layer whose tail feeds matrix j (j == nhid: the last one, feeding the output stage), 0-based
+template <int SW>
+__device__ __forceinline__ int sweep_in_layer(const SweepArgs& a, int j) { return fwd_dir<SW>() ? j : a.L - 1 - j; }
+// the 16-bit image of matrix j of `nhid` in this sweep's order (IMGB bytes each; SP: the fp16 pieces)
+template <int SW, int IMGB, int SP>
+__device__ __forceinline__ const char* sweep_image(const SweepArgs& a, int nhid, int j) {
+    if constexpr (SP) return fwd_dir<SW>() ? a.wimg16_f + (size_t)j * IMGB : a.wimg16_t + (size_t)(nhid - 1 - j) * IMGB;
+    return fwd_dir<SW>() ? a.wimg_f + (size_t)j * IMGB : a.wimg_t + (size_t)(nhid - 1 - j) * IMGB;
+}
+// fp16x3: 2^-k_j of matrix j (the pack kernel scaled its image by 2^k_j)
+template <int SW>
+__device__ __forceinline__ float sweep_unscale(const SweepArgs& a, int nhid, int j) { return a.wsc[fwd_dir<SW>() ? j : nhid - 1 - j]; }
+// float offset of (layer, tile T) in a stash array: wave-uniform, and (UW) told so — SGPR base + lane offset
+template <bool UW = true>
+__device__ __forceinline__ int64_t sweep_stash_base(const SweepArgs& a, int layer, int T) {
+    const int64_t v = (int64_t)layer * a.stash_layer + (int64_t)(16 * T) * a.np;
+    if constexpr (!UW) return v;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
 
 // RL: the array that carries this sweep's post-tail values (S / Q / A / Z by sweep) is stored with the default cache policy
 // P24: which arrays are 24-bit tile-major in this build (DudfLayout::p24): bit 0 = S, Q, A, Z; bit 1 = R, E; bit 2 = C (fixed point)
@@ -462,13 +451,5 @@ constexpr int younger_ops() {
          : SW == SWEEP_FWD_J ? 2                                        // bias loads only
          : 6 + 2;                                                       // c,zs,E loads + Z stores
 }
-
-// Two finished accumulator tiles whose elementwise tail has not run yet.  The tail of chunk r-1 is executed in
-// the middle of chunk r's MFMA stream (same basic block), so sin/cos, stash traffic and MFMAs overlap inside
-// one wave instead of serialising at every chunk barrier.
-struct Pending {
-    f32x4 acc0, acc1, o1a, o2a, o3a, o1b, o2b, o3b;
-    int64_t ub0, ub1;
-};
 
 }  // namespace

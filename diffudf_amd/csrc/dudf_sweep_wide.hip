@@ -68,23 +68,16 @@ __device__ __forceinline__ void sweep_tile_w(const SweepArgs& a, const int g_fir
     const int li = lane & 15, q = lane >> 4;
     const bool isv = !HS || (is_jet(SW) ? li == 0 : (lane & 3) == 0);
     const int nhid = a.L - 1;
-    constexpr bool kFwdDir = (BS == SWEEP_FWD || BS == SWEEP_ADJ_FWD);
+    constexpr bool kFwdDir = fwd_dir<SW>();
     const int64_t p = (int64_t)(g_first + wave) * 16 + li;
-    auto image = [&](int j) -> const char* {
-        if constexpr (SP) return kFwdDir ? a.wimg16_f + (size_t)j * G::IMGB : a.wimg16_t + (size_t)(nhid - 1 - j) * G::IMGB;
-        return kFwdDir ? a.wimg_f + (size_t)j * G::IMGB : a.wimg_t + (size_t)(nhid - 1 - j) * G::IMGB;
-    };
-    auto unscale_of = [&](int j) -> float { return a.wsc[kFwdDir ? j : nhid - 1 - j]; };
+    auto image = [&](int j) -> const char* { return sweep_image<SW, G::IMGB, SP>(a, nhid, j); };
+    auto unscale_of = [&](int j) -> float { return sweep_unscale<SW>(a, nhid, j); };
     float unscale = 1.f, sb = 1.f, inv_sb = 1.f;        // accumulators -> true values | scale of the B operand being read back
-    auto in_layer = [&](int j) -> int { return kFwdDir ? j : a.L - 1 - j; };
+    auto in_layer = [&](int j) -> int { return sweep_in_layer<SW>(a, j); };
     auto bias_ptr = [&](int layer) -> const float* {
         return a.b1s + (size_t)layer * H;              // [L][H] biases as packed (row 0 = rho b_1)
     };
-    auto stash_base = [&](int layer, int T) -> int64_t {
-        const int64_t v = (int64_t)layer * a.stash_layer + (int64_t)(16 * T) * a.np;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return (int64_t)(((uint64_t)hi << 32) | lo);
-    };
+    auto stash_base = [&](int layer, int T) -> int64_t { return sweep_stash_base(a, layer, T); };
     const unsigned vo = (unsigned)(((int64_t)q * a.np + p) * 16);
     const LaneOff vl(vo, (is_hess(SW) && !is_jet(SW)) ? (unsigned)(((int64_t)q * a.np + (p >> 2)) * 16) : vo,   // C: one copy per quad
                      P24 ? (unsigned)(((p >> 4) * 64 + lane) * 12) : 0u,                                          // 24-bit tile-major arrays
@@ -162,6 +155,8 @@ __device__ __forceinline__ void sweep_tile_w(const SweepArgs& a, const int g_fir
             if constexpr (kColScale) dudf_track(cmax, e);
             if (T + PD < G::NT) ld(T + PD, s);
             if (last) {
+                // (own copy of the output stage of dudf_sweep16.h: through it nine kernels of this unit changed and the adjoint forward
+                //  sweep of 8x512 took 1.8709 ms (median of three) against the parent's 1.8652 + 0.0044 of spread, profiles/HISTORY.md)
                 if constexpr (BS == SWEEP_FWD) {
                     const f32x4 wv = *reinterpret_cast<const f32x4*>(a.theta + a.off_wo + 16 * T + 4 * q);
                     part += e[0] * wv[0] + e[1] * wv[1] + e[2] * wv[2] + e[3] * wv[3];
@@ -223,9 +218,6 @@ __device__ __forceinline__ void sweep_tile_w(const SweepArgs& a, const int g_fir
         // read-back registers: `xa` carries the even k-blocks, `xb` the odd ones — the loop is unrolled by two so that a set
         // is never copied while its asm loads are in flight (a rolled loop would rotate them with v_mov at the back edge)
         f32x4 xa0, xa1, xb0, xb1;
-#if DUDF_SWEEP_DBG & 128
-        const unsigned long long tw0 = __builtin_amdgcn_s_memtime();
-#endif
         ld_in(lin, 0, xa0, xa1);
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(xa0), "+v"(xa1));      // k-block 0: nothing to overlap it with yet
         auto kstep = [&](int kb, f32x4& c0, f32x4& c1, f32x4& n0, f32x4& n1, auto steady) {
@@ -264,19 +256,7 @@ __device__ __forceinline__ void sweep_tile_w(const SweepArgs& a, const int g_fir
                         __builtin_amdgcn_sched_barrier(0x76);
                     }
                     f32x4 cc = acc[G::HALFT * h + T];
-                    if constexpr (SP != 0) {                    // smallest terms first: lo*hi, hi*lo, hi*hi
-                        cc = mfma_h(as_h(af[1]), as_h(bq[0]), cc);
-                        cc = mfma_h(as_h(af[0]), as_h(bq[1]), cc);
-                        cc = mfma_h(as_h(af[0]), as_h(bq[0]), cc);
-                    } else {
-                        const bf16x8 ah = as_bf(af[0]), am = as_bf(af[1]), al = as_bf(af[NPC - 1]);
-                        cc = mfma_b(am, as_bf(bq[1]), cc);          // smallest terms first
-                        cc = mfma_b(al, as_bf(bq[0]), cc);
-                        cc = mfma_b(ah, as_bf(bq[NPC - 1]), cc);
-                        cc = mfma_b(am, as_bf(bq[0]), cc);
-                        cc = mfma_b(ah, as_bf(bq[1]), cc);
-                        cc = mfma_b(ah, as_bf(bq[0]), cc);
-                    }
+                    mma_products<SP, 1, NPC>(&af, bq, &cc);
                     acc[G::HALFT * h + T] = cc;
                 }
                 gc = (gc + 1) % 3;
@@ -299,22 +279,9 @@ __device__ __forceinline__ void sweep_tile_w(const SweepArgs& a, const int g_fir
         // the last k-block's (dummy) read-back is still in flight and nothing will consume it: keep its registers until it
         // has landed, or hipcc hands them to the burst below while the load is still writing them
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(xa0), "+v"(xa1), "+v"(xb0), "+v"(xb1));
-#if DUDF_SWEEP_DBG & 128
-        const unsigned long long tw1 = __builtin_amdgcn_s_memtime();
-#endif
         tail_burst(in_layer(j + 1), j + 1 == nhid);
-#if DUDF_SWEEP_DBG & 128
-        const unsigned long long tw2 = __builtin_amdgcn_s_memtime();
-#endif
         dma_wait_b<0>();
         __syncthreads();
-#if DUDF_SWEEP_DBG & 128
-        if ((blockIdx.x == 100 || blockIdx.x == 101) && lane == 0 && (wave == 0 || wave == 4) && j < 8) {
-            const unsigned long long tw3 = __builtin_amdgcn_s_memtime();
-            unsigned long long* o = &g_stamp[SW & 3][(blockIdx.x - 100) * 2 + (wave >> 2)][j][0];
-            o[0] = tw0; o[1] = tw1; o[2] = tw2; o[3] = tw3;
-        }
-#endif
     }
     if constexpr (BS == SWEEP_FWD) {
         part += __shfl_xor(part, 16);

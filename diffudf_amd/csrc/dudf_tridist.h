@@ -3,10 +3,6 @@
 #ifndef DUDF_TRIDIST_H
 #define DUDF_TRIDIST_H
 
-#ifndef DUDF_SAMPLE_DBG
-#define DUDF_SAMPLE_DBG 0          // timing experiments (tools/build_dbg.sh): 1 no exact evaluations, 2 nothing behind pass 0, 3 no sphere setup, 4 no scans at all
-#endif
-
 // squared distance from p to triangle (a,b,c): closest point by Voronoi regions of the triangle.  In fp64, like the
 // oracle (and like nothing in fp32 can be: |p - c|^2 of coordinates ~1 carries 1e-7 absolute, 1e-4 of a near-surface
 // distance of 1e-3); 2 k triangles x 2 k queries per step is noise for the fp64 vector pipe.
@@ -59,7 +55,6 @@ __device__ __forceinline__ double tri_closest(double px, double py, double pz, c
 }
 
 __device__ __forceinline__ double tri_dist2(double px, double py, double pz, const float* t) {
-    if (DUDF_SAMPLE_DBG == 1) return px + t[0];
     double cx, cy, cz;
     return tri_closest(px, py, pz, t, cx, cy, cz);
 }

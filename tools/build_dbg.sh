@@ -1,6 +1,6 @@
 #!/bin/bash
-# Builds dbg/libdudf_<tag>.so with extra -D flags for ONE translation unit, or for a few (timing experiments with debug knobs):
-#   bash tools/build_dbg.sh <tag> <unit: sweep_bf16|sweep_wide|prep|wgrad|...> "-DDUDF_SWEEP_DBG=3"
+# Builds dbg/libdudf_<tag>.so with extra -D flags for ONE translation unit, or for a few (debug builds):
+#   bash tools/build_dbg.sh <tag> <unit: sweep_bf16|sweep_wide|prep|wgrad|...> "-DDUDF_LATE_FORCE=1"
 #   bash tools/build_dbg.sh <tag> "sweep_bf16 sweep_wide" "-DDUDF_FX_CHECK=1"
 # The other units are the objects of the regular build (make -C diffudf_amd/csrc).
 R=$(cd "$(dirname "$0")/.." && pwd)

@@ -20,11 +20,10 @@ old.dudf_sample_batch.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
 
 
-def old_sample(ds, step, lib=None):
-    lib = lib or old
+def old_sample(ds, step):
     n = sum(ds.n_local())
     x = torch.empty(n, 3, device=ds.device); nr = torch.empty(n, 3, device=ds.device); sd = torch.empty(n, device=ds.device)
-    rc = lib.dudf_sample_batch(ds.tri.data_ptr() if ds.tri is not None else None, ds.tri.shape[0] if ds.tri is not None else 0,
+    rc = old.dudf_sample_batch(ds.tri.data_ptr() if ds.tri is not None else None, ds.tri.shape[0] if ds.tri is not None else 0,
                                ds.pc_pos.data_ptr(), ds.pc_nrm.data_ptr(), ds.pc_pos.shape[0], ds.samplesOnSurface, ds.n_far, ds.n_near,
                                ds.seed, step, ds.rank, ds.world, x.data_ptr(), nr.data_ptr(), sd.data_ptr(),
                                torch.cuda.current_stream().cuda_stream)
@@ -51,11 +50,6 @@ for only in (False, True):
             a = ds.sample(step); b = old_sample(ds, step)
             same &= all(torch.equal(u, v) for u, v in zip(a, b))
         t_new = timed(lambda: ds.sample(3)); t_old = timed(lambda: old_sample(ds, 3))
-        extra = ""
-        for v in os.environ.get("SAMPLER_VARIANTS", "").split():      # timing-only builds (tools/build_dbg.sh ... -DDUDF_SAMPLE_DBG=n)
-            lv = ctypes.CDLL(os.path.join(ROOT, "dbg", f"libdudf_{v}.so"))
-            lv.dudf_sample_batch.restype = ctypes.c_int; lv.dudf_sample_batch.argtypes = old.dudf_sample_batch.argtypes
-            extra += f", {v} {timed(lambda: old_sample(ds, 3, lv)) * 1e3:.1f} us"
         print(f"onlyPCloud={only} {kw or ''} triangles {0 if ds.tri is None else ds.tri.shape[0]} cloud {ds.pc_pos.shape[0]} points {sum(ds.n_local())}: "
-              f"bit-identical {same}; new {t_new * 1e3:.1f} us, previous {t_old * 1e3:.1f} us{extra}", flush=True)
+              f"bit-identical {same}; new {t_new * 1e3:.1f} us, previous {t_old * 1e3:.1f} us", flush=True)
         assert same
