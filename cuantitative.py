@@ -4,11 +4,17 @@
 MeshUDF meshes, and write L1 / L2 Chamfer distance and normal consistency of their vertices against the ground-truth cloud.
 
     python cuantitative.py [dataset] [outfolder] [device]        defaults: data/deepfashion/  results/df_subset/  0
+    python cuantitative.py data/deepfashion/ results/df_subset/ 0 --surface-samples 100000 --fscore-taus 0.005,0.01
 
 The reference takes `chamfer_distance` from pytorch3d (a CUDA extension) and vertex normals and the cloud reader from open3d;
 here the metric runs in `diffudf_amd.metrics` (HIP kernels: nearest neighbours on direct differences, the normal term, the
 area-weighted vertex normals) and the cloud comes from `diffudf_amd.mesh.read_ply_points`.  The MeshUDF half needs the Lewiner
-tables (generate_mc.py); without them its three columns are `nan`."""
+tables (generate_mc.py); without them its three columns are `nan`.
+
+`--surface-samples N` (off by default) adds the protocol of CAP-UDF, MeshUDF and NDF in a second file, `results_surface.csv`: N
+area-uniform samples of each extracted surface against the ground truth — accuracy, completeness, L1 / L2 Chamfer distance,
+Hausdorff distance, precision / recall / F-score at the thresholds of `--fscore-taus`, normal consistency
+(`diffudf_amd.metrics.surface_metrics`).  `results.csv` is the same file with and without it."""
 import gc
 import os
 import sys
@@ -67,6 +73,31 @@ def metrics(mesh, pointcloud, norm, cuda_device):
     return cd.cpu().numpy(), nc.cpu().numpy()
 
 
+def surface_header(taus):
+    """The header of `results_surface.csv` for the thresholds `taus`."""
+    cols = ['mesh']
+    for half in ('CAP', 'MU'):
+        cols += [f'{k}_{half}' for k in ('accuracy', 'completeness', 'chamfer_l1', 'chamfer_l2', 'hausdorff')]
+        cols += [f'{k}@{t}_{half}' for k in ('precision', 'recall', 'fscore') for t in taus]
+        cols.append(f'NC_{half}')
+    return ','.join(cols)
+
+
+def surface_fields(mesh, gt_pc, gt_mesh, surface_samples, taus, cuda_device):
+    """The values of one half (CAP or MU) of a `results_surface.csv` row, in header order; all NaN for `mesh` None."""
+    if mesh is None:
+        return [float('nan')] * (6 + 3 * len(taus))
+    dev = _device(cuda_device)
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)   # noqa: E731
+    m = dmetrics.surface_metrics(up(np.asarray(mesh.vertices), torch.float64), up(np.asarray(mesh.faces), torch.int64),
+                                 up(gt_pc.points, torch.float32), up(gt_pc.normals, torch.float32),
+                                 gt_mesh=None if gt_mesh is None else (up(gt_mesh[0], torch.float64), up(gt_mesh[1], torch.int64)),
+                                 n_samples=surface_samples, taus=taus)
+    nc = m['normal_consistency']
+    return ([m[k] for k in ('accuracy', 'completeness', 'chamfer_l1', 'chamfer_l2', 'hausdorff')]
+            + [m[k][t] for k in ('precision', 'recall', 'fscore') for t in taus] + [float('nan') if nc is None else nc])
+
+
 def default_exp_config(outfolder, net_width=256, net_depth=8):
     """The experiment of reference cuantitative.py:33-59."""
     return {
@@ -90,11 +121,14 @@ def default_exp_config(outfolder, net_width=256, net_depth=8):
     }
 
 
-def run(dataset, outfolder, cuda_device, exp_config=None):
+def run(dataset, outfolder, cuda_device, exp_config=None, surface_samples=0, fscore_taus=(0.005, 0.01)):
     """The loop of reference cuantitative.py:62-108: for every folder under `dataset` that holds a `*_pc.ply` and a `*_t.obj`, train
     (`setup_train`), then write one row of `results.csv` in `outfolder`.  Experiments whose folder exists are skipped.  Returns
     the rows written, as (name, time, L1CD_CAP, L2CD_CAP, NC_CAP, L1CD_MU, L2CD_MU, NC_MU, (mesh_MU, mesh_CAP)).  A training that
-    returns no mesh raises RuntimeError naming the experiment (the reference fails there on its tuple unpacking)."""
+    returns no mesh raises RuntimeError naming the experiment (the reference fails there on its tuple unpacking).
+    surface_samples > 0: every experiment also appends a row to `results_surface.csv` (`surface_header(fscore_taus)`): the
+    surface-sampled metrics of the CAP and MU meshes against the `_pc.ply` cloud and, for the accuracy direction, the `_t.obj` mesh
+    beside it.  `results.csv` and the returned rows do not change."""
     from train import setup_train
     if not os.path.exists(outfolder):
         os.mkdir(outfolder)
@@ -103,6 +137,11 @@ def run(dataset, outfolder, cuda_device, exp_config=None):
     csv = os.path.join(outfolder, 'results.csv')
     with open(csv, 'w+') as result_file:
         result_file.write(HEADER + '\n')
+    fscore_taus = tuple(float(t) for t in fscore_taus)
+    surface_csv = os.path.join(outfolder, 'results_surface.csv')
+    if surface_samples > 0:
+        with open(surface_csv, 'w+') as result_file:
+            result_file.write(surface_header(fscore_taus) + '\n')
     rows = []
     for dirpath, dirnames, filenames in os.walk(dataset):
         clouds = [f for f in filenames if f.endswith('_pc.ply')]
@@ -140,12 +179,31 @@ def run(dataset, outfolder, cuda_device, exp_config=None):
             L2CD_MU, _ = metrics(mu_mesh, gt_pc, norm=2, cuda_device=cuda_device)
         with open(csv, 'a') as result_file:
             result_file.write(f'{experiment_name},{training_time},{L1CD_CAP},{L2CD_CAP},{NC_CAP},{L1CD_MU},{L2CD_MU},{NC_MU}\n')
+        if surface_samples > 0:
+            print('Computing surface-sampled metrics...')
+            gt_mesh = dmesh.load_obj(os.path.join(dirpath, gts[0]))
+            fields = [v for mesh in (meshCAP, meshMU)
+                      for v in surface_fields(mesh, gt_pc, gt_mesh, surface_samples, fscore_taus, cuda_device)]
+            with open(surface_csv, 'a') as result_file:
+                result_file.write(','.join([experiment_name] + [str(v) for v in fields]) + '\n')
         rows.append((experiment_name, training_time, L1CD_CAP, L2CD_CAP, NC_CAP, L1CD_MU, L2CD_MU, NC_MU, (meshMU, meshCAP)))
     return rows
 
 
+def parse_args(argv):
+    """(dataset, outfolder, cuda_device, surface_samples, fscore_taus) of a command line: up to three positionals as the reference
+    takes them, then `--surface-samples N` and `--fscore-taus a,b`."""
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('dataset', nargs='?', default='data/deepfashion/')
+    ap.add_argument('outfolder', nargs='?', default='results/df_subset/')
+    ap.add_argument('device', nargs='?', type=int, default=0)
+    ap.add_argument('--surface-samples', type=int, default=0, metavar='N')
+    ap.add_argument('--fscore-taus', default='0.005,0.01', metavar='a,b')
+    a = ap.parse_args(argv)
+    return a.dataset, a.outfolder, a.device, a.surface_samples, tuple(float(t) for t in a.fscore_taus.split(',') if t)
+
+
 if __name__ == '__main__':
-    dataset = sys.argv[1] if len(sys.argv) > 1 else 'data/deepfashion/'
-    outfolder = sys.argv[2] if len(sys.argv) > 2 else 'results/df_subset/'
-    cuda_device = int(sys.argv[3]) if len(sys.argv) > 3 else 0
-    run(dataset, outfolder, cuda_device)
+    dataset, outfolder, cuda_device, surface_samples, fscore_taus = parse_args(sys.argv[1:])
+    run(dataset, outfolder, cuda_device, surface_samples=surface_samples, fscore_taus=fscore_taus)

@@ -74,7 +74,12 @@ SYMBOLS = {
     "dudf_chamfer_terms": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
     "dudf_vertex_normals_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "dudf_vertex_normals": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
-    "dudf_knn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "dudf_mesh_sample_surface_workspace": (ctypes.c_size_t, [ctypes.c_int64]),
+    "dudf_mesh_sample_surface": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint64,
+                                                _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_distance_stats_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "dudf_distance_stats": (ctypes.c_int, [_P, ctypes.c_int64, _DBL, ctypes.c_int, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_knn_workspace_bytes":(ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     "dudf_knn_grid_build": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_size_t, _P]),
     "dudf_knn_points": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P,
                                        ctypes.c_size_t, _P]),

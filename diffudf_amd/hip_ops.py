@@ -906,6 +906,69 @@ def vertex_normals(vertices, faces):
     return out
 
 
+# ---- surface samples and threshold statistics (csrc/dudf_surfsample.hip) -----------------------------------------
+STATS_MAX_K = 16
+
+
+def mesh_sample_surface(vertices, faces, n, seed=123, start=0, uniforms=None, want_points=True, want_normals=True, want_face=False,
+                        want_face_normals=False, want_area=False):
+    """`dudf_mesh_sample_surface`: (points (n,3) float32, normals (n,3) float32, face (n,) int64, face_normals (F,3) float32, area
+    float64 CUDA tensor of 1) — None for what was not asked for — of the samples start .. start + n - 1 of the mesh vertices (V,3)
+    float64, faces (F,3) int64 (CUDA tensors; other dtypes are converted).  uniforms (n,3) float64: the three numbers of every
+    sample instead of the generator's, each in [0, 1) (checked by the caller).  ValueError for a non-finite vertex or a face index
+    out of range, DudfError for a mesh without faces or without area."""
+    vertices = _tensor(vertices, "mesh_sample_surface: vertices", torch.float64, (3,), convert=True)
+    if torch.is_tensor(faces) and faces.numel() == 0:
+        faces = faces.reshape(0, 3)
+    faces = _tensor(faces, "mesh_sample_surface: faces", torch.int64, (3,), convert=True)
+    if faces.device != vertices.device:
+        raise _lib.DudfError("mesh_sample_surface: vertices and faces live on different devices")
+    V, F, dev, n, start = vertices.shape[0], faces.shape[0], vertices.device, int(n), int(start)
+    if n < 0 or start < 0:
+        raise _lib.DudfError(f"mesh_sample_surface: n and start must not be negative; got {n}, {start}")
+    if F == 0 or V == 0:
+        raise _lib.DudfError("mesh_sample_surface: a mesh without faces has no surface (DUDF_E_BADCFG)")
+    if uniforms is not None:
+        uniforms = _tensor(uniforms, "mesh_sample_surface: uniforms", torch.float64, (3,))
+        if uniforms.shape[0] != n or uniforms.device != dev:
+            raise _lib.DudfError("mesh_sample_surface: uniforms must be (n,3) on the device of the mesh")
+    want_points = want_points or n > 0
+    points = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_points else None
+    normals = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_normals else None
+    face = torch.empty(n, dtype=torch.int64, device=dev) if want_face else None
+    face_normals = torch.empty(F, 3, dtype=torch.float32, device=dev) if want_face_normals else None
+    area = torch.empty(1, dtype=torch.float64, device=dev) if want_area else None
+    ws, nbytes = _workspace(dev, "dudf_mesh_sample_surface_workspace", F, err=-4)
+    fn = getattr(_lib.load(), "dudf_mesh_sample_surface")
+    with torch.cuda.device(dev):
+        rc = fn(_ptr(vertices), V, _ptr(faces), F, start, n, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(uniforms), _ptr(points), _ptr(normals),
+                _ptr(face), _ptr(face_normals), _ptr(area), _ptr(ws), nbytes, _stream())
+    if rc == -3:
+        raise ValueError("mesh_sample_surface: the mesh has a NaN or infinite vertex, or a face refers to a vertex that does not exist")
+    if rc == -1:
+        raise _lib.DudfError("mesh_sample_surface: every face of the mesh is degenerate: there is no area to sample (DUDF_E_BADCFG)")
+    _lib.check(rc, "dudf_mesh_sample_surface")
+    return points, normals, face, face_normals, area
+
+
+def distance_stats(dist, thresholds=()):
+    """`dudf_distance_stats` of dist (n,) float32 (a CUDA tensor): (counts (K + 1,) int64 — rows with d <= tau_k, inclusive and
+    compared in double, then the NaN rows —, max (1,) float32, sums (2,) float64: sum d and sum d*d over the rows that are not NaN),
+    CUDA tensors.  Up to 16 thresholds.  Bit-reproducible."""
+    _tensor(dist, "distance_stats: dist", torch.float32, ())
+    taus = [float(t) for t in thresholds]
+    K, n, dev = len(taus), dist.shape[0], dist.device
+    if K > STATS_MAX_K:
+        _lib.check(-4, f"dudf_distance_stats ({K} thresholds; at most {STATS_MAX_K})")
+    counts = torch.empty(K + 1, dtype=torch.int64, device=dev)
+    mx = torch.empty(1, dtype=torch.float32, device=dev)
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    ws, nbytes = _workspace(dev, "dudf_distance_stats_workspace_bytes", n)
+    _call("dudf_distance_stats", _ptr(dist), n, (ctypes.c_double * max(K, 1))(*taus), K, _ptr(counts), _ptr(mx), _ptr(sums), _ptr(ws),
+          nbytes, dev=dev)
+    return counts, mx, sums
+
+
 # ---- K nearest neighbours and normal orientation (reference generate_pc.py:40; csrc/dudf_orient.hip) ----------------------------
 KNN_MAX_K = 16
 

@@ -219,3 +219,154 @@ def mesh_distance(points, vertices, faces):
     """One-shot `MeshIndex(vertices, faces).distance(points)`."""
     dev = points.device if torch.is_tensor(points) and points.device.type == "cuda" else "cuda:0"
     return MeshIndex(vertices, faces, device=dev).distance(points)
+
+
+# ---- surface-sampled evaluation (DESIGN.md §8; csrc/dudf_surfsample.hip) ---------------------------------------------------------
+def _mesh_tensors(vertices, faces, device="cuda:0"):
+    """(vertices (V,3) float64, faces (F,3) int64) on the device: CUDA tensors as they are, numpy arrays uploaded as MeshIndex does."""
+    v = _cuda(vertices, torch.float64, device)
+    f = _cuda(faces, torch.int64, v.device)
+    if f.numel() == 0:
+        f = f.reshape(0, 3)
+    if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
+        raise DudfError(f"vertices (V,3) and faces (F,3) expected; got {tuple(v.shape)}, {tuple(f.shape)}")
+    return v, f
+
+
+def sample_surface(vertices, faces, n, seed=123, start=0, return_face=False, uniforms=None):
+    """(points (n,3) float32, normals (n,3) float32[, face (n,) int64]): area-uniform samples of a triangle mesh with the normal of
+    the face each falls on, on the device.  Sample i has the global index start + i and is a pure function of (mesh, seed, start + i):
+    `sample_surface(v, f, a + b)` is `sample_surface(v, f, a)` followed by `sample_surface(v, f, b, start=a)`, bit for bit.  Faces
+    are chosen by integer weights floor(|e1 x e2| / max * 2^32); a degenerate face is never chosen.  uniforms (n,3)
+    float64: the three numbers (face, r1, r2) of every sample instead of the generator's; an entry outside [0, 1) raises ValueError.
+    Inputs are CUDA tensors, or numpy arrays (uploaded to cuda:0)."""
+    v, f = _mesh_tensors(vertices, faces)
+    if uniforms is not None:
+        uniforms = _cuda(uniforms, torch.float64, v.device).contiguous()
+        if uniforms.numel() and not bool(((uniforms >= 0.0) & (uniforms < 1.0)).all()):
+            raise ValueError("sample_surface: uniforms must lie in [0, 1)")
+    points, normals, face, _, _ = hip_ops.mesh_sample_surface(v, f, n, seed=seed, start=start, uniforms=uniforms, want_face=return_face)
+    return (points, normals, face) if return_face else (points, normals)
+
+
+def face_normals(vertices, faces):
+    """(F,3) float32: (b - a) x (c - a) / max(|.|, 1e-300) of every face, formed in fp64 — `mesh.triangle_normals_areas` on the device."""
+    v, f = _mesh_tensors(vertices, faces)
+    return hip_ops.mesh_sample_surface(v, f, 0, want_points=False, want_normals=False, want_face_normals=True)[3]
+
+
+def surface_area(vertices, faces):
+    """The area of the mesh, a float: half the sum of |e1 x e2| in fp64 (a fixed order of additions)."""
+    v, f = _mesh_tensors(vertices, faces)
+    return float(hip_ops.mesh_sample_surface(v, f, 0, want_points=False, want_normals=False, want_area=True)[4].item())
+
+
+def _stats_dict(counts, mx, sums, K):
+    c, s = counts.tolist(), sums.tolist()
+    return {"count_le": c[:K], "nan": c[K], "max": float(mx.item()), "sum": s[0], "sum_sq": s[1]}
+
+
+def distance_stats(dist, thresholds=()):
+    """dict(count_le, nan, max, mean, mean_sq) of a distance vector (n,) float32 on the device: count_le[k] = rows with
+    d <= thresholds[k] (inclusive, compared in double), nan = NaN rows (left out of everything else; +inf is a value), max, and the
+    means of d and d*d over the rows that are not NaN (NaN when there is none).  At most 16 thresholds."""
+    dist = hip_ops._tensor(dist, "distance_stats: dist", torch.float32, (), convert=True)
+    K = len(thresholds)
+    st = _stats_dict(*hip_ops.distance_stats(dist, thresholds), K)
+    valid = dist.shape[0] - st["nan"]
+    return {"count_le": st["count_le"], "nan": st["nan"], "max": st["max"],
+            "mean": st["sum"] / valid if valid else float("nan"), "mean_sq": st["sum_sq"] / valid if valid else float("nan")}
+
+
+def fscore(precision, recall):
+    """2 P R / (P + R), and 0 when P + R = 0."""
+    return 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
+
+
+def surface_metrics(vertices, faces, gt_points, gt_normals=None, gt_mesh=None, n_samples=100000, taus=(0.005, 0.01), seed=123,
+                    point_to_surface=True):
+    """Surface-sampled evaluation of a reconstructed mesh (vertices, faces) against a ground truth, the protocol of CAP-UDF, MeshUDF
+    and NDF: a dict of floats.  The ground truth is the cloud gt_points (n,3) with gt_normals (or None), and / or the mesh
+    gt_mesh = (vertices, faces); at least one of them.  All distances are Euclidean (not squared).
+
+    Accuracy direction (reconstruction -> ground truth): `n_samples` area-uniform samples of the reconstruction (`sample_surface`
+    with `seed`); the distance of each to gt_mesh (`MeshIndex.distance`, exact) when it is given, else to its nearest row of
+    gt_points (`nearest_points`).
+    Completeness direction (ground truth -> reconstruction): the rows of gt_points, or `n_samples` samples of gt_mesh when no cloud
+    is given; the exact distance of each to the reconstructed surface (`MeshIndex.distance`), or with point_to_surface=False the
+    distance to the nearest of the accuracy direction's samples — the sample-to-sample protocol of the other papers.
+
+      accuracy, completeness    the mean distance of each direction (NaN rows left out)
+      chamfer_l1                (accuracy + completeness) / 2
+      chamfer_l2                the same over squared distances
+      hausdorff                 the larger of the two maxima
+      precision[tau]            share of the accuracy direction's rows (NaN rows left out) with distance <= tau
+      recall[tau]               the same of the completeness direction
+      fscore[tau]               2 P R / (P + R), 0 when P + R = 0
+      normal_consistency        mean of the two directions' mean |cos| between the face normal of the sample (or of the closest
+                                triangle of the reconstruction) and the matched ground-truth normal (the closest triangle's, or the
+                                nearest cloud point's); None unless both directions have ground-truth normals
+      n_samples, area           the sample count and the area of the reconstruction
+
+    precision, recall and fscore are dicts keyed by the taus as given.  Everything runs on the device; the scalars are read at the end."""
+    taus = tuple(taus)
+    n_samples = int(n_samples)
+    if n_samples <= 0:
+        raise ValueError("surface_metrics: n_samples must be positive")
+    if gt_points is None and gt_mesh is None:
+        raise ValueError("surface_metrics: give gt_points, gt_mesh or both")
+    v, f = _mesh_tensors(vertices, faces)
+    dev = v.device
+    samples, s_normals, _, rec_fn, area = hip_ops.mesh_sample_surface(v, f, n_samples, seed=seed, want_face_normals=True, want_area=True)
+    gt_fn = gt_index = None
+    if gt_mesh is not None:
+        gv, gf = _mesh_tensors(gt_mesh[0], gt_mesh[1], dev)
+        gt_index = MeshIndex(gv, gf)
+    if gt_points is not None:
+        gt = _cuda(gt_points, torch.float32, dev).contiguous()
+        gt_n = None if gt_normals is None else _cuda(gt_normals, torch.float32, dev).contiguous()
+        if gt_mesh is not None:
+            gt_fn = face_normals(gv, gf)
+    else:
+        gt, gt_n, _, gt_fn, _ = hip_ops.mesh_sample_surface(gv, gf, n_samples, seed=seed, want_face_normals=True)
+
+    cos_terms = []               # per direction with normals on both sides: (`chamfer_terms` sums, rows); mean |cos| = 1 - sums[1] / rows
+    # accuracy: the reconstruction's samples against the ground truth
+    if gt_index is not None:
+        d_acc, i_acc = gt_index.distance(samples, return_index=True)
+        acc_other = gt_fn
+    else:
+        d2, i_acc = hip_ops.nearest_points(samples, gt, 2)
+        d_acc = torch.sqrt(d2)
+        acc_other = gt_n
+    acc = hip_ops.distance_stats(d_acc, taus)
+    if acc_other is not None:
+        cos_terms.append((hip_ops.chamfer_terms(d_acc, i_acc, s_normals, acc_other), d_acc.shape[0]))
+    # completeness: the ground truth against the reconstruction
+    if point_to_surface:
+        d_comp, i_comp = MeshIndex(v, f).distance(gt, return_index=True)
+        comp_other = rec_fn
+    else:
+        d2, i_comp = hip_ops.nearest_points(gt, samples, 2)
+        d_comp = torch.sqrt(d2)
+        comp_other = s_normals
+    comp = hip_ops.distance_stats(d_comp, taus)
+    if gt_n is not None:
+        cos_terms.append((hip_ops.chamfer_terms(d_comp, i_comp, gt_n, comp_other), d_comp.shape[0]))
+
+    # the scalars leave the device here
+    K = len(taus)
+    a, c = _stats_dict(*acc, K), _stats_dict(*comp, K)
+    na, nc = d_acc.shape[0] - a["nan"], d_comp.shape[0] - c["nan"]
+    mean = lambda s, m: s / m if m else float("nan")     # noqa: E731
+    out = {"accuracy": mean(a["sum"], na), "completeness": mean(c["sum"], nc)}
+    out["chamfer_l1"] = 0.5 * (out["accuracy"] + out["completeness"])
+    out["chamfer_l2"] = 0.5 * (mean(a["sum_sq"], na) + mean(c["sum_sq"], nc))
+    out["hausdorff"] = max(a["max"], c["max"])
+    out["precision"] = {t: mean(a["count_le"][k], na) for k, t in enumerate(taus)}
+    out["recall"] = {t: mean(c["count_le"][k], nc) for k, t in enumerate(taus)}
+    out["fscore"] = {t: fscore(out["precision"][t], out["recall"][t]) if na and nc else float("nan") for t in taus}
+    out["normal_consistency"] = (0.5 * sum(1.0 - float(s[1].item()) / m for s, m in cos_terms)) if len(cos_terms) == 2 else None
+    out["n_samples"] = n_samples
+    out["area"] = float(area.item())
+    return out

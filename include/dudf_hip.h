@@ -256,6 +256,43 @@ size_t dudf_vertex_normals_workspace_bytes(int64_t n_vertices);
 int dudf_vertex_normals(const double* vertices, int64_t n_vertices, const int64_t* faces, int64_t n_faces, float* out_normals,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Surface-sampled evaluation — an area-uniform sampler of a triangle mesh and the threshold statistics of a distance vector, what
+ * `diffudf_amd.metrics.surface_metrics` (Chamfer distance on surface samples, F-score, Hausdorff) is made of.
+ * csrc/dudf_surfsample.hip; the rules are DESIGN.md §8 (tests/surface_oracle.py restates them in numpy).  These entry points arrived
+ * after ABI 8 without changing any existing signature.
+ *
+ * dudf_mesh_sample_surface — n samples with global indices start .. start + n - 1 of the mesh vertices (V,3) double, faces (F,3)
+ *   int64.  Per face in fp64: n = (b - a) x (c - a), each component two products and one difference; nn = sqrt((nx^2 + ny^2) + nz^2);
+ *   the face normal is n / max(nn, 1e-300) rounded to fp32 (out_face_normals (F,3), or NULL); out_area (device, 1 double, or NULL) =
+ *   0.5 * sum nn from per-workgroup partials added in index order.  Faces are chosen by INTEGER weights w_f = floor(nn_f / nn_max *
+ *   2^32) with nn_max the maximum over the faces, c_f their inclusive uint64 sums, W = c_{F-1}: integer sums are the same in every
+ *   order.  A face of weight 0 (degenerate, or below 2^-32 of the largest) is never chosen.  Sample g draws 64-bit words b1, b2, b3
+ *   from streams 301, 302, 303 of `seed` (the splitmix64 construction of diffudf_amd/synth.py, counter g): u1 = (b1 >> 11) 2^-53, r1
+ *   and r2 alike; with `uniforms` (device, (n,3) double: u1, r1, r2 per sample, each in [0, 1)) those replace them.  The face is the
+ *   first f with c_f > floor(u1 2^53 * W / 2^53) — `searchsorted(c, t, side="right")` —, the point ((1 - s) A + s (1 - r2) B) + s r2 C
+ *   with s = sqrt(r1), in fp64 and in that order, rounded to fp32.  out_points (n,3); out_normals (n,3, or NULL) the face's fp32
+ *   normal; out_face (n, or NULL) int64.  A row of `uniforms` outside [0, 1) gives a NaN point and face -1.  The result is a pure
+ *   function of (mesh, seed, g): samples [0, a + b) are samples [0, a) followed by [a, a + b), bit for bit.
+ *   The call reads one status word back on `stream` (it waits for the stream once; not for graph capture) and returns
+ *   DUDF_E_BADCFG for F <= 0, V <= 0, n < 0, start < 0, a NULL input or a mesh whose every face has nn = 0; DUDF_E_BADMODE for a face
+ *   index outside [0, V) (not dereferenced) or a non-finite nn; DUDF_E_UNSUPPORTED for F >= 2^31.  n == 0 still writes
+ *   out_face_normals and out_area.  workspace: dudf_mesh_sample_surface_workspace(F) (0 for an F the call refuses), 256-byte aligned,
+ *   else DUDF_E_WORKSPACE. */
+size_t dudf_mesh_sample_surface_workspace(int64_t F);
+int dudf_mesh_sample_surface(const double* vertices, int64_t V, const int64_t* faces, int64_t F, int64_t start, int64_t n,
+                             uint64_t seed, const double* uniforms, float* out_points, float* out_normals, int64_t* out_face,
+                             float* out_face_normals, double* out_area, void* workspace, size_t workspace_bytes, void* stream);
+
+/* dudf_distance_stats — of dist (n) fp32 (device), non-negative: out_counts (device, K + 1 int64) = the rows with (double)d <= tau_k
+ *   (inclusive) for the K thresholds (HOST, K doubles), then the NaN rows; out_max (device, 1 fp32) = the maximum, taken on the bits;
+ *   out_sums (device, 2 doubles) = sum d and sum d*d.  NaN rows enter the last count only; +inf is a value.  Counts and maximum do
+ *   not depend on order; the sums are per-workgroup partials added in index order (as dudf_chamfer_terms): a repeated call is
+ *   bit-identical.  n == 0: zero counts, maximum 0, zero sums.  K < 0 or K > 16: DUDF_E_UNSUPPORTED; n < 0 or a NULL pointer:
+ *   DUDF_E_BADCFG.  workspace: dudf_distance_stats_workspace_bytes(n). */
+size_t dudf_distance_stats_workspace_bytes(int64_t n);
+int dudf_distance_stats(const float* dist, int64_t n, const double* thresholds, int K, int64_t* out_counts, float* out_max,
+                        double* out_sums, void* workspace, size_t workspace_bytes, void* stream);
+
 /* K nearest neighbours and consistent normal orientation — the device side of pytorch3d's `knn_points(x, y, K=K)` and of open3d's
  * `orient_normals_consistent_tangent_plane(k)` (reference generate_pc.py:40).  csrc/dudf_orient.hip; the rules are DESIGN.md §3.7
  * (tests/orient_oracle.py restates them in numpy).  These entry points arrived after ABI 8 without changing any existing signature.
