@@ -128,6 +128,17 @@ SYMBOLS = {
     "dudf_capudf_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "dudf_capudf_count": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_double, _P, _P, ctypes.c_size_t, _P]),
     "dudf_capudf_emit": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_double, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_grid_fields_lattice": (ctypes.c_int, [_CFG, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                                ctypes.c_double, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_sparse_select_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    "dudf_sparse_select": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_grid_fields_bricks": (ctypes.c_int, [_CFG, _P, ctypes.c_int64, ctypes.c_int, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
+                                               _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_capudf_sparse_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
+    "dudf_capudf_sparse_count": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _P, _P,
+                                                ctypes.c_size_t, _P]),
+    "dudf_capudf_sparse_emit": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _P, _P, _P,
+                                               _P, ctypes.c_size_t, _P]),
     "dudf_grid_values": (ctypes.c_int, [_CFG, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
     "dudf_mc_lewiner_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
     "dudf_mc_lewiner_count": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, _P, _P, _P,

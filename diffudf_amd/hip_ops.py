@@ -5,6 +5,7 @@ PyTorch is plumbing here (device memory, streams); every number is produced by t
 hand-written HIP kernels in diffudf_amd/csrc.  No function in this module has a CPU path.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -462,6 +463,92 @@ def capudf_extract(ndf, grad, threshold=0.008, want_cells=False):
             _call("dudf_capudf_emit", _ptr(ndf), _ptr(grad), n, float(threshold), _ptr(verts), _ptr(tris), _ptr(cells), _ptr(ws),
                   nbytes)
     return (verts, tris, cells) if want_cells else (verts, tris)
+
+
+# ---- the brick-sparse narrow band (dudf_sparsegrid.hip; layout and rules: include/dudf_hip.h) ----------------------
+def sparse_dims(grid_n, brick):
+    """(m, nb, nl): cells per side, cell bricks per side, storage-lattice bricks per side; the coarse lattice has nb + 1 points."""
+    grid_n, brick = int(grid_n), int(brick)
+    if brick not in (4, 8) or grid_n < 2:
+        _lib.check(-1, f"sparse grid (N = {grid_n}, brick = {brick}: N >= 2 and a brick edge of 4 or 8)")
+    m = grid_n - 1
+    return m, -(-m // brick), m // brick + 1
+
+
+def sparse_bound(grid_n, brick, threshold, lipschitz):
+    """The selection bound of a brick for an L-Lipschitz df, in double: threshold + L * half a brick diagonal."""
+    return float(threshold) + float(lipschitz) * (math.sqrt(3.0) / 2.0) * int(brick) * (2.0 / (int(grid_n) - 1))
+
+
+def grid_fields_lattice(cfg, theta, grid_n, brick, start, count, gt_mode, alpha, out_df, out_vec=None, ws=None):
+    """Fills out_df[start:start+count] (and out_vec, when given) over the flattened (nb + 1)^3 coarse lattice at fine indices
+    min(c * brick, N - 1); out_vec None: the forward sweep only.  Returns the fallback counter as `grid_fields` (None without out_vec)."""
+    theta = _theta(cfg, theta)
+    ws = ws or query_workspace_for(cfg, count, theta.device)
+    flag = torch.zeros(1, dtype=torch.int32, device=theta.device) if out_vec is not None else None
+    _call("dudf_grid_fields_lattice", ctypes.byref(cfg), _ptr(theta), int(grid_n), int(brick), int(start), int(count),
+          INVERSE_MODES[gt_mode], float(alpha), _ptr(out_df[start:start + count]),
+          _ptr(out_vec[start:start + count] if out_vec is not None else None), _ptr(flag), _ptr(ws.buf), ws.nbytes, dev=theta.device)
+    return flag
+
+
+def sparse_select(coarse_df, grid_n, brick, bound):
+    """Brick selection (`dudf_sparse_select`) from df on the coarse lattice: (slot (nl,nl,nl) int32, stored_ids, candidate_ids) device
+    tensors, the id lists ascending int32 and cut to their counts — the one host read-back of the sparse extraction."""
+    m, nb, nl = sparse_dims(grid_n, brick)
+    coarse_df = _tensor(coarse_df, "coarse_df", torch.float32, convert=True)
+    if coarse_df.numel() != (nb + 1) ** 3:
+        raise _lib.DudfError(f"sparse_select: {(nb + 1) ** 3} lattice values expected for N = {grid_n}, brick = {brick}; got {coarse_df.numel()}")
+    dev = coarse_df.device
+    ws, nbytes = _workspace(dev, "dudf_sparse_select_bytes", int(grid_n), int(brick), err=-4)
+    slot = torch.empty(nl, nl, nl, dtype=torch.int32, device=dev)
+    stored = torch.empty(nl ** 3, dtype=torch.int32, device=dev); cands = torch.empty(nl ** 3, dtype=torch.int32, device=dev)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    _call("dudf_sparse_select", _ptr(coarse_df), int(grid_n), int(brick), float(bound), _ptr(slot), _ptr(stored), _ptr(cands),
+          _ptr(counts), _ptr(ws), nbytes, dev=dev)
+    ns, nc = [int(v) for v in counts.tolist()]
+    return slot, stored[:ns].clone(), cands[:nc].clone()
+
+
+def grid_fields_bricks(cfg, theta, grid_n, brick, stored_ids, first, count, gt_mode, alpha, out_df, out_vec, ws=None):
+    """Fills the slots first .. first+count-1 of out_df (slots, B, B, B) and out_vec (slots, B, B, B, 3) with the fields of the bricks
+    stored_ids[first:first+count]; returns the device int32 counter of points that need the Hessian-eigenvector fallback."""
+    theta = _theta(cfg, theta)
+    npts = int(count) * int(brick) ** 3
+    ws = ws or query_workspace_for(cfg, npts, theta.device)
+    flag = torch.zeros(1, dtype=torch.int32, device=theta.device)
+    _call("dudf_grid_fields_bricks", ctypes.byref(cfg), _ptr(theta), int(grid_n), int(brick), _ptr(stored_ids[first:first + count]),
+          int(count), INVERSE_MODES[gt_mode], float(alpha), _ptr(out_df[first:first + count]), _ptr(out_vec[first:first + count]),
+          _ptr(flag), _ptr(ws.buf), ws.nbytes, dev=theta.device)
+    return flag
+
+
+def capudf_sparse_extract(df, vec, slot, candidate_ids, grid_n, brick, threshold=0.008, want_cells=False, want_counts=False):
+    """`capudf_extract` on brick storage: df (slots,B,B,B), vec (slots,B,B,B,3), the slot table and the ascending candidate list of
+    `sparse_select`.  Same outputs (cells: GLOBAL cell indices, candidate bricks ascending, local (i, j, k) order inside each); one
+    host sync for the three output sizes.  want_counts: the (cells, vertices, triangles) of the count call come back last."""
+    m, nb, nl = sparse_dims(grid_n, brick)
+    df = _tensor(df, "df", torch.float32, (brick,) * 3); vec = _tensor(vec, "vec", torch.float32, (brick,) * 3 + (3,))
+    slot = _tensor(slot, "slot", torch.int32); candidate_ids = _tensor(candidate_ids, "candidate_ids", torch.int32)
+    if slot.numel() != nl ** 3 or vec.shape[0] != df.shape[0] or candidate_ids.dim() != 1:
+        raise _lib.DudfError(f"capudf_sparse_extract: a slot table of {nl}^3 entries and df / vec of the same slots expected, got "
+                             f"{tuple(slot.shape)}, {tuple(df.shape)}, {tuple(vec.shape)}")
+    dev = df.device
+    ncand = int(candidate_ids.numel())
+    counts = torch.zeros(3, dtype=torch.int64, device=dev)
+    nc = nv = nt = 0
+    if ncand:
+        ws, nbytes = _workspace(dev, "dudf_capudf_sparse_workspace_bytes", int(grid_n), int(brick), ncand, err=-4)
+        head = (_ptr(df), _ptr(vec), _ptr(slot), _ptr(candidate_ids), ncand, int(grid_n), int(brick), float(threshold))
+        _call("dudf_capudf_sparse_count", *head, _ptr(counts), _ptr(ws), nbytes, dev=dev)
+        nc, nv, nt = [int(v) for v in counts.tolist()]
+    verts = torch.empty(nv, 3, dtype=torch.float64, device=dev)
+    tris = torch.empty(nt, 3, dtype=torch.int64, device=dev)
+    cells = torch.empty(nc, 3, dtype=torch.int64, device=dev) if want_cells else None
+    if nc:
+        _call("dudf_capudf_sparse_emit", *head, _ptr(verts), _ptr(tris), _ptr(cells), _ptr(ws), nbytes, dev=dev)
+    out = (verts, tris) + ((cells,) if want_cells else ())
+    return out + ((nc, nv, nt),) if want_counts else out
 
 
 MESH_CLEAN_COUNTS = ("vertices", "faces", "welded", "unreferenced", "duplicate_faces", "degenerate_faces", "holes3", "holes4",

@@ -12,6 +12,18 @@ from . import hip_ops
 from ._lib import DudfError
 
 
+def _eigenvector_fallback(cfg, theta, N, vec, rows, idx):
+    """The rare path of `extract_fields` (reference :77-93) for both field layouts: rows `rows` of `vec` (P, 3), which are the grid
+    points of linear index `idx` (first axis slowest), are recomputed with the Hessian frame — the top eigenvector, sign-aligned
+    with what the epilogue left there."""
+    voxel = 2.0 / (N - 1)
+    xyz = torch.stack([(idx // (N * N)) % N, (idx // N) % N, idx % N], 1).float() * voxel - 1.0
+    _, _, _, _, V = hip_ops.query_frame(cfg, theta, xyz)
+    n_hat = V[:, :, 2]
+    sign = torch.where((vec[rows] * n_hat).sum(-1, keepdim=True) < 0, -1.0, 1.0)
+    vec[rows] = sign * n_hat
+
+
 def extract_fields(decoder, latent_vec, N, gt_mode, device, alpha, chunk=1 << 20):
     """Same signature and return contract as the reference: (df_values (N,N,N), vecs (N,N,N,3)) float32 tensors on
     `device`.  df = inverse(gt_mode, |f|, alpha); vecs = -normalize(grad f), or the top Hessian eigenvector aligned with
@@ -40,15 +52,8 @@ def extract_fields(decoder, latent_vec, N, gt_mode, device, alpha, chunk=1 << 20
         flags.append((start, cnt, hip_ops.grid_fields(cfg, theta, N, start, cnt, gt_mode, alpha, df, vec, w)))
         start += cnt
     if int(torch.stack([f for _, _, f in flags]).sum()) > 0:
-        # rare path: recompute the flagged points with the Hessian frame (reference :77-93)
         bad = (vec.norm(dim=-1) < 0.04).nonzero().flatten()
-        idx = bad.to(torch.int64)
-        voxel = 2.0 / (N - 1)
-        xyz = torch.stack([(idx // (N * N)) % N, (idx // N) % N, idx % N], 1).float() * voxel - 1.0
-        _, _, _, _, V = hip_ops.query_frame(cfg, theta, xyz)
-        n_hat = V[:, :, 2]
-        sign = torch.where((vec[bad] * n_hat).sum(-1, keepdim=True) < 0, -1.0, 1.0)
-        vec[bad] = sign * n_hat
+        _eigenvector_fallback(cfg, theta, N, vec, bad, bad.to(torch.int64))
     return df.reshape(N, N, N), vec.reshape(N, N, N, 3)
 
 
@@ -102,12 +107,146 @@ def extract_mesh_CAP(ndf, grad, resolution, threshold=0.008, device=None):
     if d.shape[0] != resolution:
         raise ValueError("resolution does not match the field")
     v, f = hip_ops.capudf_extract(d, g, threshold)
-    v, f = v.cpu().numpy(), f.cpu().numpy()
+    return _as_mesh(v.cpu().numpy(), f.cpu().numpy())
+
+
+def _as_mesh(v, f):
     try:
         import trimesh
         return trimesh.Trimesh(v, f, process=False)
     except ImportError:
         return TriangleSoup(v, f)
+
+
+class SparseFields:
+    """The fields of `extract_fields` on a brick-sparse narrow band (layout: include/dudf_hip.h).
+
+    N, brick, threshold, lipschitz : what the bricks were selected for;
+    slot (nl,nl,nl) int32          : slot of a stored brick or -1, nl = (N-1) // brick + 1, slots in ascending brick id;
+    stored_ids, candidate_ids      : ascending int32 brick ids ((b0 * nl + b1) * nl + b2) of the stored bricks (slot order) and of
+                                     the candidate bricks, the ones whose cells are walked;
+    df (S,B,B,B), vec (S,B,B,B,3)  : float32 fields of the stored bricks; a point beyond the grid in a partial brick holds the
+                                     value at the clamped index and is never read.
+    All device tensors.  `to_dense` / `from_dense` are a gather and a scatter with torch indexing, for tests and debugging."""
+
+    def __init__(self, N, brick, threshold, lipschitz, slot, stored_ids, candidate_ids, df, vec):
+        self.N, self.brick, self.threshold, self.lipschitz = int(N), int(brick), float(threshold), float(lipschitz)
+        self.slot, self.stored_ids, self.candidate_ids, self.df, self.vec = slot, stored_ids, candidate_ids, df, vec
+
+    @property
+    def points_stored(self):
+        return int(self.stored_ids.numel()) * self.brick ** 3
+
+    def grid_index(self):
+        """(lin, valid), both (S,B,B,B): the linear grid index (first axis slowest, clamped to the grid) of every stored point and
+        whether the point lies in the grid (False: padding of a partial brick)."""
+        return _brick_grid_index(self.stored_ids, self.N, self.brick)
+
+    def to_dense(self, fill=float("nan")):
+        """(ndf (N,N,N), vec (N,N,N,3)) with `fill` wherever nothing is stored."""
+        N = self.N
+        lin, valid = self.grid_index()
+        ndf = torch.full((N ** 3,), fill, dtype=torch.float32, device=self.df.device)
+        vec = torch.full((N ** 3, 3), fill, dtype=torch.float32, device=self.df.device)
+        ndf[lin[valid]] = self.df[valid]
+        vec[lin[valid]] = self.vec[valid]
+        return ndf.reshape(N, N, N), vec.reshape(N, N, N, 3)
+
+    @classmethod
+    def from_dense(cls, ndf, vec, threshold=0.008, brick=8, lipschitz=1.25):
+        """The bricks `dudf_sparse_select` keeps for the dense device fields ndf (N,N,N), vec (N,N,N,3), filled from them."""
+        ndf = hip_ops._tensor(ndf, "ndf", torch.float32, convert=True)
+        vec = hip_ops._tensor(vec, "vec", torch.float32, convert=True)
+        N = ndf.shape[0]
+        if ndf.shape != (N, N, N) or vec.shape != (N, N, N, 3):
+            raise DudfError(f"SparseFields.from_dense: ndf (N,N,N) and vec (N,N,N,3) expected, got {tuple(ndf.shape)}, {tuple(vec.shape)}")
+        m, nb, nl = hip_ops.sparse_dims(N, brick)
+        at = torch.clamp(torch.arange(nb + 1, device=ndf.device) * brick, max=m)
+        coarse = ndf[at][:, at][:, :, at].contiguous()
+        slot, stored, cands = hip_ops.sparse_select(coarse, N, brick, hip_ops.sparse_bound(N, brick, threshold, lipschitz))
+        lin, _ = _brick_grid_index(stored, N, brick)
+        return cls(N, brick, threshold, lipschitz, slot, stored, cands, ndf.reshape(-1)[lin].contiguous(),
+                   vec.reshape(-1, 3)[lin].contiguous())
+
+    def extract(self, threshold=None, want_cells=False, want_counts=False):
+        """`hip_ops.capudf_sparse_extract` on these fields (device tensors); `threshold` at most the one they were selected for."""
+        thr = self.threshold if threshold is None else float(threshold)
+        if thr > self.threshold:
+            raise ValueError(f"threshold {thr} exceeds the {self.threshold} these bricks were selected for: cells could be missed")
+        return hip_ops.capudf_sparse_extract(self.df, self.vec, self.slot, self.candidate_ids, self.N, self.brick, thr,
+                                             want_cells=want_cells, want_counts=want_counts)
+
+
+def _brick_grid_index(stored_ids, N, brick):
+    m, nb, nl = hip_ops.sparse_dims(N, brick)
+    ids = stored_ids.to(torch.int64)
+    loc = torch.arange(brick, device=ids.device)
+    g = [(b * brick)[:, None] + loc for b in (ids // (nl * nl), (ids // nl) % nl, ids % nl)]               # (S, B) per axis
+    g0, g1, g2 = g[0][:, :, None, None], g[1][:, None, :, None], g[2][:, None, None, :]
+    valid = (g0 <= m) & (g1 <= m) & (g2 <= m)
+    lin = (g0.clamp(max=m) * N + g1.clamp(max=m)) * N + g2.clamp(max=m)
+    return lin, valid
+
+
+def extract_fields_sparse(decoder, latent_vec, N, gt_mode, device, alpha, threshold=0.008, brick=8, lipschitz=1.25, chunk=1 << 20):
+    """`extract_fields` on a narrow band: the network is evaluated on a coarse lattice (every `brick`-th grid point, value only),
+    the bricks that can hold a cell with a corner value <= `threshold` are selected, and the fine grid is evaluated inside those
+    only.  Returns a `SparseFields`; `extract_mesh_CAP_sparse` meshes it.  A stored point has the coordinates,
+    and therefore the chunk-independent values, of the dense grid.
+
+    The selection keeps a cell brick when a corner of it has df <= threshold + lipschitz * (half the brick's diagonal).  That covers
+    every active cell IF df changes by at most `lipschitz` per unit length.  `lipschitz` is the caller's statement about their field:
+    a distance field has 1, the default 1.25 leaves a learned one a quarter of slack, and nothing here can verify it — where a
+    learned field is steeper than that between lattice points, cells can be missed.  The dense path stays the exact one
+    (`tools/bench_sparse_mc.py` reports the difference of the two emitted-cell sets for a checkpoint).
+
+    Memory: 16 bytes per stored point, plus the sweeps' workspace of one chunk — about 16 KB per point of `chunk` for an 8x256
+    network, 16 GB at the default 2^20, which `extract_fields` allocates too; `chunk=1 << 16` brings it to 1 GB."""
+    if latent_vec is not None and torch.as_tensor(latent_vec).numel() != 0:
+        raise DudfError("extract_fields_sparse: latent vectors are not part of the HIP path")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise DudfError("extract_fields_sparse: needs the GPU; there is no CPU fallback path")
+    m, nb, nl = hip_ops.sparse_dims(N, brick)
+    cfg = decoder.hip_cfg
+    theta = decoder.flat_parameters()
+    B3 = brick ** 3
+
+    def chunks(total, step):                               # one workspace, sized for a whole chunk, serves the shorter last call too
+        if total == 0:
+            return
+        ws = hip_ops.query_workspace_for(cfg, min(step, total), dev)
+        for start in range(0, total, step):
+            yield start, min(step, total - start), ws
+
+    coarse = torch.empty((nb + 1) ** 3, dtype=torch.float32, device=dev)
+    for start, cnt, w in chunks(coarse.numel(), chunk):
+        hip_ops.grid_fields_lattice(cfg, theta, N, brick, start, cnt, gt_mode, alpha, coarse, None, w)
+    slot, stored, cands = hip_ops.sparse_select(coarse, N, brick, hip_ops.sparse_bound(N, brick, threshold, lipschitz))
+    del coarse
+    S = int(stored.numel())
+    if S * B3 > 2 ** 31 - 1:
+        raise DudfError(f"extract_fields_sparse: {S} bricks of {B3} points exceed 2^31 - 1 stored points; lower N, threshold or lipschitz")
+    df = torch.empty(S, brick, brick, brick, dtype=torch.float32, device=dev)
+    vec = torch.empty(S, brick, brick, brick, 3, dtype=torch.float32, device=dev)
+    per = max(1, chunk // B3)                              # bricks per call
+    flags = [hip_ops.grid_fields_bricks(cfg, theta, N, brick, stored, s // B3, c // B3, gt_mode, alpha, df, vec, w)
+             for s, c, w in chunks(S * B3, per * B3)]
+    if flags and int(torch.stack(flags).sum()) > 0:
+        flat = vec.view(-1, 3)
+        bad = (flat.norm(dim=-1) < 0.04).nonzero().flatten()
+        lin, _ = _brick_grid_index(stored, N, brick)
+        _eigenvector_fallback(cfg, theta, N, flat, bad, lin.reshape(-1)[bad])
+    return SparseFields(N, brick, threshold, lipschitz, slot, stored, cands, df, vec)
+
+
+def extract_mesh_CAP_sparse(fields, threshold=None):
+    """`extract_mesh_CAP` on the `SparseFields` of `extract_fields_sparse`: the same per-cell code (`dudf_capudf_sparse_count` /
+    `_emit`) over the cells of the candidate bricks, so wherever both paths walk a cell they emit the same triangles bit for bit.
+    `threshold` defaults to the one the fields were selected for and may not exceed it (ValueError).  Returns a
+    `trimesh.Trimesh(process=False)` when trimesh is importable, else a `TriangleSoup`."""
+    v, f = fields.extract(threshold)
+    return _as_mesh(v.cpu().numpy(), f.cpu().numpy())
 
 
 def extract_mesh_MESHUDF(df_values, normals, device, smooth_borders=False, luts=None, clean=None, **kwargs):

@@ -14,25 +14,40 @@ The MeshUDF mesh is cleaned as the reference cleans it (weld, duplicate / degene
 where it is installed, otherwise on the device (`diffudf_amd.meshclean`).
 'siren' (reference generate_mc.py:56-65): `get_mesh_sdf` — the raw network values on the grid and Lewiner's marching cubes of
 that signed volume, both on the device; it needs the same tables, and without them prints a message, writes nothing and returns
-None (as 'both' skips its MeshUDF half), so that a training run is not lost over its mesh."""
+None (as 'both' skips its MeshUDF half), so that a training run is not lost over its mesh.
+Optional key "sparse": true (with "brick", 4 or 8, and "lipschitz"; keyword `sparse=`): 'cap' on a brick-sparse narrow band
+(`extract_fields_sparse` + `extract_mesh_CAP_sparse`) — for 1024^3 and up, where the dense fields do not fit.  The
+other algorithms need the dense volume (MeshUDF's flood is a host walk of it) and refuse the key."""
 import json
 import sys
 
 import torch
 
 from src.model import SIREN
-from src.render_mc import extract_fields, extract_mesh_CAP, extract_mesh_MESHUDF, get_mesh_sdf
+from src.render_mc import (extract_fields, extract_fields_sparse, extract_mesh_CAP, extract_mesh_CAP_sparse, extract_mesh_MESHUDF,
+                           get_mesh_sdf)
+from diffudf_amd._lib import DudfError
 from diffudf_amd.marching_cubes import MeshUDFError
 
 
-def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='meshudf', from_file=None, luts=None):
-    """`luts`: the Lewiner tables for MeshUDF and 'siren' (dict, path or None = look them up; see the module docstring)."""
+def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='meshudf', from_file=None, luts=None, sparse=False,
+                brick=8, lipschitz=1.25):
+    """`luts`: the Lewiner tables for MeshUDF and 'siren' (dict, path or None = look them up; see the module docstring).
+    `sparse`: CAP-UDF on the narrow band of `extract_fields_sparse(..., brick=brick, lipschitz=lipschitz)`; 'cap' only."""
+    if sparse and algorithm != 'cap':
+        raise DudfError(f"sparse extraction serves algorithm 'cap' only; '{algorithm}' needs the dense volume")
     if from_file is not None:
         model = SIREN(n_in_features=3, n_out_features=1, hidden_layer_config=from_file["hidden_layer_nodes"],
                       w0=from_file["w0"], ww=from_file.get("ww"), activation=from_file.get('activation', 'sine'))
         model.load_state_dict(torch.load(from_file["model_path"], weights_only=True))
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     model.to(dev)
+    if sparse:
+        mesh = extract_mesh_CAP_sparse(extract_fields_sparse(model, torch.Tensor([[]]).to(dev), N, gt_mode, dev, alpha, brick=brick,
+                                                             lipschitz=lipschitz))
+        mesh.export(output_path)
+        print(f'Saved to {output_path}')
+        return mesh
     if algorithm in ('cap', 'both', 'meshudf'):
         u, g = extract_fields(model, torch.Tensor([[]]).to(dev), N, gt_mode, dev, alpha)
         dot = output_path.rfind('.')
@@ -74,4 +89,5 @@ if __name__ == "__main__":
                 cfg["algorithm"], from_file={"w0": cfg["w0"], "model_path": cfg["model_path"],
                                              "hidden_layer_nodes": cfg["hidden_layer_nodes"],
                                              "activation": cfg.get("activation", "sine"), "ww": cfg.get("ww")},
-                luts=cfg.get("luts_path"))
+                luts=cfg.get("luts_path"), sparse=bool(cfg.get("sparse", False)), brick=cfg.get("brick", 8),
+                lipschitz=cfg.get("lipschitz", 1.25))

@@ -449,6 +449,52 @@ int dudf_capudf_count(const float* ndf, const float* grad, int64_t grid_n, doubl
 int dudf_capudf_emit(const float* ndf, const float* grad, int64_t grid_n, double threshold, double* out_vertices,
                      int64_t* out_triangles, int64_t* out_cells, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same extraction on a brick-sparse narrow band, for grids whose N^3 fields are out of reach.  The dense calls
+ * above are the exact ones; these evaluate the network only where the selection rule below allows an active cell.
+ *   grid_n = N >= 2 points per side, m = N - 1 cells, brick edge B = `brick` in {4, 8}.  Brick (b0, b1, b2) owns the grid points
+ *   [b_d B, b_d B + B) per axis; the storage lattice has nl = m / B + 1 bricks per side, brick id = (b0 nl + b1) nl + b2; the cell
+ *   bricks are those with every b_d < nb = ceil(m / B).  Storage: df [slot][B][B][B] float, vec [slot][B][B][B][3] float, slot
+ *   [nl^3] int32 = the slot of a stored brick or -1, slots in ascending brick id.  Coordinates are formed from the index as
+ *   dudf_grid_fields forms them, so a stored point has the dense grid's coordinates bit for bit; points of a partial brick beyond
+ *   index m are evaluated at the clamped index and never read.
+ * dudf_grid_fields_lattice: points start .. start+count-1 of the coarse lattice of (nb + 1)^3 points (first axis slowest) at fine
+ *   indices min(c_d B, m); out_df, out_vec, out_flag_count as dudf_grid_fields; out_vec NULL: value only, no reverse sweep, no flag
+ *   count.  Workspace of dudf_workspace_bytes_query with (cfg, count, 0).
+ * dudf_sparse_select: coarse_df = that lattice.  A cell brick is a CANDIDATE when the minimum over its 8 lattice corners, compared
+ *   as double, is <= bound, or a corner is NaN; a brick is STORED when it is a candidate b or a brick b + delta, delta in {0,1}^3,
+ *   of a candidate inside the lattice: every corner of every cell of a candidate brick is then stored exactly once.  The caller
+ *   forms bound = threshold + L (sqrt(3) / 2) B (2 / (N - 1)) in double for an L-Lipschitz df.  Outputs (device): out_slot [nl^3],
+ *   out_stored_ids and out_candidate_ids (ascending brick ids, room for nl^3 int32 each), out_counts 2 x int64 = stored, candidate
+ *   bricks.  No atomics: the result is the same on every run.  Workspace: dudf_sparse_select_bytes with (grid_n, brick).
+ * dudf_grid_fields_bricks: df and vec of the B^3 points of each of the n_bricks bricks listed at brick_ids (a range of the stored
+ *   list), through the sweeps and epilogue of dudf_grid_fields; out_df / out_vec point at the first of these bricks' slots (a range of
+ *   slots is contiguous).  Workspace of dudf_workspace_bytes_query with (cfg, n_bricks B^3, 0).
+ * dudf_capudf_sparse_count / _emit: dudf_capudf_count / _emit over the cells of the n_candidates candidate bricks, one thread per
+ *   cell, a cell's 8 corners addressed through `slot` — the active test, sign rule, table, interpolation and vertex formula (with the
+ *   GLOBAL cell index) are the dense kernels' own code.  Cells beyond m in a partial brick are skipped; a corner in a brick that is
+ *   not stored reads as NaN (the cell is skipped).  Emission order: candidate bricks ascending, cells in local (i, j, k) order.
+ *   Outputs as the dense calls; out_cells holds global cell indices.  Workspace: dudf_capudf_sparse_workspace_bytes with (grid_n, brick,
+ *   n_candidates).
+ * Refusals, all before the first device call: brick not in {4, 8}, grid_n < 2, a NULL required pointer, a range outside the lattice:
+ *   DUDF_E_BADCFG; a bad inverse_mode: DUDF_E_BADMODE; more than 2^31 - 1 lattice entries or points in one call: DUDF_E_UNSUPPORTED
+ *   — the coarse lattice sets the largest grid: (nb + 1)^3 <= 2^31 - 1, that is N <= 10313 with B = 8 and N <= 5157 with B = 4. */
+int dudf_grid_fields_lattice(const dudf_net_cfg* cfg, const float* theta, int64_t grid_n, int brick, int64_t start, int64_t count,
+                             int inverse_mode, double alpha, float* out_df, float* out_vec, int* out_flag_count, void* workspace,
+                             size_t workspace_bytes, void* stream);
+size_t dudf_sparse_select_bytes(int64_t grid_n, int brick);
+int dudf_sparse_select(const float* coarse_df, int64_t grid_n, int brick, double bound, int32_t* out_slot, int32_t* out_stored_ids,
+                       int32_t* out_candidate_ids, int64_t* out_counts, void* workspace, size_t workspace_bytes, void* stream);
+int dudf_grid_fields_bricks(const dudf_net_cfg* cfg, const float* theta, int64_t grid_n, int brick, const int32_t* brick_ids,
+                            int64_t n_bricks, int inverse_mode, double alpha, float* out_df, float* out_vec, int* out_flag_count,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t dudf_capudf_sparse_workspace_bytes(int64_t grid_n, int brick, int64_t n_candidates);
+int dudf_capudf_sparse_count(const float* df, const float* vec, const int32_t* slot, const int32_t* candidate_ids,
+                             int64_t n_candidates, int64_t grid_n, int brick, double threshold, int64_t* out_counts,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int dudf_capudf_sparse_emit(const float* df, const float* vec, const int32_t* slot, const int32_t* candidate_ids,
+                            int64_t n_candidates, int64_t grid_n, int brick, double threshold, double* out_vertices,
+                            int64_t* out_triangles, int64_t* out_cells, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The raw network output on the grid — the value loop of `get_mesh_sdf` (reference src/render_mc.py:335-348) for grid points
  * start .. start+count-1 of the regular grid_n^3 grid on [-1,1]^3 (indexing and coordinates as dudf_grid_fields): out_f (count) = f,
  * sign kept — no |.|, no inverse map, no gradient (the forward sweep only).  Workspace of dudf_workspace_bytes_query(cfg, count, 0). */
