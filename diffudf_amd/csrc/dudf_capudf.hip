@@ -84,9 +84,8 @@ int dudf_capudf_count(const float* ndf, const float* grad, int64_t grid_n, doubl
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     const int64_t nb = cap_blocks(grid_n);
-    hipLaunchKernelGGL(capudf_count_kernel<DenseAddr>, dim3((unsigned)nb), dim3(CB), 0, st, a.ad, a.w);
-    hipLaunchKernelGGL(dudf_scan_totals_kernel<3>, dim3(1), dim3(1024), 0, st, a.w.blk, a.w.off, nb, out_counts);
-    return (int)hipGetLastError();
+    DUDF_TRY(dudf_launch(capudf_count_kernel<DenseAddr>, dim3((unsigned)nb), dim3(CB), st, a.ad, a.w));
+    return dudf_launch(dudf_scan_totals_kernel<3>, dim3(1), dim3(1024), st, a.w.blk, a.w.off, nb, out_counts);
 }
 
 int dudf_capudf_emit(const float* ndf, const float* grad, int64_t grid_n, double threshold, double* out_vertices,
@@ -98,8 +97,7 @@ int dudf_capudf_emit(const float* ndf, const float* grad, int64_t grid_n, double
     a.w.verts = out_vertices; a.w.tris = out_triangles; a.w.cells = out_cells;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(capudf_emit_kernel<DenseAddr>, dim3((unsigned)cap_blocks(grid_n)), dim3(CB), 0, st, a.ad, a.w);
-    return (int)hipGetLastError();
+    return dudf_launch(capudf_emit_kernel<DenseAddr>, dim3((unsigned)cap_blocks(grid_n)), dim3(CB), st, a.ad, a.w);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 //   - a finishing kernel unpacks the keys.
 // Every pair is evaluated by the same expression, so the result is a pure function of the inputs: repeated calls are bit-identical.
 #include "dudf_context.h"
+#include "dudf_ordsum.h"
 #include "dudf_pairdist.h"
 
 namespace {
@@ -87,18 +88,14 @@ __global__ __launch_bounds__(256) void nearest_finish_kernel(const unsigned long
 }
 
 // ---- sums behind the mean reductions --------------------------------------------------------------------------------------------
-constexpr int kTermsBlock = 256;
-constexpr int kTermsMaxGroups = 256;             // partials the single finishing workgroup adds in index order
-
-// Two doubles per workgroup: sum of dist and sum of 1 - |cos(x normal, normal of the nearest y row)|.  Each thread adds its rows in
-// ascending order, the workgroup adds its threads in a fixed tree: a function of (n, inputs) only.
-__global__ __launch_bounds__(kTermsBlock) void chamfer_partial_kernel(const float* __restrict__ dist, const int64_t* __restrict__ idx,
-                                                                      int64_t n, const float* __restrict__ xn,
-                                                                      const float* __restrict__ yn, int64_t m,
-                                                                      double* __restrict__ partials) {
-    __shared__ double sd[kTermsBlock], sn[kTermsBlock];
+// Two doubles per workgroup: sum of dist and sum of 1 - |cos(x normal, normal of the nearest y row)|, as ordered sums (dudf_ordsum.h):
+// a function of (n, inputs) only.
+__global__ __launch_bounds__(kOrdSumBlock) void chamfer_partial_kernel(const float* __restrict__ dist, const int64_t* __restrict__ idx,
+                                                                       int64_t n, const float* __restrict__ xn,
+                                                                       const float* __restrict__ yn, int64_t m,
+                                                                       double* __restrict__ partials) {
     double a = 0.0, b = 0.0;
-    for (int64_t p = (int64_t)blockIdx.x * kTermsBlock + threadIdx.x; p < n; p += (int64_t)gridDim.x * kTermsBlock) {
+    for (int64_t p = (int64_t)blockIdx.x * kOrdSumBlock + threadIdx.x; p < n; p += (int64_t)gridDim.x * kOrdSumBlock) {
         a += (double)dist[p];
         if (xn) {
             const int64_t j = idx[p];
@@ -110,25 +107,17 @@ __global__ __launch_bounds__(kTermsBlock) void chamfer_partial_kernel(const floa
             b += 1.0 - fabs(c);
         }
     }
-    sd[threadIdx.x] = a; sn[threadIdx.x] = b;
-    __syncthreads();
-    for (int s = kTermsBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { sd[threadIdx.x] += sd[threadIdx.x + s]; sn[threadIdx.x] += sn[threadIdx.x + s]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { partials[2 * blockIdx.x] = sd[0]; partials[2 * blockIdx.x + 1] = sn[0]; }
+    const double sums[2] = {a, b};
+    dudf_ordsum_partial<kOrdSumBlock>(sums, partials);
 }
 
-__global__ __launch_bounds__(kTermsMaxGroups) void chamfer_final_kernel(const double* __restrict__ partials, int count, int with_normals,
-                                                                        double* __restrict__ out_sums) {
-    __shared__ double sd[kTermsMaxGroups], sn[kTermsMaxGroups];
-    if ((int)threadIdx.x < count) { sd[threadIdx.x] = partials[2 * threadIdx.x]; sn[threadIdx.x] = partials[2 * threadIdx.x + 1]; }
-    __syncthreads();
+__global__ __launch_bounds__(kOrdSumMaxGroups) void chamfer_final_kernel(const double* __restrict__ partials, int count, int with_normals,
+                                                                         double* __restrict__ out_sums) {
+    double sums[2];
+    dudf_ordsum_finish(partials, count, sums);
     if (threadIdx.x == 0) {
-        double a = 0.0, b = 0.0;
-        for (int i = 0; i < count; ++i) { a += sd[i]; b += sn[i]; }         // index order
-        out_sums[0] = a;
-        if (with_normals) out_sums[1] = b;
+        out_sums[0] = sums[0];
+        if (with_normals) out_sums[1] = sums[1];
     }
 }
 
@@ -160,8 +149,6 @@ __global__ __launch_bounds__(256) void vertex_normalize_kernel(const double* __r
     }
 }
 
-inline int terms_groups(int64_t n) { return dudf_grid_for(n, kTermsBlock, kTermsMaxGroups); }
-
 }  // namespace
 
 extern "C" {
@@ -180,8 +167,7 @@ int dudf_nearest_points(const float* x, int64_t n, const float* y, int64_t m, in
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(workspace);
-    hipError_t e = hipMemsetAsync(keys, 0xff, (size_t)n * sizeof(unsigned long long), st);
-    if (e != hipSuccess) return (int)e;
+    DUDF_TRY(hipMemsetAsync(keys, 0xff, (size_t)n * sizeof(unsigned long long), st));
     // split y so that the launch has about kNnTargetGroups workgroups, each split at least one LDS tile long
     const int64_t xgroups = (n + kNnRows - 1) / kNnRows;
     int64_t splits = kNnTargetGroups / xgroups;
@@ -192,19 +178,14 @@ int dudf_nearest_points(const float* x, int64_t n, const float* y, int64_t m, in
     const int64_t ychunk = (m + splits - 1) / splits;
     splits = (m + ychunk - 1) / ychunk;                  // no empty split: every workgroup's first index lies in [0, m)
     const dim3 grid((unsigned)xgroups, (unsigned)splits);
-    if (norm == 2)
-        hipLaunchKernelGGL(nearest_kernel<2>, grid, dim3(kNnBlock), 0, st, x, n, y, (int)m, (int)ychunk, keys);
-    else
-        hipLaunchKernelGGL(nearest_kernel<1>, grid, dim3(kNnBlock), 0, st, x, n, y, (int)m, (int)ychunk, keys);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    DUDF_TRY(dudf_launch(norm == 2 ? nearest_kernel<2> : nearest_kernel<1>, grid, dim3(kNnBlock), st, x, n, y, (int)m, (int)ychunk, keys));
     if (out_dist || out_idx)
-        hipLaunchKernelGGL(nearest_finish_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), 0, st, keys, n, (int)m,
-                           out_dist, out_idx);
-    return (int)hipGetLastError();
+        DUDF_TRY(dudf_launch(nearest_finish_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), st, keys, n, (int)m, out_dist,
+                             out_idx));
+    return 0;
 }
 
-size_t dudf_chamfer_terms_workspace_bytes(int64_t n) { return dudf_round256((size_t)terms_groups(n) * 2 * sizeof(double)); }   // >= 1 group: >= 256
+size_t dudf_chamfer_terms_workspace_bytes(int64_t n) { return dudf_round256((size_t)dudf_ordsum_groups(n) * 2 * sizeof(double)); }   // >= 1 group: >= 256
 
 int dudf_chamfer_terms(const float* dist, const int64_t* idx, int64_t n, const float* x_normals, const float* y_normals, int64_t m,
                        double* out_sums, void* workspace, size_t workspace_bytes, void* stream) {
@@ -215,14 +196,10 @@ int dudf_chamfer_terms(const float* dist, const int64_t* idx, int64_t n, const f
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     double* partials = reinterpret_cast<double*>(workspace);
-    const int groups = n > 0 ? terms_groups(n) : 0;
-    if (groups > 0) {
-        hipLaunchKernelGGL(chamfer_partial_kernel, dim3(groups), dim3(kTermsBlock), 0, st, dist, idx, n, x_normals, y_normals, m, partials);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(chamfer_final_kernel, dim3(1), dim3(kTermsMaxGroups), 0, st, partials, groups, x_normals ? 1 : 0, out_sums);
-    return (int)hipGetLastError();
+    const int groups = n > 0 ? dudf_ordsum_groups(n) : 0;
+    if (groups > 0)
+        DUDF_TRY(dudf_launch(chamfer_partial_kernel, dim3(groups), dim3(kOrdSumBlock), st, dist, idx, n, x_normals, y_normals, m, partials));
+    return dudf_launch(chamfer_final_kernel, dim3(1), dim3(kOrdSumMaxGroups), st, partials, groups, x_normals ? 1 : 0, out_sums);
 }
 
 size_t dudf_vertex_normals_workspace_bytes(int64_t n_vertices) {
@@ -238,17 +215,11 @@ int dudf_vertex_normals(const double* vertices, int64_t n_vertices, const int64_
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     double* acc = reinterpret_cast<double*>(workspace);
-    hipError_t e = hipMemsetAsync(acc, 0, (size_t)n_vertices * 3 * sizeof(double), st);
-    if (e != hipSuccess) return (int)e;
-    if (n_faces > 0) {
-        hipLaunchKernelGGL(face_normals_kernel, dim3(dudf_grid_for(n_faces, 256, kGridCap)), dim3(256), 0, st, vertices,
-                           n_vertices, faces, n_faces, acc);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(vertex_normalize_kernel, dim3(dudf_grid_for(n_vertices, 256, kGridCap)), dim3(256), 0, st, acc, n_vertices,
-                       out_normals);
-    return (int)hipGetLastError();
+    DUDF_TRY(hipMemsetAsync(acc, 0, (size_t)n_vertices * 3 * sizeof(double), st));
+    if (n_faces > 0)
+        DUDF_TRY(dudf_launch(face_normals_kernel, dim3(dudf_grid_for(n_faces, 256, kGridCap)), dim3(256), st, vertices, n_vertices, faces,
+                             n_faces, acc));
+    return dudf_launch(vertex_normalize_kernel, dim3(dudf_grid_for(n_vertices, 256, kGridCap)), dim3(256), st, acc, n_vertices, out_normals);
 }
 
 }  // extern "C"

@@ -8,23 +8,22 @@
 // thread walks its row of knn_idx twice (mean, then the centred outer products), keeps six fp64 sums and hands the lower triangle to
 // eigh3 (dudf_eigh3.h).  No array is indexed by a run-time value: nothing leaves the registers.
 //
-// Outliers.  d_i = mean of sqrt(dist) over the finite slots of row i; mu and sigma of the finite d_i by per-workgroup partials that
-// one workgroup adds in index order (as dudf_chamfer_terms does), sigma from the centred second pass; keep = d_i <= mu + ratio * sigma;
+// Outliers.  d_i = mean of sqrt(dist) over the finite slots of row i; mu and sigma of the finite d_i as ordered sums
+// (dudf_ordsum.h: per-workgroup partials that one workgroup adds in index order), sigma from the centred second pass; keep = d_i <= mu + ratio * sigma;
 // the kept rows are compacted in ascending order with dudf_wgscan.h (tile counts, dudf_scan_totals_kernel<1>, scatter).  No atomics.
 #include "dudf_context.h"
 #include "dudf_eigh3.h"
+#include "dudf_ordsum.h"
+#include "dudf_pairdist.h"
 #include "dudf_wgscan.h"
 
 namespace {
 
 constexpr int kBlock = DUDF_WG;                  // threads per workgroup; the compaction's tile
+static_assert(kBlock == kOrdSumBlock, "the sums' launches are sized by dudf_ordsum_groups");
 constexpr int kGridCap = 4096;                   // workgroups of the row-wise launches; the kernels stride over the rest
 constexpr int kMaxK = 16;
-constexpr int kSumMaxGroups = 256;               // partials the single finishing workgroup adds in index order
-constexpr float kFltMax = 3.402823466e+38f;
 constexpr double kDblMax = 1.7976931348623157e+308;
-
-__device__ __forceinline__ bool finite3(float a, float b, float c) { return fabsf(a) <= kFltMax && fabsf(b) <= kFltMax && fabsf(c) <= kFltMax; }
 
 // ---- normals -------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void cloud_pack_kernel(const float* __restrict__ pts, int64_t n, float4* __restrict__ p4) {
@@ -91,17 +90,7 @@ __global__ __launch_bounds__(kBlock) void estimate_normals_kernel(const float4* 
 }
 
 // ---- outliers: the statistics ----------------------------------------------------------------------------------------------------------
-// a workgroup's threads in a fixed tree; the result in sd[0] / sc[0]
-__device__ __forceinline__ void wg_tree_sum(double* sd, unsigned long long* sc) {
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { sd[threadIdx.x] += sd[threadIdx.x + s]; sc[threadIdx.x] += sc[threadIdx.x + s]; }
-        __syncthreads();
-    }
-}
-
-// d_i of every row, and per workgroup the sum and the number of the finite ones.  Each thread adds its rows in ascending order, the
-// workgroup adds its threads in a fixed tree: a function of (n, inputs) only.
+// d_i of every row, and per workgroup the ordered sum (dudf_ordsum.h) and the number of the finite ones: a function of (n, inputs) only.
 __global__ __launch_bounds__(kBlock) void outlier_mean_kernel(const float* __restrict__ dist, int64_t n, int K, double* __restrict__ mean_dist,
                                                               double* __restrict__ psum, unsigned long long* __restrict__ pcnt) {
     __shared__ double sd[kBlock];
@@ -121,51 +110,42 @@ __global__ __launch_bounds__(kBlock) void outlier_mean_kernel(const float* __res
         if (fabs(m) <= kDblMax) { a += m; ++cnt; }
     }
     sd[threadIdx.x] = a; sc[threadIdx.x] = cnt;
-    wg_tree_sum(sd, sc);
+    dudf_wg_tree<kBlock>(dudf_sum_of(sd), dudf_sum_of(sc));
     if (threadIdx.x == 0) { psum[blockIdx.x] = sd[0]; pcnt[blockIdx.x] = sc[0]; }
 }
 
 // stat: [0] mu, [1] sigma, [2] threshold; *total: the finite rows
-__global__ __launch_bounds__(kSumMaxGroups) void outlier_mu_kernel(const double* __restrict__ psum, const unsigned long long* __restrict__ pcnt,
-                                                                   int groups, double* __restrict__ stat, unsigned long long* __restrict__ total) {
-    __shared__ double sd[kSumMaxGroups];
-    __shared__ unsigned long long sc[kSumMaxGroups];
-    if ((int)threadIdx.x < groups) { sd[threadIdx.x] = psum[threadIdx.x]; sc[threadIdx.x] = pcnt[threadIdx.x]; }
-    __syncthreads();
+__global__ __launch_bounds__(kOrdSumMaxGroups) void outlier_mu_kernel(const double* __restrict__ psum, const unsigned long long* __restrict__ pcnt,
+                                                                      int groups, double* __restrict__ stat, unsigned long long* __restrict__ total) {
+    double a[1];
+    unsigned long long c[1];
+    dudf_ordsum_finish(psum, groups, a);
+    dudf_ordsum_finish(pcnt, groups, c);
     if (threadIdx.x == 0) {
-        double a = 0.0;
-        unsigned long long c = 0;
-        for (int i = 0; i < groups; ++i) { a += sd[i]; c += sc[i]; }     // index order
-        stat[0] = a / (double)c;                                        // no finite row: NaN, and no row passes the test
-        *total = c;
+        stat[0] = a[0] / (double)c[0];                                  // no finite row: NaN, and no row passes the test
+        *total = c[0];
     }
 }
 
 __global__ __launch_bounds__(kBlock) void outlier_var_kernel(const double* __restrict__ mean_dist, int64_t n, const double* __restrict__ stat,
                                                              double* __restrict__ psum) {
-    __shared__ double sd[kBlock];
-    __shared__ unsigned long long sc[kBlock];
     const double mu = stat[0];
     double a = 0.0;
     for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p += (int64_t)gridDim.x * kBlock) {
         const double m = mean_dist[p];
         if (fabs(m) <= kDblMax) { const double d = m - mu; a += d * d; }
     }
-    sd[threadIdx.x] = a; sc[threadIdx.x] = 0;
-    wg_tree_sum(sd, sc);
-    if (threadIdx.x == 0) psum[blockIdx.x] = sd[0];
+    const double sums[1] = {a};
+    dudf_ordsum_partial<kBlock>(sums, psum);
 }
 
-__global__ __launch_bounds__(kSumMaxGroups) void outlier_sigma_kernel(const double* __restrict__ psum, int groups,
-                                                                      const unsigned long long* __restrict__ total, double std_ratio,
-                                                                      double* __restrict__ stat, double* __restrict__ out_stats) {
-    __shared__ double sd[kSumMaxGroups];
-    if ((int)threadIdx.x < groups) sd[threadIdx.x] = psum[threadIdx.x];
-    __syncthreads();
+__global__ __launch_bounds__(kOrdSumMaxGroups) void outlier_sigma_kernel(const double* __restrict__ psum, int groups,
+                                                                         const unsigned long long* __restrict__ total, double std_ratio,
+                                                                         double* __restrict__ stat, double* __restrict__ out_stats) {
+    double a[1];
+    dudf_ordsum_finish(psum, groups, a);
     if (threadIdx.x == 0) {
-        double a = 0.0;
-        for (int i = 0; i < groups; ++i) a += sd[i];                    // index order
-        const double mu = stat[0], sigma = sqrt(a / (double)*total), thr = mu + std_ratio * sigma;
+        const double mu = stat[0], sigma = sqrt(a[0] / (double)*total), thr = mu + std_ratio * sigma;
         stat[1] = sigma; stat[2] = thr;
         if (out_stats) { out_stats[0] = mu; out_stats[1] = sigma; out_stats[2] = thr; }
     }
@@ -201,8 +181,6 @@ __global__ __launch_bounds__(kBlock) void outlier_scatter_kernel(const double* _
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------
-#define CLOUD_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
-
 inline bool cloud_sizes_supported(int64_t n, int K) { return n < ((int64_t)1 << 31) && K >= 1 && K <= kMaxK; }
 
 struct NormalsLayout { float4* p4; size_t bytes; };            // [n] the cloud, one 16-byte row per point
@@ -215,7 +193,7 @@ inline NormalsLayout carve_normals(void* ws, int64_t n) {
 }
 
 struct OutlierLayout {
-    double* psum; unsigned long long* pcnt;                    // [kSumMaxGroups] the partials of a pass
+    double* psum; unsigned long long* pcnt;                    // [kOrdSumMaxGroups] the partials of a pass
     double* stat;                                              // [4] mu, sigma, threshold
     unsigned long long* finite;                                // [1] rows with a finite d
     int64_t* kept;                                             // [1] the kept rows, when the caller does not ask for them
@@ -226,7 +204,7 @@ inline OutlierLayout carve_outliers(void* ws, int64_t n) {
     OutlierLayout l;
     l.ntiles = (n + kBlock - 1) / kBlock;
     DudfByteCarver cv = dudf_carve(ws);
-    l.psum = cv.take<double>(kSumMaxGroups); l.pcnt = cv.take<unsigned long long>(kSumMaxGroups);
+    l.psum = cv.take<double>(kOrdSumMaxGroups); l.pcnt = cv.take<unsigned long long>(kOrdSumMaxGroups);
     l.stat = cv.take<double>(4); l.finite = cv.take<unsigned long long>(1); l.kept = cv.take<int64_t>(1);
     l.blk = cv.take<uint32_t>(l.ntiles); l.off = cv.take<int64_t>(l.ntiles);
     l.bytes = cv.o;
@@ -253,12 +231,9 @@ int dudf_estimate_normals(const float* points, const int64_t* knn_idx, int64_t n
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     const dim3 rows(dudf_grid_for(n, kBlock, kGridCap)), blk(kBlock);
-    hipLaunchKernelGGL(cloud_pack_kernel, rows, blk, 0, st, points, n, l.p4);
-    CLOUD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(estimate_normals_kernel, rows, blk, 0, st, l.p4, knn_idx, n, K, include_self ? 1 : 0, out_normals, out_eigenvalues,
+    DUDF_TRY(dudf_launch(cloud_pack_kernel, rows, blk, st, points, n, l.p4));
+    return dudf_launch(estimate_normals_kernel, rows, blk, st, l.p4, knn_idx, n, K, include_self ? 1 : 0, out_normals, out_eigenvalues,
                        out_count);
-    CLOUD_CHECK_LAUNCH();
-    return 0;
 }
 
 size_t dudf_cloud_outliers_workspace_bytes(int64_t n, int K) {
@@ -277,23 +252,15 @@ int dudf_cloud_outliers(const float* knn_dist, int64_t n, int K, double std_rati
     if (int rc = dudf_check_buffer(workspace, workspace_bytes, l.bytes)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    const int groups = dudf_grid_for(n, kBlock, kSumMaxGroups);
+    const int groups = dudf_ordsum_groups(n);
     const dim3 tiles(dudf_grid_for(n, kBlock, kGridCap)), blk(kBlock);
-    hipLaunchKernelGGL(outlier_mean_kernel, dim3(groups), blk, 0, st, knn_dist, n, K, out_mean_dist, l.psum, l.pcnt);
-    CLOUD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(outlier_mu_kernel, dim3(1), dim3(kSumMaxGroups), 0, st, l.psum, l.pcnt, groups, l.stat, l.finite);
-    CLOUD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(outlier_var_kernel, dim3(groups), blk, 0, st, out_mean_dist, n, l.stat, l.psum);
-    CLOUD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(outlier_sigma_kernel, dim3(1), dim3(kSumMaxGroups), 0, st, l.psum, groups, l.finite, std_ratio, l.stat, out_stats);
-    CLOUD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(outlier_count_kernel, tiles, blk, 0, st, out_mean_dist, n, l.ntiles, l.stat, l.blk);
-    CLOUD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dudf_scan_totals_kernel<1>, dim3(1), dim3(1024), 0, st, l.blk, l.off, l.ntiles, out_counts ? out_counts : l.kept);
-    CLOUD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(outlier_scatter_kernel, tiles, blk, 0, st, out_mean_dist, n, l.ntiles, l.stat, l.off, out_keep, out_kept_idx);
-    CLOUD_CHECK_LAUNCH();
-    return 0;
+    DUDF_TRY(dudf_launch(outlier_mean_kernel, dim3(groups), blk, st, knn_dist, n, K, out_mean_dist, l.psum, l.pcnt));
+    DUDF_TRY(dudf_launch(outlier_mu_kernel, dim3(1), dim3(kOrdSumMaxGroups), st, l.psum, l.pcnt, groups, l.stat, l.finite));
+    DUDF_TRY(dudf_launch(outlier_var_kernel, dim3(groups), blk, st, out_mean_dist, n, l.stat, l.psum));
+    DUDF_TRY(dudf_launch(outlier_sigma_kernel, dim3(1), dim3(kOrdSumMaxGroups), st, l.psum, groups, l.finite, std_ratio, l.stat, out_stats));
+    DUDF_TRY(dudf_launch(outlier_count_kernel, tiles, blk, st, out_mean_dist, n, l.ntiles, l.stat, l.blk));
+    DUDF_TRY(dudf_launch(dudf_scan_totals_kernel<1>, dim3(1), dim3(1024), st, l.blk, l.off, l.ntiles, out_counts ? out_counts : l.kept));
+    return dudf_launch(outlier_scatter_kernel, tiles, blk, st, out_mean_dist, n, l.ntiles, l.stat, l.off, out_keep, out_kept_idx);
 }
 
 }  // extern "C"

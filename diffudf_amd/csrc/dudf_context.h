@@ -26,6 +26,23 @@ inline bool dudf_valid_inverse_mode(int inverse_mode) { return !(inverse_mode < 
 
 inline bool dudf_use_bf16_sweeps() { return dudf_options().sweep_family != 0; }   // 0: the f32-input MFMA kernel everywhere (A/B testing)
 
+// ---- launches and runtime calls, checked where they are made -------------------------------------------------------------------
+// a kernel with at most the default 64 KiB of dynamic LDS (the sweeps, which raise that limit, go through dudf_launch_kernel): the
+// launch's own error, 0 = launched
+template <class Kernel, class... Args>
+inline int dudf_launch_lds(Kernel kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    return (int)hipGetLastError();
+}
+// ... with none: every other launch of the geometry units
+template <class Kernel, class... Args>
+inline int dudf_launch(Kernel kernel, dim3 grid, dim3 block, hipStream_t st, const Args&... args) {
+    return dudf_launch_lds(kernel, grid, block, 0, st, args...);
+}
+// leaves the entry point with the first non-zero result of a dudf_launch, a hipMemsetAsync / hipMemcpyAsync / hipStreamSynchronize or
+// any other int-returning step: nothing after a failure is enqueued
+#define DUDF_TRY(call) do { if (const int rc_ = (int)(call)) return rc_; } while (0)
+
 // ---- a layout on a workspace and a stream ----------------------------------------------------------------------------------------
 struct DudfCtx {
     DudfLayout lo;

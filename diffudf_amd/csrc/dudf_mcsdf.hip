@@ -413,9 +413,8 @@ int dudf_mc_lewiner_count(const float* volume, int64_t nz, int64_t ny, int64_t n
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     const int64_t nb = mc_blocks(nz, ny, nx);
-    hipLaunchKernelGGL(mc_classify_kernel, dim3((unsigned)nb), dim3(CB), 0, st, a);
-    hipLaunchKernelGGL(dudf_scan_totals_kernel<2>, dim3(1), dim3(1024), 0, st, a.blk, a.off, nb, out_counts);
-    return (int)hipGetLastError();
+    DUDF_TRY(dudf_launch(mc_classify_kernel, dim3((unsigned)nb), dim3(CB), st, a));
+    return dudf_launch(dudf_scan_totals_kernel<2>, dim3(1), dim3(1024), st, a.blk, a.off, nb, out_counts);
 }
 
 int dudf_mc_lewiner_emit(const float* volume, int64_t nz, int64_t ny, int64_t nx, double level, const signed char* luts,
@@ -428,8 +427,7 @@ int dudf_mc_lewiner_emit(const float* volume, int64_t nz, int64_t ny, int64_t nx
     a.verts = out_vertices; a.faces = out_faces; a.normals = out_normals; a.values = out_values;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(mc_emit_kernel, dim3((unsigned)mc_blocks(nz, ny, nx)), dim3(CB), 0, st, a);
-    return (int)hipGetLastError();
+    return dudf_launch(mc_emit_kernel, dim3((unsigned)mc_blocks(nz, ny, nx)), dim3(CB), st, a);
 }
 
 }  // extern "C"

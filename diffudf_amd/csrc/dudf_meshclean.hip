@@ -543,19 +543,16 @@ int fill_border(int64_t V, const int64_t* faces, int64_t F, void* ws, size_t byt
 // edge table -> per-vertex ascending lists of border neighbours (and the totals); V, F >= 1
 int build_border(const BorderArgs& a, const BorderSpans& sp, void* ws, hipStream_t st) {
     char* base = static_cast<char*>(ws);
-    hipError_t e = hipMemsetAsync(base, 0, sp.zero_end, st);
-    if (e != hipSuccess) return (int)e;
-    e = hipMemsetAsync(base + sp.zero_end, 0xff, sp.ff_end - sp.zero_end, st);
-    if (e != hipSuccess) return (int)e;
+    DUDF_TRY(hipMemsetAsync(base, 0, sp.zero_end, st));
+    DUDF_TRY(hipMemsetAsync(base + sp.zero_end, 0xff, sp.ff_end - sp.zero_end, st));
     const dim3 gv((unsigned)a.nbV), gf((unsigned)blocks_of(a.F)), gs((unsigned)blocks_of(a.capE)), wg(WG);
-    hipLaunchKernelGGL(border_faces_kernel, gf, wg, 0, st, a);
-    hipLaunchKernelGGL(border_slots_kernel<0>, gs, wg, 0, st, a);
-    hipLaunchKernelGGL(border_offsets_kernel<0>, gv, wg, 0, st, a);
-    hipLaunchKernelGGL(dudf_scan_totals_kernel<2>, dim3(1), dim3(1024), 0, st, a.blk, a.off, a.nbV, a.tot);
-    hipLaunchKernelGGL(border_offsets_kernel<1>, gv, wg, 0, st, a);
-    hipLaunchKernelGGL(border_slots_kernel<1>, gs, wg, 0, st, a);
-    hipLaunchKernelGGL(border_sort_kernel, gv, wg, 0, st, a);
-    return (int)hipGetLastError();
+    DUDF_TRY(dudf_launch(border_faces_kernel, gf, wg, st, a));
+    DUDF_TRY(dudf_launch(border_slots_kernel<0>, gs, wg, st, a));
+    DUDF_TRY(dudf_launch(border_offsets_kernel<0>, gv, wg, st, a));
+    DUDF_TRY(dudf_launch(dudf_scan_totals_kernel<2>, dim3(1), dim3(1024), st, a.blk, a.off, a.nbV, a.tot));
+    DUDF_TRY(dudf_launch(border_offsets_kernel<1>, gv, wg, st, a));
+    DUDF_TRY(dudf_launch(border_slots_kernel<1>, gs, wg, st, a));
+    return dudf_launch(border_sort_kernel, gv, wg, st, a);
 }
 
 }  // namespace
@@ -576,28 +573,22 @@ int dudf_mesh_clean_count(const double* vertices, int64_t V, const int64_t* face
     if (!out_counts) return DUDF_E_BADCFG;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    if (V == 0 || F == 0) {
-        hipLaunchKernelGGL(clean_empty_kernel, dim3(1), dim3(1), 0, st, V, F, out_counts, a.head);
-        return (int)hipGetLastError();
-    }
+    if (V == 0 || F == 0) return dudf_launch(clean_empty_kernel, dim3(1), dim3(1), st, V, F, out_counts, a.head);
     char* base = static_cast<char*>(workspace);
-    hipError_t e = hipMemsetAsync(base, 0, sp.zero_end, st);
-    if (e != hipSuccess) return (int)e;
-    e = hipMemsetAsync(base + sp.ff_begin, 0xff, sp.ff_end - sp.ff_begin, st);
-    if (e != hipSuccess) return (int)e;
+    DUDF_TRY(hipMemsetAsync(base, 0, sp.zero_end, st));
+    DUDF_TRY(hipMemsetAsync(base + sp.ff_begin, 0xff, sp.ff_end - sp.ff_begin, st));
     const dim3 gv((unsigned)a.nbV), gf((unsigned)a.nbF), wg(WG);
-    hipLaunchKernelGGL(clean_validate_kernel, gf, wg, 0, st, a);
-    hipLaunchKernelGGL(clean_weld_insert_kernel, gv, wg, 0, st, a);
-    hipLaunchKernelGGL(clean_weld_resolve_kernel, gv, wg, 0, st, a);
-    hipLaunchKernelGGL(clean_remap_kernel, gf, wg, 0, st, a);
-    hipLaunchKernelGGL(clean_face_insert_kernel, gf, wg, 0, st, a);
-    hipLaunchKernelGGL(clean_face_resolve_kernel, gf, wg, 0, st, a);
-    if (a.fill) hipLaunchKernelGGL(clean_border_adj_kernel, dim3((unsigned)blocks_of(a.capE)), wg, 0, st, a);
-    hipLaunchKernelGGL(clean_holes_kernel, gv, wg, 0, st, a);
-    hipLaunchKernelGGL(dudf_scan_totals_kernel<3>, dim3(1), dim3(1024), 0, st, a.vblk, a.voff, a.nbV, a.tot);
-    hipLaunchKernelGGL(dudf_scan_totals_kernel<1>, dim3(1), dim3(1024), 0, st, a.fblk, a.foff, a.nbF, a.tot + TOT_ALIVE);
-    hipLaunchKernelGGL(clean_finish_kernel, dim3(1), dim3(1), 0, st, a, out_counts);
-    return (int)hipGetLastError();
+    DUDF_TRY(dudf_launch(clean_validate_kernel, gf, wg, st, a));
+    DUDF_TRY(dudf_launch(clean_weld_insert_kernel, gv, wg, st, a));
+    DUDF_TRY(dudf_launch(clean_weld_resolve_kernel, gv, wg, st, a));
+    DUDF_TRY(dudf_launch(clean_remap_kernel, gf, wg, st, a));
+    DUDF_TRY(dudf_launch(clean_face_insert_kernel, gf, wg, st, a));
+    DUDF_TRY(dudf_launch(clean_face_resolve_kernel, gf, wg, st, a));
+    if (a.fill) DUDF_TRY(dudf_launch(clean_border_adj_kernel, dim3((unsigned)blocks_of(a.capE)), wg, st, a));
+    DUDF_TRY(dudf_launch(clean_holes_kernel, gv, wg, st, a));
+    DUDF_TRY(dudf_launch(dudf_scan_totals_kernel<3>, dim3(1), dim3(1024), st, a.vblk, a.voff, a.nbV, a.tot));
+    DUDF_TRY(dudf_launch(dudf_scan_totals_kernel<1>, dim3(1), dim3(1024), st, a.fblk, a.foff, a.nbF, a.tot + TOT_ALIVE));
+    return dudf_launch(clean_finish_kernel, dim3(1), dim3(1), st, a, out_counts);
 }
 
 int dudf_mesh_clean_emit(const double* vertices, int64_t V, const int64_t* faces, int64_t F, int digits, int fill_holes,
@@ -611,10 +602,10 @@ int dudf_mesh_clean_emit(const double* vertices, int64_t V, const int64_t* faces
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     const dim3 gv((unsigned)a.nbV), gf((unsigned)a.nbF), wg(WG);
-    hipLaunchKernelGGL(clean_emit_vertices_kernel, gv, wg, 0, st, a);
-    hipLaunchKernelGGL(clean_emit_faces_kernel, gf, wg, 0, st, a);
-    if (a.fill) hipLaunchKernelGGL(clean_emit_holes_kernel, gv, wg, 0, st, a);
-    return (int)hipGetLastError();
+    DUDF_TRY(dudf_launch(clean_emit_vertices_kernel, gv, wg, st, a));
+    DUDF_TRY(dudf_launch(clean_emit_faces_kernel, gf, wg, st, a));
+    if (a.fill) DUDF_TRY(dudf_launch(clean_emit_holes_kernel, gv, wg, st, a));
+    return 0;
 }
 
 size_t dudf_mesh_border_workspace_bytes(int64_t V, int64_t F) {
@@ -632,15 +623,12 @@ int dudf_mesh_border_count(int64_t V, const int64_t* faces, int64_t F, int64_t* 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     if (V == 0 || F == 0) {
-        hipError_t e = hipMemsetAsync(workspace, 0, sp.zero_end, st);   // head and totals: no edges
-        if (e != hipSuccess) return (int)e;
-        e = hipMemsetAsync(out_count, 0, sizeof(int64_t), st);
-        return (int)e;
+        DUDF_TRY(hipMemsetAsync(workspace, 0, sp.zero_end, st));        // head and totals: no edges
+        return (int)hipMemsetAsync(out_count, 0, sizeof(int64_t), st);
     }
     rc = build_border(a, sp, workspace, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(border_count_kernel, dim3(1), dim3(1), 0, st, a, out_count);
-    return (int)hipGetLastError();
+    return dudf_launch(border_count_kernel, dim3(1), dim3(1), st, a, out_count);
 }
 
 int dudf_mesh_border_edges(int64_t V, const int64_t* faces, int64_t F, int64_t* out_edges, void* workspace, size_t workspace_bytes,
@@ -652,8 +640,7 @@ int dudf_mesh_border_edges(int64_t V, const int64_t* faces, int64_t F, int64_t* 
     if (V == 0 || F == 0) return 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(border_emit_kernel, dim3((unsigned)a.nbV), dim3(WG), 0, st, a, out_edges);
-    return (int)hipGetLastError();
+    return dudf_launch(border_emit_kernel, dim3((unsigned)a.nbV), dim3(WG), st, a, out_edges);
 }
 
 int dudf_mesh_smooth_borders(double* vertices_inout, int64_t V, const int64_t* faces, int64_t F, int iterations, double lambda,
@@ -669,14 +656,12 @@ int dudf_mesh_smooth_borders(double* vertices_inout, int64_t V, const int64_t* f
     if (rc) return rc;
     double* src = vertices_inout; double* dst = a.pos;
     for (int it = 0; it < iterations; ++it) {                           // ping-pong: every average reads the positions before the iteration
-        hipLaunchKernelGGL(border_smooth_kernel, dim3((unsigned)a.nbV), dim3(WG), 0, st, a, (const double*)src, dst, lambda);
+        DUDF_TRY(dudf_launch(border_smooth_kernel, dim3((unsigned)a.nbV), dim3(WG), st, a, (const double*)src, dst, lambda));
         double* t = src; src = dst; dst = t;
     }
-    if (src != vertices_inout) {
-        hipError_t e = hipMemcpyAsync(vertices_inout, src, (size_t)V * 3 * sizeof(double), hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return (int)e;
-    }
-    return (int)hipGetLastError();
+    if (src != vertices_inout)
+        DUDF_TRY(hipMemcpyAsync(vertices_inout, src, (size_t)V * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return 0;
 }
 
 }  // extern "C"

@@ -469,12 +469,10 @@ size_t dudf_mesh_index_bytes(int64_t n_tri) {
 }
 
 // header: bounds of all vertices and the non-finite flag; clears the other flags
-static hipError_t launch_bounds(const float* tri, int64_t T, unsigned* hdr, hipStream_t st) {
-    hipError_t e = hipMemsetAsync(hdr, 0, kHdrBytes, st);                     // max words 0 (below every encoded float), flags 0
-    if (e == hipSuccess) e = hipMemsetAsync(hdr, 0xff, 3 * sizeof(unsigned), st);   // min words above every encoded float
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mesh_bounds_kernel, dim3(dudf_grid_for(T, 256, 256)), dim3(256), 0, st, tri, T, hdr);
-    return hipGetLastError();
+static int launch_bounds(const float* tri, int64_t T, unsigned* hdr, hipStream_t st) {
+    DUDF_TRY(hipMemsetAsync(hdr, 0, kHdrBytes, st));                          // max words 0 (below every encoded float), flags 0
+    DUDF_TRY(hipMemsetAsync(hdr, 0xff, 3 * sizeof(unsigned), st));            // min words above every encoded float
+    return dudf_launch(mesh_bounds_kernel, dim3(dudf_grid_for(T, 256, 256)), dim3(256), st, tri, T, hdr);
 }
 
 static int check_index(const void* index, size_t index_bytes, int64_t T) { return dudf_check_buffer(index, index_bytes, carve_index(nullptr, T).total); }
@@ -486,10 +484,8 @@ int dudf_mesh_morton_codes(const float* tri, int64_t n_tri, void* index, size_t 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     unsigned* hdr = carve_index(index, n_tri).hdr;
-    hipError_t e = launch_bounds(tri, n_tri, hdr, st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mesh_codes_kernel, dim3(dudf_grid_for(n_tri, 256, kGridCap)), dim3(256), 0, st, tri, n_tri, hdr, codes);
-    return (int)hipGetLastError();
+    DUDF_TRY(launch_bounds(tri, n_tri, hdr, st));
+    return dudf_launch(mesh_codes_kernel, dim3(dudf_grid_for(n_tri, 256, kGridCap)), dim3(256), st, tri, n_tri, hdr, codes);
 }
 
 int dudf_mesh_index_build(const float* tri, int64_t n_tri, const int64_t* order, void* index, size_t index_bytes, void* stream) {
@@ -499,19 +495,13 @@ int dudf_mesh_index_build(const float* tri, int64_t n_tri, const int64_t* order,
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     const Layout y = carve_index(index, n_tri);
-    hipError_t e = launch_bounds(tri, n_tri, y.hdr, st);                      // the build stands alone: any permutation is a valid order
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mesh_gather_kernel, dim3(dudf_grid_for(n_tri, 256, kGridCap)), dim3(256), 0, st, tri, n_tri, order, y.ids,
-                       y.stri, y.hdr);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mesh_leaves_kernel, dim3(dudf_grid_for(y.L, 256, kGridCap)), dim3(256), 0, st, y.stri, n_tri, y.L, y.nodes);
-    e = hipGetLastError();
-    for (int count = y.L / 2; count >= 1 && e == hipSuccess; count /= 2) {       // level of `count` nodes starts at node count - 1
-        hipLaunchKernelGGL(mesh_level_kernel, dim3(dudf_grid_for(count, 256, kGridCap)), dim3(256), 0, st, y.nodes, count - 1, count);
-        e = hipGetLastError();
-    }
-    return (int)e;
+    DUDF_TRY(launch_bounds(tri, n_tri, y.hdr, st));                           // the build stands alone: any permutation is a valid order
+    DUDF_TRY(dudf_launch(mesh_gather_kernel, dim3(dudf_grid_for(n_tri, 256, kGridCap)), dim3(256), st, tri, n_tri, order, y.ids, y.stri,
+                         y.hdr));
+    DUDF_TRY(dudf_launch(mesh_leaves_kernel, dim3(dudf_grid_for(y.L, 256, kGridCap)), dim3(256), st, y.stri, n_tri, y.L, y.nodes));
+    for (int count = y.L / 2; count >= 1; count /= 2)                         // level of `count` nodes starts at node count - 1
+        DUDF_TRY(dudf_launch(mesh_level_kernel, dim3(dudf_grid_for(count, 256, kGridCap)), dim3(256), st, y.nodes, count - 1, count));
+    return 0;
 }
 
 // the soup alone (index == NULL: the kernels scan it) or with the sections of its index
@@ -545,13 +535,9 @@ int dudf_mesh_distance(const float* tri, int64_t n_tri, const void* index, size_
     a.m = view_of(tri, n_tri, index); a.pts = pts; a.Q = n_pts;
     a.dist = out_dist; a.idx = out_tri; a.closest = out_closest; a.stats = reinterpret_cast<unsigned long long*>(out_stats);
     const dim3 grid((unsigned)((n_pts + kBlock - 1) / kBlock));
-    if (!index) {
-        hipLaunchKernelGGL(mesh_distance_brute_kernel, grid, dim3(kBlock), 0, st, a);
-        return (int)hipGetLastError();
-    }
+    if (!index) return dudf_launch(mesh_distance_brute_kernel, grid, dim3(kBlock), st, a);
     const size_t lds = (size_t)a.m.depth * kBlock * (sizeof(int) + sizeof(float));      // <= 29 * 2 KiB
-    hipLaunchKernelGGL(mesh_distance_kernel, grid, dim3(kBlock), lds, st, a);
-    return (int)hipGetLastError();
+    return dudf_launch_lds(mesh_distance_kernel, grid, dim3(kBlock), lds, st, a);
 }
 
 int dudf_mesh_occupancy(const float* tri, int64_t n_tri, const void* index, size_t index_bytes, const float* pts, int64_t n_pts,
@@ -562,13 +548,9 @@ int dudf_mesh_occupancy(const float* tri, int64_t n_tri, const void* index, size
     OccArgs a;
     a.m = view_of(tri, n_tri, index); a.pts = pts; a.Q = n_pts; a.count = out_count; a.inside = out_inside;
     const dim3 grid((unsigned)((n_pts + kBlock - 1) / kBlock));
-    if (!index) {
-        hipLaunchKernelGGL(mesh_occupancy_brute_kernel, grid, dim3(kBlock), 0, st, a);
-        return (int)hipGetLastError();
-    }
+    if (!index) return dudf_launch(mesh_occupancy_brute_kernel, grid, dim3(kBlock), st, a);
     const size_t lds = (size_t)a.m.depth * kBlock * sizeof(int);
-    hipLaunchKernelGGL(mesh_occupancy_kernel, grid, dim3(kBlock), lds, st, a);
-    return (int)hipGetLastError();
+    return dudf_launch_lds(mesh_occupancy_kernel, grid, dim3(kBlock), lds, st, a);
 }
 
 int dudf_mesh_trace_rays(const float* tri, int64_t n_tri, const void* index, size_t index_bytes, const double* rays, double* t0,
@@ -580,15 +562,12 @@ int dudf_mesh_trace_rays(const float* tri, int64_t n_tri, const void* index, siz
     DudfProfScope prof(PROF_OTHER, st);
     const MeshView m = view_of(tri, n_tri, index);
     const dim3 grid((unsigned)((n_rays + kBlock - 1) / kBlock));
-    if (!index) {
-        hipLaunchKernelGGL(mesh_trace_kernel<false>, grid, dim3(kBlock), 0, st, m, rays, t0, mask, hits, n_rays, (float)surface_eps,
+    if (!index)
+        return dudf_launch(mesh_trace_kernel<false>, grid, dim3(kBlock), st, m, rays, t0, mask, hits, n_rays, (float)surface_eps,
                            max_iterations, bound);
-        return (int)hipGetLastError();
-    }
     const size_t lds = (size_t)m.depth * kBlock * (sizeof(int) + sizeof(float));
-    hipLaunchKernelGGL(mesh_trace_kernel<true>, grid, dim3(kBlock), lds, st, m, rays, t0, mask, hits, n_rays, (float)surface_eps,
-                       max_iterations, bound);
-    return (int)hipGetLastError();
+    return dudf_launch_lds(mesh_trace_kernel<true>, grid, dim3(kBlock), lds, st, m, rays, t0, mask, hits, n_rays, (float)surface_eps,
+                           max_iterations, bound);
 }
 
 }  // extern "C"

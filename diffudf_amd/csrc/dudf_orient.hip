@@ -30,7 +30,6 @@ constexpr int kGridCap = 4096;                   // workgroups of the row-wise l
 constexpr int kMaxK = 16;
 constexpr unsigned kInfBits = 0x7f800000u, kNanBits = 0x7fc00000u;
 constexpr unsigned long long kPadKey = ((unsigned long long)kInfBits << 32) | 0xffffffffull;     // +inf, no index
-constexpr float kFltMax = 3.402823466e+38f;
 
 // ---- the K-list --------------------------------------------------------------------------------------------------------------------
 // KC >= K slots in ascending order.  The first KC - K hold the key 0 and stay there (an insertion puts its key behind equal ones),
@@ -55,8 +54,6 @@ template <int KC>
 __device__ __forceinline__ unsigned long long klist_kth(const unsigned long long (&key)[KC], int) { return key[KC - 1]; }
 // candidates are looked at only while their distance is <= this: the K-th distance, and never +inf or NaN
 __device__ __forceinline__ float klist_threshold(unsigned long long kth) { return fminf(__uint_as_float((unsigned)(kth >> 32)), kFltMax); }
-
-__device__ __forceinline__ bool finite3(float a, float b, float c) { return fabsf(a) <= kFltMax && fabsf(b) <= kFltMax && fabsf(c) <= kFltMax; }
 
 // the list proper to the outputs of `row`; expanded by the front end (a loop with `s >= KC - K` inside is re-rolled to a dynamic trip
 // count, and the list leaves the registers)
@@ -611,36 +608,24 @@ inline GridLayout carve_grid(void* ws, int64_t n, int64_t m) {
     return g;
 }
 
-#define KNN_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
-
 // counts in `tmp` -> exclusive starts in `out` (may be tmp itself)
 int scan_cells_host(const GridLayout& g, unsigned* out, int write_end, hipStream_t st) {
-    hipLaunchKernelGGL(cell_scan_local_kernel, dim3((unsigned)g.nblocks), dim3(DUDF_WG), 0, st, g.tmp, g.ncells, out, g.blk);
-    KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dudf_scan_totals_kernel<1>, dim3(1), dim3(1024), 0, st, g.blk, g.off, g.nblocks, g.total);
-    KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(cell_scan_add_kernel, dim3((unsigned)g.nblocks), dim3(DUDF_WG), 0, st, out, g.ncells, g.off, g.total, write_end);
-    KNN_CHECK_LAUNCH();
+    DUDF_TRY(dudf_launch(cell_scan_local_kernel, dim3((unsigned)g.nblocks), dim3(DUDF_WG), st, g.tmp, g.ncells, out, g.blk));
+    DUDF_TRY(dudf_launch(dudf_scan_totals_kernel<1>, dim3(1), dim3(1024), st, g.blk, g.off, g.nblocks, g.total));
+    DUDF_TRY(dudf_launch(cell_scan_add_kernel, dim3((unsigned)g.nblocks), dim3(DUDF_WG), st, out, g.ncells, g.off, g.total, write_end));
     return 0;
 }
 
 int grid_build(const GridLayout& g, const float* y, int64_t m, hipStream_t st) {
     const dim3 rows(dudf_grid_for(m, kBlock, kGridCap));
-    hipLaunchKernelGGL(grid_init_kernel, dim3(1), dim3(64), 0, st, g.prm);
-    KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(grid_bbox_kernel, rows, dim3(kBlock), 0, st, y, (int)m, g.prm);
-    KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(grid_params_kernel, dim3(1), dim3(kBlock), 0, st, g.prm, g.G, g.below, g.above);
-    KNN_CHECK_LAUNCH();
-    hipError_t e = hipMemsetAsync(g.tmp, 0, (size_t)g.ncells * sizeof(unsigned), st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cell_count_kernel, rows, dim3(kBlock), 0, st, y, m, g.prm, 1, g.pcell, g.tmp);
-    KNN_CHECK_LAUNCH();
+    DUDF_TRY(dudf_launch(grid_init_kernel, dim3(1), dim3(64), st, g.prm));
+    DUDF_TRY(dudf_launch(grid_bbox_kernel, rows, dim3(kBlock), st, y, (int)m, g.prm));
+    DUDF_TRY(dudf_launch(grid_params_kernel, dim3(1), dim3(kBlock), st, g.prm, g.G, g.below, g.above));
+    DUDF_TRY(hipMemsetAsync(g.tmp, 0, (size_t)g.ncells * sizeof(unsigned), st));
+    DUDF_TRY(dudf_launch(cell_count_kernel, rows, dim3(kBlock), st, y, m, g.prm, 1, g.pcell, g.tmp));
     if (int rc = scan_cells_host(g, g.cstart, 1, st)) return rc;
-    e = hipMemcpyAsync(g.tmp, g.cstart, (size_t)g.ncells * sizeof(unsigned), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cell_scatter_points_kernel, rows, dim3(kBlock), 0, st, y, (int)m, g.pcell, g.tmp, g.pts);
-    KNN_CHECK_LAUNCH();
+    DUDF_TRY(hipMemcpyAsync(g.tmp, g.cstart, (size_t)g.ncells * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
+    DUDF_TRY(dudf_launch(cell_scatter_points_kernel, rows, dim3(kBlock), st, y, (int)m, g.pcell, g.tmp, g.pts));
     return 0;
 }
 
@@ -649,16 +634,12 @@ int knn_grid_run(const GridLayout& g, const float* x, int64_t n, int64_t m, int 
                  hipStream_t st) {
     const dim3 rows(dudf_grid_for(n, kBlock, kGridCap));
     // the queries in cell order: a wave's lanes then walk the same rows of cells and share their cache lines
-    hipError_t e = hipMemsetAsync(g.tmp, 0, (size_t)g.ncells * sizeof(unsigned), st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cell_count_kernel, rows, dim3(kBlock), 0, st, x, n, g.prm, 0, g.qcell, g.tmp);
-    KNN_CHECK_LAUNCH();
+    DUDF_TRY(hipMemsetAsync(g.tmp, 0, (size_t)g.ncells * sizeof(unsigned), st));
+    DUDF_TRY(dudf_launch(cell_count_kernel, rows, dim3(kBlock), st, x, n, g.prm, 0, g.qcell, g.tmp));
     if (int rc = scan_cells_host(g, g.tmp, 0, st)) return rc;
-    hipLaunchKernelGGL(cell_scatter_queries_kernel, rows, dim3(kBlock), 0, st, n, g.qcell, g.tmp, g.qorder);
-    KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(knn_grid_kernel<KC>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, x, n, (int)m, K, exclude_self,
-                       g.prm, g.below, g.above, g.G, g.pts, g.cstart, g.qorder, out_dist, out_idx);
-    KNN_CHECK_LAUNCH();
+    DUDF_TRY(dudf_launch(cell_scatter_queries_kernel, rows, dim3(kBlock), st, n, g.qcell, g.tmp, g.qorder));
+    DUDF_TRY(dudf_launch(knn_grid_kernel<KC>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), st, x, n, (int)m, K, exclude_self,
+                         g.prm, g.below, g.above, g.G, g.pts, g.cstart, g.qorder, out_dist, out_idx));
     return 0;
 }
 
@@ -677,13 +658,11 @@ template <int KC, int PPL>
 int knn_brute_run(const BruteLayout& l, const float* x, int64_t n, const float* y, int64_t m, int K, int exclude_self, float* out_dist,
                   int64_t* out_idx, hipStream_t st) {
     const BruteSplit& b = l.b;
-    hipLaunchKernelGGL((knn_brute_kernel<KC, PPL>), dim3((unsigned)b.xgroups, (unsigned)b.splits), dim3(kBlock), 0, st, x, n, y, (int)m,
-                       (int)b.ychunk, K, exclude_self, l.part);
-    KNN_CHECK_LAUNCH();
+    DUDF_TRY(dudf_launch(knn_brute_kernel<KC, PPL>, dim3((unsigned)b.xgroups, (unsigned)b.splits), dim3(kBlock), st, x, n, y, (int)m,
+                         (int)b.ychunk, K, exclude_self, l.part));
     if (out_dist || out_idx) {
-        hipLaunchKernelGGL(knn_merge_kernel<KC>, dim3(dudf_grid_for(n, kBlock, kGridCap)), dim3(kBlock), 0, st, x, n, (int)m, K,
-                           (int)b.splits, l.part, out_dist, out_idx);
-        KNN_CHECK_LAUNCH();
+        DUDF_TRY(dudf_launch(knn_merge_kernel<KC>, dim3(dudf_grid_for(n, kBlock, kGridCap)), dim3(kBlock), st, x, n, (int)m, K,
+                             (int)b.splits, l.part, out_dist, out_idx));
     }
     return 0;
 }
@@ -789,43 +768,35 @@ int dudf_orient_normals(const float* points, const float* normals, const int64_t
     DudfProfScope prof(PROF_OTHER, st);
     const dim3 vgrid(dudf_grid_for(n, kBlock, kGridCap)), sgrid(dudf_grid_for(n * K, kBlock, kGridCap)), blk(kBlock);
     int64_t launches = 0, rounds = 0;
-    hipError_t e = hipMemsetAsync(l.cnt, 0, 4 * sizeof(unsigned long long), st);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(orient_init_kernel, sgrid, blk, 0, st, normals, knn_idx, n, K, l.pp[0], l.wbits);
-    KNN_CHECK_LAUNCH(); ++launches;
+    DUDF_TRY(hipMemsetAsync(l.cnt, 0, 4 * sizeof(unsigned long long), st));
+    DUDF_TRY(dudf_launch(orient_init_kernel, sgrid, blk, st, normals, knn_idx, n, K, l.pp[0], l.wbits)); ++launches;
     // Borůvka: the components at least halve per round that hooks anything, and a round that hooks nothing is the last
     const int jumps = ceil_log2(n) > 0 ? ceil_log2(n) : 1, max_rounds = ceil_log2(n) + 1;
     int c = 0;                                                   // pp[c] is current and flat
     unsigned long long total_hooks = 0;
     for (int r = 0; r < max_rounds; ++r) {
-        if ((e = hipMemsetAsync(l.best, 0xff, (size_t)n * sizeof(unsigned long long), st)) != hipSuccess) return (int)e;
-        if ((e = hipMemsetAsync(l.flags, 0, 64 * sizeof(unsigned), st)) != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(orient_best_kernel, sgrid, blk, 0, st, knn_idx, n, K, l.pp[c], l.wbits, l.best);
-        KNN_CHECK_LAUNCH();
-        hipLaunchKernelGGL(orient_hook_kernel, vgrid, blk, 0, st, normals, knn_idx, n, K, l.pp[c], l.pp[1 - c], l.best, l.cnt);
-        KNN_CHECK_LAUNCH();
+        DUDF_TRY(hipMemsetAsync(l.best, 0xff, (size_t)n * sizeof(unsigned long long), st));
+        DUDF_TRY(hipMemsetAsync(l.flags, 0, 64 * sizeof(unsigned), st));
+        DUDF_TRY(dudf_launch(orient_best_kernel, sgrid, blk, st, knn_idx, n, K, l.pp[c], l.wbits, l.best));
+        DUDF_TRY(dudf_launch(orient_hook_kernel, vgrid, blk, st, normals, knn_idx, n, K, l.pp[c], l.pp[1 - c], l.best, l.cnt));
         c = 1 - c;
         for (int s = 0; s < jumps; ++s) {
-            hipLaunchKernelGGL(orient_jump_kernel, vgrid, blk, 0, st, n, l.pp[c], l.pp[1 - c], l.flags, s);
-            KNN_CHECK_LAUNCH();
+            DUDF_TRY(dudf_launch(orient_jump_kernel, vgrid, blk, st, n, l.pp[c], l.pp[1 - c], l.flags, s));
             c = 1 - c;
         }
         launches += 2 + jumps; ++rounds;
         unsigned long long hooks = 0;                            // the one read-back of the round
-        if ((e = hipMemcpyAsync(&hooks, l.cnt, sizeof(hooks), hipMemcpyDeviceToHost, st)) != hipSuccess) return (int)e;
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return (int)e;
+        DUDF_TRY(hipMemcpyAsync(&hooks, l.cnt, sizeof(hooks), hipMemcpyDeviceToHost, st));
+        DUDF_TRY(hipStreamSynchronize(st));
         if (hooks == total_hooks) break;
         total_hooks = hooks;
     }
-    if ((e = hipMemsetAsync(l.best, 0, (size_t)n * sizeof(unsigned long long), st)) != hipSuccess) return (int)e;
-    if ((e = hipMemsetAsync(l.minidx, 0xff, (size_t)n * sizeof(unsigned), st)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(orient_seed_kernel, vgrid, blk, 0, st, points, n, l.pp[c], l.best, l.minidx);
-    KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(orient_root_kernel, vgrid, blk, 0, st, normals, n, l.pp[c], l.best, l.rootflip, l.cnt + 1);
-    KNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(orient_write_kernel, vgrid, blk, 0, st, normals, n, l.pp[c], l.rootflip, l.minidx, l.cnt, out_normals, out_flip,
-                       out_component, out_counts);
-    KNN_CHECK_LAUNCH();
+    DUDF_TRY(hipMemsetAsync(l.best, 0, (size_t)n * sizeof(unsigned long long), st));
+    DUDF_TRY(hipMemsetAsync(l.minidx, 0xff, (size_t)n * sizeof(unsigned), st));
+    DUDF_TRY(dudf_launch(orient_seed_kernel, vgrid, blk, st, points, n, l.pp[c], l.best, l.minidx));
+    DUDF_TRY(dudf_launch(orient_root_kernel, vgrid, blk, st, normals, n, l.pp[c], l.best, l.rootflip, l.cnt + 1));
+    DUDF_TRY(dudf_launch(orient_write_kernel, vgrid, blk, st, normals, n, l.pp[c], l.rootflip, l.minidx, l.cnt, out_normals, out_flip,
+                         out_component, out_counts));
     launches += 3;
     if (host_stats) { host_stats[0] = rounds; host_stats[1] = launches; }
     return 0;

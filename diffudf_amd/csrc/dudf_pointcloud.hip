@@ -178,9 +178,8 @@ int dudf_launch_pc_propose(const DudfLayout& lo, const double* rand, int64_t ran
                            const int64_t* counter, int64_t quota, double* samples, double* proposals, float* ws, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
     const uint64_t key = dudf_splitmix64(dudf_splitmix64(seed) ^ (uint64_t)round * 0x100000001B3ull) & ~0xFull;   // streams key + 0 .. 6
-    hipLaunchKernelGGL(pc_propose_kernel, dim3(dudf_grid_for(lo.np, 256, kGridCap)), dim3(256), 0, st, rand, rand_count, key, lo.n,
-                       lo.np, surface, counter, quota, samples, proposals, ws + lo.ws_x4);
-    return (int)hipGetLastError();
+    return dudf_launch(pc_propose_kernel, dim3(dudf_grid_for(lo.np, 256, kGridCap)), dim3(256), st, rand, rand_count, key, lo.n, lo.np,
+                       surface, counter, quota, samples, proposals, ws + lo.ws_x4);
 }
 
 int dudf_launch_pc_step(const DudfLayout& lo, float* ws, double* samples, int inverse_mode, double alpha, double thresh,
@@ -192,14 +191,12 @@ int dudf_launch_pc_step(const DudfLayout& lo, float* ws, double* samples, int in
     a.inverse_mode = inverse_mode; a.alpha = alpha; a.inv_alpha = 1.0 / alpha; a.sqrt_alpha = sqrt(alpha); a.thresh = thresh;
     a.last = last; a.out_step = out_step; a.out_unit = out_unit; a.out_pre = out_pre; a.out_accept = out_accept;
     a.counter = counter; a.quota = quota;
-    hipLaunchKernelGGL(pc_step_kernel, dim3(dudf_grid_for(lo.n, 256, kGridCap)), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
+    return dudf_launch(pc_step_kernel, dim3(dudf_grid_for(lo.n, 256, kGridCap)), dim3(256), st, a);
 }
 
 int dudf_launch_pc_normals(const float* V, int64_t m, double* normals, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(pc_normals_kernel, dim3(dudf_grid_for(m, 256, kGridCap)), dim3(256), 0, st, V, m, normals);
-    return (int)hipGetLastError();
+    return dudf_launch(pc_normals_kernel, dim3(dudf_grid_for(m, 256, kGridCap)), dim3(256), st, V, m, normals);
 }
 
 // the projection loop of reference src/render_pc.py:43-56 on a context whose x4 already holds the float32 copies of `samples`:
@@ -258,11 +255,10 @@ int dudf_launch_pc_append(const unsigned char* flags, int64_t n, const double* s
     int* tile_cnt = scratch; int* tile_off = scratch + ntiles;
     if (!src_b) dst_b = nullptr;
     if (!src_f) out_f = nullptr;
-    hipLaunchKernelGGL(pc_count_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), 0, st, flags, n, ntiles, tile_cnt);
-    hipLaunchKernelGGL(pc_scan_kernel, dim3(1), dim3(256), 0, st, tile_cnt, tile_off, ntiles, capacity, quota, counter);
-    hipLaunchKernelGGL(pc_scatter_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), 0, st, flags, n, ntiles, tile_off,
-                       counter, src_a, src_b, src_f, dst_a, dst_b, out_f, rows);
-    return (int)hipGetLastError();
+    DUDF_TRY(dudf_launch(pc_count_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), st, flags, n, ntiles, tile_cnt));
+    DUDF_TRY(dudf_launch(pc_scan_kernel, dim3(1), dim3(256), st, tile_cnt, tile_off, ntiles, capacity, quota, counter));
+    return dudf_launch(pc_scatter_kernel, dim3(dudf_grid_for(n, 256, kGridCap)), dim3(256), st, flags, n, ntiles, tile_off, counter, src_a,
+                       src_b, src_f, dst_a, dst_b, out_f, rows);
 }
 
 extern "C" {
@@ -326,7 +322,6 @@ int dudf_pointcloud_round(const dudf_net_cfg* cfg, const float* theta, int64_t n
     if ((rc = dudf_check_buffer(workspace, workspace_bytes, pl.total_bytes))) return rc;
     if (!counter || !surface_points || !normals || capacity < 2 * n) return DUDF_E_BADCFG;
     DudfCtx c = dudf_ctx_at(pl.q, reinterpret_cast<float*>(workspace), reinterpret_cast<hipStream_t>(stream));
-    hipError_t e;
     if (n > 0) {
         double* samples = reinterpret_cast<double*>(c.ws + pl.o_samples);
         double* unit = reinterpret_cast<double*>(c.ws + pl.o_unit);
@@ -344,8 +339,8 @@ int dudf_pointcloud_round(const dudf_net_cfg* cfg, const float* theta, int64_t n
                                         reinterpret_cast<int*>(c.ws + pl.o_tiles), c.st))) return rc;
         if (!siren) {
             int64_t hc[4];
-            if ((e = hipMemcpyAsync(hc, counter, sizeof(hc), hipMemcpyDeviceToHost, c.st)) != hipSuccess) return (int)e;
-            if ((e = hipStreamSynchronize(c.st)) != hipSuccess) return (int)e;
+            DUDF_TRY(hipMemcpyAsync(hc, counter, sizeof(hc), hipMemcpyDeviceToHost, c.st));
+            DUDF_TRY(hipStreamSynchronize(c.st));
             const int64_t added = hc[1], base = hc[2];
             if (added < 0 || base < 0 || base + added > capacity || added > n) return DUDF_E_BADCFG;
             float* V = c.ws + pl.o_V;
@@ -364,8 +359,8 @@ int dudf_pointcloud_round(const dudf_net_cfg* cfg, const float* theta, int64_t n
         }
     }
     if (host_counter) {
-        if ((e = hipMemcpyAsync(host_counter, counter, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, c.st)) != hipSuccess) return (int)e;
-        if ((e = hipStreamSynchronize(c.st)) != hipSuccess) return (int)e;
+        DUDF_TRY(hipMemcpyAsync(host_counter, counter, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, c.st));
+        DUDF_TRY(hipStreamSynchronize(c.st));
     }
     return 0;
 }

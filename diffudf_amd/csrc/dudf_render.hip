@@ -213,29 +213,26 @@ int dudf_launch_render_setup(int64_t width, int64_t height, double fov, double n
     for (int i = 0; i < 3; ++i) a.cam[i] = cam[i];
     for (int i = 0; i < 6; ++i) a.planes[i] = planes[i];
     a.rays = rays; a.t0 = t0; a.mask = mask;
-    hipLaunchKernelGGL(render_setup_kernel, dim3(dudf_grid_for(width * height, 256, kGridCap)), dim3(256), 0, st, a);
-    return (int)hipGetLastError();
+    return dudf_launch(render_setup_kernel, dim3(dudf_grid_for(width * height, 256, kGridCap)), dim3(256), st, a);
 }
 
 int dudf_launch_render_orient(const float* frame, const float* grad, const double* rays, int64_t k, double* normals, double* pc1,
                               double* pc2, float* mean, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(render_orient_kernel, dim3(dudf_grid_for(k, 256, kGridCap)), dim3(256), 0, st, frame, grad, rays, k,
-                       normals, pc1, pc2, mean);
-    return (int)hipGetLastError();
+    return dudf_launch(render_orient_kernel, dim3(dudf_grid_for(k, 256, kGridCap)), dim3(256), st, frame, grad, rays, k, normals, pc1, pc2,
+                       mean);
 }
 
 int dudf_launch_render_colormap(const float* curv, int64_t k, const float* bounds, const double* lut, double* out, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(render_colormap_kernel, dim3(dudf_grid_for(k, 256, kGridCap)), dim3(256), 0, st, curv, k, bounds, lut, out);
-    return (int)hipGetLastError();
+    return dudf_launch(render_colormap_kernel, dim3(dudf_grid_for(k, 256, kGridCap)), dim3(256), st, curv, k, bounds, lut, out);
 }
 
 int dudf_launch_render_shade(int model, const unsigned char* hits, int64_t m, const int* rows, int64_t k, const double* pos,
                              const double* normals, const double* pc1, const double* pc2, const double* cmap, const double* light,
                              const double* camera, double shininess, double alpha1, double alpha2, double* acc, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(render_background_kernel, dim3(dudf_grid_for(m, 256, kGridCap)), dim3(256), 0, st, hits, m, acc);
+    DUDF_TRY(dudf_launch(render_background_kernel, dim3(dudf_grid_for(m, 256, kGridCap)), dim3(256), st, hits, m, acc));
     if (k > 0) {
         ShadeArgs a;
         a.model = model; a.k = k; a.rows = rows; a.pos = pos; a.normals = normals; a.pc1 = pc1; a.pc2 = pc2; a.cmap = cmap;
@@ -243,16 +240,14 @@ int dudf_launch_render_shade(int model, const unsigned char* hits, int64_t m, co
         a.shininess = shininess; a.alpha1 = alpha1; a.alpha2 = alpha2;
         a.ward_norm = 4 * 3.141592653589793 * alpha1 * alpha2;
         a.acc = acc;
-        hipLaunchKernelGGL(render_shade_kernel, dim3(dudf_grid_for(k, 256, kGridCap)), dim3(256), 0, st, a);
+        DUDF_TRY(dudf_launch(render_shade_kernel, dim3(dudf_grid_for(k, 256, kGridCap)), dim3(256), st, a));
     }
-    return (int)hipGetLastError();
+    return 0;
 }
 
 int dudf_launch_render_finish(const double* acc, int64_t count, double sample_rate, unsigned char* out, hipStream_t st) {
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(render_finish_kernel, dim3(dudf_grid_for(count, 256, kGridCap)), dim3(256), 0, st, acc, count, sample_rate,
-                       out);
-    return (int)hipGetLastError();
+    return dudf_launch(render_finish_kernel, dim3(dudf_grid_for(count, 256, kGridCap)), dim3(256), st, acc, count, sample_rate, out);
 }
 
 }  // namespace
@@ -273,8 +268,7 @@ int dudf_render_gather(const unsigned char* hits, int64_t m, const double* t0, c
     if (m < 0 || m > (1ll << 30) || !counter) return DUDF_E_BADCFG;
     if (int rc = dudf_check_buffer(workspace, workspace_bytes, dudf_pointcloud_append_workspace_bytes(m))) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e = hipMemsetAsync(counter, 0, 4 * sizeof(int64_t), st);
-    if (e != hipSuccess) return (int)e;
+    DUDF_TRY(hipMemsetAsync(counter, 0, 4 * sizeof(int64_t), st));
     if (m == 0) return 0;
     if (!hits || !t0 || !out_pos || !out_rows || (rays && !out_rays)) return DUDF_E_BADCFG;
     // the compaction's scatter leaves the image row of every gathered hit (the index behind `colors[hits] = ...`) in out_rows

@@ -231,9 +231,8 @@ int dudf_grid_fields_lattice(const dudf_net_cfg* cfg, const float* theta, int64_
     if (count == 0) return 0;
     {
         DudfProfScope prof(PROF_OTHER, c.st);
-        hipLaunchKernelGGL(make_x4_lattice_kernel, dim3(dudf_grid_for(c.lo.np, 256, kGridCap)), dim3(256), 0, c.st, c.ws + c.lo.ws_x4,
-                           c.lo.n, c.lo.np, grid_n, d.ncoarse, brick, start);
-        if ((rc = (int)hipGetLastError())) return rc;
+        DUDF_TRY(dudf_launch(make_x4_lattice_kernel, dim3(dudf_grid_for(c.lo.np, 256, kGridCap)), dim3(256), c.st, c.ws + c.lo.ws_x4,
+                             c.lo.n, c.lo.np, grid_n, d.ncoarse, brick, start));
     }
     if ((rc = dudf_forward_common(c, theta, nullptr, 0, out_vec != nullptr))) return rc;       // value only: no reverse sweep
     return dudf_launch_field_features(c.lo, c.ws, inverse_mode, alpha, out_df, out_vec, out_vec ? out_flag_count : nullptr, nullptr,
@@ -259,11 +258,10 @@ int dudf_sparse_select(const float* coarse_df, int64_t grid_n, int brick, double
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     const int64_t nblocks = (a.nbricks + DUDF_WG - 1) / DUDF_WG;
-    hipLaunchKernelGGL(sparse_flag_kernel, dim3((unsigned)nblocks), dim3(DUDF_WG), 0, st, a);
-    hipLaunchKernelGGL(sparse_count_kernel, dim3((unsigned)nblocks), dim3(DUDF_WG), 0, st, a);
-    hipLaunchKernelGGL(dudf_scan_totals_kernel<2>, dim3(1), dim3(1024), 0, st, a.blk, a.off, nblocks, out_counts);
-    hipLaunchKernelGGL(sparse_compact_kernel, dim3((unsigned)nblocks), dim3(DUDF_WG), 0, st, a);
-    return (int)hipGetLastError();
+    DUDF_TRY(dudf_launch(sparse_flag_kernel, dim3((unsigned)nblocks), dim3(DUDF_WG), st, a));
+    DUDF_TRY(dudf_launch(sparse_count_kernel, dim3((unsigned)nblocks), dim3(DUDF_WG), st, a));
+    DUDF_TRY(dudf_launch(dudf_scan_totals_kernel<2>, dim3(1), dim3(1024), st, a.blk, a.off, nblocks, out_counts));
+    return dudf_launch(sparse_compact_kernel, dim3((unsigned)nblocks), dim3(DUDF_WG), st, a);
 }
 
 int dudf_grid_fields_bricks(const dudf_net_cfg* cfg, const float* theta, int64_t grid_n, int brick, const int32_t* brick_ids,
@@ -281,9 +279,8 @@ int dudf_grid_fields_bricks(const dudf_net_cfg* cfg, const float* theta, int64_t
     if (count == 0) return 0;
     {
         DudfProfScope prof(PROF_OTHER, c.st);
-        hipLaunchKernelGGL(make_x4_bricks_kernel, dim3(dudf_grid_for(c.lo.np, 256, kGridCap)), dim3(256), 0, c.st, c.ws + c.lo.ws_x4,
-                           c.lo.n, c.lo.np, grid_n, d.nl, d.shift, brick_ids);
-        if ((rc = (int)hipGetLastError())) return rc;
+        DUDF_TRY(dudf_launch(make_x4_bricks_kernel, dim3(dudf_grid_for(c.lo.np, 256, kGridCap)), dim3(256), c.st, c.ws + c.lo.ws_x4, c.lo.n,
+                             c.lo.np, grid_n, d.nl, d.shift, brick_ids));
     }
     if ((rc = dudf_forward_common(c, theta, nullptr, 0, true))) return rc;
     return dudf_launch_field_features(c.lo, c.ws, inverse_mode, alpha, out_df, out_vec, out_flag_count, nullptr, nullptr, c.st);
@@ -306,9 +303,8 @@ int dudf_capudf_sparse_count(const float* df, const float* vec, const int32_t* s
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     const int64_t nblocks = sparse_cap_blocks(n_candidates, brick);
-    if (nblocks) hipLaunchKernelGGL(capudf_count_kernel<BrickAddr>, dim3((unsigned)nblocks), dim3(CB), 0, st, a.ad, a.w);
-    hipLaunchKernelGGL(dudf_scan_totals_kernel<3>, dim3(1), dim3(1024), 0, st, a.w.blk, a.w.off, nblocks, out_counts);
-    return (int)hipGetLastError();
+    if (nblocks) DUDF_TRY(dudf_launch(capudf_count_kernel<BrickAddr>, dim3((unsigned)nblocks), dim3(CB), st, a.ad, a.w));
+    return dudf_launch(dudf_scan_totals_kernel<3>, dim3(1), dim3(1024), st, a.w.blk, a.w.off, nblocks, out_counts);
 }
 
 int dudf_capudf_sparse_emit(const float* df, const float* vec, const int32_t* slot, const int32_t* candidate_ids,
@@ -323,8 +319,7 @@ int dudf_capudf_sparse_emit(const float* df, const float* vec, const int32_t* sl
     if (!nblocks) return 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    hipLaunchKernelGGL(capudf_emit_kernel<BrickAddr>, dim3((unsigned)nblocks), dim3(CB), 0, st, a.ad, a.w);
-    return (int)hipGetLastError();
+    return dudf_launch(capudf_emit_kernel<BrickAddr>, dim3((unsigned)nblocks), dim3(CB), st, a.ad, a.w);
 }
 
 }  // extern "C"

@@ -11,13 +11,14 @@
 // t = floor(k W / 2^53) in [0, W) and the face is the first f with c_f > t — `searchsorted(c, t, side="right")`.  A face of weight 0
 // repeats its predecessor's c and is never the first.
 #include "dudf_context.h"
+#include "dudf_ordsum.h"
 #include "dudf_rng.h"
 #include "dudf_wgscan.h"
 #include <string.h>
 
 namespace {
 
-constexpr int kFaceMaxGroups = 256;              // area partials the finishing workgroup adds in index order
+static_assert(DUDF_WG == kOrdSumBlock, "the face sum's launch is sized by dudf_ordsum_groups");
 constexpr int kGridCap = 4096;                   // workgroups of the row-wise launches; the kernels stride over the rest
 constexpr unsigned kFlagNonFinite = 1u, kFlagBadIndex = 2u;
 constexpr double kTwo32 = 4294967296.0, kTwo53 = 9007199254740992.0;
@@ -31,8 +32,8 @@ struct SampleStatus {                            // one granule of the workspace
 };
 
 // ---- faces: normal, |e1 x e2|, area partials, maximum ---------------------------------------------------------------------------
-// Each thread takes its faces in ascending order, the workgroup adds its threads in a fixed tree: partials[b] is a function of
-// (F, inputs, gridDim) only, and gridDim is a function of F.
+// The area partials are an ordered sum (dudf_ordsum.h), the maximum rides the same tree: partials[b] is a function of (F, inputs,
+// gridDim) only, and gridDim is a function of F.
 __global__ __launch_bounds__(DUDF_WG) void surf_faces_kernel(const double* __restrict__ v, int64_t nv, const int64_t* __restrict__ f,
                                                              int64_t nf, double* __restrict__ nn_out, float* __restrict__ fn_out,
                                                              double* __restrict__ partials, SampleStatus* __restrict__ status) {
@@ -61,15 +62,7 @@ __global__ __launch_bounds__(DUDF_WG) void surf_faces_kernel(const double* __res
         mx = bits > mx ? bits : mx;
     }
     sa[threadIdx.x] = a; sm[threadIdx.x] = mx;
-    __syncthreads();
-    for (int s = DUDF_WG / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            sa[threadIdx.x] += sa[threadIdx.x + s];
-            const unsigned long long o = sm[threadIdx.x + s];
-            if (o > sm[threadIdx.x]) sm[threadIdx.x] = o;
-        }
-        __syncthreads();
-    }
+    dudf_wg_tree<DUDF_WG>(dudf_sum_of(sa), dudf_max_of(sm));
     if (threadIdx.x == 0) {
         partials[blockIdx.x] = sa[0];
         atomicMax(&status->max_bits, sm[0]);
@@ -77,16 +70,11 @@ __global__ __launch_bounds__(DUDF_WG) void surf_faces_kernel(const double* __res
     if (flags) atomicOr(&status->flags, flags);
 }
 
-__global__ __launch_bounds__(kFaceMaxGroups) void surf_area_kernel(const double* __restrict__ partials, int count,
-                                                                   double* __restrict__ out_area) {
-    __shared__ double sa[kFaceMaxGroups];
-    if ((int)threadIdx.x < count) sa[threadIdx.x] = partials[threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0;
-        for (int i = 0; i < count; ++i) a += sa[i];                        // index order
-        *out_area = 0.5 * a;
-    }
+__global__ __launch_bounds__(kOrdSumMaxGroups) void surf_area_kernel(const double* __restrict__ partials, int count,
+                                                                     double* __restrict__ out_area) {
+    double a[1];
+    dudf_ordsum_finish(partials, count, a);
+    if (threadIdx.x == 0) *out_area = 0.5 * a[0];
 }
 
 // ---- integer weights and their inclusive sums -------------------------------------------------------------------------------------
@@ -168,7 +156,7 @@ inline SampleCarve carve_sample(const void* base, int64_t F) {
     SampleCarve s;
     const int64_t nblocks = (F + DUDF_WG - 1) / DUDF_WG;
     s.status = cv.take<SampleStatus>(1);
-    s.partials = cv.take<double>(kFaceMaxGroups);
+    s.partials = cv.take<double>(kOrdSumMaxGroups);
     s.nn = cv.take<double>(F);
     s.fn = cv.take<float>(F * 3);
     s.c = cv.take<unsigned long long>(F);
@@ -179,17 +167,12 @@ inline SampleCarve carve_sample(const void* base, int64_t F) {
 }
 
 // ---- threshold statistics -----------------------------------------------------------------------------------------------------------
-constexpr int kStatsBlock = 256;
-constexpr int kStatsMaxGroups = 256;             // partials the single finishing workgroup adds in index order
-
 struct StatsTaus { double tau[kStatsMaxK]; };
 
-// Counts and the maximum are integers: atomics in any order give the same words.  The two double sums go the way of
-// chamfer_partial_kernel: ascending rows per thread, a fixed tree per workgroup, partials added in index order afterwards.
-__global__ __launch_bounds__(kStatsBlock) void stats_partial_kernel(const float* __restrict__ dist, int64_t n, StatsTaus taus, int K,
-                                                                    unsigned long long* __restrict__ out_counts,
-                                                                    unsigned* __restrict__ out_max, double* __restrict__ partials) {
-    __shared__ double sd[kStatsBlock], sq[kStatsBlock];
+// Counts and the maximum are integers: atomics in any order give the same words.  The two double sums are ordered sums (dudf_ordsum.h).
+__global__ __launch_bounds__(kOrdSumBlock) void stats_partial_kernel(const float* __restrict__ dist, int64_t n, StatsTaus taus, int K,
+                                                                     unsigned long long* __restrict__ out_counts,
+                                                                     unsigned* __restrict__ out_max, double* __restrict__ partials) {
     __shared__ unsigned long long scnt[kStatsMaxK + 1];
     __shared__ unsigned smax;
     if (threadIdx.x <= kStatsMaxK) scnt[threadIdx.x] = 0;
@@ -198,7 +181,7 @@ __global__ __launch_bounds__(kStatsBlock) void stats_partial_kernel(const float*
     unsigned long long cnt[kStatsMaxK + 1] = {};
     unsigned mx = 0;
     double a = 0.0, b = 0.0;
-    for (int64_t p = (int64_t)blockIdx.x * kStatsBlock + threadIdx.x; p < n; p += (int64_t)gridDim.x * kStatsBlock) {
+    for (int64_t p = (int64_t)blockIdx.x * kOrdSumBlock + threadIdx.x; p < n; p += (int64_t)gridDim.x * kOrdSumBlock) {
         const float df = dist[p];
         if (df != df) { cnt[kStatsMaxK] += 1; continue; }
         const double d = (double)df;
@@ -218,30 +201,19 @@ __global__ __launch_bounds__(kStatsBlock) void stats_partial_kernel(const float*
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { const unsigned other = __shfl_down(mx, o); mx = other > mx ? other : mx; }
     if ((threadIdx.x & 63) == 0 && mx) atomicMax(&smax, mx);
-    sd[threadIdx.x] = a; sq[threadIdx.x] = b;
-    __syncthreads();
-    for (int s = kStatsBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { sd[threadIdx.x] += sd[threadIdx.x + s]; sq[threadIdx.x] += sq[threadIdx.x + s]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { partials[2 * blockIdx.x] = sd[0]; partials[2 * blockIdx.x + 1] = sq[0]; if (smax) atomicMax(out_max, smax); }
+    const double sums[2] = {a, b};
+    dudf_ordsum_partial<kOrdSumBlock>(sums, partials);          // its barriers also close the atomics on scnt and smax
+    if (threadIdx.x == 0 && smax) atomicMax(out_max, smax);
     if ((int)threadIdx.x < K && scnt[threadIdx.x]) atomicAdd(&out_counts[threadIdx.x], scnt[threadIdx.x]);
     if (threadIdx.x == kStatsMaxK && scnt[kStatsMaxK]) atomicAdd(&out_counts[K], scnt[kStatsMaxK]);
 }
 
-__global__ __launch_bounds__(kStatsMaxGroups) void stats_final_kernel(const double* __restrict__ partials, int count,
-                                                                      double* __restrict__ out_sums) {
-    __shared__ double sd[kStatsMaxGroups], sq[kStatsMaxGroups];
-    if ((int)threadIdx.x < count) { sd[threadIdx.x] = partials[2 * threadIdx.x]; sq[threadIdx.x] = partials[2 * threadIdx.x + 1]; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0, b = 0.0;
-        for (int i = 0; i < count; ++i) { a += sd[i]; b += sq[i]; }         // index order
-        out_sums[0] = a; out_sums[1] = b;
-    }
+__global__ __launch_bounds__(kOrdSumMaxGroups) void stats_final_kernel(const double* __restrict__ partials, int count,
+                                                                       double* __restrict__ out_sums) {
+    double sums[2];
+    dudf_ordsum_finish(partials, count, sums);
+    if (threadIdx.x == 0) { out_sums[0] = sums[0]; out_sums[1] = sums[1]; }
 }
-
-inline int stats_groups(int64_t n) { return dudf_grid_for(n, kStatsBlock, kStatsMaxGroups); }
 
 }  // namespace
 
@@ -263,50 +235,34 @@ int dudf_mesh_sample_surface(const double* vertices, int64_t V, const int64_t* f
     DudfProfScope prof(PROF_OTHER, st);
     const SampleCarve w = carve_sample(workspace, F);
     float* fn = out_face_normals ? out_face_normals : w.fn;
-    hipError_t e = hipMemsetAsync(w.status, 0, sizeof(SampleStatus), st);
-    if (e != hipSuccess) return (int)e;
-    const int groups = dudf_grid_for(F, DUDF_WG, kFaceMaxGroups);
-    hipLaunchKernelGGL(surf_faces_kernel, dim3(groups), dim3(DUDF_WG), 0, st, vertices, V, faces, F, w.nn, fn, w.partials, w.status);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    if (out_area) {
-        hipLaunchKernelGGL(surf_area_kernel, dim3(1), dim3(kFaceMaxGroups), 0, st, w.partials, groups, out_area);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
+    DUDF_TRY(hipMemsetAsync(w.status, 0, sizeof(SampleStatus), st));
+    const int groups = dudf_ordsum_groups(F);
+    DUDF_TRY(dudf_launch(surf_faces_kernel, dim3(groups), dim3(DUDF_WG), st, vertices, V, faces, F, w.nn, fn, w.partials, w.status));
+    if (out_area) DUDF_TRY(dudf_launch(surf_area_kernel, dim3(1), dim3(kOrdSumMaxGroups), st, w.partials, groups, out_area));
     // the one host read of the call: the weights need nn_max, and a mesh without area or with a bad face is refused here
     SampleStatus h;
-    e = hipMemcpyAsync(&h, w.status, sizeof(SampleStatus), hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return (int)e;
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return (int)e;
+    DUDF_TRY(hipMemcpyAsync(&h, w.status, sizeof(SampleStatus), hipMemcpyDeviceToHost, st));
+    DUDF_TRY(hipStreamSynchronize(st));
     if (h.flags & (kFlagBadIndex | kFlagNonFinite)) return DUDF_E_BADMODE;
     double nn_max;
     memcpy(&nn_max, &h.max_bits, sizeof(double));
     if (!(nn_max > 0.0)) return DUDF_E_BADCFG;
     if (n == 0) return 0;
     const int64_t nblocks = (F + DUDF_WG - 1) / DUDF_WG;
-    hipLaunchKernelGGL(surf_weights_kernel, dim3((unsigned)nblocks), dim3(DUDF_WG), 0, st, w.nn, F, nn_max, w.c, w.blk);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    DUDF_TRY(dudf_launch(surf_weights_kernel, dim3((unsigned)nblocks), dim3(DUDF_WG), st, w.nn, F, nn_max, w.c, w.blk));
     if (nblocks > 1) {
-        hipLaunchKernelGGL(dudf_scan_totals64_kernel, dim3(1), dim3(1024), 0, st, w.blk, w.off, nblocks, &w.status->total);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(surf_offsets_kernel, dim3(dudf_grid_for(F, DUDF_WG, kGridCap)), dim3(DUDF_WG), 0, st, w.c, F, w.off);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
+        DUDF_TRY(dudf_launch(dudf_scan_totals64_kernel, dim3(1), dim3(1024), st, w.blk, w.off, nblocks, &w.status->total));
+        DUDF_TRY(dudf_launch(surf_offsets_kernel, dim3(dudf_grid_for(F, DUDF_WG, kGridCap)), dim3(DUDF_WG), st, w.c, F, w.off));
     }
     SampleArgs a;
     a.v = vertices; a.f = faces; a.nf = F; a.c = w.c; a.fn = fn; a.start = start; a.n = n;
     a.k1 = dudf_splitmix64(seed * 0x100000001B3ull + 301); a.k2 = dudf_splitmix64(seed * 0x100000001B3ull + 302);
     a.k3 = dudf_splitmix64(seed * 0x100000001B3ull + 303);
     a.uniforms = uniforms; a.out_points = out_points; a.out_normals = out_normals; a.out_face = out_face;
-    hipLaunchKernelGGL(surf_sample_kernel, dim3(dudf_grid_for(n, DUDF_WG, kGridCap)), dim3(DUDF_WG), 0, st, a);
-    return (int)hipGetLastError();
+    return dudf_launch(surf_sample_kernel, dim3(dudf_grid_for(n, DUDF_WG, kGridCap)), dim3(DUDF_WG), st, a);
 }
 
-size_t dudf_distance_stats_workspace_bytes(int64_t n) { return dudf_round256((size_t)stats_groups(n) * 2 * sizeof(double)); }   // >= 256
+size_t dudf_distance_stats_workspace_bytes(int64_t n) { return dudf_round256((size_t)dudf_ordsum_groups(n) * 2 * sizeof(double)); }   // >= 256
 
 int dudf_distance_stats(const float* dist, int64_t n, const double* thresholds, int K, int64_t* out_counts, float* out_max,
                         double* out_sums, void* workspace, size_t workspace_bytes, void* stream) {
@@ -318,19 +274,13 @@ int dudf_distance_stats(const float* dist, int64_t n, const double* thresholds, 
     double* partials = reinterpret_cast<double*>(workspace);
     StatsTaus taus = {};
     for (int k = 0; k < K; ++k) taus.tau[k] = thresholds[k];
-    hipError_t e = hipMemsetAsync(out_counts, 0, (size_t)(K + 1) * sizeof(int64_t), st);
-    if (e != hipSuccess) return (int)e;
-    e = hipMemsetAsync(out_max, 0, sizeof(float), st);
-    if (e != hipSuccess) return (int)e;
-    const int groups = n > 0 ? stats_groups(n) : 0;
-    if (groups > 0) {
-        hipLaunchKernelGGL(stats_partial_kernel, dim3(groups), dim3(kStatsBlock), 0, st, dist, n, taus, K,
-                           reinterpret_cast<unsigned long long*>(out_counts), reinterpret_cast<unsigned*>(out_max), partials);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(stats_final_kernel, dim3(1), dim3(kStatsMaxGroups), 0, st, partials, groups, out_sums);
-    return (int)hipGetLastError();
+    DUDF_TRY(hipMemsetAsync(out_counts, 0, (size_t)(K + 1) * sizeof(int64_t), st));
+    DUDF_TRY(hipMemsetAsync(out_max, 0, sizeof(float), st));
+    const int groups = n > 0 ? dudf_ordsum_groups(n) : 0;
+    if (groups > 0)
+        DUDF_TRY(dudf_launch(stats_partial_kernel, dim3(groups), dim3(kOrdSumBlock), st, dist, n, taus, K,
+                             reinterpret_cast<unsigned long long*>(out_counts), reinterpret_cast<unsigned*>(out_max), partials));
+    return dudf_launch(stats_final_kernel, dim3(1), dim3(kOrdSumMaxGroups), st, partials, groups, out_sums);
 }
 
 }  // extern "C"
