@@ -128,7 +128,8 @@ def run(dataset, outfolder, cuda_device, exp_config=None, surface_samples=0, fsc
     returns no mesh raises RuntimeError naming the experiment (the reference fails there on its tuple unpacking).
     surface_samples > 0: every experiment also appends a row to `results_surface.csv` (`surface_header(fscore_taus)`): the
     surface-sampled metrics of the CAP and MU meshes against the `_pc.ply` cloud and, for the accuracy direction, the `_t.obj` mesh
-    beside it.  `results.csv` and the returned rows do not change."""
+    beside it.  `results.csv` and the returned rows do not change.  `exp_config` goes to `setup_train` as it is, this repository's
+    own keys included (`"hip_graph"`, `"sampler_index"`: train.py)."""
     from train import setup_train
     if not os.path.exists(outfolder):
         os.mkdir(outfolder)

@@ -125,6 +125,15 @@ SYMBOLS = {
     "dudf_sample_batch": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                          ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                                          _P, _P, _P, _P]),
+    "dudf_cloud_index_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "dudf_cloud_morton_codes": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_size_t, _P, _P]),
+    "dudf_cloud_index_build": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_sample_batch_indexed_at": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                    ctypes.c_int64, ctypes.c_uint64, _P, ctypes.c_int, ctypes.c_int,
+                                                    _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
+    "dudf_sample_batch_indexed": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                 ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+                                                 _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
     "dudf_capudf_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "dudf_capudf_count": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_double, _P, _P, ctypes.c_size_t, _P]),
     "dudf_capudf_emit": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_double, _P, _P, _P, _P, ctypes.c_size_t, _P]),

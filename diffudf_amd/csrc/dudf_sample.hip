@@ -1,6 +1,6 @@
 // Per-step training batch on the GPU — replaces reference src/dataset.py:14-70 `sampleTrainingData`
-// (open3d RaycastingScene on the CPU) for triangle meshes small enough for a brute-force distance
-// (the beetle has 2 053 triangles; 20 k queries x 2 k triangles is ~2.5 GFLOP, tens of microseconds).
+// (open3d RaycastingScene on the CPU).  The DEFAULT path: a brute-force distance over the whole shape, which suits small meshes
+// (the beetle has 2 053 triangles; 20 k queries x 2 k triangles is ~2.5 GFLOP, tens of microseconds); dudf_sample_indexed.hip walks a BVH.
 //
 // Batch = [on-surface | far | near]  (reference :52-68):
 //   on   : a random point of the precomputed surface cloud, its triangle normal, sdf = 0

@@ -11,13 +11,31 @@ of the three strata, so every rank keeps the on/far/near mix and the union over 
 
 `SyntheticPointCloud` draws the batch from `diffudf_amd.synth` (uniform coordinates, the same three strata);
 `PointCloud` is the mesh-backed sampler: host-side OBJ/PLY preparation in
-`diffudf_amd/mesh.py`, per-step sampling + exact point-to-triangle distance on the GPU (`csrc/dudf_sample.hip`).
+`diffudf_amd/mesh.py`, per-step sampling + exact point-to-triangle distance on the GPU (`csrc/dudf_sample.hip`: a scan of the
+whole shape, the default path; `csrc/dudf_sample_indexed.hip`: through a BVH, for large meshes and clouds — `index="tree"`).
 The reference's own one needs open3d, which this image does not have.
 """
 import numpy as np
 import torch
 
 from . import synth
+
+
+SAMPLER_INDEX_MODES = ("brute", "tree", "auto")
+# `index="auto"`: the smallest measured sizes from which the tree's [min, max] time per batch lies wholly below the scan's
+# (tools/bench_sampler_index.py on one MI355X, batch 30 000; the run is in profiles/HISTORY.md, "Sampler through a BVH").  Below
+# them the scan stays.  None: no measured size qualified — up to 1 310 720 triangles (an icosphere) the tree's slowest batch was
+# never below the scan's fastest, so "auto" keeps every mesh on the scan; clouds qualified at the 10^6 points measured (the
+# next smaller size measured, 10^5, did not).
+AUTO_TREE_MIN_TRIANGLES = None
+AUTO_TREE_MIN_POINTS = 1000000
+
+
+def check_sampler_index(index, key="index"):
+    """`index` if it names a sampler mode, else ValueError naming `key` (the keyword, or the config key it came from)."""
+    if index not in SAMPLER_INDEX_MODES:
+        raise ValueError(f"{key}: {index!r} is not one of {', '.join(repr(m) for m in SAMPLER_INDEX_MODES)}")
+    return index
 
 
 def batch_size_of(batchSize, samplingPercentiles):
@@ -68,12 +86,17 @@ class PointCloud:
     no-op), ordered [on | far | near] exactly like the reference.  `rank`/`world` shard each stratum.
     `onlyPCloud=True` (point-cloud input, reference :80-131): only `<prefix>_pc.ply` (or the in-memory cloud) is used;
     far distances go to the nearest cloud point and near distances are |offset|.  A `_pc.ply` without normals (a raw scan) gets
-    them estimated and oriented once at load (`metrics.estimate_normals`)."""
+    them estimated and oriented once at load (`metrics.estimate_normals`).
+    `index`: how the off-surface distances are found — "brute" (default) scans the whole shape per batch (`dudf_sample_batch`);
+    "tree" builds a BVH over the triangles (or, with onlyPCloud, over the cloud) once, here, and walks it
+    (`dudf_sample_batch_indexed`; ValueError for a NaN or infinite coordinate); "auto" takes the tree from
+    AUTO_TREE_MIN_TRIANGLES / AUTO_TREE_MIN_POINTS on.  The batches are bit-identical in every mode."""
 
     def __init__(self, meshPath, batchSize, samplingPercentiles, batchesPerEpoch, device=None, onlyPCloud=False,
-                 seed=123, rank=0, world=1, surfacePoints=100000):
+                 seed=123, rank=0, world=1, surfacePoints=100000, index="brute"):
         import ctypes
         from . import _lib, mesh
+        check_sampler_index(index)
         self.onlyPCloud = bool(onlyPCloud)
         self.device = torch.device("cuda", 0) if device is None else torch.device(device)
         if self.device.type != "cuda":
@@ -92,6 +115,18 @@ class PointCloud:
         self._step = 0
         self._step_dev = None            # use_device_step(): the step counter lives in device memory (graph-replayable)
         self._lib, self._ct = _lib, ctypes
+        size = self.pc_pos.shape[0] if self.tri is None else self.tri.shape[0]
+        if index == "auto":
+            least = AUTO_TREE_MIN_POINTS if self.tri is None else AUTO_TREE_MIN_TRIANGLES
+            index = "tree" if least is not None and size >= least else "brute"
+        self.index = index
+        self._mesh_index = self._cloud_index = None          # the BVH buffer (uint8), held for the sampler's lifetime
+        if index == "tree":
+            from . import hip_ops
+            if self.tri is None:
+                self._cloud_index = hip_ops.cloud_index_build(self.pc_pos)
+            else:
+                self._mesh_index = hip_ops.mesh_index_build(self.tri)
 
     def use_device_step(self):
         """Keep the step counter in DEVICE memory from now on (`dudf_sample_batch_at`; advanced on the stream after every
@@ -111,9 +146,10 @@ class PointCloud:
         """Leading on-surface points of THIS rank's batch ([on | far | near]; train.py passes it to loss_s1 as a hint)."""
         return self.n_local()[0]
 
-    def sample(self, step):
+    def sample(self, step, stats=None):
         """(x (n,3), normals (n,3), sdf (n,)) device tensors for global step `step` (None: the device counter of
-        `use_device_step`); n_on leading on-surface points."""
+        `use_device_step`); n_on leading on-surface points.  stats (index "tree" only): int64 CUDA tensor of 1, the number of
+        exact distance evaluations is ADDED to it."""
         ct, lib = self._ct, self._lib.load()
         n_on, n_far, n_near = self.n_local()
         n = n_on + n_far + n_near
@@ -125,11 +161,21 @@ class PointCloud:
             head = (P(self.tri) if self.tri is not None else None, self.tri.shape[0] if self.tri is not None else 0,
                     P(self.pc_pos), P(self.pc_nrm), self.pc_pos.shape[0], self.samplesOnSurface, self.n_far, self.n_near, self.seed)
             tail = (self.rank, self.world, P(x), P(nrm), P(sdf), ct.c_void_p(torch.cuda.current_stream().cuda_stream))
-            if step is None:
+            if self.index == "tree":
+                B = lambda t: (P(t), t.numel()) if t is not None else (None, 0)   # noqa: E731
+                tail = (self.rank, self.world, *B(self._mesh_index), *B(self._cloud_index), *tail[2:5],
+                        P(stats) if stats is not None else None, tail[5])
+                if step is None:
+                    rc = lib.dudf_sample_batch_indexed_at(*head, P(self._step_dev), *tail)
+                else:
+                    rc = lib.dudf_sample_batch_indexed(*head, step, *tail)
+            elif stats is not None:
+                raise self._lib.DudfError("PointCloud.sample: stats counts the evaluations of index='tree' only")
+            elif step is None:
                 rc = lib.dudf_sample_batch_at(*head, P(self._step_dev), *tail)
             else:
                 rc = lib.dudf_sample_batch(*head, step, *tail)
-        self._lib.check(rc, "dudf_sample_batch")
+        self._lib.check(rc, "dudf_sample_batch_indexed" if self.index == "tree" else "dudf_sample_batch")
         return x, nrm, sdf
 
     def __iter__(self):

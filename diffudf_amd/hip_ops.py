@@ -1190,6 +1190,35 @@ def mesh_index_build(tri, order=None):
     return index
 
 
+def cloud_index_build(pc_pos, order=None):
+    """Index of a point cloud pc_pos (P,3) float32 for the indexed batch sampler (`dudf_sample_batch_indexed`): a uint8 CUDA tensor.
+    The mesh index's construction over points: Morton codes on the device, a stable `torch.sort`, the leaves of 8 points, then the
+    boxes level by level; one host read at the end (the flag word).  ValueError for a NaN / infinite coordinate.  order (P,)
+    int64: a permutation of the points to build the leaves from instead of the Morton order."""
+    pc_pos = _tensor(pc_pos, "cloud_index_build: pc_pos", torch.float32, (3,), convert=True)
+    n, dev = pc_pos.shape[0], pc_pos.device
+    if n == 0:
+        raise _lib.DudfError("cloud_index_build: a cloud without points has no index (DUDF_E_BADCFG)")
+    nbytes = _bytes("dudf_cloud_index_bytes", n, err=-4)
+    index = torch.zeros(nbytes, dtype=torch.uint8, device=dev)     # zeros: the padding between the sections is part of "same bytes"
+    assert index.data_ptr() % 256 == 0
+    with torch.cuda.device(dev):
+        if order is None:
+            codes = torch.empty(n, dtype=torch.int64, device=dev)
+            _call("dudf_cloud_morton_codes", _ptr(pc_pos), n, _ptr(index), nbytes, _ptr(codes))
+            order = torch.sort(codes, stable=True).indices
+        elif not torch.is_tensor(order) or order.device != dev or order.dtype != torch.int64 or order.shape != (n,):
+            raise _lib.DudfError("cloud_index_build: order must be an int64 (P,) CUDA tensor on the device of pc_pos")
+        order = order.contiguous()
+        _call("dudf_cloud_index_build", _ptr(pc_pos), n, _ptr(order), _ptr(index), nbytes)
+    flags = int(index[MESH_INDEX_FLAGS_OFFSET:MESH_INDEX_FLAGS_OFFSET + 4].view(torch.int32).item())
+    if flags & MESH_FLAG_NONFINITE:
+        raise ValueError("cloud_index_build: the cloud has a NaN or infinite coordinate")
+    if flags & MESH_FLAG_BAD_ORDER:
+        raise _lib.DudfError("cloud_index_build: the sorted order is not a permutation of the points")
+    return index
+
+
 def _mesh_args(what, tri, index):
     """(tri (T,9) float32, index bytes) of a mesh query: the checks `mesh_distance` makes."""
     tri = _tensor(tri, f"{what}: tri", torch.float32, (9,), convert=True)

@@ -706,6 +706,45 @@ int dudf_sample_batch_at(const float* tri, int64_t n_tri, const float* pc_pos, c
                          int64_t n_on, int64_t n_far, int64_t n_near, uint64_t seed, const int64_t* step_dev, int rank, int world,
                          float* x, float* normals, float* sdf, void* stream);
 
+/* The same batches with the distances taken through an index instead of a scan of the whole shape, for meshes and clouds whose
+ * size makes the scan the step's largest cost.  csrc/dudf_sample_indexed.hip, csrc/dudf_groupwalk.h.  Like the dudf_mesh_* entry
+ * points these arrived after ABI 8 without changing any existing signature.
+ *
+ * The cloud index is the mesh index's fixed-shape Morton tree over pc_pos (n_pc,3): a sorted copy of the points as 16-byte rows,
+ * leaves of 8 points, fp32 boxes in heap order with empty boxes past the last leaf.  0 < n_pc < 2^31 (n_pc <= 0: DUDF_E_BADCFG,
+ * larger: DUDF_E_UNSUPPORTED); the buffer is 256-byte aligned device memory of dudf_cloud_index_bytes(n_pc) bytes (else
+ * DUDF_E_WORKSPACE).
+ * dudf_cloud_index_bytes — size of the index of n_pc points; 0 for an n_pc out of range.
+ * dudf_cloud_morton_codes — codes (n_pc) int64 = 63-bit Morton code of every point inside the bounding box of all of them.  The
+ *   caller sorts them — a STABLE sort — and passes the permutation on.  Uses the head of `index` as scratch.
+ * dudf_cloud_index_build — builds the index for `order` (n_pc) int64, order[s] = original index of the s-th point along the curve;
+ *   any permutation gives a correct index.  Nothing comes back to the host; the 32-bit word at byte DUDF_MESH_INDEX_FLAGS_OFFSET
+ *   of the index then holds DUDF_MESH_FLAG_NONFINITE if a coordinate is NaN or infinite and DUDF_MESH_FLAG_BAD_ORDER if an entry
+ *   of `order` lies outside [0, n_pc); an index with a flag set must not be used.  Two builds from the same inputs are
+ *   byte-identical.
+ * dudf_sample_batch_indexed / dudf_sample_batch_indexed_at — dudf_sample_batch / dudf_sample_batch_at: the same arguments, samples,
+ *   sharding and layout, and the same bits in x, normals and sdf (every distance is the minimum of the same exact fp64 values; a
+ *   subtree is skipped only on a safe-side bound STRICTLY above the best exact value).  8 adjacent lanes share a sample and walk
+ *   the tree together, a leaf per step.  n_tri > 0: far and near samples walk mesh_index, the index dudf_mesh_index_build wrote for
+ *   tri (mesh_index_bytes = dudf_mesh_index_bytes(n_tri)); cloud_index is not looked at.  n_tri == 0: far samples walk cloud_index,
+ *   built for pc_pos (cloud_index_bytes = dudf_cloud_index_bytes(n_pc)); near samples need no distance; mesh_index is not looked
+ *   at.  On-surface samples walk nothing.  *out_stats (device int64, may be NULL, ADDED to) = exact evaluations of the call.
+ *   Every check is made before the first device call: dudf_sample_batch's refusals; n_tri >= 2^31, or n_tri == 0 and
+ *   n_pc >= 2^31: DUDF_E_UNSUPPORTED; then the index the mode needs — (NULL, 0 bytes), the caller has none: DUDF_E_BADCFG; NULL
+ *   otherwise, misaligned, or not exactly the published size: DUDF_E_WORKSPACE.  The launch allocates nothing, copies nothing to
+ *   the host and does not synchronise: both forms can be captured in a graph, the _at form drawing a new batch at every replay. */
+size_t dudf_cloud_index_bytes(int64_t n_pc);
+int dudf_cloud_morton_codes(const float* pc_pos, int64_t n_pc, void* index, size_t index_bytes, int64_t* codes, void* stream);
+int dudf_cloud_index_build(const float* pc_pos, int64_t n_pc, const int64_t* order, void* index, size_t index_bytes, void* stream);
+int dudf_sample_batch_indexed(const float* tri, int64_t n_tri, const float* pc_pos, const float* pc_nrm, int64_t n_pc, int64_t n_on,
+                              int64_t n_far, int64_t n_near, uint64_t seed, uint64_t step, int rank, int world,
+                              const void* mesh_index, size_t mesh_index_bytes, const void* cloud_index, size_t cloud_index_bytes,
+                              float* x, float* normals, float* sdf, int64_t* out_stats, void* stream);
+int dudf_sample_batch_indexed_at(const float* tri, int64_t n_tri, const float* pc_pos, const float* pc_nrm, int64_t n_pc, int64_t n_on,
+                                 int64_t n_far, int64_t n_near, uint64_t seed, const int64_t* step_dev, int rank, int world,
+                                 const void* mesh_index, size_t mesh_index_bytes, const void* cloud_index, size_t cloud_index_bytes,
+                                 float* x, float* normals, float* sdf, int64_t* out_stats, void* stream);
+
 /* Measurement hook (bench.py): while enabled, every kernel the library launches is bracketed by HIP
  * events ON THE STREAM IT IS LAUNCHED ON.  dudf_profile_dump synchronises those events and writes one
  * text line per kernel kind, "<name> <launches> <total_ms>\n", into buf (host), then clears the log. */

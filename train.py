@@ -41,7 +41,7 @@ import numpy as np
 import torch
 
 from diffudf_amd import hip_ops
-from diffudf_amd.dataset import PointCloud, SyntheticPointCloud
+from diffudf_amd.dataset import PointCloud, SyntheticPointCloud, check_sampler_index
 from diffudf_amd.loss_functions import loss_siren, loss_s1, loss_s2
 from diffudf_amd.model import SIREN
 from diffudf_amd.optim import Adam
@@ -325,7 +325,15 @@ def train_model_siren(dataset, model, device, config):
     return _train(dataset, model, device, config, schedule)
 
 
+def sampler_index_of(parameter_dict):
+    """Config key "sampler_index": how `PointCloud` finds the off-surface distances — "brute" (default: a scan of the whole shape
+    per batch), "tree" (a BVH built once; for large meshes and clouds) or "auto".  The batches are the same bits in every mode.
+    Anything else: ValueError naming the key."""
+    return check_sampler_index(parameter_dict.get("sampler_index", "brute"), key='config key "sampler_index"')
+
+
 def setup_train(parameter_dict, cuda_device):
+    sampler_index = sampler_index_of(parameter_dict)
     if not torch.cuda.is_available():
         raise SystemExit("train.py: no GPU visible; the HIP training path has no CPU fallback")
     rank = world = None
@@ -356,7 +364,7 @@ def setup_train(parameter_dict, cuda_device):
         dataset = PointCloud(parameter_dict["dataset"], parameter_dict["batch_size"], sp,
                              parameter_dict["batches_per_epoch"], device=device,
                              onlyPCloud=parameter_dict.get('onlyPCloud', False), seed=seed,
-                             rank=rank or 0, world=world or 1)
+                             rank=rank or 0, world=world or 1, index=sampler_index)
 
     network_params = parameter_dict["network"]
     model = SIREN(n_in_features=3, n_out_features=1, hidden_layer_config=network_params["hidden_layer_nodes"],
