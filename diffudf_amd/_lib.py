@@ -171,6 +171,9 @@ SYMBOLS = {
     "dudf_set_wgrad_max_workgroups": (ctypes.c_int, [ctypes.c_int]),
     "dudf_debug_read_stash": (ctypes.c_int, [_CFG, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                              ctypes.c_int64, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_debug_eigh3": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P]),
+    "dudf_debug_loss_stage": (ctypes.c_int, [_CFG, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, ctypes.c_int64,
+                                             _DBL, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "dudf_debug_stash_layout": (ctypes.c_int, [_CFG, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     "dudf_debug_kernel_choice": (ctypes.c_int, [_CFG, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
     "dudf_stash_mode": (ctypes.c_int, [_CFG, ctypes.c_int64, ctypes.c_int64]),

@@ -250,16 +250,20 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(LossArgs a) {
                 float k = (gn > 0.f) ? c3 * a.w[3] * a.inv_n * 2.f * (gn - 1.f) / gn : 0.f;
                 gb = f32x4{k * g[0], k * g[1], k * g[2], 0.f};
                 if (on) {
-                    const float m0 = a.normals[p * 3], m1 = a.normals[p * 3 + 1], m2 = a.normals[p * 3 + 2];
-                    const float mn = sqrtf(m0 * m0 + m1 * m1 + m2 * m2);
-                    const float gnc = fmaxf(gn, 1e-8f), mnc = fmaxf(mn, 1e-8f);
-                    const float cs = (g[0] * m0 + g[1] * m1 + g[2] * m2) / (gnc * mnc);
-                    const float ka = -c2 * a.w[2] * a.inv_n;
-                    const float k1 = ka / (gnc * mnc);
-                    const float k2 = (gn > 1e-8f) ? ka * cs / (gnc * gnc) : 0.f;
-                    gb[0] += k1 * m0 - k2 * g[0];
-                    gb[1] += k1 * m1 - k2 * g[1];
-                    gb[2] += k1 * m2 - k2 * g[2];
+                    // d cos / d g = k1 m - k2 g in double, rounded once: where g is parallel to the normal — the state this term
+                    // trains towards — the two products cancel, and fp32 left 1e-7 of k1 |m| standing in place of a cotangent
+                    // that is zero: 1.6e-5 of the point's largest cotangent (tests/test_loss_stage_gpu.py)
+                    const double m[3] = {a.normals[p * 3], a.normals[p * 3 + 1], a.normals[p * 3 + 2]};
+                    const double gd[3] = {g[0], g[1], g[2]};
+                    const double gnd = sqrt(gd[0] * gd[0] + gd[1] * gd[1] + gd[2] * gd[2]);
+                    const double mnd = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+                    const double gnc = fmax(gnd, 1e-8), mnc = fmax(mnd, 1e-8);
+                    const double cs = (gd[0] * m[0] + gd[1] * m[1] + gd[2] * m[2]) / (gnc * mnc);
+                    const double ka = -(double)c2 * a.w[2] * a.inv_n;
+                    const double k1 = ka / (gnc * mnc);
+                    const double k2 = (gnd > 1e-8) ? ka * cs / (gnc * gnc) : 0.0;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) gb[i] += (float)(k1 * m[i] - k2 * gd[i]);
                 }
             } else {                                     // loss_s2 (reference :106-121)
                 if (on) {
@@ -297,7 +301,9 @@ __global__ void s2_terms_kernel(const double* stats, double w0, double w1, float
         const double cnt = stats[0], mu = stats[1] / cnt;
         const double var = (stats[2] - cnt * mu * mu) / (cnt - 1.0);
         out[0] = (float)(fabs(mu) * w0);
-        out[1] = (float)(sqrt(var > 0 ? var : 0.0) * w1);
+        // a cancellation residue below zero is zero; the NaN of fewer than two on-surface points (0 / 0) stays one, as torch.std's
+        // does (reference :115) — `var > 0 ? var : 0.0` reported a std of 0 for a batch whose backward is NaN
+        out[1] = (float)(sqrt(var < 0 ? 0.0 : var) * w1);
     }
 }
 

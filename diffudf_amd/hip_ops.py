@@ -733,6 +733,48 @@ def read_stash(cfg, which, layer, n, ws, channel=0):
     return out
 
 
+def debug_eigh3(H):
+    """Diagnostic: (lam (k,3) ascending, V (k,3,3) with V[m,i,j] = component i of v_j) of the device's 3x3 eigensolver on the LOWER
+    triangles of H (k,3,3) float64 — the routine of the loss kernels, the CAP-UDF frame, the curvature and the cloud normals."""
+    H = _tensor(H, "H", torch.float64, (3, 3))
+    k = H.shape[0]
+    lam = torch.empty(k, 3, dtype=torch.float64, device=H.device)
+    V = torch.empty(k, 3, 3, dtype=torch.float64, device=H.device)
+    _call("dudf_debug_eigh3", _ptr(H), k, _ptr(lam), _ptr(V), dev=H.device)
+    return lam, V
+
+
+def debug_loss_stage(cfg, mode, y, g, h, normals, sdf, n_global, weights, alpha, cot, ws, stats=None):
+    """Diagnostic: the loss kernels alone on planted fields — y (n), g (n,3), h (n_hess,3,3) or None, normals (n,3), sdf (n), cot (4),
+    all float32 on the GPU; ws = workspace_for(cfg, n, device, n_hess); stats (3 float64, loss_s2): the statistics the backward
+    uses instead of the batch's own.  No sweep runs.  Returns a dict: terms (4), stats (3 float64, loss_s2) or None, ybar (n), gbar
+    (n,3), hbar (n_hess,3,3) or None, pad_nonzero (the count of floats-owed-a-zero columns that are not, include/dudf_hip.h)."""
+    n, n_hess, dev = y.shape[0], ws.n_hess, y.device
+    y = _tensor(y, "y", torch.float32, ())
+    g = _tensor(g, "g", torch.float32, (3,))
+    normals = _tensor(normals, "normals", torch.float32, (3,))
+    sdf = _tensor(sdf, "sdf", torch.float32, ())
+    cot = _tensor(cot, "cot", torch.float32, ())
+    if n != ws.n or (h.shape[0] if h is not None else 0) != n_hess or g.shape[0] != n or normals.shape[0] != n or sdf.shape[0] != n \
+            or cot.shape[0] != 4:
+        raise _lib.DudfError(f"debug_loss_stage: {n} points with {0 if h is None else h.shape[0]} Hessians on a workspace for "
+                             f"({ws.n}, {ws.n_hess})")
+    if h is not None:
+        h = _tensor(h, "h", torch.float32, (3, 3))
+    if stats is not None:
+        stats = _tensor(stats, "stats", torch.float64, ())
+    out = {"terms": torch.empty(4, dtype=torch.float32, device=dev),
+           "stats": torch.empty(3, dtype=torch.float64, device=dev) if mode == LOSS_S2 else None,
+           "ybar": torch.empty(n, dtype=torch.float32, device=dev), "gbar": torch.empty(n, 3, dtype=torch.float32, device=dev),
+           "hbar": torch.empty(n_hess, 3, 3, dtype=torch.float32, device=dev) if n_hess else None}
+    pad = torch.empty(1, dtype=torch.int32, device=dev)
+    _call("dudf_debug_loss_stage", ctypes.byref(cfg), mode, n, n_hess, _ptr(y), _ptr(g), _ptr(h), _ptr(normals), _ptr(sdf),
+          int(n_global), _w4(weights), float(alpha), _ptr(cot), _ptr(stats), _ptr(out["terms"]), _ptr(out["stats"]), _ptr(out["ybar"]),
+          _ptr(out["gbar"]), _ptr(out["hbar"]), _ptr(pad), _ptr(ws.buf), ws.nbytes, dev=dev)
+    out["pad_nonzero"] = int(pad.item())
+    return out
+
+
 # ---- sphere-traced images (reference generate_st.py, src/render_st.py:67-245) ---------------------------------------------------
 SHADE_MODELS = {"blinn-phong": 0, "ward": 1}
 

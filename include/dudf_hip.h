@@ -652,6 +652,38 @@ int dudf_adam_step_scheduled(float* theta, const float* dtheta, float* exp_avg, 
 int dudf_debug_read_stash(const dudf_net_cfg* cfg, int which, int layer, int channel, int64_t n, int64_t n_hess,
                           float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Test/diagnostic hook: the symmetric 3x3 eigensolver of the loss kernels, the CAP-UDF eigen-frame, the curvature and the point-cloud
+ * normals (csrc/dudf_eigh3.h: cyclic Jacobi in fp64) on k matrices of the caller's choosing, one thread per matrix.  H (k,3,3) fp64 row-major,
+ * of which only the LOWER triangle is read (torch.linalg.eigh, reference src/loss_functions.py:142); out_lam (k,3) ascending;
+ * out_V[m][i][j] = component i of v_j.  All three are device pointers.  Arrived after ABI 8 without changing any existing signature.
+ *   k < 0: DUDF_E_BADCFG; k == 0: nothing is launched, 0; a NULL pointer with k > 0: DUDF_E_BADCFG. */
+int dudf_debug_eigh3(const double* H, int64_t k, double* out_lam, double* out_V, void* stream);
+
+/* Test/diagnostic hook: the loss stage of a training step on PLANTED fields — no sweep runs, so there is no theta.  The call
+ *   1. scatters y (n), g (n,3) and the Hessians h (n_hess,3,3; h[p][i][k] = d2f/dx_i dx_k) of the first n_hess points into the per-column
+ *      arrays of `workspace` the way a forward leaves them (the inverse of what dudf_fields_forward copies out; Hessian column k of
+ *      point p is column 4p+1+k).  Padded columns and the y of the quads' tangent channels, which no loss kernel may read, hold NaN;
+ *   2. zeroes the reduction scratch and fills the cotangent arrays with NaN;
+ *   3. launches exactly what dudf_loss_forward + dudf_loss_backward launch between their sweeps: loss_s1 / loss_siren: the term
+ *      kernel, then the cotangent kernel; loss_s2: the statistics, the two terms, then the cotangent kernel on `stats_in` (device, 3
+ *      doubles: those of a larger global batch) or, when NULL, on the statistics just computed;
+ *   4. gathers the cotangents per point: out_ybar (n), out_gbar (n,3), out_hbar (n_hess,3,3) with out_hbar[p][i][k] from column 4p+1+k.
+ * out_terms (4 floats; loss_s2 writes two and leaves two zero), out_stats (3 doubles (count, sum, sum of squares); loss_s2 only),
+ * out_pad_nonzero (1 int): the number of columns holding a float the stage owes a zero that is not +0 bit for bit — any of the five of a
+ * padded column (quad padding, plain padding), ybar of a quad's tangent channels, the fourth gbar float of any column.  Every pointer
+ * except cfg and weights is a device pointer.  mode, n_global, weights, alpha, cot (4 floats) as in dudf_loss_backward; the
+ * `deterministic` option applies.  workspace: dudf_workspace_bytes_hess(cfg, n, n_hess).  Arrived after ABI 8 without changing any
+ * existing signature.
+ *   Refusals, all before any device work and in this order: weights NULL: DUDF_E_BADCFG; a mode that is none of the three, loss_s2
+ *   without out_stats, n_hess != 0 outside loss_s1 with a Hessian weight: DUDF_E_BADMODE; a bad cfg, n < 0, n_hess > n: DUDF_E_BADCFG;
+ *   workspace: DUDF_E_WORKSPACE; n_global < 1 with n > 0: DUDF_E_BADCFG; n == 0: nothing is launched, 0; any other NULL pointer the
+ *   mode needs (h and out_hbar only with n_hess > 0, stats_in never): DUDF_E_BADCFG. */
+int dudf_debug_loss_stage(const dudf_net_cfg* cfg, int mode, int64_t n, int64_t n_hess, const float* y, const float* g, const float* h,
+                          const float* normals, const float* sdf, int64_t n_global, const double* weights, double alpha,
+                          const float* cot, const double* stats_in, float* out_terms, double* out_stats, float* out_ybar,
+                          float* out_gbar, float* out_hbar, int* out_pad_nonzero, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* Host-only diagnostic (no GPU work): where the per-column arrays of a training workspace sit.  out (host, 10 values):
  * byte offsets of S, C, Q, E, A, Z, R, ZS in the workspace (order of `which` above), then the byte stride between two
  * feature-quad rows and between two layers OF THE fp32 ARRAYS.  Every offset and both strides are multiples of 256: a lane

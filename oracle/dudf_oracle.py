@@ -235,6 +235,7 @@ def loss_s2_terms(y, sdf, weights, xp=np, stats=None):
     var = (sq - n * mu * mu) / (n - 1.0)                  # torch.std: unbiased
     if stats is None:                                      # two-pass form when the data is local (better conditioned)
         var = (xp.where(on, (y - mu) ** 2, zero)).sum() / (n - 1.0)
+        var = var + 0.0 * mu                              # no on-surface point: torch.std of nothing is NaN (:115), not 0 / -1
     sd = xp.sqrt(var)
     out = {"sdf_on_surf": xp.abs(mu) * weights[0], "std_on_surf": sd * weights[1]}
     ybar = xp.where(on, weights[0] * xp.sign(mu) / n + weights[1] * (y - mu) / ((n - 1.0) * sd), zero)

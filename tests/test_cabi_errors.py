@@ -80,6 +80,9 @@ CALLS = {
                              lambda L, c, n: L.dudf_workspace_bytes(ref(c), n), True, False),
     "dudf_debug_read_stash": (lambda L, c, n, ws, nb: L.dudf_debug_read_stash(ref(c), 0, 0, 0, n, 0, P, ws, nb, None),
                               lambda L, c, n: L.dudf_workspace_bytes_hess(ref(c), n, 0), True, False),
+    "dudf_debug_loss_stage": (lambda L, c, n, ws, nb: L.dudf_debug_loss_stage(ref(c), 0, n, 0, P, P, None, P, P, n, W4, 1.0, P, None, P, None, P, P,
+                                                                              None, P, ws, nb, None),
+                              lambda L, c, n: L.dudf_workspace_bytes_hess(ref(c), n, 0), True, True),
     "dudf_nearest_points": (lambda L, c, n, ws, nb: L.dudf_nearest_points(P, n, P, 4, 2, P, P, ws, nb, None),
                             lambda L, c, n: L.dudf_nearest_workspace_bytes(n), False, True),
     "dudf_chamfer_terms": (lambda L, c, n, ws, nb: L.dudf_chamfer_terms(P, None, n, None, None, 0, P, ws, nb, None),
@@ -426,6 +429,53 @@ def test_debug_read_stash_ranges():
     assert lib.dudf_debug_stash_layout(ref(cfg), N, 0, None) == E_CFG
     assert lib.dudf_debug_stash_layout(ref(cfg), N, 0, out) == OK
     assert lib.dudf_debug_kernel_choice(ref(cfg), N, 0, 0, 0, None, 0) == E_CFG
+
+
+def test_debug_loss_stage_and_eigh3_refusals():
+    """Every refusal comes before any device work: the pointers are host addresses no kernel could read, and there is no GPU here."""
+    lib, cfg = _lib.load(), good_cfg()
+    nb = need_of(lib, "dudf_debug_loss_stage", cfg, N)
+    nbh = int(lib.dudf_workspace_bytes_hess(ref(cfg), N, 2))
+    assert 0 < nbh <= (1 << 22) - 512
+
+    def stage(c=cfg, mode=_lib.LOSS_S1, n=N, n_hess=0, w=W4, ws=P, nbytes=nb, n_global=N, **null):
+        a = {k: (None if k in null else P) for k in ("y", "g", "h", "normals", "sdf", "cot", "stats_in", "out_terms", "out_stats", "out_ybar",
+                                                    "out_gbar", "out_hbar", "out_pad")}
+        return lib.dudf_debug_loss_stage(ref(c), mode, n, n_hess, a["y"], a["g"], a["h"], a["normals"], a["sdf"], n_global, w, 1.0, a["cot"],
+                                         a["stats_in"], a["out_terms"], a["out_stats"], a["out_ybar"], a["out_gbar"], a["out_hbar"],
+                                         a["out_pad"], ws, nbytes, None)
+
+    # check_loss_mode's rules, in front of cfg and workspace as in dudf_loss_backward
+    assert stage(mode=7, ws=None) == E_MODE
+    assert stage(c=None, mode=-1, ws=None) == E_MODE
+    assert stage(mode=_lib.LOSS_S2, out_stats=None, ws=None) == E_MODE             # loss_s2 needs somewhere for its statistics
+    assert stage(mode=_lib.LOSS_S2, ws=None) == E_WS
+    assert stage(mode=_lib.LOSS_S1, n_hess=2, w=W4, ws=None) == E_MODE             # Hessian-path points without a Hessian weight
+    assert stage(mode=_lib.LOSS_SIREN, n_hess=2, w=W4H, ws=None) == E_MODE
+    assert stage(mode=_lib.LOSS_S2, n_hess=2, w=W4H, ws=None) == E_MODE
+    assert stage(mode=_lib.LOSS_S1, n_hess=2, w=W4H, ws=None) == E_WS
+    assert stage(w=None, mode=7, ws=None) == E_CFG                                  # the weights are read by the mode check
+    # cfg and the counts, then the workspace
+    assert stage(c=None, ws=None) == E_CFG
+    assert stage(n_hess=N + 1, w=W4H) == E_CFG                                     # more Hessian points than points
+    assert stage(n=-1) == E_CFG
+    assert stage(nbytes=nb - 1) == E_WS
+    assert stage(ws=ctypes.c_void_p(BASE + 8)) == E_WS
+    assert stage(n_hess=2, w=W4H, nbytes=nbh - 1) == E_WS
+    assert stage(y=None, ws=None) == E_WS                                          # the workspace before the row pointers
+    # an empty call succeeds without looking at its pointers; a call with points needs them all
+    assert stage(n=0, n_global=0, y=None, g=None, sdf=None, out_terms=None, out_pad=None) == OK
+    assert stage(n_global=0) == E_CFG
+    for name in ("y", "g", "normals", "sdf", "cot", "out_terms", "out_ybar", "out_gbar", "out_pad"):
+        assert stage(**{name: None}) == E_CFG, name
+    assert stage(mode=_lib.LOSS_S2, stats_in=None, y=None) == E_CFG                # (stats_in itself is optional)
+    for name in ("h", "out_hbar"):                                                 # needed with Hessian-path points only
+        assert stage(n_hess=2, w=W4H, nbytes=nbh, **{name: None}) == E_CFG, name
+    # the eigensolver: no workspace, three device pointers
+    assert lib.dudf_debug_eigh3(P, -1, P, P, None) == E_CFG
+    assert lib.dudf_debug_eigh3(None, 0, None, None, None) == OK
+    for args in ((None, N, P, P), (P, N, None, P), (P, N, P, None)):
+        assert lib.dudf_debug_eigh3(*args, None) == E_CFG
 
 
 def test_chamfer_and_nearest_precedence():
