@@ -612,6 +612,55 @@ def mesh_smooth_borders(vertices, faces, iterations=5, lam=0.3):
     return out
 
 
+MESH_TOPOLOGY_COUNTS = ("components", "forest_edges", "manifold_edges", "border_edges", "nonmanifold_edges", "ignored_faces",
+                        "flipped_faces", "inconsistent_edges")
+
+
+def mesh_topology(faces, n_vertices, vertices=None):
+    """Winding and components of a device mesh (`dudf_mesh_topology`; the rules: DESIGN.md §3.6b).  faces (F,3) int64, vertices None
+    or (V,3) float64 (then the integer areas are filled).  Returns (oriented faces (F,3) int64, component (F,) int64, flip (F,) uint8,
+    component_faces (F,) int64, component_area_q (F,) int64 holding the bits of the uint64 sums, counts: a dict
+    over MESH_TOPOLOGY_COUNTS).  The Borůvka rounds read one word back each; the counts are one more host sync."""
+    faces = _tensor(faces, "faces", torch.int64, (3,), convert=True)
+    dev = faces.device
+    V, F = int(n_vertices), faces.shape[0]
+    if vertices is not None:
+        vertices = _tensor(vertices, "vertices", torch.float64, (3,), convert=True)
+        if vertices.device != dev:
+            raise _lib.DudfError("vertices and faces must be on one device")
+        if vertices.shape[0] != V:
+            raise _lib.DudfError(f"vertices has {vertices.shape[0]} rows, n_vertices is {V}")
+    ws, nbytes = _workspace(dev, "dudf_mesh_topology_workspace_bytes", F, err=-4)
+    out_f = torch.empty(F, 3, dtype=torch.int64, device=dev)
+    comp = torch.empty(F, dtype=torch.int64, device=dev)
+    flip = torch.empty(F, dtype=torch.uint8, device=dev)
+    nfaces = torch.empty(F, dtype=torch.int64, device=dev)
+    area_q = torch.zeros(F, dtype=torch.int64, device=dev)
+    counts = torch.zeros(len(MESH_TOPOLOGY_COUNTS), dtype=torch.int64, device=dev)
+    _call("dudf_mesh_topology", _ptr(faces), F, V, _ptr(vertices), _ptr(out_f), _ptr(comp), _ptr(flip), _ptr(nfaces), _ptr(area_q),
+          _ptr(counts), _ptr(ws), nbytes, dev=dev)
+    return out_f, comp, flip, nfaces, area_q, dict(zip(MESH_TOPOLOGY_COUNTS, (int(v) for v in counts.tolist())))
+
+
+def mesh_submesh(vertices, faces, keep):
+    """The faces with keep != 0 in their order, the vertices they use in their order, faces re-indexed (`dudf_mesh_submesh_count` /
+    `_emit`).  keep (F,) bool or uint8.  Returns (vertices (V',3) float64, faces (F',3) int64).  One host sync for the counts."""
+    vertices, faces = _mesh(vertices, faces)
+    dev = vertices.device
+    V, F = vertices.shape[0], faces.shape[0]
+    keep = _tensor(keep, "keep", torch.uint8, (), convert=True)
+    if keep.shape[0] != F or keep.device != dev:
+        raise _lib.DudfError(f"keep must be (F,) = ({F},) on the device of the mesh; got {tuple(keep.shape)} on {keep.device}")
+    ws, nbytes = _workspace(dev, "dudf_mesh_submesh_workspace_bytes", V, F, err=-4)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    _call("dudf_mesh_submesh_count", V, _ptr(faces), F, _ptr(keep), _ptr(counts), _ptr(ws), nbytes, dev=dev)
+    nv, nf = (int(v) for v in counts.tolist())
+    out_v = torch.empty(nv, 3, dtype=torch.float64, device=dev); out_f = torch.empty(nf, 3, dtype=torch.int64, device=dev)
+    if nv and nf:
+        _call("dudf_mesh_submesh_emit", _ptr(vertices), V, _ptr(faces), F, _ptr(keep), _ptr(out_v), _ptr(out_f), _ptr(ws), nbytes, dev=dev)
+    return out_v, out_f
+
+
 def _w4(weights):
     w = list(weights) + [0.0] * (4 - len(weights))
     return (ctypes.c_double * 4)(*[float(v) for v in w])

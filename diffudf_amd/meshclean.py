@@ -5,6 +5,9 @@ rint(v * 10^digits), drop degenerate, duplicate and invalid faces and unused ver
 border.  The rules are DESIGN.md §3 "Mesh clean-up"; the kernels are csrc/dudf_meshclean.hip.  Parity with trimesh's own vertex and
 face ORDER is not pinned; the result is deterministic and equals tests/meshclean_oracle.py bit for bit.
 
+Mesh topology (csrc/dudf_meshtopo.hip; what trimesh's `fix_winding` / `split` serve in the reference's workflows):
+`face_topology`, `orient_faces`, `remove_small_components`.  The pin is tests/meshtopo_oracle.py, exactly.
+
 Tensors stay on the device; each round reads its counts back once (they size the outputs)."""
 import numpy as np
 import torch
@@ -56,3 +59,71 @@ def smooth_borders(vertices, faces, iterations=5, lam=0.3, device=None):
     border edges; a new (V,3) float64 device tensor."""
     v, f = _device_mesh(vertices, faces, device)
     return hip_ops.mesh_smooth_borders(v, f, iterations, lam)
+
+
+AREA_UNIT = 2.0 ** -31                  # area of a component = its integer sum * AREA_UNIT (q = rint(min(nn, 16) * 2^30), area = nn / 2)
+
+
+def face_topology(faces, n_vertices, vertices=None, device=None):
+    """Winding, components and edge classes of a mesh.  faces (F,3), vertices None or (V,3): tensors or numpy arrays.
+    Returns a dict: `faces` (F,3) int64 consistently wound, `component` (F,) int64 (the smallest face index of the face's component)
+    and `flip` (F,) uint8 as device tensors; per component, on the host, `labels` (C,) int64 ascending, `n_faces` (C,) int64,
+    `area_q` (C,) uint64 and `area` (C,) float64 = area_q * 2^-31 (both None without vertices); and the eight counts of
+    `hip_ops.MESH_TOPOLOGY_COUNTS` by name."""
+    _, f = _device_mesh(np.zeros((0, 3)), faces, device)
+    v = None
+    if vertices is not None:
+        v, _ = _device_mesh(vertices, np.zeros((0, 3), dtype=np.int64), f.device)
+    out_f, comp, flip, nfaces, area_q, counts = hip_ops.mesh_topology(f, int(n_vertices), v)
+    labels = nfaces.nonzero().flatten()
+    out = {"faces": out_f, "component": comp, "flip": flip, "labels": labels.cpu().numpy(), "n_faces": nfaces[labels].cpu().numpy(),
+           "area_q": None, "area": None}
+    if v is not None:
+        out["area_q"] = area_q[labels].cpu().numpy().view(np.uint64)
+        out["area"] = out["area_q"].astype(np.float64) * AREA_UNIT
+    out.update(counts)
+    return out
+
+
+def orient_faces(vertices, faces, device=None):
+    """The faces (F,3) int64 on the device, wound consistently per component: the smallest face index of a component keeps its winding
+    (DESIGN.md §3.6b).  Which side is "out" is not decided here."""
+    v, f = _device_mesh(vertices, faces, device)
+    return hip_ops.mesh_topology(f, v.shape[0])[0]
+
+
+def component_filter(labels, n_faces, area_q, min_faces=0, min_area=0.0, min_area_ratio=0.0, keep_largest=None):
+    """(C,) bool: the components that stay.  One stays iff n_faces >= min_faces, area_q >= ceil(min_area * 2^31) and area_q >=
+    ceil(min_area_ratio * sum(area_q)) — comparisons of integers —; keep_largest = k then keeps the k largest of those by (area_q,
+    n_faces) descending, ties to the smaller label."""
+    import math
+    q = [int(x) for x in area_q] if area_q is not None else [0] * len(labels)
+    n = [int(x) for x in n_faces]
+    if area_q is None and (min_area > 0.0 or min_area_ratio > 0.0):
+        raise ValueError("an area threshold needs the vertices")
+    t_area = math.ceil(float(min_area) * 2147483648.0)
+    t_ratio = math.ceil(float(min_area_ratio) * float(sum(q)))
+    keep = [n[i] >= int(min_faces) and q[i] >= t_area and q[i] >= t_ratio for i in range(len(n))]
+    if keep_largest is not None:
+        order = sorted((i for i in range(len(n)) if keep[i]), key=lambda i: (-q[i], -n[i], int(labels[i])))
+        keep = [False] * len(n)
+        for i in order[:max(int(keep_largest), 0)]:
+            keep[i] = True
+    return np.array(keep, dtype=bool)
+
+
+def remove_small_components(vertices, faces, min_faces=0, min_area=0.0, min_area_ratio=0.0, keep_largest=None, device=None):
+    """Drop the floaters: the components `component_filter` rejects (sizes and integer areas from `face_topology`), then the submesh of
+    the faces that stay (`hip_ops.mesh_submesh`: face order kept, unused vertices dropped, faces re-indexed; a face with an index
+    outside [0, V) cannot be re-indexed and goes).  Returns (vertices float64, faces int64 — consistently wound —, info) on the device;
+    info holds the counts of `face_topology` and `components_kept`, `components_removed`, `faces_removed`."""
+    v, f = _device_mesh(vertices, faces, device)
+    topo = face_topology(f, v.shape[0], v)
+    keep_c = component_filter(topo["labels"], topo["n_faces"], topo["area_q"], min_faces, min_area, min_area_ratio, keep_largest)
+    by_label = torch.zeros(max(f.shape[0], 1), dtype=torch.uint8, device=f.device)
+    by_label[torch.from_numpy(topo["labels"][keep_c]).to(f.device)] = 1
+    keep_f = by_label[topo["component"]]
+    out_v, out_f = hip_ops.mesh_submesh(v, topo["faces"], keep_f)
+    info = {k: topo[k] for k in hip_ops.MESH_TOPOLOGY_COUNTS}
+    info.update(components_kept=int(keep_c.sum()), components_removed=int((~keep_c).sum()), faces_removed=int(f.shape[0] - out_f.shape[0]))
+    return out_v, out_f, info

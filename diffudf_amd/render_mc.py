@@ -94,11 +94,31 @@ class TriangleSoup:
         return path
 
 
-def extract_mesh_CAP(ndf, grad, resolution, threshold=0.008, device=None):
+_FINISH_KEYS = ("min_faces", "min_area", "min_area_ratio", "keep_largest")
+
+
+def _finish_soup(v, f, finish):
+    """The per-cell soup (device tensors) as a mesh, on the device: welded and pruned (`meshclean.clean_mesh(fill_holes=False)`),
+    wound consistently per component (`meshclean.orient_faces`; CAP-UDF signs each cell on its own, so neighbouring cells disagree
+    on about one shared edge in six), and with a dict of `meshclean.remove_small_components` keywords the floaters dropped."""
+    if finish != "mesh" and not (isinstance(finish, dict) and all(k in _FINISH_KEYS for k in finish)):
+        raise ValueError(f"finish must be None, 'mesh' or a dict over {_FINISH_KEYS}; got {finish!r}")
+    from . import meshclean
+    v, f, _ = meshclean.clean_mesh(v, f, fill_holes=False)
+    if isinstance(finish, dict):
+        v, f, _ = meshclean.remove_small_components(v, f, **finish)
+        return v, f
+    return v, meshclean.orient_faces(v, f)
+
+
+def extract_mesh_CAP(ndf, grad, resolution, threshold=0.008, device=None, finish=None):
     """Same signature as reference src/render_mc.py:201 (`ndf` (N,N,N), `grad` (N,N,N,3): numpy arrays or tensors — the
     outputs of `extract_fields` can be passed straight through without leaving the device).  Active-cell test, sign by
     gradient, per-cell marching cubes and compaction run in `dudf_capudf_count` / `dudf_capudf_emit`; returns a
-    `trimesh.Trimesh(process=False)` when trimesh is importable, else a `TriangleSoup` with the same two arrays."""
+    `trimesh.Trimesh(process=False)` when trimesh is importable, else a `TriangleSoup` with the same two arrays.
+    `finish`: None — the per-cell triangle soup (no vertex is shared between cells), as the reference; "mesh" — welded and consistently wound on the device
+    (`_finish_soup`); a dict over min_faces / min_area / min_area_ratio / keep_largest — the same, then the small components
+    dropped (`meshclean.remove_small_components`)."""
     dev = torch.device(device) if device is not None else (ndf.device if torch.is_tensor(ndf) and ndf.is_cuda else torch.device("cuda", 0))
     if dev.type != "cuda":
         raise DudfError("extract_mesh_CAP: needs the GPU; there is no CPU fallback path")
@@ -107,6 +127,8 @@ def extract_mesh_CAP(ndf, grad, resolution, threshold=0.008, device=None):
     if d.shape[0] != resolution:
         raise ValueError("resolution does not match the field")
     v, f = hip_ops.capudf_extract(d, g, threshold)
+    if finish is not None:
+        v, f = _finish_soup(v, f, finish)
     return _as_mesh(v.cpu().numpy(), f.cpu().numpy())
 
 
@@ -240,12 +262,14 @@ def extract_fields_sparse(decoder, latent_vec, N, gt_mode, device, alpha, thresh
     return SparseFields(N, brick, threshold, lipschitz, slot, stored, cands, df, vec)
 
 
-def extract_mesh_CAP_sparse(fields, threshold=None):
+def extract_mesh_CAP_sparse(fields, threshold=None, finish=None):
     """`extract_mesh_CAP` on the `SparseFields` of `extract_fields_sparse`: the same per-cell code (`dudf_capudf_sparse_count` /
     `_emit`) over the cells of the candidate bricks, so wherever both paths walk a cell they emit the same triangles bit for bit.
     `threshold` defaults to the one the fields were selected for and may not exceed it (ValueError).  Returns a
-    `trimesh.Trimesh(process=False)` when trimesh is importable, else a `TriangleSoup`."""
+    `trimesh.Trimesh(process=False)` when trimesh is importable, else a `TriangleSoup`.  `finish`: as `extract_mesh_CAP`."""
     v, f = fields.extract(threshold)
+    if finish is not None:
+        v, f = _finish_soup(v, f, finish)
     return _as_mesh(v.cpu().numpy(), f.cpu().numpy())
 
 

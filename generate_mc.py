@@ -17,7 +17,12 @@ that signed volume, both on the device; it needs the same tables, and without th
 None (as 'both' skips its MeshUDF half), so that a training run is not lost over its mesh.
 Optional key "sparse": true (with "brick", 4 or 8, and "lipschitz"; keyword `sparse=`): 'cap' on a brick-sparse narrow band
 (`extract_fields_sparse` + `extract_mesh_CAP_sparse`) — for 1024^3 and up, where the dense fields do not fit.  The
-other algorithms need the dense volume (MeshUDF's flood is a host walk of it) and refuse the key."""
+other algorithms need the dense volume (MeshUDF's flood is a host walk of it) and refuse the key.
+Optional keys "cap_finish": "mesh" (keyword `cap_finish=`): the CAP-UDF soup welded and wound consistently on the device
+(`extract_mesh_CAP(..., finish="mesh")`); "min_component_faces" / "min_component_area_ratio": components with fewer
+faces, or less than that share of the whole area, are dropped (`diffudf_amd.meshclean.remove_small_components`) — from the CAP-UDF
+mesh, which is then finished as with "cap_finish", and from the device-cleaned MeshUDF mesh of 'meshudf' and 'both'.  Without
+these keys the files are what they were."""
 import json
 import sys
 
@@ -30,10 +35,35 @@ from diffudf_amd._lib import DudfError
 from diffudf_amd.marching_cubes import MeshUDFError
 
 
+def _component_filter(min_component_faces, min_component_area_ratio):
+    """The keywords of `remove_small_components` the two optional keys stand for; empty: no filter."""
+    filt = {}
+    if min_component_faces is not None:
+        filt["min_faces"] = int(min_component_faces)
+    if min_component_area_ratio is not None:
+        filt["min_area_ratio"] = float(min_component_area_ratio)
+    return filt
+
+
+def _without_small_components(mesh, dev, filt):
+    """`mesh` (vertices, faces) without the components `filt` rejects, as the same kind of object; no filter: `mesh` itself."""
+    if not filt:
+        return mesh
+    from diffudf_amd import meshclean
+    from diffudf_amd.render_mc import _as_mesh
+    v, f, _ = meshclean.remove_small_components(mesh.vertices, mesh.faces, device=dev, **filt)
+    return _as_mesh(v.cpu().numpy(), f.cpu().numpy())
+
+
 def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='meshudf', from_file=None, luts=None, sparse=False,
-                brick=8, lipschitz=1.25):
+                brick=8, lipschitz=1.25, cap_finish=None, min_component_faces=None, min_component_area_ratio=None):
     """`luts`: the Lewiner tables for MeshUDF and 'siren' (dict, path or None = look them up; see the module docstring).
-    `sparse`: CAP-UDF on the narrow band of `extract_fields_sparse(..., brick=brick, lipschitz=lipschitz)`; 'cap' only."""
+    `sparse`: CAP-UDF on the narrow band of `extract_fields_sparse(..., brick=brick, lipschitz=lipschitz)`; 'cap' only.
+    `cap_finish`, `min_component_faces`, `min_component_area_ratio`: see the module docstring; all None: nothing changes."""
+    if cap_finish not in (None, "mesh"):
+        raise ValueError(f"cap_finish must be None or 'mesh'; got {cap_finish!r}")
+    filt = _component_filter(min_component_faces, min_component_area_ratio)
+    finish = dict(filt) if filt else cap_finish
     if sparse and algorithm != 'cap':
         raise DudfError(f"sparse extraction serves algorithm 'cap' only; '{algorithm}' needs the dense volume")
     if from_file is not None:
@@ -44,7 +74,7 @@ def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='m
     model.to(dev)
     if sparse:
         mesh = extract_mesh_CAP_sparse(extract_fields_sparse(model, torch.Tensor([[]]).to(dev), N, gt_mode, dev, alpha, brick=brick,
-                                                             lipschitz=lipschitz))
+                                                             lipschitz=lipschitz), finish=finish)
         mesh.export(output_path)
         print(f'Saved to {output_path}')
         return mesh
@@ -53,10 +83,11 @@ def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='m
         dot = output_path.rfind('.')
         if algorithm == 'meshudf':
             _, _, mesh = extract_mesh_MESHUDF(u, g, dev, smooth_borders=True, luts=luts)
+            mesh = _without_small_components(mesh, dev, filt)
             mesh.export(output_path)
             print(f'Saved to {output_path}')
             return mesh
-        mesh = extract_mesh_CAP(u, g, N)                       # device tensors straight through: no host round trip
+        mesh = extract_mesh_CAP(u, g, N, finish=finish)        # device tensors straight through: no host round trip
         if algorithm == 'cap':
             mesh.export(output_path)
             print(f'Saved to {output_path}')
@@ -68,6 +99,7 @@ def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='m
         except MeshUDFError as e:                              # no look-up tables: the CAP half is still written, and says so
             print(f'Saved to {path_cap} (MeshUDF half skipped: {e})')
             return None, mesh
+        mesh_mu = _without_small_components(mesh_mu, dev, filt)
         mesh_mu.export(path_mu)
         print(f'Saved to {path_mu}, {path_cap}')
         return mesh_mu, mesh
@@ -90,4 +122,5 @@ if __name__ == "__main__":
                                              "hidden_layer_nodes": cfg["hidden_layer_nodes"],
                                              "activation": cfg.get("activation", "sine"), "ww": cfg.get("ww")},
                 luts=cfg.get("luts_path"), sparse=bool(cfg.get("sparse", False)), brick=cfg.get("brick", 8),
-                lipschitz=cfg.get("lipschitz", 1.25))
+                lipschitz=cfg.get("lipschitz", 1.25), cap_finish=cfg.get("cap_finish"),
+                min_component_faces=cfg.get("min_component_faces"), min_component_area_ratio=cfg.get("min_component_area_ratio"))

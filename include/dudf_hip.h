@@ -557,6 +557,40 @@ int dudf_mesh_border_edges(int64_t V, const int64_t* faces, int64_t F, int64_t* 
 int dudf_mesh_smooth_borders(double* vertices_inout, int64_t V, const int64_t* faces, int64_t F, int iterations, double lambda,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* Mesh topology on the device — consistent winding, connected components and their sizes: what the reference's users ask of trimesh's
+ * `fix_winding` / `split`.  csrc/dudf_meshtopo.hip; the rules are DESIGN.md §3.6b (tests/meshtopo_oracle.py restates them; the device
+ * result equals it exactly and is the same from run to run).  faces (F,3) int64, vertices (V,3) double or NULL, on the device;
+ * 0 <= V < 2^31, 6 F < 2^32 (DUDF_E_UNSUPPORTED beyond, before any device call); F = 0 is valid.
+ *   - a face with an index outside [0, V) or two equal indices is IGNORED: never dereferenced, no edge, its own component, flip 0;
+ *   - every other face uses its three directed edges under the undirected key (min << 32) | max.  One use: a BORDER edge.  Two uses:
+ *     a MANIFOLD edge, which links its two faces with the sign s = 1 iff both traverse it in the same direction.  More: NON-MANIFOLD,
+ *     counted, links nothing;
+ *   - the minimum spanning forest of the face graph under the key (every key is one link: the forest is unique) carries the flip
+ *     parity; a face's component label is the smallest face index of its component, that face keeps its winding and every other
+ *     face's flip is its parity relative to it.  A flipped face (a, b, c) is written (a, c, b);
+ *   - INCONSISTENT edges are the manifold edges both faces still traverse the same way after the flips (a non-orientable component).
+ * Outputs (device): out_faces (F,3) int64 (may not alias faces), out_component (F,) int64, out_flip (F,) uint8, out_component_faces
+ * (F,) int64 and out_component_area_q (F,) uint64 (non-zero at label positions only), out_counts 8 x int64: components (ignored faces
+ * included), forest edges, manifold, border, non-manifold edges, ignored faces, flipped faces, inconsistent edges.  With vertices the
+ * area of a component is sum(q) * 2^-31, q = (uint64) rint(min(nn, 16) * 2^30) per face and nn = sqrt((n0 n0 + n1 n1) + n2 n2) of
+ * n = (b - a) x (c - a) as in dudf_mesh_sample_surface (a non-finite nn: q = 0); integer sums, the same in any order.  Without: zeros.
+ * One small read-back per Borůvka round (at most ceil(log2 F) + 1 rounds). */
+size_t dudf_mesh_topology_workspace_bytes(int64_t F);
+int dudf_mesh_topology(const int64_t* faces, int64_t F, int64_t V, const double* vertices, int64_t* out_faces, int64_t* out_component,
+                       unsigned char* out_flip, int64_t* out_component_faces, uint64_t* out_component_area_q, int64_t* out_counts,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* Submesh by face mask: the faces with keep[f] != 0 in their order (a kept face with an index outside [0, V) counts as not kept), the
+ * vertices they use in their relative order, faces re-indexed.  keep (F,) uint8.  V, F < 2^31.
+ *   dudf_mesh_submesh_count -> out_counts (device, 2 x int64): V', F'; the maps stay in the workspace;
+ *   dudf_mesh_submesh_emit  -> out_vertices (V',3) double, out_faces (F',3) int64; same arguments and workspace as the count call (a
+ *                              workspace that does not hold that call's result is left alone: nothing is written). */
+size_t dudf_mesh_submesh_workspace_bytes(int64_t V, int64_t F);
+int dudf_mesh_submesh_count(int64_t V, const int64_t* faces, int64_t F, const unsigned char* keep, int64_t* out_counts, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int dudf_mesh_submesh_emit(const double* vertices, int64_t V, const int64_t* faces, int64_t F, const unsigned char* keep,
+                           double* out_vertices, int64_t* out_faces, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Forward half of loss_s1 / loss_siren (reference src/loss_functions.py:123-155, :82-104):
  * SIREN forward, df/dx, the four weighted loss terms.  out_terms (device, 4 floats) receives
  * THIS RANK's share  sum_local(term_i) * weight / n_global  in the reference's dict order
