@@ -168,6 +168,11 @@ SYMBOLS = {
     "dudf_mesh_submesh_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
     "dudf_mesh_submesh_count": (ctypes.c_int, [ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, ctypes.c_size_t, _P]),
     "dudf_mesh_submesh_emit": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_mesh_simplify_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "dudf_mesh_simplify_keys": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, _DBL, ctypes.c_double, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_mesh_simplify_count": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, _DBL, ctypes.c_double, ctypes.c_double,
+                                                ctypes.c_double, _P, _P, ctypes.c_int, _P, _P, ctypes.c_size_t, _P]),
+    "dudf_mesh_simplify_emit": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "dudf_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "dudf_split_mode": (ctypes.c_int, []),
     "dudf_profile_dump": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t]),

@@ -661,6 +661,53 @@ def mesh_submesh(vertices, faces, keep):
     return out_v, out_f
 
 
+MESH_SIMPLIFY_COUNTS = ("vertices", "faces", "cells", "collapsed", "duplicate", "invalid", "border_edges", "fallback")
+
+
+def _simplify_count(vertices, faces, origin, cell, boundary_weight, tau, place):
+    """`dudf_mesh_simplify_keys`, the stable sort of the corner keys (plumbing, as the Morton order of `mesh_index_build`) and
+    `dudf_mesh_simplify_count`: (counts, what `_emit` needs).  One host sync: the counts."""
+    vertices, faces = _mesh(vertices, faces)
+    dev = vertices.device
+    V, F = vertices.shape[0], faces.shape[0]
+    org = _dbl(origin.tolist() if hasattr(origin, "tolist") else origin, 3, "origin")
+    ws, nbytes = _workspace(dev, "dudf_mesh_simplify_workspace_bytes", V, F, err=-4)
+    keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
+    head = (_ptr(vertices), V, _ptr(faces), F)
+    _call("dudf_mesh_simplify_keys", *head, org, float(cell), _ptr(keys), _ptr(ws), nbytes, dev=dev)
+    skeys, order = torch.sort(keys, stable=True)
+    counts = torch.zeros(len(MESH_SIMPLIFY_COUNTS), dtype=torch.int64, device=dev)
+    _call("dudf_mesh_simplify_count", *head, org, float(cell), float(boundary_weight), float(tau), _ptr(skeys), _ptr(order),
+          int(bool(place)), _ptr(counts), _ptr(ws), nbytes, dev=dev)
+    return dict(zip(MESH_SIMPLIFY_COUNTS, (int(v) for v in counts.tolist()))), (head, ws, nbytes, dev, (vertices, faces))
+
+
+def mesh_simplify_count(vertices, faces, origin, cell):
+    """The counts of `mesh_simplify` at lattice edge `cell` without the per-cell sums and placement (`fallback` is -1): what a search
+    over the lattice for a face count asks.  One host sync."""
+    return _simplify_count(vertices, faces, origin, cell, 0.0, 1e-3, False)[0]
+
+
+def mesh_simplify(vertices, faces, origin, cell, boundary_weight=1.0, tau=1e-3, want_quadrics=False):
+    """Quadric vertex clustering of a device mesh on the lattice of edge `cell` at `origin` (3 numbers) with border quadrics
+    (`dudf_mesh_simplify_keys` / `_count` / `_emit`; the rules: DESIGN.md §3.6c).  Returns (vertices (V',3) float64, faces (F',3) int64,
+    counts: a dict over MESH_SIMPLIFY_COUNTS) and with want_quadrics, per occupied cell in ascending key order, (quadrics (C,10), xhat
+    (C,3), cell_keys (C,) int64, records (C,) int64, fell_back (C,) uint8).  One host sync: the counts, which size the outputs."""
+    c, (head, ws, nbytes, dev, _mesh_alive) = _simplify_count(vertices, faces, origin, cell, boundary_weight, tau, True)
+    nv, nf, nc = c["vertices"], c["faces"], c["cells"]
+    out_v = torch.empty(max(nv, 1), 3, dtype=torch.float64, device=dev)              # emit wants the pointers even when nothing survives
+    out_f = torch.empty(max(nf, 1), 3, dtype=torch.int64, device=dev)
+    extra = ()
+    if want_quadrics:
+        extra = (torch.empty(nc, 10, dtype=torch.float64, device=dev), torch.empty(nc, 3, dtype=torch.float64, device=dev),
+                 torch.empty(nc, dtype=torch.int64, device=dev), torch.empty(nc, dtype=torch.int64, device=dev),
+                 torch.empty(nc, dtype=torch.uint8, device=dev))
+    if nc:
+        opt = tuple(_ptr(t) for t in extra) if extra else (None,) * 5
+        _call("dudf_mesh_simplify_emit", *head, _ptr(out_v), _ptr(out_f), *opt, _ptr(ws), nbytes, dev=dev)
+    return (out_v[:nv], out_f[:nf], c) + extra
+
+
 def _w4(weights):
     w = list(weights) + [0.0] * (4 - len(weights))
     return (ctypes.c_double * 4)(*[float(v) for v in w])

@@ -8,6 +8,9 @@ face ORDER is not pinned; the result is deterministic and equals
 Mesh topology (csrc/dudf_meshtopo.hip; what trimesh's `fix_winding` / `split` serve in the reference's workflows):
 `face_topology`, `orient_faces`, `remove_small_components`.  The pin is tests/meshtopo_oracle.py, exactly.
 
+Simplification (csrc/dudf_meshsimplify.hip; what trimesh / open3d decimation serve in the reference's workflows):
+`simplify_mesh`, quadric vertex clustering with border quadrics.  The pin is tests/simplify_oracle.py.
+
 Tensors stay on the device; each round reads its counts back once (they size the outputs)."""
 import numpy as np
 import torch
@@ -126,4 +129,61 @@ def remove_small_components(vertices, faces, min_faces=0, min_area=0.0, min_area
     out_v, out_f = hip_ops.mesh_submesh(v, topo["faces"], keep_f)
     info = {k: topo[k] for k in hip_ops.MESH_TOPOLOGY_COUNTS}
     info.update(components_kept=int(keep_c.sum()), components_removed=int((~keep_c).sum()), faces_removed=int(f.shape[0] - out_f.shape[0]))
+    return out_v, out_f, info
+
+
+SIMPLIFY_MAX_GRID = 2 ** 20
+
+
+def simplify_mesh(vertices, faces, grid=None, cell=None, target_faces=None, boundary_weight=1.0, origin=None, orient=False, device=None):
+    """Quadric vertex clustering on a uniform lattice with border quadrics (csrc/dudf_meshsimplify.hip): every occupied
+    lattice cell becomes one vertex at the minimum of its summed plane and border quadrics, faces that keep three distinct cells survive
+    (duplicates by cell set dropped, order and winding kept).  Exactly one of
+      grid = n           the lattice edge is the longest extent of the finite vertices / n;
+      cell = h           the lattice edge itself;
+      target_faces = t   integer bisection over n in [1, 2^20] with the count-only call (at most 21 calls): the mesh of the largest n
+                         tried whose face count is <= t.  The face count is NOT strictly monotone in n (a finer lattice can merge two
+                         faces into one cell set that a coarser one kept apart), so this is the largest such n the bisection MEETS, not
+                         the largest there is; the guarantee is faces <= t, or n == 1.
+    `origin` (3 numbers) defaults to the bounding-box minimum of the finite vertices.  `boundary_weight` = 1.0 is a default, not a
+    measurement (tools/bench_simplify.py prints the border's deviation for 0, 1 and 10); 0 leaves borders to erode.  Clustering can
+    fold a face over or make an edge non-manifold and nothing re-winds the result: orient=True runs `orient_faces` on it.
+    Returns (vertices float64, faces int64, info) on the device; info holds `hip_ops.MESH_SIMPLIFY_COUNTS` and `cell`, `grid` (None with
+    cell=), `origin`, `count_calls`."""
+    if sum(x is not None for x in (grid, cell, target_faces)) != 1:
+        raise ValueError("simplify_mesh takes exactly one of grid, cell and target_faces")
+    v, f = _device_mesh(vertices, faces, device)
+    fin = v[torch.isfinite(v).all(1)]
+    if fin.shape[0] == 0:
+        lo, ext = [0.0, 0.0, 0.0], 0.0
+    else:
+        mn, mx = torch.amin(fin, 0), torch.amax(fin, 0)
+        lo, ext = mn.tolist(), float((mx - mn).max())
+    org = [float(x) for x in (origin.tolist() if hasattr(origin, "tolist") else origin)] if origin is not None else lo
+    if len(org) != 3:
+        raise ValueError("origin takes 3 numbers")
+    edge = lambda n: (ext if ext > 0.0 else 1.0) / n   # noqa: E731
+    calls = 0
+    if cell is not None:
+        h, n = float(cell), None
+    elif grid is not None:
+        n = int(grid)
+        if not 1 <= n <= SIMPLIFY_MAX_GRID:
+            raise ValueError(f"grid must lie in [1, {SIMPLIFY_MAX_GRID}]; got {grid}")
+        h = edge(n)
+    else:
+        t = int(target_faces)
+        lo_n, hi_n, n = 1, SIMPLIFY_MAX_GRID, 1                          # invariant: n is the largest lattice tried with faces <= t
+        while lo_n <= hi_n:                                              # at most 21 halvings of [1, 2^20]
+            mid = (lo_n + hi_n) // 2
+            calls += 1
+            if hip_ops.mesh_simplify_count(v, f, org, edge(mid))["faces"] <= t:
+                n, lo_n = max(n, mid), mid + 1
+            else:
+                hi_n = mid - 1
+        h = edge(n)
+    out_v, out_f, info = hip_ops.mesh_simplify(v, f, org, h, boundary_weight=boundary_weight)
+    if orient and out_f.shape[0]:
+        out_f = orient_faces(out_v, out_f)
+    info.update(cell=h, grid=n, origin=org, count_calls=calls)
     return out_v, out_f, info

@@ -94,21 +94,32 @@ class TriangleSoup:
         return path
 
 
-_FINISH_KEYS = ("min_faces", "min_area", "min_area_ratio", "keep_largest")
+_FINISH_KEYS = ("min_faces", "min_area", "min_area_ratio", "keep_largest", "simplify")
+
+
+_SIMPLIFY_KEYS = ("grid", "cell", "target_faces", "boundary_weight", "origin")
 
 
 def _finish_soup(v, f, finish):
     """The per-cell soup (device tensors) as a mesh, on the device: welded and pruned (`meshclean.clean_mesh(fill_holes=False)`),
     wound consistently per component (`meshclean.orient_faces`; CAP-UDF signs each cell on its own, so neighbouring cells disagree
-    on about one shared edge in six), and with a dict of `meshclean.remove_small_components` keywords the floaters dropped."""
+    on about one shared edge in six), and with a dict of `meshclean.remove_small_components` keywords the floaters dropped.  The dict
+    key "simplify" holds a dict of `meshclean.simplify_mesh` keywords (grid / cell / target_faces, boundary_weight, origin): the mesh is
+    then clustered last, behind welding, winding and the component filter, and wound again (orient=True)."""
     if finish != "mesh" and not (isinstance(finish, dict) and all(k in _FINISH_KEYS for k in finish)):
         raise ValueError(f"finish must be None, 'mesh' or a dict over {_FINISH_KEYS}; got {finish!r}")
+    simplify = finish.get("simplify") if isinstance(finish, dict) else None
+    if simplify is not None and not (isinstance(simplify, dict) and all(k in _SIMPLIFY_KEYS for k in simplify)):
+        raise ValueError(f"finish['simplify'] must be a dict over {_SIMPLIFY_KEYS}; got {simplify!r}")
     from . import meshclean
     v, f, _ = meshclean.clean_mesh(v, f, fill_holes=False)
     if isinstance(finish, dict):
-        v, f, _ = meshclean.remove_small_components(v, f, **finish)
-        return v, f
-    return v, meshclean.orient_faces(v, f)
+        v, f, _ = meshclean.remove_small_components(v, f, **{k: x for k, x in finish.items() if k != "simplify"})
+    else:
+        f = meshclean.orient_faces(v, f)
+    if simplify is not None:
+        v, f, _ = meshclean.simplify_mesh(v, f, orient=True, **simplify)
+    return v, f
 
 
 def extract_mesh_CAP(ndf, grad, resolution, threshold=0.008, device=None, finish=None):
@@ -118,7 +129,7 @@ def extract_mesh_CAP(ndf, grad, resolution, threshold=0.008, device=None, finish
     `trimesh.Trimesh(process=False)` when trimesh is importable, else a `TriangleSoup` with the same two arrays.
     `finish`: None — the per-cell triangle soup (no vertex is shared between cells), as the reference; "mesh" — welded and consistently wound on the device
     (`_finish_soup`); a dict over min_faces / min_area / min_area_ratio / keep_largest — the same, then the small components
-    dropped (`meshclean.remove_small_components`)."""
+    dropped (`meshclean.remove_small_components`); its key "simplify": a dict of `meshclean.simplify_mesh` keywords, applied last."""
     dev = torch.device(device) if device is not None else (ndf.device if torch.is_tensor(ndf) and ndf.is_cuda else torch.device("cuda", 0))
     if dev.type != "cuda":
         raise DudfError("extract_mesh_CAP: needs the GPU; there is no CPU fallback path")

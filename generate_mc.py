@@ -21,8 +21,13 @@ other algorithms need the dense volume (MeshUDF's flood is a host walk of it) an
 Optional keys "cap_finish": "mesh" (keyword `cap_finish=`): the CAP-UDF soup welded and wound consistently on the device
 (`extract_mesh_CAP(..., finish="mesh")`); "min_component_faces" / "min_component_area_ratio": components with fewer
 faces, or less than that share of the whole area, are dropped (`diffudf_amd.meshclean.remove_small_components`) — from the CAP-UDF
-mesh, which is then finished as with "cap_finish", and from the device-cleaned MeshUDF mesh of 'meshudf' and 'both'.  Without
-these keys the files are what they were."""
+mesh, which is then finished as with "cap_finish", and from the device-cleaned MeshUDF mesh of 'meshudf' and 'both'.
+Optional keys "simplify_target_faces" / "simplify_grid" (one of them) and "simplify_boundary_weight" (keywords of the same names): the
+mesh is simplified last, on the device, by quadric vertex clustering with border quadrics (`diffudf_amd.meshclean.simplify_mesh`,
+DESIGN.md §3.6c) down to at most that many faces, or on a lattice of that many cells along the longest extent, and wound again.  For
+'cap' (dense or sparse) the CAP-UDF mesh is finished as with "cap_finish" first; for 'meshudf', 'both' and 'siren' the keys serve the
+device-resident result (no trimesh, a GPU) and raise `DudfError` naming the key where that is not what ran.  Without these keys the
+files are what they were."""
 import json
 import sys
 
@@ -55,15 +60,46 @@ def _without_small_components(mesh, dev, filt):
     return _as_mesh(v.cpu().numpy(), f.cpu().numpy())
 
 
+def _simplify_keywords(simplify_target_faces, simplify_grid, simplify_boundary_weight):
+    """The keywords of `simplify_mesh` the optional keys stand for; empty: no simplification."""
+    if simplify_target_faces is not None and simplify_grid is not None:
+        raise ValueError("simplify_target_faces and simplify_grid exclude each other")
+    if simplify_target_faces is None and simplify_grid is None:
+        if simplify_boundary_weight is not None:
+            raise ValueError("simplify_boundary_weight needs simplify_target_faces or simplify_grid")
+        return {}
+    simp = {"target_faces": int(simplify_target_faces)} if simplify_target_faces is not None else {"grid": int(simplify_grid)}
+    if simplify_boundary_weight is not None:
+        simp["boundary_weight"] = float(simplify_boundary_weight)
+    return simp
+
+
+def _simplified(mesh, dev, simp):
+    """`mesh` simplified on the device (`simplify_mesh(orient=True)`); no keys: `mesh` itself.  Only a device-resident result is served:
+    a trimesh object (the trimesh clean-up ran) or a CPU device raises, naming the key."""
+    if not simp:
+        return mesh
+    from diffudf_amd import meshclean
+    from diffudf_amd.render_mc import TriangleSoup
+    key = "simplify_target_faces" if "target_faces" in simp else "simplify_grid"
+    if dev.type != "cuda" or not isinstance(mesh, TriangleSoup):
+        raise DudfError(f"'{key}' serves the device-resident mesh only ({'a CPU device' if dev.type != 'cuda' else 'the trimesh clean-up ran'})")
+    v, f, _ = meshclean.simplify_mesh(mesh.vertices, mesh.faces, orient=True, device=dev, **simp)
+    return TriangleSoup(v.cpu().numpy(), f.cpu().numpy())
+
+
 def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='meshudf', from_file=None, luts=None, sparse=False,
-                brick=8, lipschitz=1.25, cap_finish=None, min_component_faces=None, min_component_area_ratio=None):
+                brick=8, lipschitz=1.25, cap_finish=None, min_component_faces=None, min_component_area_ratio=None,
+                simplify_target_faces=None, simplify_grid=None, simplify_boundary_weight=None):
     """`luts`: the Lewiner tables for MeshUDF and 'siren' (dict, path or None = look them up; see the module docstring).
     `sparse`: CAP-UDF on the narrow band of `extract_fields_sparse(..., brick=brick, lipschitz=lipschitz)`; 'cap' only.
-    `cap_finish`, `min_component_faces`, `min_component_area_ratio`: see the module docstring; all None: nothing changes."""
+    `cap_finish`, `min_component_faces`, `min_component_area_ratio`, `simplify_target_faces`, `simplify_grid`,
+    `simplify_boundary_weight`: see the module docstring; all None: nothing changes."""
     if cap_finish not in (None, "mesh"):
         raise ValueError(f"cap_finish must be None or 'mesh'; got {cap_finish!r}")
     filt = _component_filter(min_component_faces, min_component_area_ratio)
-    finish = dict(filt) if filt else cap_finish
+    simp = _simplify_keywords(simplify_target_faces, simplify_grid, simplify_boundary_weight)
+    finish = dict(filt, **({"simplify": simp} if simp else {})) if filt or simp else cap_finish
     if sparse and algorithm != 'cap':
         raise DudfError(f"sparse extraction serves algorithm 'cap' only; '{algorithm}' needs the dense volume")
     if from_file is not None:
@@ -83,7 +119,7 @@ def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='m
         dot = output_path.rfind('.')
         if algorithm == 'meshudf':
             _, _, mesh = extract_mesh_MESHUDF(u, g, dev, smooth_borders=True, luts=luts)
-            mesh = _without_small_components(mesh, dev, filt)
+            mesh = _simplified(_without_small_components(mesh, dev, filt), dev, simp)
             mesh.export(output_path)
             print(f'Saved to {output_path}')
             return mesh
@@ -99,7 +135,7 @@ def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='m
         except MeshUDFError as e:                              # no look-up tables: the CAP half is still written, and says so
             print(f'Saved to {path_cap} (MeshUDF half skipped: {e})')
             return None, mesh
-        mesh_mu = _without_small_components(mesh_mu, dev, filt)
+        mesh_mu = _simplified(_without_small_components(mesh_mu, dev, filt), dev, simp)
         mesh_mu.export(path_mu)
         print(f'Saved to {path_mu}, {path_cap}')
         return mesh_mu, mesh
@@ -109,6 +145,7 @@ def generate_mc(model, gt_mode, device, N, output_path, alpha=None, algorithm='m
         except MeshUDFError as e:                              # no look-up tables: nothing is written, and the caller (a training) goes on
             print(f'{output_path} not written (signed marching cubes skipped: {e})')
             return None
+        mesh = _simplified(mesh, dev, simp)
         mesh.export(output_path)
         print(f'Saved to {output_path}')
         return mesh
@@ -123,4 +160,6 @@ if __name__ == "__main__":
                                              "activation": cfg.get("activation", "sine"), "ww": cfg.get("ww")},
                 luts=cfg.get("luts_path"), sparse=bool(cfg.get("sparse", False)), brick=cfg.get("brick", 8),
                 lipschitz=cfg.get("lipschitz", 1.25), cap_finish=cfg.get("cap_finish"),
-                min_component_faces=cfg.get("min_component_faces"), min_component_area_ratio=cfg.get("min_component_area_ratio"))
+                min_component_faces=cfg.get("min_component_faces"), min_component_area_ratio=cfg.get("min_component_area_ratio"),
+                simplify_target_faces=cfg.get("simplify_target_faces"), simplify_grid=cfg.get("simplify_grid"),
+                simplify_boundary_weight=cfg.get("simplify_boundary_weight"))

@@ -591,6 +591,47 @@ int dudf_mesh_submesh_count(int64_t V, const int64_t* faces, int64_t F, const un
 int dudf_mesh_submesh_emit(const double* vertices, int64_t V, const int64_t* faces, int64_t F, const unsigned char* keep,
                            double* out_vertices, int64_t* out_faces, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Mesh simplification: quadric vertex clustering on a uniform lattice (Lindstrom's one-pass simplification) with border quadrics.
+ * vertices (V,3) double, faces (F,3) int64, origin: 3 doubles ON THE HOST, cell: the lattice edge h.  The rules (DESIGN.md §3.6c,
+ * restated by tests/simplify_oracle.py):
+ *   - a face with an index outside [0, V) or a non-finite coordinate is INVALID: dropped, counted, never dereferenced; another face with
+ *     a repeated index is dropped and counted with `collapsed`;
+ *   - the cell of a vertex is c_d = floor((v_d - origin_d) * inv), inv = 1.0 / h, saturated to [0, 2^21 - 1]; its key is
+ *     c_0 << 42 | c_1 << 21 | c_2.  Corner k of a valid face contributes a RECORD iff no corner j < k of the face has the same key;
+ *     records are ordered by (key, face index); the occupied cells are the distinct keys, ascending;
+ *   - a record adds, in the frame u = (p - o_c) * inv of its cell (o_c = origin + (c + 0.5) * h), the plane quadric of the unnormalised
+ *     normal n = (u_1 - u_0) x (u_2 - u_0) (weight: area squared) and, with boundary_weight > 0, for k = 0, 1, 2 the quadric of the plane
+ *     through edge k perpendicular to the face, times boundary_weight / (e.e), when edge k is used by exactly one valid face and one of
+ *     its endpoints lies in the cell.  A cell's ten numbers are summed sequentially in record order, in fp64, by one thread; beside
+ *     them the record count and xhat, the mean of each record's first corner in the cell;
+ *   - placement: the eigen-decomposition of A; from xhat, the minimiser's components along the eigenvectors with lam_i > tau * max|lam|;
+ *     xhat itself (FALLBACK, counted) if an eigenvalue is not finite, all are zero or the result leaves the cell (not every
+ *     |x_d| <= 0.5).  Position ((c_d + 0.5) + x_d) * h + origin_d;
+ *   - faces over cells: fewer than three distinct cells: `collapsed`; of the faces with one set of cells the smallest index survives
+ *     (`duplicate`); survivors keep order and winding; cells no survivor uses drop out, the others keep ascending key order.
+ * Three calls around one stable sort of int64 keys, which is the caller's (as the Morton order of dudf_mesh_index_build):
+ *   dudf_mesh_simplify_keys  -> out_keys (device, 3 F int64): per face corner its cell key, or -1 (sorts first) for a corner without a
+ *                               record; the edge table and the face states stay in the workspace;
+ *   dudf_mesh_simplify_count -> out_counts (device, 8 x int64): V', F', occupied cells C, collapsed, duplicate, invalid faces, border
+ *                               edges, fallback cells.  sorted_keys / order: out_keys sorted ascending (stable) and the index each came
+ *                               from.  place = 0 skips the per-cell sums and placement (fallback is then -1, and emit writes nothing): the
+ *                               face count alone, for a search over h;
+ *   dudf_mesh_simplify_emit  -> out_vertices (V',3) double, out_faces (F',3) int64 and, all five or none, per occupied cell
+ *                               out_quadrics (C,10), out_xhat (C,3), out_cell_keys (C,), out_records (C,) int64, out_fallback (C,)
+ *                               uint8.  Same mesh and workspace as the count call (a workspace that does not hold that call's result is
+ *                               left alone: nothing is written).
+ * Limits: V < 2^31 and 3 F < 2^31, else DUDF_E_UNSUPPORTED (workspace_bytes: 0); cell and 1 / cell finite and positive, origin finite,
+ * boundary_weight >= 0, 0 < tau < 1, required pointers non-NULL, else DUDF_E_BADCFG; all checked before the first device call. */
+size_t dudf_mesh_simplify_workspace_bytes(int64_t V, int64_t F);
+int dudf_mesh_simplify_keys(const double* vertices, int64_t V, const int64_t* faces, int64_t F, const double* origin, double cell,
+                            int64_t* out_keys, void* workspace, size_t workspace_bytes, void* stream);
+int dudf_mesh_simplify_count(const double* vertices, int64_t V, const int64_t* faces, int64_t F, const double* origin, double cell,
+                             double boundary_weight, double tau, const int64_t* sorted_keys, const int64_t* order, int place,
+                             int64_t* out_counts, void* workspace, size_t workspace_bytes, void* stream);
+int dudf_mesh_simplify_emit(const double* vertices, int64_t V, const int64_t* faces, int64_t F, double* out_vertices, int64_t* out_faces,
+                            double* out_quadrics, double* out_xhat, int64_t* out_cell_keys, int64_t* out_records,
+                            unsigned char* out_fallback, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Forward half of loss_s1 / loss_siren (reference src/loss_functions.py:123-155, :82-104):
  * SIREN forward, df/dx, the four weighted loss terms.  out_terms (device, 4 floats) receives
  * THIS RANK's share  sum_local(term_i) * weight / n_global  in the reference's dict order
