@@ -3,33 +3,21 @@
 // numpy and the device result equals it bit for bit.  Built with -ffp-contract=off (the degenerate test and the smoothing repeat
 // the oracle's double arithmetic).  Index work only: integer atomics on hash-table slots and counters, no float atomics.
 //
-// Hash tables (open addressing, linear probing, capacity a power of two >= 2n, nothing is ever deleted):
-//   vertices  a slot holds the index of SOME vertex with the slot's key, claimed with atomicCAS and lowered with atomicMin — it ends
-//             as the smallest index with that key, whatever the arrival order.  Keys are compared by recomputing them from the
-//             immutable input: no thread waits for, or reads, what another thread of the same launch writes beside the slot word;
-//   faces     the same over the sorted remapped triple (read from `g`, which the launch before wrote);
-//   edges     a slot holds the key itself, (min << 32 | max), claimed with a 64-bit atomicCAS; `einfo` beside it counts the uses
-//             (bits 0..30) and notes whether min -> max occurs as a directed edge (bit 31).
-// Every probe loop is bounded by the capacity.
-#include "dudf_context.h"
-#include "dudf_wgscan.h"
+// Hash tables, by the rules of dudf_meshtab.h:
+//   vertices  smallest index per rounded position (VertItems below), capacity >= 2 V;
+//   faces     smallest index per sorted remapped triple (read from `g`, which the launch before wrote), capacity >= 2 F;
+//   edges     capacity >= 6 F; `einfo` beside a slot counts the uses (bits 0..30) and notes whether min -> max occurs as a directed
+//             edge (bit 31).
+#include "dudf_meshtab.h"
 
 namespace {
 
 constexpr int WG = DUDF_WG;
-constexpr uint32_t EMPTY32 = 0xffffffffu;
-constexpr unsigned long long EMPTY64 = ~0ull;
 constexpr uint32_t DIR_BIT = 0x80000000u;
 constexpr int64_t MAGIC_CLEAN = 0x6475646643314c4ell, MAGIC_BORDER = 0x6475646642314f52ll;
 enum { ST_INVALID = 0, ST_DEGENERATE = 1, ST_DUPLICATE = 2, ST_ALIVE = 3 };
 enum { CTR_INVALID = 0, CTR_REFERENCED, CTR_DISTINCT, CTR_DEGENERATE, CTR_DUPLICATE, N_CTR };
 enum { TOT_KEEP = 0, TOT_H3, TOT_H4, TOT_ALIVE, N_TOT };
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {       // splitmix64's finaliser: lattice keys must not cluster
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
 
 struct VKey { int64_t x, y, z; };
 __device__ __forceinline__ int64_t key1(double c, double scale) {      // rint(c * 10^digits), saturated at the ends of int64
@@ -37,56 +25,25 @@ __device__ __forceinline__ int64_t key1(double c, double scale) {      // rint(c
     k = fmin(fmax(k, -9223372036854775808.0), 9223372036854774784.0);
     return (int64_t)k;
 }
-__device__ __forceinline__ VKey vertex_key(const double* __restrict__ vert, int64_t v, double scale) {
-    return VKey{key1(vert[3 * v], scale), key1(vert[3 * v + 1], scale), key1(vert[3 * v + 2], scale)};
-}
-__device__ __forceinline__ bool same(const VKey& a, const VKey& b) { return a.x == b.x && a.y == b.y && a.z == b.z; }
-__device__ __forceinline__ uint64_t hash(const VKey& k) { return mix64(mix64(mix64((uint64_t)k.x) ^ (uint64_t)k.y) ^ (uint64_t)k.z); }
+struct VertItems {                                             // the vertices by their position rounded to `digits` decimals
+    const double* vert; double scale;
+    __device__ __forceinline__ VKey key(int64_t v) const {
+        return VKey{key1(vert[3 * v], scale), key1(vert[3 * v + 1], scale), key1(vert[3 * v + 2], scale)};
+    }
+    __device__ __forceinline__ static bool same(const VKey& a, const VKey& b) { return a.x == b.x && a.y == b.y && a.z == b.z; }
+    __device__ __forceinline__ static uint64_t hash(const VKey& k) {
+        return dudf_mix64(dudf_mix64(dudf_mix64((uint64_t)k.x) ^ (uint64_t)k.y) ^ (uint64_t)k.z);
+    }
+};
 
-struct FKey { int32_t a, b, c; };                              // a <= b <= c
-__device__ __forceinline__ FKey face_key(const int32_t* __restrict__ g, int64_t f) {
-    int32_t a = g[3 * f], b = g[3 * f + 1], c = g[3 * f + 2], t;
-    if (a > b) { t = a; a = b; b = t; }
-    if (b > c) { t = b; b = c; c = t; }
-    if (a > b) { t = a; a = b; b = t; }
-    return FKey{a, b, c};
-}
-__device__ __forceinline__ bool same(const FKey& p, const FKey& q) { return p.a == q.a && p.b == q.b && p.c == q.c; }
-__device__ __forceinline__ uint64_t hash(const FKey& k) {
-    return mix64(mix64(((uint64_t)(uint32_t)k.a << 32) | (uint32_t)k.b) ^ (uint32_t)k.c);
-}
-
-__device__ __forceinline__ unsigned long long edge_key(int32_t u, int32_t w) {
-    return u < w ? ((unsigned long long)(uint32_t)u << 32) | (uint32_t)w : ((unsigned long long)(uint32_t)w << 32) | (uint32_t)u;
-}
-// one use of the directed edge from -> to (from != to)
+// one use of the directed edge from -> to (from != to, both in [0, 2^31))
 __device__ __forceinline__ void edge_insert(unsigned long long* __restrict__ etab, uint32_t* __restrict__ einfo, int64_t cap, int32_t from,
                                             int32_t to) {
-    const unsigned long long key = edge_key(from, to);
-    int64_t s = (int64_t)(mix64(key) & (uint64_t)(cap - 1));
-    for (int64_t i = 0; i < cap; ++i, s = (s + 1) & (cap - 1)) {
-        const unsigned long long cur = atomicCAS(&etab[s], EMPTY64, key);
-        if (cur == EMPTY64 || cur == key) {
-            atomicAdd(&einfo[s], 1u);
-            if (from < to) atomicOr(&einfo[s], DIR_BIT);
-            return;
-        }
-    }
+    const int64_t s = dudf_edge_claim(etab, cap, dudf_edge_key((uint32_t)from, (uint32_t)to));
+    if (s < 0) return;
+    atomicAdd(&einfo[s], 1u);
+    if (from < to) atomicOr(&einfo[s], DIR_BIT);
 }
-// einfo of the edge {u, w}, 0 when the table does not hold it (tables complete: read only)
-__device__ __forceinline__ uint32_t edge_find(const unsigned long long* __restrict__ etab, const uint32_t* __restrict__ einfo, int64_t cap,
-                                              int32_t u, int32_t w) {
-    const unsigned long long key = edge_key(u, w);
-    int64_t s = (int64_t)(mix64(key) & (uint64_t)(cap - 1));
-    for (int64_t i = 0; i < cap; ++i, s = (s + 1) & (cap - 1)) {
-        const unsigned long long cur = etab[s];
-        if (cur == key) return einfo[s];
-        if (cur == EMPTY64) return 0;
-    }
-    return 0;
-}
-
-__device__ __forceinline__ int64_t item() { return (int64_t)blockIdx.x * WG + threadIdx.x; }
 
 // ---------------------------------------------------------------------------------------------------------------- clean-up round
 struct CleanArgs {
@@ -109,75 +66,46 @@ struct CleanArgs {
     double* out_v; int64_t* out_f;
 };
 
-__device__ __forceinline__ void add_total(unsigned long long* ctr, unsigned total) {
-    if (threadIdx.x == 0 && total) atomicAdd(ctr, (unsigned long long)total);
-}
-
 __global__ __launch_bounds__(WG) void clean_validate_kernel(CleanArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     bool bad = false;
     if (f < a.F) {
         const int64_t i0 = a.face[3 * f], i1 = a.face[3 * f + 1], i2 = a.face[3 * f + 2];
-        bool ok = i0 >= 0 && i0 < a.V && i1 >= 0 && i1 < a.V && i2 >= 0 && i2 < a.V;
-        if (ok) {                                                       // coordinates are read only behind the range check
-            const int64_t idx[3] = {i0, i1, i2};
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) ok = ok && isfinite(a.vert[3 * idx[k] + c]);
-        }
+        const bool ok = dudf_face_in_range(i0, i1, i2, a.V) && dudf_face_finite(a.vert, i0, i1, i2);
         a.fstate[f] = ok ? ST_ALIVE : ST_INVALID;
         if (ok) { a.vref[i0] = 1; a.vref[i1] = 1; a.vref[i2] = 1; }
         bad = !ok;
     }
     unsigned total;
     dudf_wg_rank(bad, wt, &total);
-    add_total(a.ctr + CTR_INVALID, total);
+    dudf_wg_add_total(a.ctr + CTR_INVALID, total);
 }
 
 __global__ __launch_bounds__(WG) void clean_weld_insert_kernel(CleanArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     const bool ref = v < a.V && a.vref[v];
-    bool claimed = false;
-    if (ref) {
-        const VKey k = vertex_key(a.vert, v, a.scale);
-        int64_t s = (int64_t)(hash(k) & (uint64_t)(a.capV - 1));
-        for (int64_t i = 0; i < a.capV; ++i, s = (s + 1) & (a.capV - 1)) {
-            const uint32_t cur = atomicCAS(&a.vtab[s], EMPTY32, (uint32_t)v);
-            if (cur == EMPTY32) { claimed = true; break; }
-            if (same(vertex_key(a.vert, cur, a.scale), k)) { atomicMin(&a.vtab[s], (uint32_t)v); break; }
-        }
-    }
+    const bool claimed = ref && dudf_first_insert(a.vtab, a.capV, VertItems{a.vert, a.scale}, v, a.V);
     unsigned total;
     dudf_wg_rank(ref, wt, &total);
-    add_total(a.ctr + CTR_REFERENCED, total);
+    dudf_wg_add_total(a.ctr + CTR_REFERENCED, total);
     dudf_wg_rank(claimed, wt, &total);
-    add_total(a.ctr + CTR_DISTINCT, total);
+    dudf_wg_add_total(a.ctr + CTR_DISTINCT, total);
 }
 
 __global__ __launch_bounds__(WG) void clean_weld_resolve_kernel(CleanArgs a) {
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     if (v >= a.V) return;
-    int32_t r = -1;
-    if (a.vref[v]) {
-        const VKey k = vertex_key(a.vert, v, a.scale);
-        int64_t s = (int64_t)(hash(k) & (uint64_t)(a.capV - 1));
-        for (int64_t i = 0; i < a.capV; ++i, s = (s + 1) & (a.capV - 1)) {
-            const uint32_t cur = a.vtab[s];
-            if (cur == EMPTY32) break;
-            if (same(vertex_key(a.vert, cur, a.scale), k)) { r = (int32_t)cur; break; }
-        }
-    }
-    a.rep[v] = r;
+    const VertItems items{a.vert, a.scale};
+    a.rep[v] = a.vref[v] ? (int32_t)dudf_first_find(a.vtab, a.capV, items, items.key(v), a.V) : -1;      // absent: kTabEmpty32 is -1 too
 }
 
 __device__ __forceinline__ double sq3(double x, double y, double z) { return (x * x + y * y) + z * z; }
 
 __global__ __launch_bounds__(WG) void clean_remap_kernel(CleanArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     bool deg = false;
     if (f < a.F && a.fstate[f] == ST_ALIVE) {
         const int32_t g0 = a.rep[a.face[3 * f]], g1 = a.rep[a.face[3 * f + 1]], g2 = a.rep[a.face[3 * f + 2]];
@@ -193,36 +121,24 @@ __global__ __launch_bounds__(WG) void clean_remap_kernel(CleanArgs a) {
     }
     unsigned total;
     dudf_wg_rank(deg, wt, &total);
-    add_total(a.ctr + CTR_DEGENERATE, total);
+    dudf_wg_add_total(a.ctr + CTR_DEGENERATE, total);
 }
 
 __global__ __launch_bounds__(WG) void clean_face_insert_kernel(CleanArgs a) {
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     if (f >= a.F || a.fstate[f] != ST_ALIVE) return;
-    const FKey k = face_key(a.g, f);
-    int64_t s = (int64_t)(hash(k) & (uint64_t)(a.capF - 1));
-    for (int64_t i = 0; i < a.capF; ++i, s = (s + 1) & (a.capF - 1)) {
-        const uint32_t cur = atomicCAS(&a.ftab[s], EMPTY32, (uint32_t)f);
-        if (cur == EMPTY32) return;
-        if (same(face_key(a.g, cur), k)) { atomicMin(&a.ftab[s], (uint32_t)f); return; }
-    }
+    dudf_first_insert(a.ftab, a.capF, DudfTriItems{a.g}, f, a.F);
 }
 
 // a face survives when it is the smallest index of its vertex set; survivors mark their vertices and enter their edges
 __global__ __launch_bounds__(WG) void clean_face_resolve_kernel(CleanArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     bool alive = false, dup = false;
     if (f < a.F && a.fstate[f] == ST_ALIVE) {
-        const FKey k = face_key(a.g, f);
-        int64_t s = (int64_t)(hash(k) & (uint64_t)(a.capF - 1));
-        uint32_t first = (uint32_t)f;
-        for (int64_t i = 0; i < a.capF; ++i, s = (s + 1) & (a.capF - 1)) {
-            const uint32_t cur = a.ftab[s];
-            if (cur == EMPTY32) break;
-            if (same(face_key(a.g, cur), k)) { first = cur; break; }
-        }
-        alive = first == (uint32_t)f;
+        const DudfTriItems items{a.g};
+        const uint32_t first = dudf_first_find(a.ftab, a.capF, items, items.key(f), a.F);
+        alive = first == (uint32_t)f || first == kTabEmpty32;            // a triple the table does not hold: the face stands for itself
         dup = !alive;
         if (dup) a.fstate[f] = ST_DUPLICATE;
         else {
@@ -237,17 +153,17 @@ __global__ __launch_bounds__(WG) void clean_face_resolve_kernel(CleanArgs a) {
     }
     unsigned total;
     dudf_wg_rank(dup, wt, &total);
-    add_total(a.ctr + CTR_DUPLICATE, total);
+    dudf_wg_add_total(a.ctr + CTR_DUPLICATE, total);
     dudf_wg_rank(alive, wt, &total);
     if (threadIdx.x == 0) a.fblk[blockIdx.x] = total;
 }
 
 // border edges (one use) -> degree and the first two neighbours of their endpoints
 __global__ __launch_bounds__(WG) void clean_border_adj_kernel(CleanArgs a) {
-    const int64_t s = item();
+    const int64_t s = dudf_wg_item();
     if (s >= a.capE) return;
     const unsigned long long key = a.etab[s];
-    if (key == EMPTY64 || (a.einfo[s] & ~DIR_BIT) != 1u) return;
+    if (key == kTabEmpty64 || (a.einfo[s] & ~DIR_BIT) != 1u) return;
     const int32_t u = (int32_t)(key >> 32), w = (int32_t)(key & 0xffffffffu);
     int i = atomicAdd(&a.bdeg[u], 1);
     if (i < 2) a.bnb[2 * (int64_t)u + i] = w;
@@ -275,7 +191,7 @@ __device__ __forceinline__ int hole_walk(const CleanArgs& a, int32_t va, int32_t
 
 __global__ __launch_bounds__(WG) void clean_holes_kernel(CleanArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     const bool keep = v < a.V && a.vkeep[v];
     int h = 0;
     if (keep && a.fill && a.bdeg[v] == 2) {
@@ -322,7 +238,7 @@ __device__ __forceinline__ bool clean_head_ok(const CleanArgs& a) {
 __global__ __launch_bounds__(WG) void clean_emit_vertices_kernel(CleanArgs a) {
     __shared__ unsigned wt[WG / 64];
     if (!clean_head_ok(a)) return;                                      // uniform: the whole grid leaves
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     const bool keep = v < a.V && a.vkeep[v];
     unsigned total;
     const unsigned r = dudf_wg_rank(keep, wt, &total);
@@ -336,7 +252,7 @@ __global__ __launch_bounds__(WG) void clean_emit_vertices_kernel(CleanArgs a) {
 __global__ __launch_bounds__(WG) void clean_emit_faces_kernel(CleanArgs a) {
     __shared__ unsigned wt[WG / 64];
     if (!clean_head_ok(a)) return;
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     const bool alive = f < a.F && a.fstate[f] == ST_ALIVE;
     unsigned total;
     const unsigned r = dudf_wg_rank(alive, wt, &total);
@@ -350,14 +266,15 @@ __global__ __launch_bounds__(WG) void clean_emit_faces_kernel(CleanArgs a) {
 __global__ __launch_bounds__(WG) void clean_emit_holes_kernel(CleanArgs a) {
     __shared__ unsigned wt[WG / 64];
     if (!clean_head_ok(a)) return;
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     const unsigned h = v < a.V ? a.hole[v] : 0;
     unsigned total;
     const unsigned before = dudf_wg_scan(h, wt, &total);
     if (!h) return;
     int32_t b, c, d;
     if (hole_walk(a, (int32_t)v, &b, &c, &d) != (int)h + 2) return;
-    const bool rev = (edge_find(a.etab, a.einfo, a.capE, (int32_t)v, b) & DIR_BIT) != 0;     // a face already runs a -> b
+    const int64_t s = dudf_edge_slot(a.etab, a.capE, dudf_edge_key((uint32_t)v, (uint32_t)b));
+    const bool rev = s >= 0 && (a.einfo[s] & DIR_BIT) != 0;            // a face already runs a -> b
     const int64_t n = a.tot[TOT_ALIVE] + a.voff[3 * (int64_t)blockIdx.x + 1] + 2 * a.voff[3 * (int64_t)blockIdx.x + 2] + before;
     const int64_t na = a.vnew[v], nb = a.vnew[b], nd = a.vnew[d];
     int64_t* o = a.out_f + 3 * n;
@@ -370,21 +287,18 @@ __global__ __launch_bounds__(WG) void clean_emit_holes_kernel(CleanArgs a) {
     }
 }
 
-int64_t pow2_at_least(int64_t n) { int64_t c = 2; while (c < n) c <<= 1; return c; }
-int64_t blocks_of(int64_t n) { return (n + WG - 1) / WG; }
 bool sizes_ok(int64_t V, int64_t F) { return V >= 0 && F >= 0 && V < (1ll << 31) && F < (1ll << 31); }
 
-// zero-initialised arrays first, 0xff-initialised tables second, the rest behind: two memsets per call
-struct CleanSpans { size_t zero_end, ff_begin, ff_end, total; };
-CleanSpans carve_clean(void* ws, int64_t V, int64_t F, CleanArgs* a) {
+// zero-initialised arrays first, 0xff-initialised tables second, the rest behind (dudf_init_spans)
+DudfSpans carve_clean(void* ws, int64_t V, int64_t F, CleanArgs* a) {
     DudfByteCarver cv = dudf_carve(ws);
     a->V = V; a->F = F;
-    a->capV = pow2_at_least(2 * V); a->capF = pow2_at_least(2 * F); a->capE = pow2_at_least(6 * F);
-    a->nbV = blocks_of(V); a->nbF = blocks_of(F);
+    a->capV = dudf_pow2_at_least(2 * V); a->capF = dudf_pow2_at_least(2 * F); a->capE = dudf_pow2_at_least(6 * F);
+    a->nbV = dudf_wg_count(V); a->nbF = dudf_wg_count(F);
     a->head = cv.take<int64_t>(4); a->tot = cv.take<int64_t>(N_TOT); a->ctr = cv.take<unsigned long long>(N_CTR);
     a->vref = cv.take<uint8_t>(V); a->vkeep = cv.take<uint8_t>(V); a->hole = cv.take<uint8_t>(V);
     a->bdeg = cv.take<int32_t>(V); a->einfo = cv.take<uint32_t>(a->capE);
-    CleanSpans sp;
+    DudfSpans sp;
     sp.zero_end = sp.ff_begin = cv.o;
     a->vtab = cv.take<uint32_t>(a->capV); a->ftab = cv.take<uint32_t>(a->capF); a->etab = cv.take<unsigned long long>(a->capE);
     sp.ff_end = cv.o;
@@ -399,7 +313,7 @@ CleanSpans carve_clean(void* ws, int64_t V, int64_t F, CleanArgs* a) {
 const double kPow10[16] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15};
 
 int fill_clean(const double* vertices, int64_t V, const int64_t* faces, int64_t F, int digits, int fill, void* ws, size_t bytes,
-               CleanArgs* a, CleanSpans* sp) {
+               CleanArgs* a, DudfSpans* sp) {
     if (V < 0 || F < 0 || digits < 0 || digits > 15 || (fill != 0 && fill != 1)) return DUDF_E_BADCFG;
     if (!sizes_ok(V, F)) return DUDF_E_UNSUPPORTED;
     if ((V > 0 && !vertices) || (F > 0 && !faces)) return DUDF_E_BADCFG;
@@ -424,10 +338,10 @@ struct BorderArgs {
 };
 
 __global__ __launch_bounds__(WG) void border_faces_kernel(BorderArgs a) {
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     if (f >= a.F) return;
     const int64_t i0 = a.face[3 * f], i1 = a.face[3 * f + 1], i2 = a.face[3 * f + 2];
-    if (!(i0 >= 0 && i0 < a.V && i1 >= 0 && i1 < a.V && i2 >= 0 && i2 < a.V)) return;        // skipped, never dereferenced
+    if (!dudf_face_in_range(i0, i1, i2, a.V)) return;                   // skipped, never dereferenced
     const int32_t g0 = (int32_t)i0, g1 = (int32_t)i1, g2 = (int32_t)i2;
     if (g0 != g1) edge_insert(a.etab, a.einfo, a.capE, g0, g1);
     if (g1 != g2) edge_insert(a.etab, a.einfo, a.capE, g1, g2);
@@ -436,10 +350,10 @@ __global__ __launch_bounds__(WG) void border_faces_kernel(BorderArgs a) {
 
 template <int FILL>
 __global__ __launch_bounds__(WG) void border_slots_kernel(BorderArgs a) {
-    const int64_t s = item();
+    const int64_t s = dudf_wg_item();
     if (s >= a.capE) return;
     const unsigned long long key = a.etab[s];
-    if (key == EMPTY64 || (a.einfo[s] & ~DIR_BIT) != 1u) return;
+    if (key == kTabEmpty64 || (a.einfo[s] & ~DIR_BIT) != 1u) return;
     const int32_t u = (int32_t)(key >> 32), w = (int32_t)(key & 0xffffffffu);
     if (!FILL) {
         atomicAdd(&a.deg[u], 1); atomicAdd(&a.deg[w], 1); atomicAdd(&a.up[u], 1);
@@ -452,7 +366,7 @@ __global__ __launch_bounds__(WG) void border_slots_kernel(BorderArgs a) {
 template <int PASS>
 __global__ __launch_bounds__(WG) void border_offsets_kernel(BorderArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     const unsigned d = v < a.V ? (unsigned)a.deg[v] : 0u, u = v < a.V ? (unsigned)a.up[v] : 0u;
     unsigned t0, t1;
     const unsigned b0 = dudf_wg_scan(d, wt, &t0);
@@ -466,7 +380,7 @@ __global__ __launch_bounds__(WG) void border_offsets_kernel(BorderArgs a) {
 }
 
 __global__ __launch_bounds__(WG) void border_sort_kernel(BorderArgs a) {
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     if (v == 0) { a.head[0] = MAGIC_BORDER; a.head[1] = a.V; a.head[2] = a.F; }
     if (v >= a.V) return;
     int32_t* l = a.nbr + a.coff[v];
@@ -487,7 +401,7 @@ __global__ void border_count_kernel(BorderArgs a, int64_t* out_count) {
 
 __global__ __launch_bounds__(WG) void border_emit_kernel(BorderArgs a, int64_t* __restrict__ out_edges) {
     if (!border_head_ok(a)) return;
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     if (v >= a.V) return;
     const int32_t* l = a.nbr + a.coff[v];
     const int n = a.deg[v];
@@ -499,7 +413,7 @@ __global__ __launch_bounds__(WG) void border_emit_kernel(BorderArgs a, int64_t* 
 // one Jacobi iteration src -> dst: border vertices move towards the mean of their border neighbours, the others are copied
 __global__ __launch_bounds__(WG) void border_smooth_kernel(BorderArgs a, const double* __restrict__ src, double* __restrict__ dst, double lam) {
     if (!border_head_ok(a)) return;
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     if (v >= a.V) return;
     const double x = src[3 * v], y = src[3 * v + 1], z = src[3 * v + 2];
     const int n = a.deg[v];
@@ -511,14 +425,13 @@ __global__ __launch_bounds__(WG) void border_smooth_kernel(BorderArgs a, const d
     dst[3 * v] = x + lam * (sx / dn - x); dst[3 * v + 1] = y + lam * (sy / dn - y); dst[3 * v + 2] = z + lam * (sz / dn - z);
 }
 
-struct BorderSpans { size_t zero_end, ff_end, total; };
-BorderSpans carve_border(void* ws, int64_t V, int64_t F, BorderArgs* a) {
+DudfSpans carve_border(void* ws, int64_t V, int64_t F, BorderArgs* a) {
     DudfByteCarver cv = dudf_carve(ws);
-    a->V = V; a->F = F; a->capE = pow2_at_least(6 * F); a->nbV = blocks_of(V);
+    a->V = V; a->F = F; a->capE = dudf_pow2_at_least(6 * F); a->nbV = dudf_wg_count(V);
     a->head = cv.take<int64_t>(3); a->tot = cv.take<int64_t>(2);
     a->deg = cv.take<int32_t>(V); a->up = cv.take<int32_t>(V); a->cur = cv.take<int32_t>(V); a->einfo = cv.take<uint32_t>(a->capE);
-    BorderSpans sp;
-    sp.zero_end = cv.o;
+    DudfSpans sp;
+    sp.zero_end = sp.ff_begin = cv.o;
     a->etab = cv.take<unsigned long long>(a->capE);
     sp.ff_end = cv.o;
     a->coff = cv.take<int64_t>(V); a->uoff = cv.take<int64_t>(V); a->nbr = cv.take<int32_t>(6 * F);
@@ -530,7 +443,7 @@ BorderSpans carve_border(void* ws, int64_t V, int64_t F, BorderArgs* a) {
 
 bool border_sizes_ok(int64_t V, int64_t F) { return sizes_ok(V, F) && 6 * F < (1ll << 32); }   // block sums of degrees are 32-bit
 
-int fill_border(int64_t V, const int64_t* faces, int64_t F, void* ws, size_t bytes, BorderArgs* a, BorderSpans* sp) {
+int fill_border(int64_t V, const int64_t* faces, int64_t F, void* ws, size_t bytes, BorderArgs* a, DudfSpans* sp) {
     if (V < 0 || F < 0) return DUDF_E_BADCFG;
     if (!border_sizes_ok(V, F)) return DUDF_E_UNSUPPORTED;
     if (F > 0 && !faces) return DUDF_E_BADCFG;
@@ -541,11 +454,9 @@ int fill_border(int64_t V, const int64_t* faces, int64_t F, void* ws, size_t byt
 }
 
 // edge table -> per-vertex ascending lists of border neighbours (and the totals); V, F >= 1
-int build_border(const BorderArgs& a, const BorderSpans& sp, void* ws, hipStream_t st) {
-    char* base = static_cast<char*>(ws);
-    DUDF_TRY(hipMemsetAsync(base, 0, sp.zero_end, st));
-    DUDF_TRY(hipMemsetAsync(base + sp.zero_end, 0xff, sp.ff_end - sp.zero_end, st));
-    const dim3 gv((unsigned)a.nbV), gf((unsigned)blocks_of(a.F)), gs((unsigned)blocks_of(a.capE)), wg(WG);
+int build_border(const BorderArgs& a, const DudfSpans& sp, void* ws, hipStream_t st) {
+    DUDF_TRY(dudf_init_spans(ws, sp, st));
+    const dim3 gv((unsigned)a.nbV), gf((unsigned)dudf_wg_count(a.F)), gs((unsigned)dudf_wg_count(a.capE)), wg(WG);
     DUDF_TRY(dudf_launch(border_faces_kernel, gf, wg, st, a));
     DUDF_TRY(dudf_launch(border_slots_kernel<0>, gs, wg, st, a));
     DUDF_TRY(dudf_launch(border_offsets_kernel<0>, gv, wg, st, a));
@@ -567,16 +478,14 @@ size_t dudf_mesh_clean_workspace_bytes(int64_t V, int64_t F) {
 
 int dudf_mesh_clean_count(const double* vertices, int64_t V, const int64_t* faces, int64_t F, int digits, int fill_holes,
                           int64_t* out_counts, void* workspace, size_t workspace_bytes, void* stream) {
-    CleanArgs a; CleanSpans sp;
+    CleanArgs a; DudfSpans sp;
     int rc = fill_clean(vertices, V, faces, F, digits, fill_holes, workspace, workspace_bytes, &a, &sp);
     if (rc) return rc;
     if (!out_counts) return DUDF_E_BADCFG;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     if (V == 0 || F == 0) return dudf_launch(clean_empty_kernel, dim3(1), dim3(1), st, V, F, out_counts, a.head);
-    char* base = static_cast<char*>(workspace);
-    DUDF_TRY(hipMemsetAsync(base, 0, sp.zero_end, st));
-    DUDF_TRY(hipMemsetAsync(base + sp.ff_begin, 0xff, sp.ff_end - sp.ff_begin, st));
+    DUDF_TRY(dudf_init_spans(workspace, sp, st));
     const dim3 gv((unsigned)a.nbV), gf((unsigned)a.nbF), wg(WG);
     DUDF_TRY(dudf_launch(clean_validate_kernel, gf, wg, st, a));
     DUDF_TRY(dudf_launch(clean_weld_insert_kernel, gv, wg, st, a));
@@ -584,7 +493,7 @@ int dudf_mesh_clean_count(const double* vertices, int64_t V, const int64_t* face
     DUDF_TRY(dudf_launch(clean_remap_kernel, gf, wg, st, a));
     DUDF_TRY(dudf_launch(clean_face_insert_kernel, gf, wg, st, a));
     DUDF_TRY(dudf_launch(clean_face_resolve_kernel, gf, wg, st, a));
-    if (a.fill) DUDF_TRY(dudf_launch(clean_border_adj_kernel, dim3((unsigned)blocks_of(a.capE)), wg, st, a));
+    if (a.fill) DUDF_TRY(dudf_launch(clean_border_adj_kernel, dim3((unsigned)dudf_wg_count(a.capE)), wg, st, a));
     DUDF_TRY(dudf_launch(clean_holes_kernel, gv, wg, st, a));
     DUDF_TRY(dudf_launch(dudf_scan_totals_kernel<3>, dim3(1), dim3(1024), st, a.vblk, a.voff, a.nbV, a.tot));
     DUDF_TRY(dudf_launch(dudf_scan_totals_kernel<1>, dim3(1), dim3(1024), st, a.fblk, a.foff, a.nbF, a.tot + TOT_ALIVE));
@@ -593,7 +502,7 @@ int dudf_mesh_clean_count(const double* vertices, int64_t V, const int64_t* face
 
 int dudf_mesh_clean_emit(const double* vertices, int64_t V, const int64_t* faces, int64_t F, int digits, int fill_holes,
                          double* out_vertices, int64_t* out_faces, void* workspace, size_t workspace_bytes, void* stream) {
-    CleanArgs a; CleanSpans sp;
+    CleanArgs a; DudfSpans sp;
     int rc = fill_clean(vertices, V, faces, F, digits, fill_holes, workspace, workspace_bytes, &a, &sp);
     if (rc) return rc;
     if (!out_vertices || !out_faces) return DUDF_E_BADCFG;
@@ -616,7 +525,7 @@ size_t dudf_mesh_border_workspace_bytes(int64_t V, int64_t F) {
 
 int dudf_mesh_border_count(int64_t V, const int64_t* faces, int64_t F, int64_t* out_count, void* workspace, size_t workspace_bytes,
                            void* stream) {
-    BorderArgs a; BorderSpans sp;
+    BorderArgs a; DudfSpans sp;
     int rc = fill_border(V, faces, F, workspace, workspace_bytes, &a, &sp);
     if (rc) return rc;
     if (!out_count) return DUDF_E_BADCFG;
@@ -633,7 +542,7 @@ int dudf_mesh_border_count(int64_t V, const int64_t* faces, int64_t F, int64_t* 
 
 int dudf_mesh_border_edges(int64_t V, const int64_t* faces, int64_t F, int64_t* out_edges, void* workspace, size_t workspace_bytes,
                            void* stream) {
-    BorderArgs a; BorderSpans sp;
+    BorderArgs a; DudfSpans sp;
     int rc = fill_border(V, faces, F, workspace, workspace_bytes, &a, &sp);
     if (rc) return rc;
     if (!out_edges) return DUDF_E_BADCFG;
@@ -645,7 +554,7 @@ int dudf_mesh_border_edges(int64_t V, const int64_t* faces, int64_t F, int64_t* 
 
 int dudf_mesh_smooth_borders(double* vertices_inout, int64_t V, const int64_t* faces, int64_t F, int iterations, double lambda,
                              void* workspace, size_t workspace_bytes, void* stream) {
-    BorderArgs a; BorderSpans sp;
+    BorderArgs a; DudfSpans sp;
     int rc = fill_border(V, faces, F, workspace, workspace_bytes, &a, &sp);
     if (rc) return rc;
     if (iterations < 0 || (V > 0 && !vertices_inout)) return DUDF_E_BADCFG;

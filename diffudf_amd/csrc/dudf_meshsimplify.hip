@@ -9,21 +9,15 @@
 // sorted keys and the permutation to `_count`, which finds the occupied cells (heads of the runs), remaps and prunes the faces, sums and
 // places every cell and publishes the eight counts; `_emit` compacts the used cells and the surviving faces.
 //
-// Hash tables (open addressing, linear probing, capacity a power of two, nothing is ever deleted; every probe loop is bounded by the
-// capacity):
-//   edges   as in dudf_meshclean.hip: a slot holds the key (min << 32 | max), claimed with a 64-bit atomicCAS, beside it the use
-//           count.  A second table, not a shared header: that unit keeps a direction bit in the same word and this one does not;
-//   faces   a slot holds the smallest face index with the slot's sorted triple of cell ids (atomicCAS, lowered with atomicMin); triples
-//           are compared by re-reading `g`, which the launch before wrote.
-#include "dudf_context.h"
+// Hash tables, by the rules of dudf_meshtab.h:
+//   edges   capacity >= 6 F, beside a slot the use count;
+//   faces   smallest face index per sorted triple of cell ids (read from `g`, which the launch before wrote), capacity >= 2 F.
+#include "dudf_meshtab.h"
 #include "dudf_eigh3.h"
-#include "dudf_wgscan.h"
 
 namespace {
 
 constexpr int WG = DUDF_WG;
-constexpr uint32_t EMPTY32 = 0xffffffffu;
-constexpr unsigned long long EMPTY64 = ~0ull;
 constexpr int64_t KEY_NONE = -1;                               // a corner without a record: sorts in front of every cell (the
                                                                // all-saturated cell's key is 2^63 - 1: nothing sorts behind it)
 constexpr int64_t CELL_MASK = (1ll << 21) - 1;
@@ -32,19 +26,6 @@ enum { ST_INVALID = 0, ST_REPEATED = 1, ST_VALID = 2, ST_COLLAPSED = 3, ST_DUPLI
 enum { CTR_INVALID = 0, CTR_COLLAPSED, CTR_DUPLICATE, CTR_BORDER, CTR_FALLBACK, N_CTR };
 enum { TOT_CELLS = 0, TOT_USED, TOT_FACES, N_TOT };
 enum { HEAD_MAGIC = 0, HEAD_V, HEAD_F, HEAD_PLACED, N_HEAD };
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {       // splitmix64's finaliser: lattice keys must not cluster
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ unsigned long long edge_key(uint32_t u, uint32_t w) {
-    return u < w ? ((unsigned long long)u << 32) | w : ((unsigned long long)w << 32) | u;
-}
-__device__ __forceinline__ int64_t item() { return (int64_t)blockIdx.x * WG + threadIdx.x; }
-__device__ __forceinline__ void add_total(unsigned long long* ctr, unsigned total) {
-    if (threadIdx.x == 0 && total) atomicAdd(ctr, (unsigned long long)total);
-}
 
 struct SimpArgs {
     const double* vert; const int64_t* face; int64_t V, F, capE, capF, Cmax, nbS, nbF, nbC;
@@ -87,18 +68,11 @@ __device__ __forceinline__ int64_t cell_key(const SimpArgs& a, int64_t v) {
 // one thread per face: validity, the three corner keys, the face's edge uses
 __global__ __launch_bounds__(WG) void simp_keys_kernel(SimpArgs a, int64_t* __restrict__ out_keys) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     bool invalid = false, repeated = false;
     if (f < a.F) {
         const int64_t i0 = a.face[3 * f], i1 = a.face[3 * f + 1], i2 = a.face[3 * f + 2];
-        bool ok = i0 >= 0 && i0 < a.V && i1 >= 0 && i1 < a.V && i2 >= 0 && i2 < a.V;
-        if (ok) {                                                       // coordinates are read only behind the range check
-            const int64_t idx[3] = {i0, i1, i2};
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) ok = ok && isfinite(a.vert[3 * idx[k] + c]);
-        }
+        const bool ok = dudf_face_in_range(i0, i1, i2, a.V) && dudf_face_finite(a.vert, i0, i1, i2);
         invalid = !ok;
         repeated = ok && (i0 == i1 || i1 == i2 || i2 == i0);
         int64_t k0 = KEY_NONE, k1 = KEY_NONE, k2 = KEY_NONE;
@@ -110,12 +84,8 @@ __global__ __launch_bounds__(WG) void simp_keys_kernel(SimpArgs a, int64_t* __re
             const uint32_t idx[3] = {(uint32_t)i0, (uint32_t)i1, (uint32_t)i2};
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const unsigned long long key = edge_key(idx[c], idx[c == 2 ? 0 : c + 1]);
-                int64_t s = (int64_t)(mix64(key) & (uint64_t)(a.capE - 1));
-                for (int64_t i = 0; i < a.capE; ++i, s = (s + 1) & (a.capE - 1)) {
-                    const unsigned long long cur = atomicCAS(&a.etab[s], EMPTY64, key);
-                    if (cur == EMPTY64 || cur == key) { atomicAdd(&a.ecnt[s], 1u); break; }
-                }
+                const int64_t s = dudf_edge_claim(a.etab, a.capE, dudf_edge_key(idx[c], idx[c == 2 ? 0 : c + 1]));
+                if (s >= 0) atomicAdd(&a.ecnt[s], 1u);
             }
         }
         a.fstate[f] = invalid ? ST_INVALID : repeated ? ST_REPEATED : ST_VALID;
@@ -123,26 +93,20 @@ __global__ __launch_bounds__(WG) void simp_keys_kernel(SimpArgs a, int64_t* __re
         out_keys[3 * f] = k0; out_keys[3 * f + 1] = k1; out_keys[3 * f + 2] = k2;
     }
     unsigned total;
-    dudf_wg_rank(invalid, wt, &total);  add_total(a.ctr + CTR_INVALID, total);
-    dudf_wg_rank(repeated, wt, &total); add_total(a.ctr + CTR_COLLAPSED, total);
+    dudf_wg_rank(invalid, wt, &total);  dudf_wg_add_total(a.ctr + CTR_INVALID, total);
+    dudf_wg_rank(repeated, wt, &total); dudf_wg_add_total(a.ctr + CTR_COLLAPSED, total);
 }
 
 // uses of the edge {u, w}, 0 when the table does not hold it (table complete: read only)
 __device__ __forceinline__ uint32_t edge_uses(const SimpArgs& a, uint32_t u, uint32_t w) {
-    const unsigned long long key = edge_key(u, w);
-    int64_t s = (int64_t)(mix64(key) & (uint64_t)(a.capE - 1));
-    for (int64_t i = 0; i < a.capE; ++i, s = (s + 1) & (a.capE - 1)) {
-        const unsigned long long cur = a.etab[s];
-        if (cur == key) return a.ecnt[s];
-        if (cur == EMPTY64) return 0;
-    }
-    return 0;
+    const int64_t s = dudf_edge_slot(a.etab, a.capE, dudf_edge_key(u, w));
+    return s >= 0 ? a.ecnt[s] : 0u;
 }
 
 // one thread per face: which of its edges exactly one valid face uses (each border edge belongs to one face: counted once)
 __global__ __launch_bounds__(WG) void simp_border_kernel(SimpArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     unsigned m = 0;
     if (f < a.F && a.fstate[f] == ST_VALID) {
         const uint32_t i0 = (uint32_t)a.face[3 * f], i1 = (uint32_t)a.face[3 * f + 1], i2 = (uint32_t)a.face[3 * f + 2];
@@ -151,14 +115,14 @@ __global__ __launch_bounds__(WG) void simp_border_kernel(SimpArgs a) {
     if (f < a.F) a.fborder[f] = (uint8_t)m;
     unsigned total;
     dudf_wg_scan((unsigned)__popc(m), wt, &total);
-    add_total(a.ctr + CTR_BORDER, total);
+    dudf_wg_add_total(a.ctr + CTR_BORDER, total);
 }
 
 // one thread per sorted slot.  PASS 0: heads of the runs per workgroup; PASS 1: the cell id of every record, the cell's start and key
 template <int PASS>
 __global__ __launch_bounds__(WG) void simp_heads_kernel(SimpArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t i = item(), n = 3 * a.F;
+    const int64_t i = dudf_wg_item(), n = 3 * a.F;
     const int64_t key = i < n ? a.skey[i] : KEY_NONE;
     const bool rec = key >= 0;
     const bool hd = rec && (i == 0 || a.skey[i - 1] != key);
@@ -176,21 +140,10 @@ __global__ __launch_bounds__(WG) void simp_heads_kernel(SimpArgs a) {
     }
 }
 
-struct Tri { int32_t a, b, c; };                               // a <= b <= c
-__device__ __forceinline__ Tri face_key(const int32_t* __restrict__ g, int64_t f) {
-    int32_t a = g[3 * f], b = g[3 * f + 1], c = g[3 * f + 2], t;
-    if (a > b) { t = a; a = b; b = t; }
-    if (b > c) { t = b; b = c; c = t; }
-    if (a > b) { t = a; a = b; b = t; }
-    return Tri{a, b, c};
-}
-__device__ __forceinline__ bool same(const Tri& p, const Tri& q) { return p.a == q.a && p.b == q.b && p.c == q.c; }
-__device__ __forceinline__ uint64_t hash(const Tri& k) { return mix64(mix64(((uint64_t)(uint32_t)k.a << 32) | (uint32_t)k.b) ^ (uint32_t)k.c); }
-
 // one thread per face: the cell ids of all three corners; fewer than three distinct cells collapse
 __global__ __launch_bounds__(WG) void simp_remap_kernel(SimpArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     bool col = false;
     if (f < a.F && a.fstate[f] == ST_VALID) {
         const int32_t g0 = a.g[3 * f];
@@ -202,44 +155,33 @@ __global__ __launch_bounds__(WG) void simp_remap_kernel(SimpArgs a) {
     }
     unsigned total;
     dudf_wg_rank(col, wt, &total);
-    add_total(a.ctr + CTR_COLLAPSED, total);
+    dudf_wg_add_total(a.ctr + CTR_COLLAPSED, total);
 }
 
 // the faces with three cells enter the face table (triples are read from `g`, which the launch before wrote)
 __global__ __launch_bounds__(WG) void simp_face_insert_kernel(SimpArgs a) {
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     if (f >= a.F || a.fstate[f] != ST_ALIVE) return;
-    const Tri k = face_key(a.g, f);
-    int64_t s = (int64_t)(hash(k) & (uint64_t)(a.capF - 1));
-    for (int64_t i = 0; i < a.capF; ++i, s = (s + 1) & (a.capF - 1)) {
-        const uint32_t cur = atomicCAS(&a.ftab[s], EMPTY32, (uint32_t)f);
-        if (cur == EMPTY32) return;
-        if (cur < a.F && same(face_key(a.g, cur), k)) { atomicMin(&a.ftab[s], (uint32_t)f); return; }
-    }
+    dudf_first_insert(a.ftab, a.capF, DudfTriItems{a.g}, f, a.F);
 }
 
 // a face survives when it is the smallest index of its cell set; survivors mark their cells
 __global__ __launch_bounds__(WG) void simp_resolve_kernel(SimpArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     bool alive = false, dup = false;
     if (f < a.F && a.fstate[f] == ST_ALIVE) {
-        const Tri k = face_key(a.g, f);
-        int64_t s = (int64_t)(hash(k) & (uint64_t)(a.capF - 1));
-        uint32_t firstf = (uint32_t)f;
-        for (int64_t i = 0; i < a.capF; ++i, s = (s + 1) & (a.capF - 1)) {
-            const uint32_t cur = a.ftab[s];
-            if (cur == EMPTY32) break;
-            if (cur < a.F && same(face_key(a.g, cur), k)) { firstf = cur; break; }
-        }
-        alive = firstf == (uint32_t)f;
+        const DudfTriItems items{a.g};
+        const DudfTri k = items.key(f);
+        const uint32_t firstf = dudf_first_find(a.ftab, a.capF, items, k, a.F);
+        alive = firstf == (uint32_t)f || firstf == kTabEmpty32;          // a triple the table does not hold: the face stands for itself
         dup = !alive;
         if (!dup) { a.cuse[k.a] = 1; a.cuse[k.b] = 1; a.cuse[k.c] = 1; }
     }
     if (dup) a.fstate[f] = ST_DUPLICATE;                                // no probe reads another face's state
     unsigned total;
     dudf_wg_rank(dup, wt, &total);
-    add_total(a.ctr + CTR_DUPLICATE, total);
+    dudf_wg_add_total(a.ctr + CTR_DUPLICATE, total);
     dudf_wg_rank(alive, wt, &total);
     if (threadIdx.x == 0) a.fblk[blockIdx.x] = total;
 }
@@ -262,7 +204,7 @@ __device__ __forceinline__ void add_border(double (&q)[10], double wb, const dou
 // one thread per occupied cell: walks the cell's run of records in order (rule 6), then places the representative (rule 7)
 __global__ __launch_bounds__(WG) void simp_cells_kernel(SimpArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t c = item(), n3 = 3 * a.F;
+    const int64_t c = dudf_wg_item(), n3 = 3 * a.F;
     bool fell = false;
     if (c < a.Cmax && c < a.tot[TOT_CELLS]) {
         const int64_t key = a.ckey[c];
@@ -331,12 +273,12 @@ __global__ __launch_bounds__(WG) void simp_cells_kernel(SimpArgs a) {
     }
     unsigned total;
     dudf_wg_rank(fell, wt, &total);
-    add_total(a.ctr + CTR_FALLBACK, total);
+    dudf_wg_add_total(a.ctr + CTR_FALLBACK, total);
 }
 
 __global__ __launch_bounds__(WG) void simp_used_kernel(SimpArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t c = item();
+    const int64_t c = dudf_wg_item();
     unsigned total;
     dudf_wg_rank(c < a.Cmax && a.cuse[c], wt, &total);
     if (threadIdx.x == 0) a.cblk[blockIdx.x] = total;
@@ -361,7 +303,7 @@ __global__ __launch_bounds__(WG) void simp_emit_cells_kernel(SimpArgs a, double*
                                                              int64_t* __restrict__ out_records, uint8_t* __restrict__ out_fell) {
     __shared__ unsigned wt[WG / 64];
     if (!head_ok(a)) return;                                            // uniform: the whole grid leaves
-    const int64_t c = item();
+    const int64_t c = dudf_wg_item();
     const bool occ = c < a.Cmax && c < a.tot[TOT_CELLS];
     const bool use = occ && a.cuse[c];
     unsigned total;
@@ -382,7 +324,7 @@ __global__ __launch_bounds__(WG) void simp_emit_cells_kernel(SimpArgs a, double*
 __global__ __launch_bounds__(WG) void simp_emit_faces_kernel(SimpArgs a, int64_t* __restrict__ out_f) {
     __shared__ unsigned wt[WG / 64];
     if (!head_ok(a)) return;
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     const bool alive = f < a.F && a.fstate[f] == ST_ALIVE;
     unsigned total;
     const unsigned r = dudf_wg_rank(alive, wt, &total);
@@ -399,22 +341,19 @@ __global__ void simp_empty_kernel(int64_t* out_counts, int64_t* head) {
     head[HEAD_MAGIC] = 0;
 }
 
-int64_t pow2_at_least(int64_t n) { int64_t c = 2; while (c < n) c <<= 1; return c; }
-int64_t blocks_of(int64_t n) { return (n + WG - 1) / WG; }
 bool sizes_ok(int64_t V, int64_t F) { return V >= 0 && F >= 0 && V < (1ll << 31) && 3 * F < (1ll << 31); }
 
-// zero-initialised arrays first, 0xff-initialised second, the rest behind: two memsets per call
-struct SimpSpans { size_t zero_end, ff_end, total; };
-SimpSpans carve_simp(void* ws, int64_t V, int64_t F, SimpArgs* a) {
+// zero-initialised arrays first, 0xff-initialised second, the rest behind (dudf_init_spans)
+DudfSpans carve_simp(void* ws, int64_t V, int64_t F, SimpArgs* a) {
     DudfByteCarver cv = dudf_carve(ws);
     a->V = V; a->F = F;
-    a->capE = pow2_at_least(6 * F); a->capF = pow2_at_least(2 * F);
+    a->capE = dudf_pow2_at_least(6 * F); a->capF = dudf_pow2_at_least(2 * F);
     a->Cmax = 3 * F < V ? 3 * F : V;                                    // every occupied cell holds a vertex and a record
-    a->nbS = blocks_of(3 * F); a->nbF = blocks_of(F); a->nbC = blocks_of(a->Cmax > 0 ? a->Cmax : 1);
+    a->nbS = dudf_wg_count(3 * F); a->nbF = dudf_wg_count(F); a->nbC = dudf_wg_count(a->Cmax > 0 ? a->Cmax : 1);
     a->head = cv.take<int64_t>(N_HEAD); a->tot = cv.take<int64_t>(N_TOT); a->ctr = cv.take<unsigned long long>(N_CTR);
     a->ecnt = cv.take<uint32_t>(a->capE); a->cuse = cv.take<uint8_t>(a->Cmax);
-    SimpSpans sp;
-    sp.zero_end = cv.o;
+    DudfSpans sp;
+    sp.zero_end = sp.ff_begin = cv.o;
     a->etab = cv.take<unsigned long long>(a->capE); a->ftab = cv.take<uint32_t>(a->capF); a->g = cv.take<int32_t>(3 * F);
     a->cstart = cv.take<int32_t>(a->Cmax);
     sp.ff_end = cv.o;
@@ -430,7 +369,7 @@ SimpSpans carve_simp(void* ws, int64_t V, int64_t F, SimpArgs* a) {
 }
 
 // the checks of rule 10 that all three calls share, in front of any device call
-int fill_simp(const double* vertices, int64_t V, const int64_t* faces, int64_t F, void* ws, size_t bytes, SimpArgs* a, SimpSpans* sp) {
+int fill_simp(const double* vertices, int64_t V, const int64_t* faces, int64_t F, void* ws, size_t bytes, SimpArgs* a, DudfSpans* sp) {
     if (V < 0 || F < 0) return DUDF_E_BADCFG;
     if (!sizes_ok(V, F)) return DUDF_E_UNSUPPORTED;
     if (F > 0 && (!faces || (V > 0 && !vertices))) return DUDF_E_BADCFG;
@@ -463,17 +402,15 @@ size_t dudf_mesh_simplify_workspace_bytes(int64_t V, int64_t F) {
 int dudf_mesh_simplify_keys(const double* vertices, int64_t V, const int64_t* faces, int64_t F, const double* origin, double cell,
                             int64_t* out_keys, void* workspace, size_t workspace_bytes, void* stream) {
     if (!cell_ok(origin, cell)) return DUDF_E_BADCFG;
-    SimpArgs a; SimpSpans sp;
+    SimpArgs a; DudfSpans sp;
     int rc = fill_simp(vertices, V, faces, F, workspace, workspace_bytes, &a, &sp);
     if (rc) return rc;
     if (F > 0 && !out_keys) return DUDF_E_BADCFG;
     a.org[0] = origin[0]; a.org[1] = origin[1]; a.org[2] = origin[2]; a.h = cell; a.inv = 1.0 / cell;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
-    char* base = static_cast<char*>(workspace);
-    DUDF_TRY(hipMemsetAsync(base, 0, sp.zero_end, st));
-    if (F == 0) return 0;
-    DUDF_TRY(hipMemsetAsync(base + sp.zero_end, 0xff, sp.ff_end - sp.zero_end, st));
+    if (F == 0) return (int)hipMemsetAsync(workspace, 0, sp.zero_end, st);                  // head and counters: no faces
+    DUDF_TRY(dudf_init_spans(workspace, sp, st));
     return dudf_launch(simp_keys_kernel, dim3((unsigned)a.nbF), dim3(WG), st, a, out_keys);
 }
 
@@ -481,7 +418,7 @@ int dudf_mesh_simplify_count(const double* vertices, int64_t V, const int64_t* f
                              double boundary_weight, double tau, const int64_t* sorted_keys, const int64_t* order, int place,
                              int64_t* out_counts, void* workspace, size_t workspace_bytes, void* stream) {
     if (!cell_ok(origin, cell) || !(boundary_weight >= 0.0) || !(tau > 0.0 && tau < 1.0) || (place != 0 && place != 1)) return DUDF_E_BADCFG;
-    SimpArgs a; SimpSpans sp;
+    SimpArgs a; DudfSpans sp;
     int rc = fill_simp(vertices, V, faces, F, workspace, workspace_bytes, &a, &sp);
     if (rc) return rc;
     if (!out_counts || (F > 0 && (!sorted_keys || !order))) return DUDF_E_BADCFG;
@@ -509,7 +446,7 @@ int dudf_mesh_simplify_count(const double* vertices, int64_t V, const int64_t* f
 int dudf_mesh_simplify_emit(const double* vertices, int64_t V, const int64_t* faces, int64_t F, double* out_vertices, int64_t* out_faces,
                             double* out_quadrics, double* out_xhat, int64_t* out_cell_keys, int64_t* out_records,
                             unsigned char* out_fallback, void* workspace, size_t workspace_bytes, void* stream) {
-    SimpArgs a; SimpSpans sp;
+    SimpArgs a; DudfSpans sp;
     int rc = fill_simp(vertices, V, faces, F, workspace, workspace_bytes, &a, &sp);
     if (rc) return rc;
     if (!out_vertices || !out_faces) return DUDF_E_BADCFG;

@@ -4,8 +4,7 @@
 // -ffp-contract=off (the face-normal length repeats the oracle's double arithmetic).  Index work only: integer atomics on hash-table
 // slots, union-find words and counters, no float atomics.
 //
-// Edge table (open addressing, linear probing, capacity a power of two >= 6 F, nothing is ever deleted): a slot holds the key
-// (min << 32 | max), claimed with a 64-bit atomicCAS; beside it the use count and the atomicMin / atomicMax of the face-slot ids
+// Edge table (dudf_meshtab.h, capacity >= 6 F): beside a slot the use count and the atomicMin / atomicMax of the face-slot ids
 // e = 3 f + c that use it — the two faces of a manifold edge, whatever the arrival order.  Directions are re-read from the immutable
 // faces.  A resolve pass turns the table into link[e]: the partner face-slot of e and the relative sign, or NONE; the rounds below
 // never probe for their own edges again.
@@ -15,31 +14,16 @@
 // representative) and flattens (parent, parity) by pointer doubling between two buffers.  Keys are distinct per link, so hooks form
 // no cycle but the mutual pair.  Every loop has a trip count known at launch: probe loops are bounded by the capacity, rounds by
 // ceil(log2 F) + 1, doubling steps by ceil(log2 F).
-#include "dudf_context.h"
-#include "dudf_wgscan.h"
+#include "dudf_meshtab.h"
 
 namespace {
 
 constexpr int WG = DUDF_WG;
 constexpr uint32_t NONE32 = 0xffffffffu;
 constexpr uint32_t SAME_BIT = 0x80000000u;
-constexpr unsigned long long EMPTY64 = ~0ull;
 constexpr int64_t MAGIC_SUBMESH = 0x6475646653314d42ll;
 enum { CTR_COMPONENTS = 0, CTR_FOREST, CTR_MANIFOLD,            // the order of out_counts
  CTR_BORDER, CTR_NONMANIFOLD, CTR_IGNORED, CTR_FLIPPED, CTR_INCONSISTENT, N_CTR };
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {       // splitmix64's finaliser: lattice keys must not cluster
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ unsigned long long edge_key(uint32_t u, uint32_t w) {
-    return u < w ? ((unsigned long long)u << 32) | w : ((unsigned long long)w << 32) | u;
-}
-__device__ __forceinline__ int64_t item() { return (int64_t)blockIdx.x * WG + threadIdx.x; }
-__device__ __forceinline__ void add_total(unsigned long long* ctr, unsigned total) {
-    if (threadIdx.x == 0 && total) atomicAdd(ctr, (unsigned long long)total);
-}
 
 struct TopoArgs {
     const int64_t* face; const double* vert; int64_t F, V, cap;
@@ -60,25 +44,15 @@ __device__ __forceinline__ void slot_edge(const int64_t* __restrict__ face, uint
     const uint32_t f = e / 3u, c = e - 3u * f, d = c == 2u ? 0u : c + 1u;
     *from = (uint32_t)face[3 * (int64_t)f + c]; *to = (uint32_t)face[3 * (int64_t)f + d];
 }
-// the slot of a key the table holds, -1 otherwise (table complete: read only)
-__device__ __forceinline__ int64_t edge_slot(const unsigned long long* __restrict__ etab, int64_t cap, unsigned long long key) {
-    int64_t s = (int64_t)(mix64(key) & (uint64_t)(cap - 1));
-    for (int64_t i = 0; i < cap; ++i, s = (s + 1) & (cap - 1)) {
-        const unsigned long long cur = etab[s];
-        if (cur == key) return s;
-        if (cur == EMPTY64) return -1;
-    }
-    return -1;
-}
 
 // one thread per face: validity, the face's own union-find word, its three edge uses
 __global__ __launch_bounds__(WG) void topo_insert_kernel(TopoArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     bool ignored = false;
     if (f < a.F) {
         const int64_t i0 = a.face[3 * f], i1 = a.face[3 * f + 1], i2 = a.face[3 * f + 2];
-        const bool ok = i0 >= 0 && i0 < a.V && i1 >= 0 && i1 < a.V && i2 >= 0 && i2 < a.V && i0 != i1 && i1 != i2 && i2 != i0;
+        const bool ok = dudf_face_in_range(i0, i1, i2, a.V) && i0 != i1 && i1 != i2 && i2 != i0;
         a.valid[f] = ok ? 1 : 0;
         a.pp[0][f] = (uint32_t)f << 1;                           // every face its own root, parity 0
         ignored = !ok;
@@ -86,36 +60,29 @@ __global__ __launch_bounds__(WG) void topo_insert_kernel(TopoArgs a) {
             const uint32_t idx[3] = {(uint32_t)i0, (uint32_t)i1, (uint32_t)i2};
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const unsigned long long key = edge_key(idx[c], idx[c == 2 ? 0 : c + 1]);
                 const uint32_t e = 3u * (uint32_t)f + (uint32_t)c;
-                int64_t s = (int64_t)(mix64(key) & (uint64_t)(a.cap - 1));
-                for (int64_t i = 0; i < a.cap; ++i, s = (s + 1) & (a.cap - 1)) {
-                    const unsigned long long cur = atomicCAS(&a.etab[s], EMPTY64, key);
-                    if (cur == EMPTY64 || cur == key) {
-                        atomicAdd(&a.ecnt[s], 1u); atomicMin(&a.emin[s], e); atomicMax(&a.emax[s], e);
-                        break;
-                    }
-                }
+                const int64_t s = dudf_edge_claim(a.etab, a.cap, dudf_edge_key(idx[c], idx[c == 2 ? 0 : c + 1]));
+                if (s >= 0) { atomicAdd(&a.ecnt[s], 1u); atomicMin(&a.emin[s], e); atomicMax(&a.emax[s], e); }
             }
         }
     }
     unsigned total;
     dudf_wg_rank(ignored, wt, &total);
-    add_total(a.ctr + CTR_IGNORED, total);
+    dudf_wg_add_total(a.ctr + CTR_IGNORED, total);
 }
 
 // one thread per face-slot: its partner over a manifold edge and the relative sign; the edge classes, each edge counted once (by
 // its smallest face-slot)
 __global__ __launch_bounds__(WG) void topo_resolve_kernel(TopoArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t e = item();
+    const int64_t e = dudf_wg_item();
     bool border = false, manifold = false, fin = false;
     if (e < 3 * a.F) {
         uint32_t l = NONE32;
         if (a.valid[e / 3]) {
             uint32_t from, to;
             slot_edge(a.face, (uint32_t)e, &from, &to);
-            const int64_t s = edge_slot(a.etab, a.cap, edge_key(from, to));
+            const int64_t s = dudf_edge_slot(a.etab, a.cap, dudf_edge_key(from, to));
             if (s >= 0) {
                 const uint32_t n = a.ecnt[s], lo = a.emin[s], hi = a.emax[s];
                 const bool first = lo == (uint32_t)e;
@@ -131,14 +98,14 @@ __global__ __launch_bounds__(WG) void topo_resolve_kernel(TopoArgs a) {
         a.link[e] = l;
     }
     unsigned total;
-    dudf_wg_rank(border, wt, &total);   add_total(a.ctr + CTR_BORDER, total);
-    dudf_wg_rank(manifold, wt, &total); add_total(a.ctr + CTR_MANIFOLD, total);
-    dudf_wg_rank(fin, wt, &total);      add_total(a.ctr + CTR_NONMANIFOLD, total);
+    dudf_wg_rank(border, wt, &total);   dudf_wg_add_total(a.ctr + CTR_BORDER, total);
+    dudf_wg_rank(manifold, wt, &total); dudf_wg_add_total(a.ctr + CTR_MANIFOLD, total);
+    dudf_wg_rank(fin, wt, &total);      dudf_wg_add_total(a.ctr + CTR_NONMANIFOLD, total);
 }
 
 // one thread per face-slot; a link is handled by its smaller face-slot.  pp is flat: the parent is the representative
 __global__ __launch_bounds__(WG) void topo_best_kernel(TopoArgs a, const uint32_t* __restrict__ pp) {
-    const int64_t e = item();
+    const int64_t e = dudf_wg_item();
     if (e >= 3 * a.F) return;
     const uint32_t l = a.link[e];
     if (l == NONE32) return;
@@ -148,7 +115,7 @@ __global__ __launch_bounds__(WG) void topo_best_kernel(TopoArgs a, const uint32_
     if (ra == rb || ra >= a.F || rb >= a.F) return;
     uint32_t from, to;
     slot_edge(a.face, (uint32_t)e, &from, &to);
-    const unsigned long long key = edge_key(from, to);
+    const unsigned long long key = dudf_edge_key(from, to);
     atomicMin(&a.best[ra], key);
     atomicMin(&a.best[rb], key);
 }
@@ -157,13 +124,13 @@ __global__ __launch_bounds__(WG) void topo_best_kernel(TopoArgs a, const uint32_
 // cur -> nxt for every face (the others are copied)
 __global__ __launch_bounds__(WG) void topo_hook_kernel(TopoArgs a, const uint32_t* __restrict__ cur, uint32_t* __restrict__ nxt) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     bool hooked = false;
     if (v < a.F) {
         uint32_t word = cur[v];
         const unsigned long long key = a.best[v];
-        if ((word >> 1) == (uint32_t)v && key != EMPTY64) {
-            const int64_t s = edge_slot(a.etab, a.cap, key);
+        if ((word >> 1) == (uint32_t)v && key != kTabEmpty64) {
+            const int64_t s = dudf_edge_slot(a.etab, a.cap, key);
             if (s >= 0) {
                 const uint32_t ea = a.emin[s], eb = a.emax[s];
                 if (ea < 3 * a.F && eb < 3 * a.F) {
@@ -182,7 +149,7 @@ __global__ __launch_bounds__(WG) void topo_hook_kernel(TopoArgs a, const uint32_
     }
     unsigned total;
     dudf_wg_rank(hooked, wt, &total);
-    add_total(a.ctr + CTR_FOREST, total);
+    dudf_wg_add_total(a.ctr + CTR_FOREST, total);
 }
 
 // one pointer-doubling step cur -> nxt of (parent, parity); flags[step] says whether anything moved, and a step whose predecessor
@@ -190,7 +157,7 @@ __global__ __launch_bounds__(WG) void topo_hook_kernel(TopoArgs a, const uint32_
 __global__ __launch_bounds__(WG) void topo_jump_kernel(int64_t F, const uint32_t* __restrict__ cur, uint32_t* __restrict__ nxt,
                                                        unsigned* __restrict__ flags, int step) {
     if (step > 0 && flags[step - 1] == 0u) return;
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     bool moved = false;
     if (v < F) {
         const uint32_t w = cur[v], p = w >> 1;
@@ -206,7 +173,7 @@ __global__ __launch_bounds__(WG) void topo_jump_kernel(int64_t F, const uint32_t
 }
 
 __global__ __launch_bounds__(WG) void topo_label_kernel(TopoArgs a, const uint32_t* __restrict__ pp) {
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     if (v >= a.F) return;
     const uint32_t r = pp[v] >> 1;
     if (r < a.F) atomicMin(&a.label[r], (uint32_t)v);
@@ -227,7 +194,7 @@ __global__ __launch_bounds__(WG) void topo_write_kernel(TopoArgs a, const uint32
                                                         int64_t* __restrict__ out_component, uint8_t* __restrict__ out_flip,
                                                         unsigned long long* __restrict__ out_nfaces, unsigned long long* __restrict__ out_area) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     bool flipped = false, is_label = false;
     if (f < a.F) {
         const uint32_t w = pp[f], r = w >> 1;
@@ -245,14 +212,14 @@ __global__ __launch_bounds__(WG) void topo_write_kernel(TopoArgs a, const uint32
         flipped = flip != 0u; is_label = lab == (uint32_t)f;
     }
     unsigned total;
-    dudf_wg_rank(flipped, wt, &total);  add_total(a.ctr + CTR_FLIPPED, total);
-    dudf_wg_rank(is_label, wt, &total); add_total(a.ctr + CTR_COMPONENTS, total);
+    dudf_wg_rank(flipped, wt, &total);  dudf_wg_add_total(a.ctr + CTR_FLIPPED, total);
+    dudf_wg_rank(is_label, wt, &total); dudf_wg_add_total(a.ctr + CTR_COMPONENTS, total);
 }
 
 // one thread per face-slot: the manifold edges both faces still traverse the same way
 __global__ __launch_bounds__(WG) void topo_inconsistent_kernel(TopoArgs a, const uint8_t* __restrict__ flip) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t e = item();
+    const int64_t e = dudf_wg_item();
     bool bad = false;
     if (e < 3 * a.F) {
         const uint32_t l = a.link[e];
@@ -263,27 +230,24 @@ __global__ __launch_bounds__(WG) void topo_inconsistent_kernel(TopoArgs a, const
     }
     unsigned total;
     dudf_wg_rank(bad, wt, &total);
-    add_total(a.ctr + CTR_INCONSISTENT, total);
+    dudf_wg_add_total(a.ctr + CTR_INCONSISTENT, total);
 }
 
 __global__ void topo_finish_kernel(const unsigned long long* __restrict__ ctr, int64_t* __restrict__ out_counts) {
     if (threadIdx.x < N_CTR && blockIdx.x == 0) out_counts[threadIdx.x] = (int64_t)ctr[threadIdx.x];
 }
 
-int64_t pow2_at_least(int64_t n) { int64_t c = 2; while (c < n) c <<= 1; return c; }
-int64_t blocks_of(int64_t n) { return (n + WG - 1) / WG; }
 int ceil_log2(int64_t n) { int b = 0; while (((int64_t)1 << b) < n) ++b; return b; }
 bool topo_sizes_ok(int64_t F) { return F >= 0 && 6 * F < (1ll << 32); }
 
-// zero-initialised arrays first, 0xff-initialised second, the rest behind: two memsets per call
-struct TopoSpans { size_t zero_end, ff_end, total; };
-TopoSpans carve_topo(void* ws, int64_t F, TopoArgs* a) {
+// zero-initialised arrays first, 0xff-initialised second, the rest behind (dudf_init_spans)
+DudfSpans carve_topo(void* ws, int64_t F, TopoArgs* a) {
     DudfByteCarver cv = dudf_carve(ws);
-    a->F = F; a->cap = pow2_at_least(6 * F);
+    a->F = F; a->cap = dudf_pow2_at_least(6 * F);
     a->ctr = cv.take<unsigned long long>(N_CTR); a->flags = cv.take<unsigned>(64);
     a->ecnt = cv.take<uint32_t>(a->cap); a->emax = cv.take<uint32_t>(a->cap);
-    TopoSpans sp;
-    sp.zero_end = cv.o;
+    DudfSpans sp;
+    sp.zero_end = sp.ff_begin = cv.o;
     a->etab = cv.take<unsigned long long>(a->cap); a->emin = cv.take<uint32_t>(a->cap); a->label = cv.take<uint32_t>(F);
     sp.ff_end = cv.o;
     a->pp[0] = cv.take<uint32_t>(F); a->pp[1] = cv.take<uint32_t>(F); a->best = cv.take<unsigned long long>(F);
@@ -307,11 +271,11 @@ struct SubArgs {
 
 __global__ __launch_bounds__(WG) void sub_mark_kernel(SubArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     bool k = false;
     if (f < a.F) {
         const int64_t i0 = a.face[3 * f], i1 = a.face[3 * f + 1], i2 = a.face[3 * f + 2];
-        k = a.keep[f] != 0 && i0 >= 0 && i0 < a.V && i1 >= 0 && i1 < a.V && i2 >= 0 && i2 < a.V;
+        k = a.keep[f] != 0 && dudf_face_in_range(i0, i1, i2, a.V);
         a.fkeep[f] = k ? 1 : 0;
         if (k) { a.vuse[i0] = 1; a.vuse[i1] = 1; a.vuse[i2] = 1; }
     }
@@ -322,7 +286,7 @@ __global__ __launch_bounds__(WG) void sub_mark_kernel(SubArgs a) {
 
 __global__ __launch_bounds__(WG) void sub_vertices_kernel(SubArgs a) {
     __shared__ unsigned wt[WG / 64];
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     unsigned total;
     dudf_wg_rank(v < a.V && a.vuse[v], wt, &total);
     if (threadIdx.x == 0) a.vblk[blockIdx.x] = total;
@@ -345,7 +309,7 @@ __device__ __forceinline__ bool sub_head_ok(const SubArgs& a) { return a.head[0]
 __global__ __launch_bounds__(WG) void sub_emit_vertices_kernel(SubArgs a) {
     __shared__ unsigned wt[WG / 64];
     if (!sub_head_ok(a)) return;                                         // uniform: the whole grid leaves
-    const int64_t v = item();
+    const int64_t v = dudf_wg_item();
     const bool use = v < a.V && a.vuse[v];
     unsigned total;
     const unsigned r = dudf_wg_rank(use, wt, &total);
@@ -359,7 +323,7 @@ __global__ __launch_bounds__(WG) void sub_emit_vertices_kernel(SubArgs a) {
 __global__ __launch_bounds__(WG) void sub_emit_faces_kernel(SubArgs a) {
     __shared__ unsigned wt[WG / 64];
     if (!sub_head_ok(a)) return;
-    const int64_t f = item();
+    const int64_t f = dudf_wg_item();
     const bool k = f < a.F && a.fkeep[f];
     unsigned total;
     const unsigned r = dudf_wg_rank(k, wt, &total);
@@ -371,13 +335,12 @@ __global__ __launch_bounds__(WG) void sub_emit_faces_kernel(SubArgs a) {
 
 bool sub_sizes_ok(int64_t V, int64_t F) { return V >= 0 && F >= 0 && V < (1ll << 31) && F < (1ll << 31); }
 
-struct SubSpans { size_t zero_end, total; };
-SubSpans carve_sub(void* ws, int64_t V, int64_t F, SubArgs* a) {
+DudfSpans carve_sub(void* ws, int64_t V, int64_t F, SubArgs* a) {
     DudfByteCarver cv = dudf_carve(ws);
-    a->V = V; a->F = F; a->nbV = blocks_of(V); a->nbF = blocks_of(F);
+    a->V = V; a->F = F; a->nbV = dudf_wg_count(V); a->nbF = dudf_wg_count(F);
     a->head = cv.take<int64_t>(3); a->tot = cv.take<int64_t>(2); a->vuse = cv.take<uint8_t>(V);
-    SubSpans sp;
-    sp.zero_end = cv.o;
+    DudfSpans sp;
+    sp.zero_end = sp.ff_begin = sp.ff_end = cv.o;                       // no table here
     a->vnew = cv.take<int32_t>(V); a->fkeep = cv.take<uint8_t>(F);
     a->vblk = cv.take<uint32_t>(a->nbV); a->voff = cv.take<int64_t>(a->nbV);
     a->fblk = cv.take<uint32_t>(a->nbF); a->foff = cv.take<int64_t>(a->nbF);
@@ -385,7 +348,7 @@ SubSpans carve_sub(void* ws, int64_t V, int64_t F, SubArgs* a) {
     return sp;
 }
 
-int fill_sub(int64_t V, const int64_t* faces, int64_t F, const uint8_t* keep, void* ws, size_t bytes, SubArgs* a, SubSpans* sp) {
+int fill_sub(int64_t V, const int64_t* faces, int64_t F, const uint8_t* keep, void* ws, size_t bytes, SubArgs* a, DudfSpans* sp) {
     if (V < 0 || F < 0) return DUDF_E_BADCFG;
     if (!sub_sizes_ok(V, F)) return DUDF_E_UNSUPPORTED;
     if (F > 0 && (!faces || !keep)) return DUDF_E_BADCFG;
@@ -414,18 +377,16 @@ int dudf_mesh_topology(const int64_t* faces, int64_t F, int64_t V, const double*
     if (F > 0 && (!faces || !out_faces || !out_component || !out_flip || !out_component_faces || !out_component_area_q)) return DUDF_E_BADCFG;
     if (F > 0 && out_faces == faces) return DUDF_E_BADCFG;           // every round re-reads the directions from the input
     TopoArgs a;
-    const TopoSpans sp = carve_topo(workspace, F, &a);
+    const DudfSpans sp = carve_topo(workspace, F, &a);
     if (int rc = dudf_check_buffer(workspace, workspace_bytes, sp.total)) return rc;
     a.face = faces; a.vert = vertices; a.V = V;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     if (F == 0) return (int)hipMemsetAsync(out_counts, 0, N_CTR * sizeof(int64_t), st);
-    char* base = static_cast<char*>(workspace);
-    DUDF_TRY(hipMemsetAsync(base, 0, sp.zero_end, st));
-    DUDF_TRY(hipMemsetAsync(base + sp.zero_end, 0xff, sp.ff_end - sp.zero_end, st));
+    DUDF_TRY(dudf_init_spans(workspace, sp, st));
     DUDF_TRY(hipMemsetAsync(out_component_faces, 0, (size_t)F * sizeof(int64_t), st));
     DUDF_TRY(hipMemsetAsync(out_component_area_q, 0, (size_t)F * sizeof(uint64_t), st));
-    const dim3 gf((unsigned)blocks_of(F)), gs((unsigned)blocks_of(3 * F)), wg(WG);
+    const dim3 gf((unsigned)dudf_wg_count(F)), gs((unsigned)dudf_wg_count(3 * F)), wg(WG);
     DUDF_TRY(dudf_launch(topo_insert_kernel, gf, wg, st, a));
     DUDF_TRY(dudf_launch(topo_resolve_kernel, gs, wg, st, a));
     // Borůvka: the components at least halve per round that hooks anything, and a round that hooks nothing is the last
@@ -464,14 +425,14 @@ size_t dudf_mesh_submesh_workspace_bytes(int64_t V, int64_t F) {
 
 int dudf_mesh_submesh_count(int64_t V, const int64_t* faces, int64_t F, const unsigned char* keep, int64_t* out_counts, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    SubArgs a; SubSpans sp;
+    SubArgs a; DudfSpans sp;
     int rc = fill_sub(V, faces, F, keep, workspace, workspace_bytes, &a, &sp);
     if (rc) return rc;
     if (!out_counts) return DUDF_E_BADCFG;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);
     if (V == 0 || F == 0) return dudf_launch(sub_empty_kernel, dim3(1), dim3(1), st, out_counts, a.head);
-    DUDF_TRY(hipMemsetAsync(workspace, 0, sp.zero_end, st));
+    DUDF_TRY(dudf_init_spans(workspace, sp, st));
     const dim3 gv((unsigned)a.nbV), gf((unsigned)a.nbF), wg(WG);
     DUDF_TRY(dudf_launch(sub_mark_kernel, gf, wg, st, a));
     DUDF_TRY(dudf_launch(sub_vertices_kernel, gv, wg, st, a));
@@ -482,7 +443,7 @@ int dudf_mesh_submesh_count(int64_t V, const int64_t* faces, int64_t F, const un
 
 int dudf_mesh_submesh_emit(const double* vertices, int64_t V, const int64_t* faces, int64_t F, const unsigned char* keep,
                            double* out_vertices, int64_t* out_faces, void* workspace, size_t workspace_bytes, void* stream) {
-    SubArgs a; SubSpans sp;
+    SubArgs a; DudfSpans sp;
     int rc = fill_sub(V, faces, F, keep, workspace, workspace_bytes, &a, &sp);
     if (rc) return rc;
     if ((V > 0 && !vertices) || !out_vertices || !out_faces) return DUDF_E_BADCFG;

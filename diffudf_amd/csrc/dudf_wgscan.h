@@ -1,6 +1,7 @@
 // Index and compaction toolkit of the extraction units (point cloud and render gather, CAP-UDF cells, Lewiner marching cubes): device
 // code only.  Internal: not installed, nothing here is part of the C ABI.
 //   dudf_wg_rank, dudf_wg_scan: ballot rank and exclusive scan over a workgroup of DUDF_WG = 256 threads (four waves);
+//   dudf_wg_item, dudf_wg_add_total: the thread's item, and a workgroup total added to a 64-bit counter;
 //   dudf_scan_totals_kernel<K>: exclusive scan of per-workgroup totals, one 1024-thread workgroup
 //   dudf_wg_scan64, dudf_scan_totals64_kernel: the same two over 64-bit unsigned integers (the surface sampler's cumulative weights)
 #pragma once
@@ -22,6 +23,13 @@ __device__ __forceinline__ unsigned dudf_wg_rank(bool flag, unsigned* wave_tot, 
     __syncthreads();
     *total = sum;
     return before;
+}
+
+// The item of this thread in a grid of DUDF_WG-thread workgroups, one thread per item.
+__device__ __forceinline__ int64_t dudf_wg_item() { return (int64_t)blockIdx.x * DUDF_WG + threadIdx.x; }
+// Thread 0 adds the workgroup's total (the *total of a rank or a scan) to a 64-bit counter: one atomic per workgroup that counted anything.
+__device__ __forceinline__ void dudf_wg_add_total(unsigned long long* ctr, unsigned total) {
+    if (threadIdx.x == 0 && total) atomicAdd(ctr, (unsigned long long)total);
 }
 
 // Exclusive scan of a small count over the workgroup's threads (thread order); *total = the sum.  wave_tot as above; the leading

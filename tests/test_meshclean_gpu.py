@@ -13,6 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import meshclean_oracle as O  # noqa: E402
+import meshtab_cases as M  # noqa: E402
 from test_meshclean_cpu import fixture_meshes  # noqa: E402
 from test_meshudf import G10, LUTS  # noqa: E402
 
@@ -95,6 +96,17 @@ def test_workgroup_boundaries(V):
         for k in seen:
             seen[k] += wc[k]
     assert V == 1 or all(n > 0 for n in seen.values()), seen
+
+
+def test_probe_chain_wraps_round_the_table():
+    """`meshtab_cases.wrap_mesh`: three edges whose home is the last of the 32 slots of the edge table, two triples whose home is the
+    last of the 8 of the face table.  Four lone triangles: each is a 3-hole of its own."""
+    v, f = M.wrap_mesh()
+    wc = check_round(v, f, "wrap")[2]
+    assert (wc["vertices"], wc["faces"], wc["holes3"], wc["unreferenced"]) == (12, 8, 4, 28)
+    assert check_round(v, f, "wrap, no fill", fill=False)[2]["faces"] == 4
+    ge = hip_ops.mesh_border_edges(dev(f), len(v)).cpu().numpy()
+    assert len(ge) == 12 and np.array_equal(ge, O.border_edges(f, len(v)))
 
 
 def test_empty_and_all_degenerate(monkeypatch):

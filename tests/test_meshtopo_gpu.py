@@ -13,6 +13,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import meshtab_cases as M  # noqa: E402
 import meshtopo_oracle as T  # noqa: E402
 from test_capudf import analytic_fields  # noqa: E402
 from test_meshtopo_cpu import same_direction_edges  # noqa: E402
@@ -110,6 +111,27 @@ def test_grid_plane_lattice_keys():
     v, f = T.grid_plane(64, 64)
     r = check(v, T.scramble(f, 31), "grid 64 x 64")
     assert len(f) == 8192 and r["components"] == 1 and r["inconsistent_edges"] == 0 and r["border_edges"] == 256
+
+
+def test_probe_chain_wraps_round_the_table():
+    """`meshtab_cases.wrap_mesh`: three edges whose home is the last of the 32 slots."""
+    v, f = M.wrap_mesh()
+    r = check(v, f, "wrap")
+    assert (r["components"], r["border_edges"], r["ignored_faces"]) == (4, 12, 0)
+
+
+def test_the_three_edge_tables_agree():
+    """The clean-up's, the topology's and the simplification's edge table on one mesh of valid faces without repeated indices: the
+    edges with one use, counted in numpy; the topology's edges with three or more.  Without and with a third face on one edge."""
+    for extra_face in (False, True):
+        v, f = M.holed_grid(extra_face)
+        uses = M.edge_use_counts(f)
+        border, fins = int((uses == 1).sum()), int((uses >= 3).sum())
+        assert border > 64 and fins == int(extra_face)
+        assert len(hip_ops.mesh_border_edges(dev(f), len(v))) == border
+        cnt = hip_ops.mesh_topology(dev(f), len(v), dev(v))[5]
+        assert (cnt["border_edges"], cnt["nonmanifold_edges"]) == (border, fins), cnt
+        assert hip_ops.mesh_simplify_count(dev(v), dev(f), [0.0, 0.0, -0.5], 1.0 / 64)["border_edges"] == border
 
 
 @pytest.mark.parametrize("kind,n", [("sheet", 33), ("sphere", 33), ("sheet", 65)])

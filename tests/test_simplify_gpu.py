@@ -17,6 +17,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import meshtab_cases as M  # noqa: E402
 import meshtopo_oracle as T  # noqa: E402
 import simplify_oracle as S  # noqa: E402
 from test_capudf import analytic_fields  # noqa: E402
@@ -42,8 +43,11 @@ def run(name, w):
 def check(name, w):
     """The device result on an input against the oracle's.  Returns (oracle result, worst quadric, xhat and position figures)."""
     v, f, origin, h, _ = S.inputs()[name]
-    want = S.result(name, w)
-    ov, of, cnt, quad, xhat, keys, records, fell = run(name, w)
+    return check_mesh(name, w, v, f, origin, h, S.result(name, w))
+
+
+def check_mesh(name, w, v, f, origin, h, want):
+    ov, of, cnt, quad, xhat, keys, records, fell = hip_ops.mesh_simplify(dev(v), dev(f), origin, h, boundary_weight=w, want_quadrics=True)
     assert ov.dtype == torch.float64 and of.dtype == torch.int64 and ov.shape[1:] == (3,) and of.shape[1:] == (3,)
     quad, xhat, keys, records, fell = (t.cpu().numpy() for t in (quad, xhat, keys, records, fell))
     ov, of = ov.cpu().numpy(), of.cpu().numpy()
@@ -112,6 +116,15 @@ def test_scrambled_strips(n):
 def test_grid_plane(grid, w):
     want, _ = check(f"grid plane, grid {grid}", w)
     assert want["counts"]["faces"] == 2 * grid * grid and want["counts"]["border_edges"] == 256
+
+
+def test_probe_chain_wraps_round_the_table():
+    """`meshtab_cases.wrap_mesh`: three edges whose home is the last of the 32 slots.  Every vertex has its own cell: the identity up to
+    the order of the vertices, 12 border edges."""
+    v, f = M.wrap_mesh()
+    for w in (0.0, 1.0):
+        c = check_mesh("wrap", w, v, f, np.zeros(3), M.WRAP_H, S.simplify(v, f, np.zeros(3), M.WRAP_H, w))[0]["counts"]
+        assert (c["vertices"], c["faces"], c["cells"], c["border_edges"]) == (12, 4, 12, 12)
 
 
 def test_a_thousand_tetrahedra():
