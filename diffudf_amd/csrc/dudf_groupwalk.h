@@ -8,56 +8,22 @@
 // what it wrote itself, so no lane depends on another's store; the only cross-lane traffic is the shuffles, whose partners take
 // the same branch.  No barrier; every node is entered at most once, so the walk ends whatever the numbers are.
 //
-// Internal step and pruning are walk_nearest's: nearer child first; a subtree is skipped only when
-// lb * 0.99999 > (float)best * 1.00001 + 1e-37 in fp32, on meeting the node and again on popping it.  The result is the minimum of
-// exact fp64 values over a set that contains every minimiser — a number that does not depend on the order of visits — so it is
-// the brute-force scan's bit for bit.  Only the value is kept, not who attains it.
+// Internal step and pruning are walk_nearest's: nearer child first; a subtree is skipped only on the safe-side test of dudf_bvh.h
+// (box_lb > bound_of), on meeting the node and again on popping it.  The result is the minimum of exact fp64 values over a set that
+// contains every minimiser — a number that does not depend on the order of visits — so it is the brute-force scan's bit for bit.
+// Only the value is kept, not who attains it.
 //
-// The tree is the fixed-shape one of the mesh index (include/dudf_hip.h): L = the leaf count rounded up to a power of two, nodes in
-// heap order as two float4 (lo.xyz hi.x | hi.yz - -), empty boxes (lo = +inf, hi = -inf) past the last leaf.  Two indexes have it:
-// the mesh index dudf_mesh_index_build writes (leaves of 8 sorted triangles, 9 floats each) and the cloud index of
-// dudf_sample_indexed.hip (leaves of 8 sorted points as 16-byte rows).
+// The tree is the fixed-shape one of dudf_bvh.h, which two indexes have: the mesh index (leaves of 8 sorted triangles, 9 floats
+// each) and the cloud index (leaves of 8 sorted points as 16-byte rows).
 #ifndef DUDF_GROUPWALK_H
 #define DUDF_GROUPWALK_H
-#include "dudf_context.h"
+#include "dudf_bvh.h"
 #include "dudf_tridist.h"
 
-constexpr int kGwSplit = 8;                           // lanes per query = primitives per leaf
+constexpr int kGwSplit = kBvhLeaf;                    // lanes per query = primitives per leaf
 constexpr int kGwBlock = 256;                         // threads per workgroup
 constexpr int kGwGroups = kGwBlock / kGwSplit;        // queries per workgroup
-constexpr int kGwHdrBytes = 256;                      // header of either index: 3 + 3 encoded bounds, flags
 static_assert(64 % kGwSplit == 0, "a group lies inside one wave");
-
-// L leaf slots (a power of two) and the stack entries a walk can need for n primitives
-inline void gw_shape(int64_t n, int& L, int& depth) {
-    const int64_t leaves = (n + kGwSplit - 1) / kGwSplit;
-    int lg = 0;
-    while (((int64_t)1 << lg) < leaves) ++lg;
-    L = 1 << lg; depth = lg + 1;
-}
-
-// the published layout of the mesh index: header, ids [T], sorted triangles [T][9], nodes [2L - 1][2], each on a 256-byte granule
-struct GwMeshLayout { unsigned* hdr; int* ids; float* stri; float4* nodes; int L, depth; size_t total; };
-inline GwMeshLayout gw_carve_mesh(const void* index, int64_t T) {
-    GwMeshLayout y;
-    gw_shape(T, y.L, y.depth);
-    DudfByteCarver cv = dudf_carve(index);
-    y.hdr = cv.take<unsigned>(kGwHdrBytes / sizeof(unsigned));
-    y.ids = cv.take<int>(T); y.stri = cv.take<float>(T * 9); y.nodes = cv.take<float4>((2 * (int64_t)y.L - 1) * 2);
-    y.total = cv.o;
-    return y;
-}
-// ... and of the cloud index: header, sorted points [n] as (x, y, z, 0), nodes [2L - 1][2]
-struct GwCloudLayout { unsigned* hdr; float4* rows; float4* nodes; int L, depth; size_t total; };
-inline GwCloudLayout gw_carve_cloud(const void* index, int64_t n) {
-    GwCloudLayout y;
-    gw_shape(n, y.L, y.depth);
-    DudfByteCarver cv = dudf_carve(index);
-    y.hdr = cv.take<unsigned>(kGwHdrBytes / sizeof(unsigned));
-    y.rows = cv.take<float4>(n); y.nodes = cv.take<float4>((2 * (int64_t)y.L - 1) * 2);
-    y.total = cv.o;
-    return y;
-}
 
 struct GwTree {                       // what a walk reads
     const float4* nodes; const void* prims;
@@ -80,16 +46,6 @@ struct GwPointLeaf {                  // sorted points [n] float4: the expressio
     }
 };
 
-// safe-side fp32 lower bound of the squared distance from p to a box (0 inside; +inf for an empty box)
-__device__ __forceinline__ float gw_box_lb(const float4& b0, const float4& b1, float px, float py, float pz) {
-    const float dx = fmaxf(fmaxf(b0.x - px, px - b0.w), 0.f);
-    const float dy = fmaxf(fmaxf(b0.y - py, py - b1.x), 0.f);
-    const float dz = fmaxf(fmaxf(b0.z - pz, pz - b1.y), 0.f);
-    return (dx * dx + dy * dy + dz * dz) * 0.99999f;
-}
-// fp32 upper bound of the best exact squared distance
-__device__ __forceinline__ float gw_bound_of(double best) { return (float)best * 1.00001f + 1e-37f; }
-
 // The minimum over all primitives of Leaf::eval for the query (fx, fy, fz) the kGwSplit lanes of a group share; `part` = this
 // lane's place in its group; snode / slb: the group's column of the [entry][group] stacks (entry e at [e * kGwGroups]).  Called by
 // all lanes of a group or by none.  evals += this lane's exact evaluations.  `best`: the value the caller's scan starts from — the
@@ -99,7 +55,7 @@ template <class Leaf>
 __device__ __forceinline__ double gw_walk_nearest(const GwTree& t, int* snode, float* slb, float fx, float fy, float fz, int part,
                                                   double best, unsigned long long& evals) {
     const double px = fx, py = fy, pz = fz;
-    float bestf = gw_bound_of(best);
+    float bestf = bound_of(best);
     const int first_leaf = t.L - 1;
     int node = 0, sp = 0;
     for (;;) {
@@ -111,11 +67,11 @@ __device__ __forceinline__ double gw_walk_nearest(const GwTree& t, int* snode, f
 #pragma unroll
             for (int m = 1; m < kGwSplit; m <<= 1) d2 = fmin(d2, __shfl_xor(d2, m));
             if (d2 < best) best = d2;
-            bestf = gw_bound_of(best);
+            bestf = bound_of(best);
         } else {
             const float4* c = t.nodes + 2 * (2 * (int64_t)node + 1);
             const float4 l0 = c[0], l1 = c[1], r0 = c[2], r1 = c[3];
-            float ln = gw_box_lb(l0, l1, fx, fy, fz), lf = gw_box_lb(r0, r1, fx, fy, fz);
+            float ln = box_lb(l0, l1, fx, fy, fz), lf = box_lb(r0, r1, fx, fy, fz);
             int nn = 2 * node + 1, nf = nn + 1;
             if (lf < ln) { const float s = ln; ln = lf; lf = s; nn = nf; nf = nn - 1; }
             if (!(ln > bestf)) {                  // the nearer child may hold the answer; the farther one waits on the stack

@@ -3,20 +3,11 @@
 // occupancy by ray parity and the sphere-tracing march against the mesh.
 // Kernels and their C entry points (include/dudf_hip.h).
 //
-// Index: a bounding-volume hierarchy without pointers.
-//   - Morton code (3 x 21 bits) of every triangle's centroid inside the mesh's bounding box; the caller sorts the codes (stable)
-//     and hands the order back;
-//   - the sorted triangles are copied once (a leaf's triangles are then 288 contiguous bytes) next to their original indices;
-//   - leaf j holds sorted triangles [8 j, 8 j + 8); the leaves are the last level of a complete binary tree in heap order
-//     (node i has children 2 i + 1 and 2 i + 2) over L = the next power of two of the leaf count; slots past the last leaf
-//     carry an empty box (lo = +inf, hi = -inf) that no query ever finds near;
-//   - a node is its fp32 AABB, two float4 (lo.xyz hi.x | hi.yz - -): min / max of fp32 vertices, exact.  One kernel per level.
-// Everything is a function of (triangles, order): two builds give the same bytes.
+// The index — a bounding-volume hierarchy without pointers, leaves of 8 sorted triangles — is dudf_bvh.h's; dudf_bvh.hip builds it.
 //
 // Query: one lane per point, depth-first with a per-lane stack in LDS ([entry][lane]: conflict-free), nearer child first.
-//   A subtree is skipped only when  lb * 0.99999 > best * 1.00001 + tiny  in fp32, lb the squared distance to its box: the fp32
-//   box distance is within a few 2^-24 of the true one and the factors cover that many times over, so a skipped box holds no
-//   triangle at or below the best exact value so far — equal distances are still evaluated and the smallest original index wins.
+//   A subtree is skipped only on the safe-side test of dudf_bvh.h (box_lb > bound_of), so a skipped box holds no triangle at or
+//   below the best exact value so far — equal distances are still evaluated and the smallest original index wins.
 //   Every triangle evaluation is the fp64 Voronoi-region arithmetic of dudf_tridist.h, called through ONE non-inlined function by
 //   the indexed and the brute-force kernel alike: the same machine code, hence the same bits.  The answer is the minimum of those
 //   values over a set that contains every minimiser, so the index changes what is skipped, never what is returned.
@@ -26,145 +17,13 @@
 // inside / outside by the parity of the triangles a +x ray crosses (`compute_occupancy`, behind `compute_signed_distance`): a
 // walk that visits the boxes the ray meets and one non-inlined crossing test whose edge functions are antisymmetric by
 // construction (eval_cross, edge_fn).
-#include "dudf_context.h"
+#include "dudf_bvh.h"
 #include "dudf_tridist.h"
 
 namespace {
 
-constexpr int kLeaf = 8;                         // triangles per leaf
 constexpr int kBlock = 256;                      // threads per workgroup of the query kernels
-constexpr int kHdrBytes = 256;                   // header: 3 + 3 encoded bounds, flags
-constexpr int kGridCap = 8192;                   // workgroups of the build launches; the kernels stride over the rest
-constexpr unsigned kFlagNonFinite = 1u, kFlagBadOrder = 2u;
 
-struct Layout {                                  // the sections of the index (null for a null index) and its size
-    int64_t n_leaves; int L, depth;              // L leaf slots (power of two), depth = stack entries a lane can need
-    unsigned* hdr; int* ids; float* stri; float4* nodes; size_t total;
-};
-// the published layout (include/dudf_hip.h): header, ids [T], sorted triangles [T][9], nodes [2L - 1][2], each on a 256-byte granule
-inline Layout carve_index(const void* index, int64_t T) {
-    Layout y;
-    y.n_leaves = (T + kLeaf - 1) / kLeaf;
-    int lg = 0;
-    while (((int64_t)1 << lg) < y.n_leaves) ++lg;
-    y.L = 1 << lg; y.depth = lg + 1;
-    DudfByteCarver cv = dudf_carve(index);
-    y.hdr = cv.take<unsigned>(kHdrBytes / sizeof(unsigned));
-    y.ids = cv.take<int>(T); y.stri = cv.take<float>(T * 9); y.nodes = cv.take<float4>((2 * (int64_t)y.L - 1) * 2);
-    y.total = cv.o;
-    return y;
-}
-
-// fp32 -> uint32 whose unsigned order is the float order (for atomicMin / atomicMax of bounds)
-__device__ __forceinline__ unsigned enc(float f) { const unsigned b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
-__device__ __forceinline__ float dec(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-
-// header words 0..2 = min, 3..5 = max of all vertices (encoded), 6 = flags
-__global__ __launch_bounds__(256) void mesh_bounds_kernel(const float* __restrict__ tri, int64_t T, unsigned* __restrict__ hdr) {
-    __shared__ float smin[3][256], smax[3][256];
-    __shared__ unsigned sflag;
-    if (threadIdx.x == 0) sflag = 0;
-    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    bool bad = false;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += (int64_t)gridDim.x * blockDim.x) {
-        const float* v = tri + t * 9;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const float f = v[k];
-            bad |= !(fabsf(f) <= 3.402823466e38f);                 // NaN or infinity
-            lo[k % 3] = fminf(lo[k % 3], f); hi[k % 3] = fmaxf(hi[k % 3], f);
-        }
-    }
-    __syncthreads();
-    if (bad) atomicOr(&sflag, kFlagNonFinite);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { smin[a][threadIdx.x] = lo[a]; smax[a][threadIdx.x] = hi[a]; }
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                smin[a][threadIdx.x] = fminf(smin[a][threadIdx.x], smin[a][threadIdx.x + s]);
-                smax[a][threadIdx.x] = fmaxf(smax[a][threadIdx.x], smax[a][threadIdx.x + s]);
-            }
-        __syncthreads();
-    }
-    if (threadIdx.x < 3) {
-        atomicMin(&hdr[threadIdx.x], enc(smin[threadIdx.x][0]));
-        atomicMax(&hdr[3 + threadIdx.x], enc(smax[threadIdx.x][0]));
-    }
-    if (threadIdx.x == 0 && sflag) atomicOr(&hdr[6], sflag);
-}
-
-__device__ __forceinline__ unsigned long long spread21(unsigned long long x) {         // bit i -> bit 3 i
-    x &= 0x1fffffull;
-    x = (x | (x << 32)) & 0x1f00000000ffffull;
-    x = (x | (x << 16)) & 0x1f0000ff0000ffull;
-    x = (x | (x << 8)) & 0x100f00f00f00f00full;
-    x = (x | (x << 4)) & 0x10c30c30c30c30c3ull;
-    x = (x | (x << 2)) & 0x1249249249249249ull;
-    return x;
-}
-
-__global__ __launch_bounds__(256) void mesh_codes_kernel(const float* __restrict__ tri, int64_t T, const unsigned* __restrict__ hdr,
-                                                         int64_t* __restrict__ codes) {
-    double lo[3], ext[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { lo[a] = dec(hdr[a]); ext[a] = (double)dec(hdr[3 + a]) - lo[a]; }
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += (int64_t)gridDim.x * blockDim.x) {
-        const float* v = tri + t * 9;
-        unsigned long long code = 0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double c = ((double)v[a] + (double)v[3 + a] + (double)v[6 + a]) * (1.0 / 3.0);
-            double q = ext[a] > 0.0 ? (c - lo[a]) / ext[a] * 2097152.0 : 0.0;
-            if (!(q >= 0.0)) q = 0.0;                                 // also NaN (the build is refused anyway: header flag)
-            if (q > 2097151.0) q = 2097151.0;
-            code |= spread21((unsigned long long)q) << (2 - a);       // x in the most significant position
-        }
-        codes[t] = (int64_t)code;
-    }
-}
-
-__global__ __launch_bounds__(256) void mesh_gather_kernel(const float* __restrict__ tri, int64_t T, const int64_t* __restrict__ order,
-                                                          int* __restrict__ ids, float* __restrict__ stri, unsigned* __restrict__ hdr) {
-    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < T; s += (int64_t)gridDim.x * blockDim.x) {
-        int64_t id = order[s];
-        if (id < 0 || id >= T) { atomicOr(&hdr[6], kFlagBadOrder); id = 0; }      // not dereferenced; the build is refused
-        ids[s] = (int)id;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) stri[s * 9 + k] = tri[id * 9 + k];
-    }
-}
-
-__device__ __forceinline__ void store_box(float4* __restrict__ nodes, int64_t node, const float* lo, const float* hi) {
-    nodes[2 * node] = make_float4(lo[0], lo[1], lo[2], hi[0]);
-    nodes[2 * node + 1] = make_float4(hi[1], hi[2], 0.f, 0.f);
-}
-
-// leaf slot j -> node L - 1 + j: the box of sorted triangles [8 j, 8 j + 8), empty past the last triangle
-__global__ __launch_bounds__(256) void mesh_leaves_kernel(const float* __restrict__ stri, int64_t T, int L, float4* __restrict__ nodes) {
-    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < L; j += (int64_t)gridDim.x * blockDim.x) {
-        float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-        for (int64_t s = j * kLeaf; s < T && s < (j + 1) * kLeaf; ++s)
-#pragma unroll
-            for (int k = 0; k < 9; ++k) { const float f = stri[s * 9 + k]; lo[k % 3] = fminf(lo[k % 3], f); hi[k % 3] = fmaxf(hi[k % 3], f); }
-        store_box(nodes, (int64_t)L - 1 + j, lo, hi);
-    }
-}
-
-// nodes [first, first + count) of one level from their children on the level below
-__global__ __launch_bounds__(256) void mesh_level_kernel(float4* __restrict__ nodes, int first, int count) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
-        const int64_t n = (int64_t)first + i;
-        const float4 a0 = nodes[2 * (2 * n + 1)], a1 = nodes[2 * (2 * n + 1) + 1], b0 = nodes[2 * (2 * n + 2)], b1 = nodes[2 * (2 * n + 2) + 1];
-        const float lo[3] = {fminf(a0.x, b0.x), fminf(a0.y, b0.y), fminf(a0.z, b0.z)};
-        const float hi[3] = {fmaxf(a0.w, b0.w), fmaxf(a1.x, b1.x), fmaxf(a1.y, b1.y)};
-        store_box(nodes, n, lo, hi);
-    }
-}
-
-// ---- queries ---------------------------------------------------------------------------------------------------------------------
 // The one copy of the exact evaluation every distance kernel calls (see the head of the file).
 __device__ __noinline__ double eval_tri(double px, double py, double pz, const float* t) { return tri_dist2(px, py, pz, t); }
 
@@ -179,16 +38,6 @@ struct QueryArgs {
     const float* pts; int64_t Q;
     float* dist; int64_t* idx; float* closest; unsigned long long* stats;
 };
-
-// safe-side fp32 lower bound of the squared distance from p to a box (0 inside; +inf for an empty box)
-__device__ __forceinline__ float box_lb(const float4& b0, const float4& b1, float px, float py, float pz) {
-    const float dx = fmaxf(fmaxf(b0.x - px, px - b0.w), 0.f);
-    const float dy = fmaxf(fmaxf(b0.y - py, py - b1.x), 0.f);
-    const float dz = fmaxf(fmaxf(b0.z - pz, pz - b1.y), 0.f);
-    return (dx * dx + dy * dy + dz * dz) * 0.99999f;
-}
-// fp32 upper bound of the best exact squared distance
-__device__ __forceinline__ float bound_of(double best) { return (float)best * 1.00001f + 1e-37f; }
 
 #define DUDF_TAKE(d2, id) if ((d2) < best || ((d2) == best && (id) < best_id)) { best = (d2); best_id = (id); }
 
@@ -213,8 +62,8 @@ __device__ __forceinline__ void walk_nearest(const MeshView& m, int* snode, floa
     for (;;) {                                    // every node is entered at most once: the walk ends whatever the numbers are
         bool pop = true;
         if (node >= first_leaf) {
-            const int64_t s0 = (int64_t)(node - first_leaf) * kLeaf;
-            const int64_t s1 = (m.T - s0 < kLeaf) ? m.T : s0 + kLeaf;
+            const int64_t s0 = (int64_t)(node - first_leaf) * kBvhLeaf;
+            const int64_t s1 = (m.T - s0 < kBvhLeaf) ? m.T : s0 + kBvhLeaf;
             for (int64_t s = s0; s < s1; ++s) {
                 const double d2 = eval_tri(px, py, pz, m.stri + s * 9);
                 const int id = m.ids[s];
@@ -438,8 +287,8 @@ __global__ __launch_bounds__(kBlock) void mesh_occupancy_kernel(OccArgs a) {
         while (go) {                                              // every node is entered at most once
             bool pop = true;
             if (node >= first_leaf) {
-                const int64_t s0 = (int64_t)(node - first_leaf) * kLeaf;
-                const int64_t s1 = (a.m.T - s0 < kLeaf) ? a.m.T : s0 + kLeaf;
+                const int64_t s0 = (int64_t)(node - first_leaf) * kBvhLeaf;
+                const int64_t s1 = (a.m.T - s0 < kBvhLeaf) ? a.m.T : s0 + kBvhLeaf;
                 for (int64_t s = s0; s < s1; ++s) count += eval_cross(fx, fy, fz, a.m.stri + s * 9);
             } else {
                 const float4* c = a.m.nodes + 2 * (2 * (int64_t)node + 1);
@@ -463,53 +312,15 @@ __global__ __launch_bounds__(kBlock) void mesh_occupancy_kernel(OccArgs a) {
 
 extern "C" {
 
-size_t dudf_mesh_index_bytes(int64_t n_tri) {
-    if (n_tri <= 0 || n_tri >= ((int64_t)1 << 31)) return 0;
-    return carve_index(nullptr, n_tri).total;
-}
-
-// header: bounds of all vertices and the non-finite flag; clears the other flags
-static int launch_bounds(const float* tri, int64_t T, unsigned* hdr, hipStream_t st) {
-    DUDF_TRY(hipMemsetAsync(hdr, 0, kHdrBytes, st));                          // max words 0 (below every encoded float), flags 0
-    DUDF_TRY(hipMemsetAsync(hdr, 0xff, 3 * sizeof(unsigned), st));            // min words above every encoded float
-    return dudf_launch(mesh_bounds_kernel, dim3(dudf_grid_for(T, 256, 256)), dim3(256), st, tri, T, hdr);
-}
-
-static int check_index(const void* index, size_t index_bytes, int64_t T) { return dudf_check_buffer(index, index_bytes, carve_index(nullptr, T).total); }
-
-int dudf_mesh_morton_codes(const float* tri, int64_t n_tri, void* index, size_t index_bytes, int64_t* codes, void* stream) {
-    if (n_tri <= 0 || !tri || !codes) return DUDF_E_BADCFG;
-    if (n_tri >= ((int64_t)1 << 31)) return DUDF_E_UNSUPPORTED;
-    if (int rc = check_index(index, index_bytes, n_tri)) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    DudfProfScope prof(PROF_OTHER, st);
-    unsigned* hdr = carve_index(index, n_tri).hdr;
-    DUDF_TRY(launch_bounds(tri, n_tri, hdr, st));
-    return dudf_launch(mesh_codes_kernel, dim3(dudf_grid_for(n_tri, 256, kGridCap)), dim3(256), st, tri, n_tri, hdr, codes);
-}
-
-int dudf_mesh_index_build(const float* tri, int64_t n_tri, const int64_t* order, void* index, size_t index_bytes, void* stream) {
-    if (n_tri <= 0 || !tri || !order) return DUDF_E_BADCFG;
-    if (n_tri >= ((int64_t)1 << 31)) return DUDF_E_UNSUPPORTED;
-    if (int rc = check_index(index, index_bytes, n_tri)) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    DudfProfScope prof(PROF_OTHER, st);
-    const Layout y = carve_index(index, n_tri);
-    DUDF_TRY(launch_bounds(tri, n_tri, y.hdr, st));                           // the build stands alone: any permutation is a valid order
-    DUDF_TRY(dudf_launch(mesh_gather_kernel, dim3(dudf_grid_for(n_tri, 256, kGridCap)), dim3(256), st, tri, n_tri, order, y.ids, y.stri,
-                         y.hdr));
-    DUDF_TRY(dudf_launch(mesh_leaves_kernel, dim3(dudf_grid_for(y.L, 256, kGridCap)), dim3(256), st, y.stri, n_tri, y.L, y.nodes));
-    for (int count = y.L / 2; count >= 1; count /= 2)                         // level of `count` nodes starts at node count - 1
-        DUDF_TRY(dudf_launch(mesh_level_kernel, dim3(dudf_grid_for(count, 256, kGridCap)), dim3(256), st, y.nodes, count - 1, count));
-    return 0;
-}
+// a query accepts any buffer that holds the index: there, aligned, at least the published size
+static int check_index(const void* index, size_t index_bytes, int64_t T) { return dudf_check_buffer(index, index_bytes, gw_carve_mesh(nullptr, T).total); }
 
 // the soup alone (index == NULL: the kernels scan it) or with the sections of its index
 static MeshView view_of(const float* tri, int64_t n_tri, const void* index) {
     MeshView m;
     m.tri = tri; m.T = n_tri; m.ids = nullptr; m.stri = nullptr; m.nodes = nullptr; m.L = 0; m.depth = 0;
     if (index) {
-        const Layout y = carve_index(index, n_tri);
+        const GwMeshLayout y = gw_carve_mesh(index, n_tri);
         m.ids = y.ids; m.stri = y.stri; m.nodes = y.nodes; m.L = y.L; m.depth = y.depth;
     }
     return m;

@@ -169,13 +169,6 @@ struct GridParams {                              // the head of the workspace, w
     float lo[3], inv_h;
 };
 
-// order-preserving code of a float: unsigned order of the codes is numeric order
-__device__ __forceinline__ unsigned float_code(float f) {
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float code_float(unsigned c) { return __uint_as_float((c & 0x80000000u) ? (c & 0x7fffffffu) : ~c); }
-
 // the cell of a coordinate along one axis: monotone non-decreasing in p (each step is), NaN and anything out of range clamped
 __device__ __forceinline__ int axis_cell(float p, float lo, float inv_h, int G) {
     float t = (p - lo) * inv_h;

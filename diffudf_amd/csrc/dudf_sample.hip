@@ -17,33 +17,10 @@
 // Random numbers are counter-based — a pure function of (seed, step, stream, GLOBAL sample index), the same
 // splitmix64 construction as diffudf_amd/synth.py — so rank r of W produces exactly its slice of the global batch
 // and the numpy restatement in oracle/sampler_oracle.py reproduces every sample.
-#include "dudf_internal.h"
-
-#include "dudf_rng.h"              // dudf_splitmix64, dudf_uniform01
+#include "dudf_samplegen.h"        // the batch itself: keys, strata, sharding, checks, the store
 #include "dudf_tridist.h"          // tri_dist2
 
 namespace {
-
-__host__ __device__ __forceinline__ uint64_t stream_key(uint64_t seed, uint64_t stream) {
-    return dudf_splitmix64(seed * 0x100000001B3ull + stream);
-}
-
-struct SampleArgs {
-    const float *tri, *pc_pos, *pc_nrm;
-    float *x, *normals, *sdf;
-    int64_t n_tri, n_pc;
-    int64_t n_on, n_far, n_near;           // GLOBAL stratum sizes
-    int64_t on0, on1, far0, far1, near0, near1;   // this rank's [begin, end) inside each stratum
-    uint64_t k_on, k_fx, k_fy, k_fz, k_pick, k_n1, k_n2;
-    uint64_t seed; const int64_t* step_dev;         // step_dev != nullptr: the keys are derived in the kernel from (seed, *step_dev)
-};
-
-__host__ __device__ __forceinline__ void sample_keys(SampleArgs& a, uint64_t seed, uint64_t step) {
-    const uint64_t base = 1000ull * step;
-    a.k_on = stream_key(seed, base + 400); a.k_fx = stream_key(seed, base + 401); a.k_fy = stream_key(seed, base + 402);
-    a.k_fz = stream_key(seed, base + 403); a.k_pick = stream_key(seed, base + 404);
-    a.k_n1 = stream_key(seed, base + 405); a.k_n2 = stream_key(seed, base + 406);
-}
 
 constexpr int QSPLIT = 8;                 // lanes that share one query point (each scans every QSPLIT-th primitive)
 constexpr int SPH_CAP = 2304;             // bounding spheres held in LDS at a time (36 KiB); larger meshes go through in chunks
@@ -115,9 +92,7 @@ __device__ __forceinline__ unsigned screen_near2(const float4* __restrict__ g, f
 }
 
 __global__ __launch_bounds__(256) void sample_batch_kernel(SampleArgs a) {
-    // no a*b+c -> fma here: the oracle (numpy) rounds the product of normal and offset to fp32 before the add, and HIP's
-    // __fmul_rn / __fadd_rn are plain operators that hipcc's default -ffp-contract=fast would fuse (measured: 48 of 999
-    // near points off by one ulp)
+    // no a*b+c -> fma here either: the exact distances below are the oracle's arithmetic (see sample_point)
 #pragma clang fp contract(off)
     if (a.step_dev) sample_keys(a, a.seed, (uint64_t)*a.step_dev);     // graph replay: this launch's step lives in device memory
     __shared__ float4 ts[SPH_CAP];                      // spheres (centre, radius) of a chunk of triangles | two tiles of cloud points
@@ -131,31 +106,7 @@ __global__ __launch_bounds__(256) void sample_batch_kernel(SampleArgs a) {
     float px = 0.f, py = 0.f, pz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f, known = 0.f;
     bool query = false;
     const bool cloud_only = a.n_tri == 0;
-    if (live) {
-        if (i < n_on_l) {
-            const int64_t g = a.on0 + i;
-            const int64_t c = (int64_t)(dudf_uniform01(a.k_on, (uint64_t)g) * (double)a.n_pc);
-            px = a.pc_pos[c * 3]; py = a.pc_pos[c * 3 + 1]; pz = a.pc_pos[c * 3 + 2];
-            nx = a.pc_nrm[c * 3]; ny = a.pc_nrm[c * 3 + 1]; nz = a.pc_nrm[c * 3 + 2];
-        } else if (i < n_on_l + n_far_l) {
-            const uint64_t g = (uint64_t)(a.far0 + (i - n_on_l));
-            px = (float)(dudf_uniform01(a.k_fx, g) * 2.0 - 1.0);
-            py = (float)(dudf_uniform01(a.k_fy, g) * 2.0 - 1.0);
-            pz = (float)(dudf_uniform01(a.k_fz, g) * 2.0 - 1.0);
-            query = true;
-        } else {
-            const uint64_t g = (uint64_t)(a.near0 + (i - n_on_l - n_far_l));
-            const int64_t k = (int64_t)(dudf_uniform01(a.k_pick, g) * (double)a.n_on);       // which on-surface sample
-            const int64_t c = (int64_t)(dudf_uniform01(a.k_on, (uint64_t)k) * (double)a.n_pc);
-            const double u1 = dudf_uniform01(a.k_n1, g), u2 = dudf_uniform01(a.k_n2, g);
-            const float off = (float)(0.01 * sqrt(-2.0 * log1p(-u1)) * cos(6.283185307179586476925 * u2));
-            px = __fadd_rn(a.pc_pos[c * 3], __fmul_rn(a.pc_nrm[c * 3], off));
-            py = __fadd_rn(a.pc_pos[c * 3 + 1], __fmul_rn(a.pc_nrm[c * 3 + 1], off));
-            pz = __fadd_rn(a.pc_pos[c * 3 + 2], __fmul_rn(a.pc_nrm[c * 3 + 2], off));
-            query = !cloud_only;
-            known = fabsf(off);
-        }
-    }
+    if (live) query = sample_point(a, i, n_on_l, n_far_l, cloud_only, px, py, pz, nx, ny, nz, known);
     double best = 3.0e38;
     const double dpx = px, dpy = py, dpz = pz;
     const bool any_query = __syncthreads_or(query) != 0;          // a workgroup of on-surface points has nothing to measure
@@ -271,15 +222,7 @@ __global__ __launch_bounds__(256) void sample_batch_kernel(SampleArgs a) {
     // the QSPLIT lanes of a point are adjacent lanes of one wave (256 % QSPLIT == 0, 64 % QSPLIT == 0)
 #pragma unroll
     for (int m = 1; m < QSPLIT; m <<= 1) best = fmin(best, __shfl_xor(best, m));
-    if (live && part == 0) {
-        a.x[i * 3] = px; a.x[i * 3 + 1] = py; a.x[i * 3 + 2] = pz;
-        a.normals[i * 3] = nx; a.normals[i * 3 + 1] = ny; a.normals[i * 3 + 2] = nz;
-        // off-surface samples keep sdf > 0: a far point that lies exactly on a triangle, or a near point whose offset rounds to 0, would
-        // otherwise carry the "on surface" marker (sdf == 0) in the wrong stratum — the loss kernels' n_hess layout check turns that
-        // into NaN for the rest of the run.  FLT_MIN as a distance is 0 to every later computation.
-        const float sd = query ? (float)sqrt(best) : known;
-        a.sdf[i] = (i < n_on_l) ? sd : fmaxf(sd, 1.17549435e-38f);
-    }
+    if (live && part == 0) sample_store(a, i, n_on_l, px, py, pz, nx, ny, nz, query, best, known);
 }
 
 }  // namespace
@@ -288,18 +231,9 @@ static int sample_batch_impl(const float* tri, int64_t n_tri, const float* pc_po
                              int64_t n_pc, int64_t n_on, int64_t n_far, int64_t n_near, uint64_t seed,
                              uint64_t step, const int64_t* step_dev, int rank, int world, float* x, float* normals, float* sdf,
                              void* stream) {
-    if (n_tri < 0 || (n_tri > 0 && !tri) || n_pc <= 0 || world < 1 || rank < 0 || rank >= world || n_on < 0 || n_far < 0 || n_near < 0)
-        return DUDF_E_BADCFG;
-    if (n_near > 0 && n_on == 0) return DUDF_E_BADCFG;
     SampleArgs a;
-    a.tri = tri; a.pc_pos = pc_pos; a.pc_nrm = pc_nrm; a.x = x; a.normals = normals; a.sdf = sdf;
-    a.n_tri = n_tri; a.n_pc = n_pc; a.n_on = n_on; a.n_far = n_far; a.n_near = n_near;
-    auto lo = [&](int64_t m) { return m * rank / world; };
-    auto hi = [&](int64_t m) { return m * (rank + 1) / world; };
-    a.on0 = lo(n_on); a.on1 = hi(n_on); a.far0 = lo(n_far); a.far1 = hi(n_far); a.near0 = lo(n_near); a.near1 = hi(n_near);
-    a.seed = seed; a.step_dev = step_dev;
-    sample_keys(a, seed, step);
-    const int64_t n_l = (a.on1 - a.on0) + (a.far1 - a.far0) + (a.near1 - a.near0);
+    if (int rc = sample_args(a, tri, n_tri, pc_pos, pc_nrm, n_pc, n_on, n_far, n_near, seed, step, step_dev, rank, world, x, normals, sdf)) return rc;
+    const int64_t n_l = sample_count(a);
     if (n_l == 0) return 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     DudfProfScope prof(PROF_OTHER, st);

@@ -1295,8 +1295,37 @@ def cloud_outliers(knn_dist, std_ratio=2.0):
     return mean, keep, stats, kept, counts
 
 
-# ---- distance to a triangle mesh (reference generate_df.py:108-110, open3d RaycastingScene; csrc/dudf_meshdist.hip) -------------
+# ---- distance to a triangle mesh (reference generate_df.py:108-110, open3d RaycastingScene; csrc/dudf_bvh.hip, csrc/dudf_meshdist.hip) --
 MESH_INDEX_FLAGS_OFFSET, MESH_FLAG_NONFINITE, MESH_FLAG_BAD_ORDER = 24, 1, 2       # include/dudf_hip.h
+
+
+def _index_build(what, prefix, rows, width, order, nouns):
+    """The index of `rows` (n, width) float32 through the entry points `prefix`_index_bytes / _morton_codes / _index_build: Morton
+    codes on the device, a stable `torch.sort` (or the caller's `order`), then the boxes level by level; one host read at the end (the
+    flag word).  nouns = (the shape, one row, the rows, its size letter, the argument's name), for the messages."""
+    shape, row, plural, letter, arg = nouns
+    rows = _tensor(rows, f"{what}: {arg}", torch.float32, (width,), convert=True)
+    n, dev = rows.shape[0], rows.device
+    if n == 0:
+        raise _lib.DudfError(f"{what}: a {shape} without {plural} has no index (DUDF_E_BADCFG)")
+    nbytes = _bytes(f"{prefix}_index_bytes", n, err=-4)
+    index = torch.zeros(nbytes, dtype=torch.uint8, device=dev)     # zeros: the padding between the sections is part of "same bytes"
+    assert index.data_ptr() % 256 == 0
+    with torch.cuda.device(dev):
+        if order is None:
+            codes = torch.empty(n, dtype=torch.int64, device=dev)
+            _call(f"{prefix}_morton_codes", _ptr(rows), n, _ptr(index), nbytes, _ptr(codes))
+            order = torch.sort(codes, stable=True).indices
+        elif not torch.is_tensor(order) or order.device != dev or order.dtype != torch.int64 or order.shape != (n,):
+            raise _lib.DudfError(f"{what}: order must be an int64 ({letter},) CUDA tensor on the device of {arg}")
+        order = order.contiguous()
+        _call(f"{prefix}_index_build", _ptr(rows), n, _ptr(order), _ptr(index), nbytes)
+    flags = int(index[MESH_INDEX_FLAGS_OFFSET:MESH_INDEX_FLAGS_OFFSET + 4].view(torch.int32).item())
+    if flags & MESH_FLAG_NONFINITE:
+        raise ValueError(f"{what}: the {shape} has a NaN or infinite {row}")
+    if flags & MESH_FLAG_BAD_ORDER:
+        raise _lib.DudfError(f"{what}: the sorted order is not a permutation of the {plural}")
+    return index
 
 
 def mesh_index_build(tri, order=None):
@@ -1304,28 +1333,7 @@ def mesh_index_build(tri, order=None):
     `torch.sort`, then the boxes level by level; one host read at the end (the flag word).  ValueError for a NaN / infinite vertex.
     order (T,) int64: a permutation of the triangles to build the leaves from instead of the Morton order (any permutation gives
     the same answers, more slowly)."""
-    tri = _tensor(tri, "mesh_index_build: tri", torch.float32, (9,), convert=True)
-    T, dev = tri.shape[0], tri.device
-    if T == 0:
-        raise _lib.DudfError("mesh_index_build: a mesh without triangles has no index (DUDF_E_BADCFG)")
-    nbytes = _bytes("dudf_mesh_index_bytes", T, err=-4)
-    index = torch.zeros(nbytes, dtype=torch.uint8, device=dev)     # zeros: the padding between the sections is part of "same bytes"
-    assert index.data_ptr() % 256 == 0
-    with torch.cuda.device(dev):
-        if order is None:
-            codes = torch.empty(T, dtype=torch.int64, device=dev)
-            _call("dudf_mesh_morton_codes", _ptr(tri), T, _ptr(index), nbytes, _ptr(codes))
-            order = torch.sort(codes, stable=True).indices
-        elif not torch.is_tensor(order) or order.device != dev or order.dtype != torch.int64 or order.shape != (T,):
-            raise _lib.DudfError("mesh_index_build: order must be an int64 (T,) CUDA tensor on the device of tri")
-        order = order.contiguous()
-        _call("dudf_mesh_index_build", _ptr(tri), T, _ptr(order), _ptr(index), nbytes)
-    flags = int(index[MESH_INDEX_FLAGS_OFFSET:MESH_INDEX_FLAGS_OFFSET + 4].view(torch.int32).item())
-    if flags & MESH_FLAG_NONFINITE:
-        raise ValueError("mesh_index_build: the mesh has a NaN or infinite vertex")
-    if flags & MESH_FLAG_BAD_ORDER:
-        raise _lib.DudfError("mesh_index_build: the sorted order is not a permutation of the triangles")
-    return index
+    return _index_build("mesh_index_build", "dudf_mesh", tri, 9, order, ("mesh", "vertex", "triangles", "T", "tri"))
 
 
 def cloud_index_build(pc_pos, order=None):
@@ -1333,28 +1341,7 @@ def cloud_index_build(pc_pos, order=None):
     The mesh index's construction over points: Morton codes on the device, a stable `torch.sort`, the leaves of 8 points, then the
     boxes level by level; one host read at the end (the flag word).  ValueError for a NaN / infinite coordinate.  order (P,)
     int64: a permutation of the points to build the leaves from instead of the Morton order."""
-    pc_pos = _tensor(pc_pos, "cloud_index_build: pc_pos", torch.float32, (3,), convert=True)
-    n, dev = pc_pos.shape[0], pc_pos.device
-    if n == 0:
-        raise _lib.DudfError("cloud_index_build: a cloud without points has no index (DUDF_E_BADCFG)")
-    nbytes = _bytes("dudf_cloud_index_bytes", n, err=-4)
-    index = torch.zeros(nbytes, dtype=torch.uint8, device=dev)     # zeros: the padding between the sections is part of "same bytes"
-    assert index.data_ptr() % 256 == 0
-    with torch.cuda.device(dev):
-        if order is None:
-            codes = torch.empty(n, dtype=torch.int64, device=dev)
-            _call("dudf_cloud_morton_codes", _ptr(pc_pos), n, _ptr(index), nbytes, _ptr(codes))
-            order = torch.sort(codes, stable=True).indices
-        elif not torch.is_tensor(order) or order.device != dev or order.dtype != torch.int64 or order.shape != (n,):
-            raise _lib.DudfError("cloud_index_build: order must be an int64 (P,) CUDA tensor on the device of pc_pos")
-        order = order.contiguous()
-        _call("dudf_cloud_index_build", _ptr(pc_pos), n, _ptr(order), _ptr(index), nbytes)
-    flags = int(index[MESH_INDEX_FLAGS_OFFSET:MESH_INDEX_FLAGS_OFFSET + 4].view(torch.int32).item())
-    if flags & MESH_FLAG_NONFINITE:
-        raise ValueError("cloud_index_build: the cloud has a NaN or infinite coordinate")
-    if flags & MESH_FLAG_BAD_ORDER:
-        raise _lib.DudfError("cloud_index_build: the sorted order is not a permutation of the points")
-    return index
+    return _index_build("cloud_index_build", "dudf_cloud", pc_pos, 3, order, ("cloud", "coordinate", "points", "P", "pc_pos"))
 
 
 def _mesh_args(what, tri, index):
@@ -1412,16 +1399,11 @@ def mesh_distance(tri, index, points, want_idx=False, want_closest=False, stats=
     the soup tri (T,9), the nearest triangle (smallest index among ties) and the closest point on it.  index: what
     `mesh_index_build(tri)` returned, or None for the brute-force scan (same bits).  stats: int64 CUDA tensor of 1, the number of
     exact triangle evaluations is ADDED to it."""
-    tri = _tensor(tri, "mesh_distance: tri", torch.float32, (9,), convert=True)
+    tri, nbytes = _mesh_args("mesh_distance", tri, index)
     points = _tensor(points, "mesh_distance: points", torch.float32, (3,), convert=True)
     if points.device != tri.device:
         raise _lib.DudfError("mesh_distance: tri and points live on different devices")
     T, Q, dev = tri.shape[0], points.shape[0], tri.device
-    nbytes = 0
-    if index is not None:
-        if not torch.is_tensor(index) or index.device != dev or index.dtype != torch.uint8 or not index.is_contiguous():
-            raise _lib.DudfError("mesh_distance: index must be the uint8 CUDA tensor of mesh_index_build on the device of tri")
-        nbytes = index.numel()
     if stats is not None and (not torch.is_tensor(stats) or stats.device != dev or stats.dtype != torch.int64 or stats.numel() != 1):
         raise _lib.DudfError("mesh_distance: stats must be an int64 CUDA tensor of 1")
     dist = torch.empty(Q, dtype=torch.float32, device=dev)

@@ -366,7 +366,7 @@ int dudf_cloud_outliers(const float* knn_dist, int64_t n, int K, double std_rati
                         void* stream);
 
 /* Exact unsigned distance from points to a triangle mesh with a bounding-volume hierarchy — the device side of open3d's
- * `RaycastingScene.add_triangles / compute_distance` (reference generate_df.py:108-110).  csrc/dudf_meshdist.hip.  Like the Chamfer
+ * `RaycastingScene.add_triangles / compute_distance` (reference generate_df.py:108-110).  csrc/dudf_bvh.hip (the index), csrc/dudf_meshdist.hip (the queries).  Like the Chamfer
  * entry points these arrived after ABI 8 without changing any existing signature.  tri (n_tri,9) fp32 is the triangle soup
  * dudf_sample_batch takes; 0 < n_tri < 2^31 (n_tri <= 0: DUDF_E_BADCFG, larger: DUDF_E_UNSUPPORTED).
  *
@@ -814,7 +814,7 @@ int dudf_sample_batch_at(const float* tri, int64_t n_tri, const float* pc_pos, c
                          float* x, float* normals, float* sdf, void* stream);
 
 /* The same batches with the distances taken through an index instead of a scan of the whole shape, for meshes and clouds whose
- * size makes the scan the step's largest cost.  csrc/dudf_sample_indexed.hip, csrc/dudf_groupwalk.h.  Like the dudf_mesh_* entry
+ * size makes the scan the step's largest cost.  csrc/dudf_sample_indexed.hip, csrc/dudf_groupwalk.h; the cloud index: csrc/dudf_bvh.hip.  Like the dudf_mesh_* entry
  * points these arrived after ABI 8 without changing any existing signature.
  *
  * The cloud index is the mesh index's fixed-shape Morton tree over pc_pos (n_pc,3): a sorted copy of the points as 16-byte rows,
